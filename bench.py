@@ -18,7 +18,16 @@ BASELINE.json's metric has two halves, so the ONE JSON line rank 0 prints carrie
   * `eval_fwd` = the eval-mode forward (BASELINE configs[1]) with one and two batches in flight in bf16, and in the f32
     parity mode (the mode whose outputs meet north_star's <= 1e-4 gate).
 
-`--workload train|forward|retrieval` runs one leg alone (tools/, profiling); the default `all` runs the three.
+A plain run measures the headline alone: `value` / `ms_per_step` of the --steps timed training steps.  Everything else
+(`roofline`, `kernels`, `cpu_baseline`, the eager and hipGraph steps beside the taped one, the f32 and T_a = 1024
+training legs, `retrieval`, `eval_fwd`, `north_star_contraction`) is measured under `--full`.
+
+`--workload train|forward|retrieval` runs one leg alone (tools/, profiling); the default `all` runs the three (`--full`).
+
+`--dump-outputs DIR`: after the timed steps, what the timed path returned in its last step goes to DIR/<name>.npy (float32,
+float64 for float64 and integer outputs; see _dump_outputs).  What every timed step reads -- batch, weights, dropout seed --
+is the same in every run with the same arguments (the training steps run at zero learning rates for this: see TRAIN_LRS),
+so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -44,6 +53,11 @@ HBM_PEAK_GBS = 8000.0
 PMC_FILE = os.path.join(ROOT, "profiles", "r06_pmc_summary.json")   # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (tools/profile_round6.sh), per leg
 ROCPROF_AVG_FILE = os.path.join(ROOT, "profiles", "r06_kernel_avg_us.json")   # per-leg, per-kernel average durations of the committed rocprofv3 --kernel-trace --stats runs
 STEP_CEILING_PAIRS_S = {"train": 62000.0, "eval": 186000.0}          # MFMA ceilings of the whole step (fwd+bwd / fwd)
+# Learning rates of every training step the benchmark issues: zero.  The step does the same work at any value (made_adam_step computes and
+# writes the update either way), and every step then starts from the same weights in every run.  At a nonzero rate it would not: the weight
+# gradients are summed with f32 atomic adds, and Adam moves a weight whose gradient is near zero by about lr x sign(g) -- the last bit of a
+# sum decides a move of lr, so the inputs of step k would differ between two runs by far more than rounding.
+TRAIN_LRS = (0.0, 0.0, 0.0)
 
 
 
@@ -119,6 +133,11 @@ def parse():
     p.add_argument("--in-flight", type=int, default=2,
                    help="forward workload: independent batches in flight (one engine, workspace, stream and graph each); steps "
                         "are issued round-robin over them")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: roofline and per-kernel figures, CPU baselines, the eager and "
+                        "hipGraph steps, the other precisions and shapes, retrieval and the eval forward")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the timed path returned in its last step to DIR/<name>.npy")
     return p.parse_args()
 
 
@@ -200,6 +219,39 @@ def _barrier(dist):
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
+
+
+def _settle(step, seconds: float = 0.75) -> None:
+    """A freshly booted box, or a GPU that idled through a capture or a CPU baseline, runs its next second of work at low clocks: bring
+    it to its working state before the W warmup steps."""
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        step()
+    torch.cuda.synchronize()
+
+
+DUMP_SAMPLE = 1 << 18            # elements kept of a larger output (--dump-outputs)
+DUMP_BUDGET_BYTES = 64 << 20     # all files of one dump together
+
+
+def _dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: one DIR/<name>.npy per tensor of `arrays` (float32; float64 for float64 and integer outputs).  An output of more than
+    DUMP_SAMPLE elements is stored as its flattened elements at fixed indices: np.unique(default_rng(0).integers(0, numel, DUMP_SAMPLE)),
+    the same in every run, so two builds compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in sorted(arrays.items()):
+        if not isinstance(t, torch.Tensor):
+            continue
+        a = t.detach()
+        if a.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.numel(), DUMP_SAMPLE))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        a = a.to(torch.float64 if (a.dtype == torch.float64 or not a.is_floating_point()) else torch.float32).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_BUDGET_BYTES >> 20} MB at {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------- CPU baselines (oracle)
@@ -320,7 +372,7 @@ def north_star_contraction(dev) -> dict:
 
 
 # ------------------------------------------------------------------------------------------------- legs
-def retrieval_leg(args, rank, world, local, dist, steps: int, warmup: int) -> dict:
+def retrieval_leg(args, rank, world, local, dist, steps: int, warmup: int, dump_dir=None) -> dict:
     """BASELINE.json configs[3]: all-pairs video x music similarity, videos row-sharded over the ranks, music side
     all-gathered once per pass (RCCL).  A step = one full pass (exchange + scoring).  Strong scaling: the problem is fixed."""
     from mgsv_amd.config import cfg_native
@@ -354,11 +406,13 @@ def retrieval_leg(args, rank, world, local, dist, steps: int, warmup: int) -> di
         rows = step()
     _barrier(dist)
     elapsed = _max_over_ranks(time.perf_counter() - t0, dist, dev)
+    if dump_dir and rank == 0:
+        _dump_outputs(dump_dir, {"sim_rows": rows})
     assert rows.shape == (vhi - vlo, N_m) and bool(torch.isfinite(rows).all())
     alg_bytes = 4.0 * (N_m * S * D + N_m * S + N_v * D + N_m * D + N_v * N_m)      # inputs once + sim matrix once
     pairs = float(N_v) * N_m
     roof, per_kernel = None, {}
-    if rank == 0:
+    if rank == 0 and args.full:
         # dominant kernel, timed live with HIP events on its launch stream; executed flops: 4 * valid segments * D (scores +
         # pooling) + 2 D^2 (Linear) per pair, the padded segments of a track are skipped by the kernel and not counted here
         with ops.KernelTimer() as kt:
@@ -368,7 +422,7 @@ def retrieval_leg(args, rank, world, local, dist, steps: int, warmup: int) -> di
         per_kernel = _per_kernel(summ, 1)
     sec = elapsed / steps
     other_ms = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # the other D = 256 kernel (made_xpool_fused: the whole pair chain with the per-pair Linear, rounds 2-4's default) on the same pass, AFTER the
         # timed region: reported beside the default path (made_xpool_sims for tracks of at most 96 segments), not part of `value`
         try:
@@ -389,8 +443,8 @@ def retrieval_leg(args, rank, world, local, dist, steps: int, warmup: int) -> di
                                if S <= 96 else "made_xpool_fused (one kernel per chunk of tracks)"),
                       "made_xpool_fused_ms_per_step": other_ms},
            "roofline": roof, "kernels": per_kernel,
-           "cpu_baseline": (cpu_baseline_retrieval(cfg, synth.make_state_dict(cfg, seed=0), S) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None)}
-    if rank == 0 and world == 1 and args.dtype == "bf16" and os.environ.get("MADE_BENCH_RETRIEVAL_F32", "1") != "0":
+           "cpu_baseline": (cpu_baseline_retrieval(cfg, synth.make_state_dict(cfg, seed=0), S) if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None)}
+    if args.full and rank == 0 and world == 1 and args.dtype == "bf16" and os.environ.get("MADE_BENCH_RETRIEVAL_F32", "1") != "0":
         # the same pass in the f32 parity mode (exact-f32 MFMA, f32 intermediates): the mode whose similarities meet north_star's <= 1e-4 against
         # the oracle (tests/test_engine_gpu.py::test_retrieval_parity_sampled_at_the_timed_size: 3e-7 at this size) -- the arithmetic
         # test-MaDe.py:392-403 runs.  One warm-up on a corner of the problem, ONE timed pass; reported beside `value`, never as it.
@@ -406,7 +460,7 @@ def retrieval_leg(args, rank, world, local, dist, steps: int, warmup: int) -> di
             out["f32x3_parity_mode"] = {"error": f"{type(ex).__name__}: {ex}"}
     del eng, sr, rows, v, seg, mu
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and os.environ.get("MADE_BENCH_RETRIEVAL_512", "1") != "0":
+    if args.full and rank == 0 and world == 1 and os.environ.get("MADE_BENCH_RETRIEVAL_512", "1") != "0":
         # "also report S = 512, D = 512" -- the headline model's width and segment count.  made_xpool_fused (one kernel per
         # pair chain) is built for D = 256; this shape takes made_xpool_attention (round 4: the attention of a whole track in two passes
         # with the probabilities in LDS, LayerNorm2's normalisation in its tail) + the folded Linear + made_xpool_tail over chunks of
@@ -479,7 +533,7 @@ def _retrieval_512(args, n_v: int = 8192, n_m: int = 512, S: int = 512) -> dict:
                      else "separate launches (made_attention_wide, LayerNorm2, Linear, made_xpool_tail)")}
 
 
-def train_leg(args, rank, world, local, dist, steps: int, warmup: int) -> dict:
+def train_leg(args, rank, world, local, dist, steps: int, warmup: int, dump_dir=None) -> dict:
     """BASELINE.json configs[2] (N = 1) / configs[4] (N > 1, per-rank B = 64): one full training iteration per step --
     train-mode forward (dropout on), matcher + criterion, hand-written backward, data-parallel gradient all-reduce (RCCL, one
     flat f32 buffer), three-group clipping + Adam, re-derivation of the bf16 weights (reference train-MaDe.py:337-381)."""
@@ -500,36 +554,33 @@ def train_leg(args, rank, world, local, dist, steps: int, warmup: int) -> dict:
 
     def eager_step():
         it[0] += 1
-        return trn.train_step(*batch, seed=it[0], lrs=(1e-4, 1e-4, 1e-4), max_grad_norm=1.0, dist=dist)
+        return trn.train_step(*batch, seed=it[0], lrs=TRAIN_LRS, max_grad_norm=1.0, dist=dist)
 
     step = eager_step
-    # a freshly booted box runs its first second of work at low clocks: bring the GPU to its working state before the W warmup steps
-    t_pre = time.perf_counter()
-    while time.perf_counter() - t_pre < 0.75:
-        step()
-    torch.cuda.synchronize()
+    if args.full:
+        _settle(step)
     # The iteration also exists as hipGraph(s) (MadeTrainer.capture_train_step -- seed / Adam step / learning rates in
     # device memory, the all-reduces between the graphs).  It is measured beside the eager step and NOT used for `value`: on this
     # ROCm a replay costs the host as much as issuing the ~600 launches itself and the device time is the same.
     graph_ms = None
-    if args.launch == "graph" and world == 1:
+    if args.full and args.launch == "graph" and world == 1:
         try:
             graph = trn.capture_train_step(*batch, max_grad_norm=1.0)
             for _ in range(3):
                 it[0] += 1
-                graph.step(*batch, seed=it[0], lrs=(1e-4, 1e-4, 1e-4))
+                graph.step(*batch, seed=it[0], lrs=TRAIN_LRS)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(10):
                 it[0] += 1
-                graph.step(*batch, seed=it[0], lrs=(1e-4, 1e-4, 1e-4))
+                graph.step(*batch, seed=it[0], lrs=TRAIN_LRS)
             torch.cuda.synchronize()
             graph_ms = round((time.perf_counter() - t0) / 10 * 1e3, 3)
             del graph
         except Exception as ex:                      # report, do not hide
             print(f"[bench] hipGraph capture of the training step failed ({type(ex).__name__}: {ex})", file=sys.stderr)
     # The library's own launch tape (made_tape_*: the step's ~560 launches recorded once, replayed from one C loop onto the same two
-    # streams): what `value` is measured with when it is available (--launch graph) -- the eager step beside it.
+    # streams): what `value` is measured with when it is available (--launch graph) -- the eager step beside it (--full).
     launch, eager_ms = "eager", None
     if args.launch == "graph" and os.environ.get("MADE_BENCH_TAPE", "1") != "0":
         try:
@@ -541,18 +592,22 @@ def train_leg(args, rank, world, local, dist, steps: int, warmup: int) -> dict:
 
             def tape_step():
                 it[0] += 1
-                return tape.step(*tbatch, seed=it[0], lrs=(1e-4, 1e-4, 1e-4))
-            for _ in range(3):
-                eager_step()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(10):
-                eager_step()
-            torch.cuda.synchronize()
-            eager_ms = round((time.perf_counter() - t0) / 10 * 1e3, 3)
+                return tape.step(*tbatch, seed=it[0], lrs=TRAIN_LRS)
+            if args.full:
+                for _ in range(3):
+                    eager_step()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    eager_step()
+                torch.cuda.synchronize()
+                eager_ms = round((time.perf_counter() - t0) / 10 * 1e3, 3)
             step, launch = tape_step, "tape"
         except Exception as ex:                      # report, do not hide
             print(f"[bench] launch tape of the training step failed ({type(ex).__name__}: {ex}); using eager launches", file=sys.stderr)
+    _settle(step)
+    it[0] = 0                                        # the dropout seeds of the warmup and timed steps: 1, 2, ... in every run (the
+    # settling loop's number of steps depends on time; at TRAIN_LRS the weights it leaves are the ones it started from)
     for _ in range(max(warmup, 1)):
         out = step()
     _barrier(dist)
@@ -561,10 +616,12 @@ def train_leg(args, rank, world, local, dist, steps: int, warmup: int) -> dict:
         out = step()
     _barrier(dist)
     elapsed = _max_over_ranks(time.perf_counter() - t0, dist, dev)
+    if dump_dir and rank == 0:
+        _dump_outputs(dump_dir, dict(out, params_after_step=trn.flat_param))
     assert bool(torch.isfinite(out["localization_loss"]).all()) and bool(torch.isfinite(out["retrieval_loss"]).all())
     assert bool(torch.isfinite(trn.flat_param).all())
     per_kernel, roof, executed_gflop = {}, None, 0.0
-    if rank == 0:
+    if rank == 0 and args.full:
         with ops.KernelTimer() as kt:                # per-kernel HIP events need the eager launches (a replay is one launch)
             for _ in range(2):
                 eager_step()
@@ -592,17 +649,18 @@ def train_leg(args, rank, world, local, dist, steps: int, warmup: int) -> dict:
                       "step_ceiling_pairs_s": STEP_CEILING_PAIRS_S["train"],
                       "step_ceiling_note": "SURVEY 8(d)'s ceiling counts the NOMINAL flops of the padded batch (2 575 GFLOP per step); the path executes "
                                            "the valid rows / keys only -- mfma_frac_over_step is the executed work against the MFMA peak",
-                      "executed_gflop_per_step": round(executed_gflop, 1) if rank == 0 else None,
-                      "mfma_frac_over_step": round(executed_gflop / 1e3 / sec / PEAK_TFLOPS[args.dtype], 4) if rank == 0 else None},
+                      "executed_gflop_per_step": round(executed_gflop, 1) if roof is not None else None,
+                      "mfma_frac_over_step": round(executed_gflop / 1e3 / sec / PEAK_TFLOPS[args.dtype], 4) if roof is not None else None},
            "roofline": roof,
-           "cpu_baseline": (cpu_baseline_train(cfg, sd, inp) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None),
+           "cpu_baseline": (cpu_baseline_train(cfg, sd, inp) if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None),
            "kernels": per_kernel}
     del trn, t, out
     torch.cuda.empty_cache()
     return res
 
 
-def eval_leg(args, rank, world, local, dist, dtype: str, n_lanes: int, steps: int, warmup: int, with_roofline: bool, with_cpu: bool) -> dict:
+def eval_leg(args, rank, world, local, dist, dtype: str, n_lanes: int, steps: int, warmup: int, with_roofline: bool, with_cpu: bool,
+             dump_dir=None) -> dict:
     """BASELINE.json configs[1]: eval-mode `Uni_model.forward` (reference model/model_Uni.py:177-322) over B=64 batches resident in HBM.
     Steps are independent batches; `n_lanes` of them are kept in flight (one engine, workspace, stream and captured graph each), issued
     round-robin: one batch's decoder -- a chain of dependent launches that leaves most of the chip idle -- then runs beside another
@@ -648,18 +706,13 @@ def eval_leg(args, rank, world, local, dist, dtype: str, n_lanes: int, steps: in
     def run():
         l = issued[0] % n_lanes
         issued[0] += 1
-        if n_lanes == 1:
-            graphs[0].replay() if graphs else step(0)
-            return
-        with torch.cuda.stream(lane_stream[l]):
-            graphs[l].replay() if graphs else step(l)
+        with torch.cuda.stream(lane_stream[l]) if n_lanes > 1 else contextlib.nullcontext():
+            if graphs:
+                graphs[l].replay()
+            else:
+                outs[l] = step(l)
 
-    # the GPU idles through a CPU baseline or a capture in front of this leg and starts its next second of work at low clocks: bring it
-    # to its working state before the W warmup steps (as the training leg does)
-    t_pre = time.perf_counter()
-    while time.perf_counter() - t_pre < 0.75:
-        run()
-    torch.cuda.synchronize()
+    _settle(run)
     for _ in range(warmup):
         run()
     _barrier(dist)
@@ -670,6 +723,8 @@ def eval_leg(args, rank, world, local, dist, dtype: str, n_lanes: int, steps: in
     elapsed = _max_over_ranks(time.perf_counter() - t0, dist, dev)
     ms = elapsed / steps * 1e3
     value = world * B * steps / elapsed
+    if dump_dir and rank == 0:                       # (every batch in flight: which of them ran last depends on the settling loop)
+        _dump_outputs(dump_dir, outs[0] if n_lanes == 1 else {f"lane{l}_{k}": v for l, o in enumerate(outs) for k, v in o.items()})
 
     torch.cuda.synchronize()
     for o in outs:                                   # sanity: the step really produced finite losses and a valid matching
@@ -826,43 +881,45 @@ def main():
         import torch.distributed as dist
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))      # backend "nccl" is RCCL on ROCm
 
+    dump = args.dump_outputs
     if args.workload == "train":
-        line = train_leg(args, rank, world, local, dist, args.steps, args.warmup)
+        line = train_leg(args, rank, world, local, dist, args.steps, args.warmup, dump)
     elif args.workload == "retrieval":
-        line = retrieval_leg(args, rank, world, local, dist, args.steps, args.warmup)
+        line = retrieval_leg(args, rank, world, local, dist, args.steps, args.warmup, dump)
     elif args.workload == "forward":
-        line = eval_leg(args, rank, world, local, dist, args.dtype, args.in_flight, args.steps, args.warmup, True, True)
+        line = eval_leg(args, rank, world, local, dist, args.dtype, args.in_flight, args.steps, args.warmup, args.full, args.full, dump)
         line.update(n_gpus=world, steps=args.steps, warmup=args.warmup, higher_is_better=True, scaling="weak", vs_baseline=None, data="synthetic")
     else:
-        # the headline line: the training step is `value`; retrieval and the eval forward ride along as sub-objects
-        line = train_leg(args, rank, world, local, dist, args.steps, args.warmup)
-        # the same training step in the f32 parity mode (exact-f32 MFMA, f32 activations): the mode whose forward meets north_star's
-        # <= 1e-4 gate and whose gradients are held to the oracle's autograd at 5e-3 (tests/test_trainer_gpu.py)
-        import copy
-        a32 = copy.copy(args)
-        a32.dtype, a32.launch, a32.no_cpu_baseline = "f32", "eager", True
-        t32 = train_leg(a32, rank, world, local, dist, max(3, min(args.steps, 10)), 2)
-        line["train_f32_parity_mode"] = {k: t32[k] for k in ("metric", "value", "unit", "ms_per_step", "dtype", "config", "roofline")}
-        # the per-GPU shape of BASELINE configs[4] (B = 64 per GPU, T_a = 1024 long music): the same training step, one GPU's share of it
-        a1k = copy.copy(args)
-        a1k.ta, a1k.no_cpu_baseline = 1024, True
-        t1k = train_leg(a1k, rank, world, local, dist, max(3, min(args.steps, 10)), 2)
-        line["train_ta1024"] = {k: t1k[k] for k in ("metric", "value", "unit", "ms_per_step", "dtype", "config", "roofline")}
-        r_steps = max(2, min(5, args.steps))
-        line["retrieval"] = retrieval_leg(args, rank, world, local, dist, r_steps, 1)
-        ev = {}
-        ev["bf16_two_in_flight"] = eval_leg(args, rank, world, local, dist, "bf16", 2, max(args.steps, 40), args.warmup, True, True)
-        ev["bf16_one_in_flight"] = eval_leg(args, rank, world, local, dist, "bf16", 1, max(args.steps, 20), args.warmup, False, False)
-        ev["f32_parity_mode_one_in_flight"] = eval_leg(args, rank, world, local, dist, "f32", 1, 10, 2, False, False)
-        ev["f32x3_parity_mode_one_in_flight"] = eval_leg(args, rank, world, local, dist, "f32x3", 1, 10, 2, False, False)
-        ev["note"] = ("f32_parity_mode (exact-f32 MFMA) and f32x3_parity_mode (f32 storage, split-bf16 products) are the modes whose logits / spans meet north_star's <= 1e-4 gate against the oracle and the reference goldens "
-                      "(tests/test_engine_gpu.py); the bf16 modes are checked at 4.5e-2 (logits) / 7e-3 (spans) = 2x the measured error")
-        line["eval_fwd"] = ev
-        if rank == 0 and world == 1:
-            try:
-                line["north_star_contraction"] = north_star_contraction(torch.device("cuda", local))
-            except Exception as ex:                  # report, do not hide
-                line["north_star_contraction"] = {"error": f"{type(ex).__name__}: {ex}"}
+        # the headline line: the training step is `value`; retrieval and the eval forward ride along as sub-objects (--full)
+        line = train_leg(args, rank, world, local, dist, args.steps, args.warmup, dump)
+        if args.full:
+            # the same training step in the f32 parity mode (exact-f32 MFMA, f32 activations): the mode whose forward meets north_star's
+            # <= 1e-4 gate and whose gradients are held to the oracle's autograd at 5e-3 (tests/test_trainer_gpu.py)
+            import copy
+            a32 = copy.copy(args)
+            a32.dtype, a32.launch, a32.no_cpu_baseline = "f32", "eager", True
+            t32 = train_leg(a32, rank, world, local, dist, max(3, min(args.steps, 10)), 2)
+            line["train_f32_parity_mode"] = {k: t32[k] for k in ("metric", "value", "unit", "ms_per_step", "dtype", "config", "roofline")}
+            # the per-GPU shape of BASELINE configs[4] (B = 64 per GPU, T_a = 1024 long music): the same training step, one GPU's share of it
+            a1k = copy.copy(args)
+            a1k.ta, a1k.no_cpu_baseline = 1024, True
+            t1k = train_leg(a1k, rank, world, local, dist, max(3, min(args.steps, 10)), 2)
+            line["train_ta1024"] = {k: t1k[k] for k in ("metric", "value", "unit", "ms_per_step", "dtype", "config", "roofline")}
+            r_steps = max(2, min(5, args.steps))
+            line["retrieval"] = retrieval_leg(args, rank, world, local, dist, r_steps, 1)
+            ev = {}
+            ev["bf16_two_in_flight"] = eval_leg(args, rank, world, local, dist, "bf16", 2, max(args.steps, 40), args.warmup, True, True)
+            ev["bf16_one_in_flight"] = eval_leg(args, rank, world, local, dist, "bf16", 1, max(args.steps, 20), args.warmup, False, False)
+            ev["f32_parity_mode_one_in_flight"] = eval_leg(args, rank, world, local, dist, "f32", 1, 10, 2, False, False)
+            ev["f32x3_parity_mode_one_in_flight"] = eval_leg(args, rank, world, local, dist, "f32x3", 1, 10, 2, False, False)
+            ev["note"] = ("f32_parity_mode (exact-f32 MFMA) and f32x3_parity_mode (f32 storage, split-bf16 products) are the modes whose logits / spans meet north_star's <= 1e-4 gate against the oracle and the reference goldens "
+                          "(tests/test_engine_gpu.py); the bf16 modes are checked at 4.5e-2 (logits) / 7e-3 (spans) = 2x the measured error")
+            line["eval_fwd"] = ev
+            if rank == 0 and world == 1:
+                try:
+                    line["north_star_contraction"] = north_star_contraction(torch.device("cuda", local))
+                except Exception as ex:                  # report, do not hide
+                    line["north_star_contraction"] = {"error": f"{type(ex).__name__}: {ex}"}
         line["metric"] = "video-music pairs/s fwd+bwd at B=64 (full training step); sub-objects: retrieval sim-matrix GB/s, eval forward pairs/s"
     if rank == 0:
         print(json.dumps(line))

@@ -2,7 +2,7 @@
 export MADE_DEBUG_VARIANTS=1          # (measurement knobs are honoured only under this switch)
 TAG=$1; shift
 O=gpurun_out/$TAG; mkdir -p $O
-run() { env $2 timeout 200 python bench.py --workload train --no-cpu-baseline --steps 40 > $O/$1.json 2>$O/$1.err; python - <<PY
+run() { env $2 timeout 200 python bench.py --full --workload train --no-cpu-baseline --steps 40 > $O/$1.json 2>$O/$1.err; python - <<PY
 import json
 try:
     d = json.load(open("$O/$1.json")); print("%-40s %.3f ms (eager %s)" % ("$2" or "default", d["ms_per_step"], d["config"].get("eager_ms_per_step")))

@@ -6,25 +6,25 @@
 set -x
 TAG=${1:-r06x}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench_default.json 2>$O/bench_default.err
-rm -rf /tmp/p1; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -- python3 $R/bench.py --workload train --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_train_under_rocprof.json 2>/dev/null
+python3 $R/bench.py --full > $O/bench_default.json 2>$O/bench_default.err
+rm -rf $TMPDIR/p1; rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/p1 -- python3 $R/bench.py --full --workload train --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_train_under_rocprof.json 2>/dev/null
 T1=$(find /tmp/p1 -name "*kernel_trace.csv" | head -1)
 cp $(find /tmp/p1 -name "*kernel_stats.csv" | head -1) $O/kernel_stats_train_bf16.csv; python3 $R/tools/trace_summary.py $T1 adam_update_kernel 90 > $O/train_trace_summary.txt
 python3 $R/tools/trace_timeline.py $T1 adam_update_kernel -7 > $O/train_step_timeline_tape_under_rocprof.txt
 python3 $R/tools/kernel_avg.py train $T1 $O/kernel_avg_us.json > /dev/null
-rm -rf /tmp/p2; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p2 -- python3 $R/bench.py --workload forward --steps 10 --warmup 3 --no-cpu-baseline --launch eager --in-flight 1 > $O/bench_eval_under_rocprof.json 2>/dev/null
+rm -rf $TMPDIR/p2; rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/p2 -- python3 $R/bench.py --full --workload forward --steps 10 --warmup 3 --no-cpu-baseline --launch eager --in-flight 1 > $O/bench_eval_under_rocprof.json 2>/dev/null
 T2=$(find /tmp/p2 -name "*kernel_trace.csv" | head -1)
 cp $(find /tmp/p2 -name "*kernel_stats.csv" | head -1) $O/kernel_stats_eval_eager_bf16.csv; python3 $R/tools/trace_summary.py $T2 sine_pe_kernel 50 > $O/eval_trace_summary.txt
 python3 $R/tools/kernel_avg.py eval $T2 $O/kernel_avg_us.json > /dev/null
-rm -rf /tmp/p3; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p3 -- python3 $R/bench.py --workload retrieval --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_retrieval_under_rocprof.json 2>/dev/null
+rm -rf $TMPDIR/p3; rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/p3 -- python3 $R/bench.py --full --workload retrieval --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_retrieval_under_rocprof.json 2>/dev/null
 T3=$(find /tmp/p3 -name "*kernel_trace.csv" | head -1)
 cp $(find /tmp/p3 -name "*kernel_stats.csv" | head -1) $O/kernel_stats_retrieval_bf16.csv
 python3 $R/tools/kernel_avg.py retrieval $T3 $O/kernel_avg_us.json > /dev/null
 for leg in train eval retrieval; do
   case $leg in
-    train) A="--workload train --steps 2 --warmup 1 --no-cpu-baseline --launch eager";;
-    eval) A="--workload forward --steps 2 --warmup 1 --no-cpu-baseline --launch eager --in-flight 1";;
-    retrieval) A="--workload retrieval --steps 1 --warmup 1 --no-cpu-baseline";;
+    train) A="--full --workload train --steps 2 --warmup 1 --no-cpu-baseline --launch eager";;
+    eval) A="--full --workload forward --steps 2 --warmup 1 --no-cpu-baseline --launch eager --in-flight 1";;
+    retrieval) A="--full --workload retrieval --steps 1 --warmup 1 --no-cpu-baseline";;
   esac
   rm -rf /tmp/pf /tmp/pw
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pf -- python3 $R/bench.py $A > /dev/null 2>&1
