@@ -935,6 +935,40 @@ int made_span_pairwise(const float* spans1, const float* spans2, float* iou, flo
 int made_span_iou_se(const float* pred_se, const float* gt_moment, const float* m_duration, int64_t N, float max_m_duration,
                      int32_t clamp_to_max, int32_t discounted, float* iou_out, void* stream);
 
+/* ==========================================================================================
+ * Grounding: each video's best K tracks and the localization batch of arbitrary (video, track) pairs (mgsv_amd/grounding.py).
+ * The reference has no counterpart: it predicts a moment in the ground-truth track only (utils/util_test.py:202-226).
+ * ========================================================================================== */
+
+/* made_topk_groups: the best K groups of every row of sims [Nv, Nm] f32 (row stride ld >= Nm).  group_id [Nm] int32 (may be NULL:
+ * every column is its own group) maps columns to groups 0 .. n_groups-1, the convention of made_recall_ranks (columns with an id
+ * outside that range are ignored).  A group's score is its maximum and its representative column the lowest column attaining it.
+ * idx_out [Nv, K] int32 = representative columns, score_out [Nv, K] f32 = scores, in a strict total order: score descending, then
+ * column ascending (exact and deterministic); NaN ranks below every number, -0 equals +0.  Positions past the number of non-empty
+ * groups hold -1 / -inf.  idx_out[i, 0] equals made_recall_ranks' top1_out[i] (same "lowest index among equal maxima" rule).
+ * 1 <= K <= 256; with groups n_groups <= 32768 (one LDS table per row); Nm <= 2^24.  Rows of more than 32768 columns without
+ * groups select per block of columns and then over the blocks' candidates: they need `ws` of
+ * made_topk_groups_ws_bytes(Nv, Nm, K) bytes (0 otherwise: ws may be NULL). */
+int64_t made_topk_groups_ws_bytes(int64_t Nv, int64_t Nm, int64_t K);
+int made_topk_groups(const float* sims, int64_t ld, const int32_t* group_id, int64_t Nv, int64_t Nm, int64_t n_groups,
+                     int64_t K, int32_t* idx_out, float* score_out, void* ws, int64_t ws_bytes, void* stream);
+
+/* made_gather_pairs: the localization batch of P (video, track) pairs vi[P], mi[P] (device int32) from per-item tower outputs, in
+ * one launch -- what the temporal encoders of a forward over those pairs leave behind.  Video side: frame tokens [Nv, Tv, D]
+ * (`dtype`, item stride v_tok_stride elements, rows contiguous), frame mask [Nv, Tv] f32, clip vector [Nv, D] f32; music side
+ * the same with Ta segments.  The item strides let the packed music records of the sharded retrieval be read in place.
+ * Outputs: frame_out [P, Tv, D] and seg_out [P, Ta, D] (pair strides frame_out_stride / seg_out_stride: both halves of the concat
+ * fusion's DETR input, or the CA fusion's two buffers), fmask_out [P, Tv], smask_out [P, Ta], video_out / music_out [P, D] f32.
+ * Token rows, token strides and D * element size must be 16-byte aligned (16-byte copies).  A pair with an index outside
+ * [0, Nv) x [0, Nm) reads nothing and is written as all padding; its localization outputs are unspecified. */
+int made_gather_pairs(const int32_t* vi, const int32_t* mi, int64_t P, int64_t Nv, int64_t Nm,
+                      const void* v_tok, int64_t v_tok_stride, const float* v_mask, int64_t v_mask_stride,
+                      const float* v_vec, int64_t v_vec_stride,
+                      const void* m_tok, int64_t m_tok_stride, const float* m_mask, int64_t m_mask_stride,
+                      const float* m_vec, int64_t m_vec_stride, int64_t Tv, int64_t Ta, int64_t D, int32_t dtype,
+                      void* frame_out, int64_t frame_out_stride, void* seg_out, int64_t seg_out_stride,
+                      float* fmask_out, float* smask_out, float* video_out, float* music_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,6 +277,10 @@ SIGNATURES = {
     "made_span_pairwise": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, vp]),
     "made_span_iou_se": (C.c_int, [vp, vp, vp, i64, f32, i32, i32, vp, vp]),
     "made_set_criterion": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, f32, vp, vp, vp, vp]),
+    "made_topk_groups_ws_bytes": (C.c_int64, [i64, i64, i64]),
+    "made_topk_groups": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, i64, vp]),
+    "made_gather_pairs": (C.c_int, [vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32,
+                                    vp, i64, vp, i64, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -1,0 +1,353 @@
+// Grounding: the best K tracks of every video row of the similarity matrix (made_topk_groups) and the localization batch of
+// arbitrary (video, track) pairs assembled from per-item tower outputs (made_gather_pairs).  Neither has a counterpart in the
+// reference, which predicts a moment only in the ground-truth track.
+#include "common.h"
+
+namespace {
+
+constexpr int GT = 256;                 // threads per workgroup; the final sort gives every thread one candidate (K <= 256)
+constexpr int CAP = 32768;              // items one workgroup selects from: 128 KiB of keys in LDS
+constexpr uint32_t SLOT_OUT = 0xFFFFFFFFu;
+constexpr uint32_t TIE = 0x40000000u;   // group table: TIE + (lowest column of the group at the threshold score)
+constexpr uint32_t TIE_NONE = 0x7FFFFFFFu;
+
+// Order-preserving unsigned key of a score: NaN -> 1 (below -inf), 0 is "no item" (fill), -0 is +0.  Finite values and the
+// infinities map to keys >= 0x007FFFFF, so the two reserved keys never collide with a number.
+__device__ __forceinline__ uint32_t score_key(float f) {
+    if (f != f) return 1u;
+    const uint32_t u = f == 0.f ? 0u : __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float key_score(uint32_t k) {
+    if (k == 0u) return -INFINITY;
+    if (k == 1u) return __uint_as_float(0x7FC00000u);
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
+struct TopkShared {
+    int hist[256];
+    uint32_t cand_key[256];
+    int cand_col[256];
+    int wsum[GT / 64];
+    int sel[2];
+    int cnt;
+};
+
+// Histogram add with the lanes of a wave that share a bin folded into one atomic (the top bytes of similarity scores sit in
+// one or two bins, where plain LDS atomics serialise 64-fold); after a few distinct bins the rest fall back to plain atomics.
+__device__ __forceinline__ void hist_add(int* hist, bool active, int bin) {
+    const int lane = threadIdx.x & 63;
+    for (int it = 0; it < 4; ++it) {
+        const unsigned long long act = __ballot(active);
+        if (act == 0ull) return;
+        const int leader = __ffsll((long long)act) - 1;
+        const int b0 = __shfl(bin, leader);
+        const unsigned long long same = __ballot(active && bin == b0);
+        if (lane == leader) atomicAdd(&hist[b0], __popcll(same));
+        if (bin == b0) active = false;
+    }
+    if (active) atomicAdd(&hist[bin], 1);
+}
+
+// The kk-th largest key of v[0..n) (1 <= kk <= n), MSB-first radix select over 8-bit digits.  Returns the key t and writes to
+// *need how many items equal to t belong to the top kk.
+__device__ uint32_t radix_select(const uint32_t* v, int n, int kk, TopkShared& sh, int* need_out) {
+    uint32_t prefix = 0u, mask = 0u;
+    int need = kk;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int b = threadIdx.x; b < 256; b += GT) sh.hist[b] = 0;
+        __syncthreads();
+        for (int base = 0; base < n; base += GT) {
+            const int i = base + threadIdx.x;
+            const uint32_t x = i < n ? v[i] : 0u;
+            hist_add(sh.hist, i < n && (x & mask) == prefix, (int)((x >> shift) & 255u));
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {                              // lane l owns bins 255-4l .. 252-4l (descending)
+            const int lane = threadIdx.x;
+            int c[4], s = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { c[q] = sh.hist[255 - 4 * lane - q]; s += c[q]; }
+            int incl = s;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int y = __shfl_up(incl, o);
+                if (lane >= o) incl += y;
+            }
+            const int excl = incl - s;
+            if (excl < need && incl >= need) {
+                int cum = excl;
+                for (int q = 0; q < 4; ++q) {
+                    if (cum + c[q] >= need) { sh.sel[0] = 255 - 4 * lane - q; sh.sel[1] = need - cum; break; }
+                    cum += c[q];
+                }
+            }
+        }
+        __syncthreads();
+        prefix |= (uint32_t)sh.sel[0] << shift;
+        mask |= 0xFFu << shift;
+        need = sh.sel[1];
+        __syncthreads();
+    }
+    *need_out = need;
+    return prefix;
+}
+
+// Exclusive prefix count of `flag` over the workgroup (thread order); *total = the workgroup's count.
+__device__ __forceinline__ int block_excl_count(bool flag, TopkShared& sh, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(flag);
+    const int pre = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) sh.wsum[w] = __popcll(b);
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int q = 0; q < GT / 64; ++q) { off += q < w ? sh.wsum[q] : 0; tot += sh.wsum[q]; }
+    __syncthreads();
+    *total = tot;
+    return off + pre;
+}
+
+// One workgroup selects the best K of one row's items and writes them sorted (score descending, column ascending).
+//   mode 0: columns [c0, c0 + n) of the row, one item each;
+//   mode 1: groups -- item g = group g, key = the group's best column, column = the lowest column attaining it;
+//   mode 2: the sorted candidate lists of a previous pass (key, column), item order ascending in column among equal keys.
+// Workgroup x: row = x / nblk, block b = x % nblk.  final_out: idx / score [row, K]; else key / column candidates [row, nblk, K].
+__global__ __launch_bounds__(GT) void topk_kernel(const float* sims, int64_t ld, const int32_t* gid, int Nm, int G,
+                                                  const uint32_t* ckey_in, const int32_t* ccol_in, int n_in, int per_block,
+                                                  int K, int mode, int nblk, int32_t* idx_out, float* score_out,
+                                                  uint32_t* ckey_out, int32_t* ccol_out) {
+    extern __shared__ uint32_t v[];
+    __shared__ TopkShared sh;
+    const int64_t row = blockIdx.x / nblk;
+    const int b = blockIdx.x % nblk;
+    const float* s = sims ? sims + row * ld : nullptr;
+    int n, i0 = 0;
+    if (mode == 0) {
+        i0 = b * per_block;
+        n = min(per_block, Nm - i0);
+        for (int i = threadIdx.x; i < n; i += GT) v[i] = score_key(s[i0 + i]);
+    } else if (mode == 1) {
+        n = G;
+        for (int g = threadIdx.x; g < G; g += GT) v[g] = 0u;
+        __syncthreads();
+        for (int j = threadIdx.x; j < Nm; j += GT) {
+            const int g = gid[j];
+            if ((unsigned)g < (unsigned)G) atomicMax(&v[g], score_key(s[j]));
+        }
+    } else {
+        i0 = b * per_block;
+        n = min(per_block, n_in - i0);
+        const uint32_t* kin = ckey_in + row * n_in + i0;
+        for (int i = threadIdx.x; i < n; i += GT) v[i] = kin[i];
+    }
+    if (threadIdx.x == 0) sh.cnt = 0;
+    __syncthreads();
+    const int kk = min(K, n);
+    int m = 0;
+    const uint32_t t = radix_select(v, n, kk, sh, &m);
+    const int32_t* cin = mode == 2 ? ccol_in + row * n_in + i0 : nullptr;
+
+    // items above the threshold (fewer than kk of them), then the m lowest columns among the items AT the threshold
+    if (mode == 1) {
+        for (int g = threadIdx.x; g < G; g += GT) {
+            const uint32_t k = v[g];
+            if (k > t) {
+                const int slot = atomicAdd(&sh.cnt, 1);
+                sh.cand_key[slot] = k; sh.cand_col[slot] = 0x7FFFFFFF; v[g] = (uint32_t)slot;
+            } else {
+                v[g] = (k == t && t != 0u) ? TIE_NONE : SLOT_OUT;
+            }
+        }
+        __syncthreads();
+        for (int j = threadIdx.x; j < Nm; j += GT) {           // representative columns: lowest index attaining the group's maximum
+            const int g = gid[j];
+            if ((unsigned)g >= (unsigned)G) continue;
+            const uint32_t e = v[g];
+            if (e == SLOT_OUT) continue;
+            const uint32_t k = score_key(s[j]);
+            if (e < 256u) { if (k == sh.cand_key[e]) atomicMin(&sh.cand_col[e], j); }
+            else if (k == t) atomicMin(&v[g], TIE + (uint32_t)j);
+        }
+    } else {
+        for (int i = threadIdx.x; i < n; i += GT) {
+            const uint32_t k = v[i];
+            if (k > t) {
+                const int slot = atomicAdd(&sh.cnt, 1);
+                sh.cand_key[slot] = k; sh.cand_col[slot] = mode == 0 ? i0 + i : cin[i];
+            }
+        }
+    }
+    __syncthreads();
+    const int n_above = sh.cnt;
+    int taken = 0;
+    const int want = t != 0u ? kk - n_above : 0;
+    const int scan_n = mode == 1 ? Nm : n;
+    for (int base = 0; base < scan_n && taken < want; base += GT) {     // (uniform: `taken` is the same in every thread)
+        const int i = base + threadIdx.x;
+        bool f = false;
+        if (i < scan_n) {
+            if (mode == 1) { const int g = gid[i]; f = (unsigned)g < (unsigned)G && v[g] == TIE + (uint32_t)i; }
+            else f = v[i] == t;
+        }
+        int tot;
+        const int pos = block_excl_count(f, sh, &tot);
+        if (f && taken + pos < want) {
+            sh.cand_key[n_above + taken + pos] = t;
+            sh.cand_col[n_above + taken + pos] = mode == 2 ? cin[i] : (mode == 0 ? i0 + i : i);
+        }
+        taken += tot;
+    }
+    __syncthreads();
+    const int total = n_above + min(taken, want);
+
+    // rank sort of the (at most 256) candidates; the tail past `total` is filled
+    const int64_t o = (row * nblk + b) * (int64_t)K;
+    if ((int)threadIdx.x < total) {
+        const uint32_t k = sh.cand_key[threadIdx.x];
+        const int c = sh.cand_col[threadIdx.x];
+        int r = 0;
+        for (int q = 0; q < total; ++q) {
+            const uint32_t kq = sh.cand_key[q];
+            r += (kq > k || (kq == k && sh.cand_col[q] < c)) ? 1 : 0;
+        }
+        if (idx_out) { idx_out[o + r] = c; score_out[o + r] = key_score(k); }
+        else { ckey_out[o + r] = k; ccol_out[o + r] = c; }
+    }
+    for (int r = total + threadIdx.x; r < K; r += GT) {
+        if (idx_out) { idx_out[o + r] = -1; score_out[o + r] = -INFINITY; }
+        else { ckey_out[o + r] = 0u; ccol_out[o + r] = -1; }
+    }
+}
+
+}  // namespace
+
+namespace {
+
+// One workgroup per pair: frame tokens, segment tokens (16-byte accesses), the two masks and the two clip vectors.  A pair with
+// an index outside [0, Nv) x [0, Nm) is written as all padding (zeros) and nothing of the inputs is read for it.
+__global__ __launch_bounds__(256) void gather_pairs_kernel(const int32_t* vi, const int32_t* mi, int64_t Nv, int64_t Nm,
+                                                           const uint4* v_tok, int64_t v_tok_s, const float* v_mask, int64_t v_mask_s,
+                                                           const float* v_vec, int64_t v_vec_s,
+                                                           const uint4* m_tok, int64_t m_tok_s, const float* m_mask, int64_t m_mask_s,
+                                                           const float* m_vec, int64_t m_vec_s, int Tv, int Ta, int D, int64_t nv16,
+                                                           int64_t na16, uint4* frame_out, int64_t frame_s, uint4* seg_out, int64_t seg_s,
+                                                           float* fmask_out, float* smask_out, float* video_out, float* music_out) {
+    const int64_t p = blockIdx.x;
+    const int64_t a = vi[p], c = mi[p];
+    const bool ok = a >= 0 && a < Nv && c >= 0 && c < Nm;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    const uint4* vt = v_tok + (ok ? a * v_tok_s : 0);
+    const uint4* mt = m_tok + (ok ? c * m_tok_s : 0);
+    uint4* fo = frame_out + p * frame_s;
+    uint4* so = seg_out + p * seg_s;
+    for (int64_t i = threadIdx.x; i < nv16; i += 256) fo[i] = ok ? vt[i] : z;
+    for (int64_t i = threadIdx.x; i < na16; i += 256) so[i] = ok ? mt[i] : z;
+    for (int i = threadIdx.x; i < Tv; i += 256) fmask_out[p * Tv + i] = ok ? v_mask[a * v_mask_s + i] : 0.f;
+    for (int i = threadIdx.x; i < Ta; i += 256) smask_out[p * Ta + i] = ok ? m_mask[c * m_mask_s + i] : 0.f;
+    for (int i = threadIdx.x; i < D; i += 256) {
+        video_out[p * D + i] = ok ? v_vec[a * v_vec_s + i] : 0.f;
+        music_out[p * D + i] = ok ? m_vec[c * m_vec_s + i] : 0.f;
+    }
+}
+
+int64_t topk_blocks(int64_t Nm) { return (Nm + CAP - 1) / CAP; }
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+}  // namespace
+
+extern "C" int64_t made_topk_groups_ws_bytes(int64_t Nv, int64_t Nm, int64_t K) {
+    if (Nv <= 0 || Nm <= CAP || K < 1 || K > 256) return 0;
+    const int64_t nb0 = topk_blocks(Nm);
+    const int64_t fan = (CAP / K) * K;
+    const int64_t nb1 = (nb0 * K + fan - 1) / fan;
+    return (nb0 + nb1) * Nv * K * 8;
+}
+
+extern "C" int made_topk_groups(const float* sims, int64_t ld, const int32_t* group_id, int64_t Nv, int64_t Nm, int64_t n_groups,
+                                int64_t K, int32_t* idx_out, float* score_out, void* ws, int64_t ws_bytes, void* stream) {
+    MADE_REQUIRE(sims && idx_out && score_out, "made_topk_groups: null pointer");
+    MADE_REQUIRE(Nv >= 0 && Nm > 0 && ld >= Nm, "made_topk_groups: bad dims (Nv >= 0, Nm > 0, ld >= Nm)");
+    MADE_REQUIRE(K >= 1 && K <= 256, "made_topk_groups: K must lie in [1, 256]");
+    MADE_REQUIRE(Nm <= (1LL << 24), "made_topk_groups: at most 2^24 columns");
+    if (group_id) MADE_REQUIRE(n_groups >= 1 && n_groups <= 32768, "made_topk_groups: n_groups must lie in [1, 32768] (LDS table)");
+    const int64_t need = group_id ? 0 : made_topk_groups_ws_bytes(Nv, Nm, K);
+    MADE_REQUIRE(need == 0 || (ws && ws_bytes >= need), "made_topk_groups: workspace of %lld bytes needed", (long long)need);
+    MADE_REQUIRE(Nv * topk_blocks(Nm) < (1LL << 31), "made_topk_groups: too many rows");
+    if (Nv == 0) return MADE_OK;
+    static bool attr_done = false;
+    if (!attr_done) {
+        (void)hipFuncSetAttribute((const void*)topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * 4);
+        attr_done = true;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    if (group_id) {
+        hipLaunchKernelGGL(topk_kernel, dim3((unsigned)Nv), dim3(GT), (size_t)n_groups * 4, st, sims, ld, group_id, (int)Nm, (int)n_groups,
+                           (const uint32_t*)nullptr, (const int32_t*)nullptr, 0, 0, (int)K, 1, 1, idx_out, score_out, (uint32_t*)nullptr,
+                           (int32_t*)nullptr);
+        return made_check_launch("made_topk_groups");
+    }
+    if (Nm <= CAP) {
+        hipLaunchKernelGGL(topk_kernel, dim3((unsigned)Nv), dim3(GT), (size_t)Nm * 4, st, sims, ld, (const int32_t*)nullptr, (int)Nm, 0,
+                           (const uint32_t*)nullptr, (const int32_t*)nullptr, 0, (int)Nm, (int)K, 0, 1, idx_out, score_out,
+                           (uint32_t*)nullptr, (int32_t*)nullptr);
+        return made_check_launch("made_topk_groups");
+    }
+    // long rows: the best K of every block of CAP columns, then passes over the blocks' sorted candidate lists (CAP / K lists per
+    // workgroup) until one list per row is left.  Workspace: lists of pass 0 (nb0 per row) | lists of pass 1 (nb1 per row); later
+    // passes alternate between the two (each has fewer lists than the one before).
+    const int64_t nb0 = topk_blocks(Nm);
+    const int64_t fan = (CAP / K) * K;
+    const int64_t nb1 = (nb0 * K + fan - 1) / fan;
+    char* base = (char*)ws;
+    uint32_t* keys[2] = {(uint32_t*)base, (uint32_t*)(base + nb0 * Nv * K * 8)};
+    int32_t* cols[2] = {(int32_t*)(base + nb0 * Nv * K * 4), (int32_t*)(base + nb0 * Nv * K * 8 + nb1 * Nv * K * 4)};
+    hipLaunchKernelGGL(topk_kernel, dim3((unsigned)(Nv * nb0)), dim3(GT), (size_t)CAP * 4, st, sims, ld, (const int32_t*)nullptr, (int)Nm, 0,
+                       (const uint32_t*)nullptr, (const int32_t*)nullptr, 0, CAP, (int)K, 0, (int)nb0, (int32_t*)nullptr, (float*)nullptr,
+                       keys[0], cols[0]);
+    int64_t nb = nb0;
+    int cur = 0;
+    while (true) {
+        const int64_t n_in = nb * K;
+        const int64_t nxt = (n_in + fan - 1) / fan;
+        const bool last = nxt == 1;
+        hipLaunchKernelGGL(topk_kernel, dim3((unsigned)(Nv * nxt)), dim3(GT), (size_t)min(n_in, fan) * 4, st, (const float*)nullptr, ld,
+                           (const int32_t*)nullptr, (int)Nm, 0, (const uint32_t*)keys[cur], (const int32_t*)cols[cur], (int)n_in, (int)fan,
+                           (int)K, 2, (int)nxt, last ? idx_out : (int32_t*)nullptr, last ? score_out : (float*)nullptr,
+                           last ? (uint32_t*)nullptr : keys[cur ^ 1], last ? (int32_t*)nullptr : cols[cur ^ 1]);
+        if (last) break;
+        nb = nxt;
+        cur ^= 1;
+    }
+    return made_check_launch("made_topk_groups");
+}
+
+extern "C" int made_gather_pairs(const int32_t* vi, const int32_t* mi, int64_t P, int64_t Nv, int64_t Nm,
+                                 const void* v_tok, int64_t v_tok_stride, const float* v_mask, int64_t v_mask_stride,
+                                 const float* v_vec, int64_t v_vec_stride,
+                                 const void* m_tok, int64_t m_tok_stride, const float* m_mask, int64_t m_mask_stride,
+                                 const float* m_vec, int64_t m_vec_stride, int64_t Tv, int64_t Ta, int64_t D, int32_t dtype,
+                                 void* frame_out, int64_t frame_out_stride, void* seg_out, int64_t seg_out_stride,
+                                 float* fmask_out, float* smask_out, float* video_out, float* music_out, void* stream) {
+    MADE_REQUIRE(vi && mi && v_tok && v_mask && v_vec && m_tok && m_mask && m_vec && frame_out && seg_out && fmask_out && smask_out &&
+                 video_out && music_out, "made_gather_pairs: null pointer");
+    MADE_REQUIRE(dtype == MADE_F32 || dtype == MADE_BF16, "made_gather_pairs: dtype must be MADE_F32 or MADE_BF16");
+    MADE_REQUIRE(P >= 0 && Nv >= 0 && Nm >= 0 && Tv >= 1 && Ta >= 1 && D >= 1 && P < (1LL << 31), "made_gather_pairs: bad dims");
+    const int64_t esz = dtype == MADE_F32 ? 4 : 2;
+    MADE_REQUIRE(v_tok_stride >= Tv * D && m_tok_stride >= Ta * D && frame_out_stride >= Tv * D && seg_out_stride >= Ta * D &&
+                 v_mask_stride >= Tv && m_mask_stride >= Ta && v_vec_stride >= D && m_vec_stride >= D,
+                 "made_gather_pairs: a per-item stride is shorter than the item");
+    MADE_REQUIRE((D * esz) % 16 == 0 && (v_tok_stride * esz) % 16 == 0 && (m_tok_stride * esz) % 16 == 0 &&
+                 (frame_out_stride * esz) % 16 == 0 && (seg_out_stride * esz) % 16 == 0 && aligned16(v_tok) && aligned16(m_tok) &&
+                 aligned16(frame_out) && aligned16(seg_out), "made_gather_pairs: token rows and strides must be 16-byte aligned");
+    if (P == 0) return MADE_OK;
+    const int64_t s16 = 16 / esz;
+    hipLaunchKernelGGL(gather_pairs_kernel, dim3((unsigned)P), dim3(256), 0, (hipStream_t)stream, vi, mi, Nv, Nm,
+                       (const uint4*)v_tok, v_tok_stride / s16, v_mask, v_mask_stride, v_vec, v_vec_stride,
+                       (const uint4*)m_tok, m_tok_stride / s16, m_mask, m_mask_stride, m_vec, m_vec_stride, (int)Tv, (int)Ta, (int)D,
+                       Tv * D / s16, Ta * D / s16, (uint4*)frame_out, frame_out_stride / s16, (uint4*)seg_out, seg_out_stride / s16,
+                       fmask_out, smask_out, video_out, music_out);
+    return made_check_launch("made_gather_pairs");
+}

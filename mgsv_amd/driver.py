@@ -22,7 +22,7 @@ import os
 import random
 import sys
 import time
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -68,7 +68,8 @@ TEST_DROPS = {"matching_lr", "detection_lr"}                  # the test parser 
 # additions of this build (not in the reference)
 EXTRA = [("synthetic_features", int, 0, None), ("max_samples", int, 0, None), ("compute_dtype", str, "bf16", ["bf16", "f32"]),
          ("fused_step", int, 1, None),
-         ("eval_in_flight", int, 2, None)]                    # evaluation: independent batches in flight (engine workspace + stream each)
+         ("eval_in_flight", int, 2, None),                    # evaluation: independent batches in flight (engine workspace + stream each)
+         ("ground_topk", int, 0, None)]                       # evaluation: > 0 also grounds every video in the split's tracks (top k + moment)
 
 
 def build_parser(for_test: bool = False) -> argparse.ArgumentParser:
@@ -337,13 +338,18 @@ def train_one_epoch(epoch, args, model, loader, optimizer, device, dist, logger,
 
 
 @torch.no_grad()
-def eval_epoch(epoch, args, model, loader, device, dist, logger):
+def eval_epoch(epoch, args, model, loader, device, dist, logger, split: str = "val", ground_out: Optional[dict] = None):
     """reference train-MaDe.py:430-625 / test-MaDe.py:255-470: per-batch forward, then the all-pairs similarity matrix
-    (X-Pool + dual tower), de-duplicated recall, span IoU and the composite metrics -- all but the final scalars on the GPU."""
+    (X-Pool + dual tower), de-duplicated recall, span IoU and the composite metrics -- all but the final scalars on the GPU.
+    --ground_topk k > 0: every video is also grounded in the split's tracks (mgsv_amd/grounding.py); the grounded recall
+    GR{1,5,10}_iou{0.5,0.7} is logged and stored in `ground_out`, the results go to <path_log>/ground_<split>_<epoch>.json."""
+    from .grounding import similarity_matrix
     from .utils.util_test import Composite_metrics, IoU_metrics, Recall_metrics, detr_iou_device
     model.eval()
     t0 = time.time()
     vids, mids, V, M, S, SM, IOU = [], [], [], [], [], [], []
+    k_ground = int(getattr(args, "ground_topk", 0) or 0)
+    GF, GFM, GVD, GMD, GGT = [], [], [], [], []                 # (--ground_topk) frame tokens, frame masks, durations, moments
     # Batches are independent: keep `eval_in_flight` of them in flight, each on its own HIP stream with its own engine workspace
     # (one batch's decoder, a chain of dependent launches, then runs beside the next batch's encoders), and read nothing back
     # until the loop is over: the loss is accumulated on the device.
@@ -365,16 +371,15 @@ def eval_epoch(epoch, args, model, loader, device, dist, logger):
             vids.extend(meta_map["video_id"]); mids.extend(meta_map["music_id"])
             iou = _batch_iou(args, model, om, meta_map, device)
             IOU.append(iou)
+            if k_ground > 0:                                   # (feat_map holds f32 copies of compute-dtype tokens: the cast back is exact)
+                GF.append(feat["frame_feats"].to(model._engine_ready().tc, copy=True)); GFM.append(fm); GVD.append(vdur)
+                GMD.append(meta_map["m_duration"].to(device, torch.float32))
+                GGT.append(meta_map["gt_moment"].to(device, torch.float32).reshape(ff.shape[0], -1)[:, :2])
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     loss_sum = float(sum(loss_acc))
     video, music, seg, segm, iou = torch.cat(V), torch.cat(M), torch.cat(S), torch.cat(SM), torch.cat(IOU)
-    if "XA" not in args.vmr_fusion or args.vmr_loss == "dual":
-        sim = model._engine_ready().dual_sims(video, music)
-    elif args.vmr_loss == "single":
-        sim = model._engine_ready().xpool_sims(video, seg.to(model._engine_ready().tc), segm if args.fusion_mask == 1 else None)
-    else:
-        sim = model.retrieval_sim_matrix(video, seg, segm, music)
+    sim = similarity_matrix(model._engine_ready(), video, seg, segm, music)
     ret_metrics, ranks, _ = Recall_metrics(sim, dedup=True, all_music_ids_list=mids)
     iou_list = iou.cpu().tolist()
     loc_metrics = IoU_metrics(iou_list)
@@ -386,8 +391,45 @@ def eval_epoch(epoch, args, model, loader, device, dist, logger):
         logger.info(f"Music Moment Localization Eval >>> mIoU: {loc_metrics['mIoU']:.4f} - IoU0.5: {loc_metrics['IoU@0.5']:.2f} - IoU0.7: {loc_metrics['IoU@0.7']:.2f}")
         logger.info(f"Composite Eval >> IoU0.5 - R1: {com_metrics['R1_iou0.5']:.2f} - R10: {com_metrics['R10_iou0.5']:.2f} - R100: {com_metrics['R100_iou0.5']:.2f}"
                     f" >> IoU0.7 - R1: {com_metrics['R1_iou0.7']:.2f} - R10: {com_metrics['R10_iou0.7']:.2f} - R100: {com_metrics['R100_iou0.7']:.2f}")
+    if k_ground > 0:
+        gm = _ground_split(args, model, k_ground, sim, video, music, seg, segm, GF, GFM, GVD, GMD, GGT, vids, mids, split, epoch, logger)
+        if ground_out is not None:
+            ground_out.update(gm)
+    if args.rank == 0:
         logger.info(f"Eval takes {datetime.timedelta(seconds=int(time.time() - t0))} ({n} pairs)")
     return loss_sum / max(n, 1), ret_metrics, loc_metrics, com_metrics
+
+
+def _ground_split(args, model, k, sim, video, music, seg, segm, GF, GFM, GVD, GMD, GGT, vids, mids, split, epoch, logger) -> dict:
+    """--ground_topk: every video of the split against the split's tracks (groups = music ids, as the de-duplicated recall), on the
+    similarity matrix the evaluation has just ranked with.  Returns the grounded recall."""
+    import json
+    from .engine import Encoded
+    from .grounding import ground, grounded_recall, moment_iou
+    eng = model._engine_ready()
+    lut: Dict[str, int] = {}
+    gid = [lut.setdefault(m, len(lut)) for m in mids]
+    m_dur, gt = torch.cat(GMD), torch.cat(GGT)
+    videos = Encoded(tokens=torch.cat(GF), mask=torch.cat(GFM).contiguous(), vec=video, duration=torch.cat(GVD))
+    tracks = Encoded(tokens=seg.to(eng.tc), mask=segm.contiguous(), vec=music, duration=m_dur)
+    g = ground(eng, videos, tracks, k, sims=sim, group_id=gid)
+    iou = moment_iou(g.start, g.end, gt, m_dur, float(args.max_m_duration))
+    tr = g.track.cpu().numpy()
+    gid_np = np.asarray(gid, dtype=np.int64)
+    tg = np.where(tr >= 0, gid_np[np.maximum(tr, 0)], -1)
+    metrics = grounded_recall(tg, gid_np, iou.cpu().numpy())
+    if args.rank == 0:
+        logger.info("Grounding Eval (top %d) >> " % g.k + " - ".join(f"{key}: {v:.2f}" for key, v in metrics.items()))
+        recs = g.to_records(vids, mids)
+        gts = gt.cpu().numpy()
+        for r, mid, m in zip(recs, mids, gts):
+            r["music_id"] = mid
+            r["gt_moment"] = [float(m[0]), float(m[1])]
+            r["tracks"] = r.pop("tracks")
+        os.makedirs(args.path_log, exist_ok=True)
+        with open(os.path.join(args.path_log, f"ground_{split}_{epoch}.json"), "w") as f:
+            json.dump(recs, f)
+    return metrics
 
 
 def main_train(argv=None):
@@ -418,9 +460,12 @@ def main_train(argv=None):
                 sampler.set_epoch(epoch)
             tl, tm = train_one_epoch(epoch, args, model, train_loader, optimizer, device, dist, logger, total_step, warmup_steps)
             logger.info(f"Epoch {epoch}/{args.epochs} Finished, Train Loss: {tl:.4f}, train mIoU {tm['mIoU']:.4f}")
-            vl, ret, loc, com = eval_epoch(epoch, args, model, val_loader, device, dist, logger)
+            gr: dict = {}
+            vl, ret, loc, com = eval_epoch(epoch, args, model, val_loader, device, dist, logger, split="val", ground_out=gr)
             results[epoch] = dict(train_loss=tl, val_loss=vl, R1=ret["R1"], mIoU=loc["mIoU"], R5=ret["R5"], R1_iou05=com["R1_iou0.5"],
                                   R1_iou07=com["R1_iou0.7"])
+            if args.ground_topk > 0:
+                results[epoch]["ground"] = gr
             if args.rank == 0:
                 now = {"R1": ret["R1"], "mIoU": loc["mIoU"], "R1_iou0.5": com["R1_iou0.5"], "R1_iou0.7": com["R1_iou0.7"]}
                 for key, b in best.items():
@@ -431,8 +476,11 @@ def main_train(argv=None):
                             best["R1"]["v"], best["R1"]["epoch"], best["mIoU"]["v"], best["mIoU"]["epoch"], best["R1_iou0.5"]["v"],
                             best["R1_iou0.5"]["epoch"], best["R1_iou0.7"]["v"], best["R1_iou0.7"]["epoch"])
     elif args.do_eval:
-        vl, ret, loc, com = eval_epoch(0, args, model, val_loader, device, dist, logger)
+        gr = {}
+        vl, ret, loc, com = eval_epoch(0, args, model, val_loader, device, dist, logger, split="val", ground_out=gr)
         results[0] = dict(val_loss=vl, R1=ret["R1"], mIoU=loc["mIoU"])
+        if args.ground_topk > 0:
+            results[0]["ground"] = gr
     if dist is not None:
         dist.barrier(); dist.destroy_process_group()
     return results
@@ -451,16 +499,22 @@ def main_test(argv=None):
 
     def run(path, tag):
         _, epoch, _ = load_model(args, logger, model, path)
-        vl, ret, loc, com = eval_epoch(epoch, args, model, loader, device, dist, logger)
+        gr: dict = {}
+        vl, ret, loc, com = eval_epoch(epoch, args, model, loader, device, dist, logger, split="test", ground_out=gr)
         out[tag] = dict(loss=vl, ret=ret, loc=loc, com=com, epoch=epoch)
+        if args.ground_topk > 0:
+            out[tag]["ground"] = gr
         return out[tag]
 
     path = args.load_uni_model_path
     if path == "":
         # the reference does nothing without a checkpoint; scoring fresh weights is only useful as a plumbing check -- say so loudly
         logger.warning("test: no --load_uni_model_path given -- evaluating FRESHLY INITIALISED weights (plumbing check only)")
-        vl, ret, loc, com = eval_epoch(0, args, model, loader, device, dist, logger)
+        gr = {}
+        vl, ret, loc, com = eval_epoch(0, args, model, loader, device, dist, logger, split="test", ground_out=gr)
         out.update(loss=vl, ret=ret, loc=loc, com=com)
+        if args.ground_topk > 0:
+            out["ground"] = gr
     elif os.path.basename(path).split(".")[0] == "pytorch_model" and not os.path.isdir(path):
         out.update(run(path, os.path.basename(path)))
     elif args.test_best == 1:

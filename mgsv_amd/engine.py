@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import math
 import os
+from dataclasses import dataclass
 from typing import Dict, Optional
 
 import numpy as np
@@ -30,6 +31,19 @@ from .config import MadeConfig
 from .ops import Seg, round_up
 
 Tensor = torch.Tensor
+
+
+@dataclass
+class Encoded:
+    """Per-item tower outputs (MadeEngine.encode_videos / encode_music): tokens [N, T, D] in the compute dtype (any item stride,
+    contiguous rows), mask [N, T] f32, vec [N, D] f32 (the L2-normalised clip / track vector), duration [N] f32 seconds or None."""
+    tokens: Tensor
+    mask: Tensor
+    vec: Tensor
+    duration: Optional[Tensor] = None
+
+    def __len__(self) -> int:
+        return self.tokens.shape[0]
 
 
 class MadeEngine:
@@ -304,8 +318,10 @@ class MadeEngine:
                       q_skip_mask=key_mask if skip is not None else None, order=order)
         return att
 
-    def _encode(self, feats: Tensor, mask: Tensor, which: str, wsall: Dict[str, Tensor], row_off: int, rows=None, order=None) -> None:
-        """reference model/model_Base.py:544-617 -> writes fus[:, row_off:row_off+T] and mean/normalised vector."""
+    def _encode(self, feats: Tensor, mask: Tensor, which: str, wsall: Dict[str, Tensor], row_off: int, rows=None, order=None,
+                out: Optional[tuple] = None) -> None:
+        """reference model/model_Base.py:544-617 -> writes fus[:, row_off:row_off+T] and mean/normalised vector.
+        out = (tokens [B, T, D] view with contiguous rows, vector [B, D] f32): write there instead (encode_videos / encode_music)."""
         c, P = self.cfg, self.P
         ws = wsall if which == "audio" else {**wsall, **{k[2:]: v for k, v in wsall.items() if k.startswith("v_")}}
         B, T, Kin = feats.shape
@@ -315,11 +331,15 @@ class MadeEngine:
         nrow = B * T
         mflat = mask.reshape(-1)
         act = ops.ACT_QUICKGELU if c.with_act_after_proj else ops.ACT_NONE
-        if "concat" in c.mml_fusion:
+        if out is not None:
+            local = out[0]
+        elif "concat" in c.mml_fusion:
             local = ws["fus"][:, row_off:row_off + T]                   # [B, T, D] view
         else:
             local = ws["frame_buf"] if which == "video" else ws["seg_buf"]
         mean, vec = (ws["vmean"], ws["video"]) if which == "video" else (ws["mmean"], ws["music"])
+        if out is not None:
+            vec = out[1]
         if c.agg_module == "mlp":
             return self._encode_mlp(feats, mask, which, ws, local, mean, vec)
         if c.with_cls_token:
@@ -661,6 +681,22 @@ class MadeEngine:
         if with_losses:
             out["retrieval_loss"] = ws["ret_loss"]
 
+        return self._localize(ws, out, B, Tv, Ta, fm, sm, video, music, frame, pos, rows_f, order_f, dec_early, pooled, spans_target,
+                              v_duration, with_losses, cur, side)
+
+    def _localize(self, ws, out: Dict[str, Tensor], B: int, Tv: int, Ta: int, fm: Tensor, sm: Tensor, video: Tensor, music: Tensor,
+                  frame: Tensor, pos: Tensor, rows_f, order_f: Tensor, dec_early, pooled: Optional[Tensor], spans_target: Optional[Tensor],
+                  v_duration: Optional[Tensor], with_losses: bool, cur, side) -> Dict[str, Tensor]:
+        """Everything after the towers and the fusion (K8-K14): DETR encoder, decoder, heads and (with_losses) matcher + criterion,
+        on the fused input ws["fus"] / ws["fus_mask"].  Shared by `forward` and `localize_pairs`.  dec_early: the event of decoder
+        layer 0's query side when it already ran beside the encoder (forward's side stream), else None."""
+        c, P = self.cfg, self.P
+        regression = "regression" in c.mml_localization
+        concat = "concat" in c.mml_fusion
+        D, L, Q, nd = c.D, (Tv + Ta if concat else Ta), c.num_moment_queries, c.detr_dec_layers
+        H = c.detr_nheads
+        fus, fus_mask = ws["fus"], ws["fus_mask"]
+
         # ---- DETR encoder (K8, K9)
         rows = B * L
         src = fus.view(rows, D)
@@ -849,6 +885,102 @@ class MadeEngine:
                    matcher_status=status, criterion_losses=losses, localization_loss=total)
         cur.wait_stream(side)
         return out
+
+    # ------------------------------------------------------------------ grounding: towers once per item, localization per pair
+    @torch.no_grad()
+    def encode_videos(self, frame_feats: Tensor, frame_masks: Tensor, v_duration: Optional[Tensor] = None, batch: int = 64) -> "Encoded":
+        """The video temporal tower only (no X-Pool, no DETR) over [N, T_v, vit_dim] features, `batch` items per launch sequence."""
+        return self._encode_items(frame_feats, frame_masks, v_duration, "video", batch)
+
+    @torch.no_grad()
+    def encode_music(self, segment_feats: Tensor, segment_masks: Tensor, m_duration: Optional[Tensor] = None, batch: int = 64) -> "Encoded":
+        """The music temporal tower only over [N, T_a, ast_dim] features."""
+        return self._encode_items(segment_feats, segment_masks, m_duration, "audio", batch)
+
+    def _encode_items(self, feats: Tensor, masks: Tensor, duration: Optional[Tensor], which: str, batch: int) -> "Encoded":
+        self._set_products()
+        dev, D = self.device, self.cfg.D
+        N, T, _ = feats.shape
+        feats = feats.to(dev, torch.float32).contiguous()
+        masks = masks.to(dev, torch.float32).contiguous()
+        rec = Encoded(tokens=torch.empty(N, T, D, device=dev, dtype=self.tc), mask=masks,
+                      vec=torch.empty(N, D, device=dev, dtype=torch.float32),
+                      duration=duration.to(dev, torch.float32).contiguous() if duration is not None else None)
+        for n0 in range(0, N, batch):
+            B = min(batch, N - n0)
+            m = masks[n0:n0 + B]
+            if which == "video":
+                ws = self._buffers(B, T, 1)
+                rows, order = ops.row_index(m, out=ws["rows_v"]), ops.batch_order(m, out=ws["order_v"])
+            else:
+                ws = self._buffers(B, 1, T)
+                rows, order = ops.row_index(m, out=ws["rows_a"]), ops.batch_order(m, out=ws["order_a"])
+            self._encode(feats[n0:n0 + B], m, which, ws, 0, rows=rows, order=order, out=(rec.tokens[n0:n0 + B], rec.vec[n0:n0 + B]))
+        return rec
+
+    def _localize_chunks(self, videos: "Encoded", music: "Encoded", vi: Tensor, mi: Tensor, pair_batch: int):
+        """Yields (p0, n, out) per batch of pairs: out["pred_logits"] / out["pred_spans"] of pairs p0 .. p0+n-1 are views into the
+        engine's workspace, valid until the next batch is launched.  A short last batch is padded with copies of its last pair
+        (pairs are independent: the padding changes no other pair's result) so that every batch uses the same workspace."""
+        c = self.cfg
+        if c.moment_query_type == "xpool":
+            raise NotImplementedError("moment_query_type=xpool: the decoder query is the track's pooled vector averaged over the videos of "
+                                      "the batch (reference model/model_Uni.py:222-223), a property of the batch with no per-pair meaning")
+        if c.predict_center == 1 and videos.duration is None:
+            raise ValueError("predict_center=1 needs the videos' durations (encode_videos(..., v_duration=...))")
+        self._set_products()
+        dev = self.device
+        vi = torch.as_tensor(vi).to(dev, torch.int32).reshape(-1).contiguous()
+        mi = torch.as_tensor(mi).to(dev, torch.int32).reshape(-1).contiguous()
+        P = vi.numel()
+        assert mi.numel() == P and videos.tokens.dtype == music.tokens.dtype == self.tc
+        if P == 0:
+            return
+        B = max(1, min(pair_batch, P))
+        if P % B:
+            pad = B - P % B
+            vi = torch.cat([vi, vi[-1:].expand(pad)]).contiguous()
+            mi = torch.cat([mi, mi[-1:].expand(pad)]).contiguous()
+        Tv, Ta = videos.tokens.shape[1], music.tokens.shape[1]
+        concat = "concat" in c.mml_fusion
+        ws = self._buffers(B, Tv, Ta)
+        if "pair_fm" not in ws:
+            ws["pair_fm"] = torch.empty(B, Tv, device=dev, dtype=torch.float32)
+            ws["pair_sm"] = torch.empty(B, Ta, device=dev, dtype=torch.float32)
+        fm, sm, fus, fus_mask = ws["pair_fm"], ws["pair_sm"], ws["fus"], ws["fus_mask"]
+        video, music_v = ws["video"], ws["music"]
+        frame, seg = (fus[:, :Tv], fus[:, Tv:]) if concat else (ws["frame_buf"], ws["seg_buf"])
+        cur = torch.cuda.current_stream()
+        for p0 in range(0, P, B):
+            ops.gather_pairs(vi[p0:p0 + B], mi[p0:p0 + B], videos.tokens, videos.mask, videos.vec, music.tokens, music.mask, music.vec,
+                             frame, seg, fm, sm, video, music_v)
+            ops.concat_cols(fm if concat else None, sm, fus_mask)
+            pos = ops.sine_pe(fus_mask, self.P["dim_t"], out=ws["pos"])
+            rows_f = ops.row_index(fus_mask, out=ws["rows_f"])
+            order_f = ops.batch_order(fus_mask, out=ws["order_f"])
+            if not concat:
+                self._ca_fusion(ws, frame, seg, fm, sm, B, Tv, Ta)
+            vdur = videos.duration[vi[p0:p0 + B].long()] if c.predict_center == 1 else None
+            out: Dict[str, Tensor] = dict(video_feats=video, music_feats=music_v, frame_feats=frame, segment_feats=seg)
+            out = self._localize(ws, out, B, Tv, Ta, fm, sm, video, music_v, frame, pos, rows_f, order_f, None, None, None, vdur,
+                                 False, cur, cur)
+            yield p0, min(B, P - p0), out
+
+    @torch.no_grad()
+    def localize_pairs(self, videos: "Encoded", music: "Encoded", vi, mi, pair_batch: int = 64) -> Dict[str, Optional[Tensor]]:
+        """Moment localization of arbitrary (video vi[p], track mi[p]) pairs from per-item tower outputs (encode_videos /
+        encode_music): per batch of pairs one made_gather_pairs, then the eval path after the towers (fusion, DETR, heads) -- no
+        X-Pool, no losses.  Returns pred_logits [P, Q, 2] (None for the regression head) and pred_spans [P, Q, 2] f32."""
+        c = self.cfg
+        P = int(torch.as_tensor(vi).numel())
+        Q = 1 if "regression" in c.mml_localization else c.num_moment_queries
+        logits = None if "regression" in c.mml_localization else torch.empty(P, Q, 2, device=self.device, dtype=torch.float32)
+        spans = torch.empty(P, Q, 2, device=self.device, dtype=torch.float32)
+        for p0, n, out in self._localize_chunks(videos, music, vi, mi, pair_batch):
+            if logits is not None:
+                logits[p0:p0 + n].copy_(out["pred_logits"][:n])
+            spans[p0:p0 + n].copy_(out["pred_spans"][:n])
+        return dict(pred_logits=logits, pred_spans=spans)
 
     def _skinny(self, ws, A: Tensor, wkey: str, **kw):
         """Linear on the B*Q decoder rows: K split over workgroups so the launch fills the chip."""

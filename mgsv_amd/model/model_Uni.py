@@ -332,3 +332,23 @@ class Uni_model(nn.Module):
         return eng.retrieval_sim_matrix(video_embeds.to(dev, torch.float32).contiguous(), segment_embeds.to(dev).contiguous(),
                                         segment_masks.to(dev, torch.float32).contiguous(),
                                         music_embeds.to(dev, torch.float32).contiguous())
+
+    # ---- grounding (mgsv_amd/grounding.py): each video's best k tracks and the moment in each
+    @torch.no_grad()
+    def ground(self, frame_feats, frame_masks, video_feats, segment_feats, segment_masks, music_feats, k: int, v_duration=None,
+               m_duration=None, sims=None, group_id=None, pair_batch: int = 64):
+        """Tower outputs as this module's forward returns them (feat_map["frame_feats"] / ["video_feats"] with mask_map["frame_masks"]
+        for the videos, feat_map["segment_feats"] / ["music_feats"] with mask_map["segment_masks"] for the tracks; any device, f32 or
+        the compute dtype) -> grounding.Grounding with device tensors [N_v, k].  group_id [N_m]: columns sharing a music id."""
+        from ..engine import Encoded
+        from ..grounding import ground
+        eng = self._engine_ready()
+        dev, f32 = eng.device, torch.float32
+
+        def rec(tok, mask, vec, dur):
+            return Encoded(tokens=tok.to(dev, eng.tc).contiguous(), mask=mask.to(dev, f32).contiguous(), vec=vec.to(dev, f32).contiguous(),
+                           duration=dur.to(dev, f32).contiguous() if torch.is_tensor(dur) else None)
+
+        return ground(eng, rec(frame_feats, frame_masks, video_feats, v_duration), rec(segment_feats, segment_masks, music_feats, m_duration),
+                      k, sims=sims, group_id=group_id, pair_batch=pair_batch)
+

@@ -803,3 +803,55 @@ def set_criterion(pred_logits: Tensor, pred_spans: Tensor, targets: Tensor, pred
                                    _p(_f32(empty_weight, "empty_weight")), nl, B, Q, G, Dc, fg_label, temperature,
                                    _p(_f32(weights, "weights")), _p(losses), _p(total), _stream()), "made_set_criterion")
     return losses, total
+
+
+def topk_groups_ws_bytes(Nv: int, Nm: int, K: int) -> int:
+    return int(lib().made_topk_groups_ws_bytes(Nv, Nm, K))
+
+
+def topk_groups(sims: Tensor, K: int, group_id: Optional[Tensor] = None, n_groups: Optional[int] = None,
+                idx: Optional[Tensor] = None, score: Optional[Tensor] = None, ws: Optional[Tensor] = None):
+    """made_topk_groups: the best K groups of every row of sims [Nv, Nm] f32 (unit column stride) -> (idx [Nv, K] int32 representative
+    columns, score [Nv, K] f32), score descending then column ascending; -1 / -inf past the number of groups.  group_id [Nm] int32
+    (None: every column is its own group) with ids in [0, n_groups) (default: group_id.max() + 1, one host read)."""
+    assert sims.dim() == 2 and sims.dtype == torch.float32 and sims.stride(1) == 1
+    Nv, Nm = sims.shape
+    dev = sims.device
+    G = 0
+    if group_id is not None:
+        assert group_id.dtype == torch.int32 and group_id.is_contiguous() and group_id.numel() == Nm
+        G = int(group_id.max()) + 1 if n_groups is None else int(n_groups)
+    if idx is None:
+        idx = torch.empty(Nv, K, device=dev, dtype=torch.int32)
+    if score is None:
+        score = torch.empty(Nv, K, device=dev, dtype=torch.float32)
+    assert idx.is_contiguous() and score.is_contiguous() and idx.shape == (Nv, K) and score.shape == (Nv, K)
+    need = topk_groups_ws_bytes(Nv, Nm, K) if group_id is None and 1 <= K <= 256 else 0
+    if need and (ws is None or ws.numel() * ws.element_size() < need):
+        ws = torch.empty(need, device=dev, dtype=torch.uint8)
+    check(lib().made_topk_groups(_p(sims), sims.stride(0), _p(group_id), Nv, Nm, G, K, _p(idx), _p(score),
+                                 _p(ws) if need else None, need, _stream()), "made_topk_groups")
+    return idx, score
+
+
+def gather_pairs(vi: Tensor, mi: Tensor, v_tok: Tensor, v_mask: Tensor, v_vec: Tensor, m_tok: Tensor, m_mask: Tensor, m_vec: Tensor,
+                 frame_out: Tensor, seg_out: Tensor, fmask_out: Tensor, smask_out: Tensor, video_out: Tensor, music_out: Tensor) -> None:
+    """made_gather_pairs: the localization batch of the pairs (vi[p], mi[p]) from per-item tower outputs.  v_tok [Nv, Tv, D] / m_tok
+    [Nm, Ta, D] (compute dtype, any item stride, contiguous rows), masks [N, T] and vectors [N, D] f32 (unit inner stride); outputs
+    frame_out [P, Tv, D] / seg_out [P, Ta, D] (any pair stride, contiguous rows), masks [P, T] and vectors [P, D] contiguous f32."""
+    P = vi.numel()
+    Nv, Tv, D = v_tok.shape
+    Nm, Ta, _ = m_tok.shape
+    assert vi.dtype == mi.dtype == torch.int32 and vi.is_contiguous() and mi.is_contiguous() and mi.numel() == P
+    assert v_tok.dtype == m_tok.dtype == frame_out.dtype == seg_out.dtype
+    for t in (v_tok, m_tok, frame_out, seg_out):
+        assert t.stride(2) == 1 and t.stride(1) == D, "token rows must be contiguous"
+    for t in (v_mask, m_mask, v_vec, m_vec):
+        assert t.dtype == torch.float32 and t.stride(1) == 1
+    for t in (fmask_out, smask_out, video_out, music_out):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert frame_out.shape == (P, Tv, D) and seg_out.shape == (P, Ta, D) and fmask_out.shape == (P, Tv) and smask_out.shape == (P, Ta)
+    check(lib().made_gather_pairs(_p(vi), _p(mi), P, Nv, Nm, _p(v_tok), v_tok.stride(0), _p(v_mask), v_mask.stride(0), _p(v_vec), v_vec.stride(0),
+                                  _p(m_tok), m_tok.stride(0), _p(m_mask), m_mask.stride(0), _p(m_vec), m_vec.stride(0), Tv, Ta, D, dt_of(v_tok),
+                                  _p(frame_out), frame_out.stride(0), _p(seg_out), seg_out.stride(0), _p(fmask_out), _p(smask_out),
+                                  _p(video_out), _p(music_out), _stream()), "made_gather_pairs")
