@@ -969,6 +969,37 @@ int made_gather_pairs(const int32_t* vi, const int32_t* mi, int64_t P, int64_t N
                       void* frame_out, int64_t frame_out_stride, void* seg_out, int64_t seg_out_stride,
                       float* fmask_out, float* smask_out, float* video_out, float* music_out, void* stream);
 
+/* ==========================================================================================
+ * Frames: decoded video frames -> the input of the CLIP ViT-B/32 visual tower (mgsv_amd/frames.py).  The reference extracts its
+ * frame features with OpenAI's clip package (model/model_Base.py:286-289,406-450) after torchvision preprocessing
+ * (dataloaders/dataloader_MGSV_EC_rawdata.py:16-25); the tower itself runs on made_linear / made_layernorm / made_attention.
+ * ========================================================================================== */
+
+#define MADE_FRAMES_MAX (1 << 20)      /* most frames one made_frames_preprocess call takes */
+
+/* One frame of the packed input.  The coefficient block at coef[coef ..] holds 224 rows of (first input column, tap count, kh
+ * int32 taps) for the crop's output columns, then 224 rows of (first input row, tap count, kv taps) for its output rows: PIL's
+ * bicubic taps in 22-bit fixed point, computed on the host (mgsv_amd/frames.py pil_taps) with the centre crop folded in.  A pass
+ * PIL skips (that side is already 224) is one tap of 1 << 22 at the cropped position. */
+typedef struct MadeFrameDesc {
+    int64_t offset;        /* byte offset of the frame's first pixel in `frames` (RGB, 3 bytes per pixel, rows of 3 W bytes) */
+    int64_t coef;          /* index (int32 elements) of the frame's coefficient block */
+    int32_t H, W;          /* input rows and columns */
+    int32_t kh, kv;        /* taps per row of the horizontal / vertical block, 1 .. 255 */
+} MadeFrameDesc;
+
+/* made_frames_preprocess: torchvision Resize(224, BICUBIC) + CenterCrop(224) + ToTensor + Normalize(CLIP mean, std) of n_frames
+ * frames of any and mixed sizes, in one launch (a workgroup per frame and band of 16 output rows; the horizontal pass through
+ * LDS, integer arithmetic as PIL's, so the crop is bit-exact).  desc [n_frames] and coef [n_coef] are device arrays.  Writes the
+ * 49 patch rows of every frame: patches[(f * 49 + p) * ld_patch + c * 1024 + y * 32 + x] = (u / 255 - mean_c) / std_c (f32, one
+ * rounding per operation) for pixel (y, x) of patch p = 7 * patch row + patch column, channel c -- the A operand of conv1
+ * (conv1.weight.reshape(768, 3072)); patch_dtype MADE_F32 or MADE_BF16 (rounded from that f32 value).  crop_out (may be NULL):
+ * the uint8 crop [n_frames, 224, 224, 3].  Reads stay inside each frame and block; a descriptor that does not fit frames_bytes /
+ * n_coef gives NaN patch rows and a zero crop. */
+int made_frames_preprocess(const uint8_t* frames, int64_t frames_bytes, const MadeFrameDesc* desc, int64_t n_frames,
+                           const int32_t* coef, int64_t n_coef, void* patches, int32_t patch_dtype, int64_t ld_patch,
+                           uint8_t* crop_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,10 @@ class MadeRepackDesc(C.Structure):
                 ("dtype", i32), ("_pad", i32)]
 
 
+class MadeFrameDesc(C.Structure):
+    _fields_ = [("offset", i64), ("coef", i64), ("H", i32), ("W", i32), ("kh", i32), ("kv", i32)]
+
+
 # name -> (restype, argtypes); every symbol include/made_hip.h declares
 SIGNATURES = {
     "made_abi_version": (C.c_int, []),
@@ -281,6 +285,7 @@ SIGNATURES = {
     "made_topk_groups": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, i64, vp]),
     "made_gather_pairs": (C.c_int, [vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32,
                                     vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+    "made_frames_preprocess": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i32, i64, vp, vp]),
 }
 
 _lib = None

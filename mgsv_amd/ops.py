@@ -855,3 +855,19 @@ def gather_pairs(vi: Tensor, mi: Tensor, v_tok: Tensor, v_mask: Tensor, v_vec: T
                                   _p(m_tok), m_tok.stride(0), _p(m_mask), m_mask.stride(0), _p(m_vec), m_vec.stride(0), Tv, Ta, D, dt_of(v_tok),
                                   _p(frame_out), frame_out.stride(0), _p(seg_out), seg_out.stride(0), _p(fmask_out), _p(smask_out),
                                   _p(video_out), _p(music_out), _stream()), "made_gather_pairs")
+
+
+def frames_preprocess(frames: Tensor, desc: Tensor, coef: Tensor, patches: Tensor, crop: Optional[Tensor] = None) -> Tensor:
+    """made_frames_preprocess: the 49 conv1 patch rows of every frame's 224 x 224 CLIP crop (mgsv_amd/frames.py builds the tables).
+    frames: uint8 bytes holding every frame (any shape, contiguous); desc: uint8 [n, 32] or int64 [n, 4] device rows laid out as
+    MadeFrameDesc; coef: int32 [n_coef]; patches [>= n * 49, >= 3072] f32 or bf16 (unit column stride); crop: uint8 [n, 224, 224, 3]."""
+    assert frames.dtype == torch.uint8 and frames.is_contiguous()
+    assert desc.is_contiguous() and desc.numel() * desc.element_size() % C.sizeof(_lib.MadeFrameDesc) == 0
+    n = desc.numel() * desc.element_size() // C.sizeof(_lib.MadeFrameDesc)
+    assert coef.dtype == torch.int32 and coef.is_contiguous()
+    assert patches.dim() == 2 and patches.stride(1) == 1 and patches.shape[0] >= n * 49 and patches.shape[1] >= 3072
+    if crop is not None:
+        assert crop.dtype == torch.uint8 and crop.is_contiguous() and tuple(crop.shape) == (n, 224, 224, 3)
+    check(lib().made_frames_preprocess(_p(frames), frames.numel(), _p(desc), n, _p(coef), coef.numel(), _p(patches), dt_of(patches),
+                                       patches.stride(0), _p(crop), _stream()), "made_frames_preprocess")
+    return patches

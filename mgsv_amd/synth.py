@@ -261,3 +261,29 @@ def make_ranked_retrieval_inputs(N: int, S: int, D: int, seed: int = 21, hard: b
     v = m + sigma / np.sqrt(D) * rng.standard_normal((N, D), dtype=np.float32)
     v /= np.linalg.norm(v, axis=-1, keepdims=True)
     return dict(video_embeds=v.astype(np.float32), segment_embeds=seg, segment_masks=masks, music_embeds=m.astype(np.float32))
+
+
+def make_clip_visual_state_dict(seed: int = 0, prefix: str = "visual.") -> "OrderedDict[str, torch.Tensor]":
+    """Random f32 weights for CLIP ViT-B/32's visual tower (mgsv_amd/frames.py) at the scales CLIP initialises them with: conv1 and the
+    Linears U(+-1/sqrt(fan_in)), the packed in-projection Xavier-uniform, class / positional embeddings and proj width^-1/2 normals.
+    The LayerNorms and the attention biases (1 / 0 at initialisation) get small perturbations so that every parameter matters."""
+    import torch
+    from .frames import WIDTH, visual_shapes
+    g = torch.Generator().manual_seed(seed)
+    fan_in = {"conv1.weight": 3 * 32 * 32, "attn.out_proj.weight": WIDTH, "mlp.c_fc.weight": WIDTH, "mlp.c_fc.bias": WIDTH,
+              "mlp.c_proj.weight": 4 * WIDTH, "mlp.c_proj.bias": 4 * WIDTH}
+    sd = OrderedDict()
+    for k, shape in visual_shapes().items():
+        leaf = k[len("transformer.resblocks.") + k[len("transformer.resblocks."):].index(".") + 1:] if k.startswith("transformer.") else k
+        if leaf.startswith("ln_") and leaf.endswith(".weight"):
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        elif leaf.startswith("ln_") or leaf in ("attn.in_proj_bias", "attn.out_proj.bias"):
+            t = 0.02 * torch.randn(shape, generator=g)
+        elif leaf in ("class_embedding", "positional_embedding", "proj"):
+            t = WIDTH ** -0.5 * torch.randn(shape, generator=g)
+        elif leaf == "attn.in_proj_weight":
+            t = (torch.rand(shape, generator=g) * 2 - 1) * (6.0 / (shape[0] + shape[1])) ** 0.5
+        else:
+            t = (torch.rand(shape, generator=g) * 2 - 1) / fan_in[leaf] ** 0.5
+        sd[prefix + k] = t.float()
+    return sd
