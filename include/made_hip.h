@@ -1000,6 +1000,62 @@ int made_frames_preprocess(const uint8_t* frames, int64_t frames_bytes, const Ma
                            const int32_t* coef, int64_t n_coef, void* patches, int32_t patch_dtype, int64_t ld_patch,
                            uint8_t* crop_out, void* stream);
 
+/* ==========================================================================================
+ * Audio: decoded PCM -> the input of the AST tower (mgsv_amd/music.py).  The reference computes its AST segment features from raw
+ * audio (dataloaders/dataloader_MGSV_EC_rawdata.py:95-158 get_ast_rawaudio, model/model_Base.py:273-282,472-499): torchaudio's
+ * resample to 16 kHz, sliding segments, Kaldi fbank, then a DeiT-base AST; the tower itself runs on made_linear / made_layernorm /
+ * made_attention.
+ * ========================================================================================== */
+
+#define MADE_AUDIO_TRACKS_MAX (1 << 16)   /* most tracks one made_audio_resample call takes */
+#define MADE_AUDIO_SEGS_MAX (1 << 20)     /* most segments one made_audio_fbank / made_ast_patches call takes */
+#define MADE_RESAMPLE_TILE 1024           /* output samples per workgroup of made_audio_resample */
+#define MADE_RESAMPLE_SLAB 12288          /* most input samples a workgroup stages: ((TILE - 1) / m + 1) * o + taps must fit */
+#define MADE_AUDIO_ROWS 1024              /* spectrogram rows (AST's input_tdim) */
+#define MADE_AUDIO_MELS 128               /* mel bins */
+
+/* One track of made_audio_resample: torchaudio.functional.resample's polyphase FIR (sinc_interp_hann, lowpass_filter_width 6,
+ * rolloff 0.99) from o to m (the rates divided by their gcd) with the taps computed on the host (mgsv_amd/music.py resample_taps).
+ * The tap block at taps[taps ..] is k-major: K[p, k] at taps[taps + k * m + p] for k < 2 width + o, p < m.  o == m == 1 is a copy. */
+typedef struct MadeResampleDesc {
+    int64_t offset;        /* index (floats) of the track's first sample in `pcm` (one channel) */
+    int64_t n;             /* input samples */
+    int64_t taps;          /* index (floats) of the track's tap block (unused for a copy) */
+    int32_t o, m;          /* reduced input / output rates */
+    int32_t width;         /* the FIR's half width: `width` zeros in front of the input, width + o behind */
+    int32_t _pad;
+} MadeResampleDesc;
+
+/* made_audio_resample: n_tracks tracks of mixed rates in one launch (a workgroup per track and tile of MADE_RESAMPLE_TILE outputs; the
+ * input slab the tile reads is staged in LDS, the taps are read through the cache).  out [n_tracks, out_len] f32: row t holds
+ * y[j] = sum_k K[p, k] x~[b o + k] (j = b m + p, f32 accumulation in k order) for j < min(ceil(m n / o), out_len) and 0 after, x~
+ * being the input with `width` zeros in front.  A copy writes x[j] unchanged for j < min(n, out_len).  A descriptor that does not fit
+ * pcm_len / n_taps, or whose slab exceeds MADE_RESAMPLE_SLAB, gives a NaN row. */
+int made_audio_resample(const float* pcm, int64_t pcm_len, const MadeResampleDesc* desc, int64_t n_tracks, const float* taps,
+                        int64_t n_taps, float* out, int64_t out_len, void* stream);
+
+/* One segment of made_audio_fbank: samples pcm[first .. first + count) of the 16 kHz buffer. */
+typedef struct MadeAudioSegDesc {
+    int64_t first;
+    int64_t count;
+} MadeAudioSegDesc;
+
+/* made_audio_fbank: torchaudio.compliance.kaldi.fbank(seg, htk_compat=True, sample_frequency=16000, use_energy=False,
+ * window_type='hanning', num_mel_bins=128, dither=0.0, frame_shift=10) of n_segs segments, padded / truncated to 1024 rows and
+ * normalised as (x + 4.2677393) / 9.1379948 (f32), the reference's `audio` tensor.  A workgroup per segment and tile of 16 rows; each
+ * wave takes one 400-sample frame (every 160 samples; n_frames = 1 + (count - 400) / 160, 0 when count < 400): mean removal,
+ * pre-emphasis 0.97, the window, a 512-point radix-2 FFT in LDS (f32), |X|^2, the mel filters, log(max(e, 2^-23)) (the floor's log
+ * is a constant).  window [400] f32, twiddle [512] f32 (cos(2 pi k / 512) for k < 256, then sin), mel [128, mel_ld] f32 rows of
+ * (first bin, bin count, weights), all computed on the host in float64 (mgsv_amd/music.py fbank_tables).  Rows >= n_frames hold the
+ * padded value 4.2677393f / 9.1379948f.  spec [n_segs, 1024, 128] f32.  A segment that does not fit pcm_len gives NaN rows. */
+int made_audio_fbank(const float* pcm, int64_t pcm_len, const MadeAudioSegDesc* segs, int64_t n_segs, const float* window,
+                     const float* twiddle, const float* mel, int32_t mel_ld, float* spec, void* stream);
+
+/* made_ast_patches: the patch rows of AST's Conv2d(1 -> 768, 16 x 16, stride 10) over the transposed spectrogram, as a GEMM operand
+ * (patch_embed.proj.weight.reshape(768, 256)): patches[(s * 1212 + 101 fi + ti) * ld_patch + 16 k + l] = spec[s, 10 ti + l, 10 fi + k]
+ * for fi < 12, ti < 101, k, l < 16.  spec [n_segs, 1024, 128] f32; patch_dtype MADE_F32 or MADE_BF16 (rounded). */
+int made_ast_patches(const float* spec, int64_t n_segs, void* patches, int32_t patch_dtype, int64_t ld_patch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

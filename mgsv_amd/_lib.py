@@ -195,6 +195,14 @@ class MadeFrameDesc(C.Structure):
     _fields_ = [("offset", i64), ("coef", i64), ("H", i32), ("W", i32), ("kh", i32), ("kv", i32)]
 
 
+class MadeResampleDesc(C.Structure):
+    _fields_ = [("offset", i64), ("n", i64), ("taps", i64), ("o", i32), ("m", i32), ("width", i32), ("_pad", i32)]
+
+
+class MadeAudioSegDesc(C.Structure):
+    _fields_ = [("first", i64), ("count", i64)]
+
+
 # name -> (restype, argtypes); every symbol include/made_hip.h declares
 SIGNATURES = {
     "made_abi_version": (C.c_int, []),
@@ -286,6 +294,9 @@ SIGNATURES = {
     "made_gather_pairs": (C.c_int, [vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32,
                                     vp, i64, vp, i64, vp, vp, vp, vp, vp]),
     "made_frames_preprocess": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i32, i64, vp, vp]),
+    "made_audio_resample": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp]),
+    "made_audio_fbank": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, i32, vp, vp]),
+    "made_ast_patches": (C.c_int, [vp, i64, vp, i32, i64, vp]),
 }
 
 _lib = None

@@ -26,6 +26,7 @@ import torch
 
 from . import _lib, ops
 from .ops import Seg
+from .vit import prenorm_blocks
 
 Tensor = torch.Tensor
 
@@ -315,15 +316,7 @@ class FrameEncoder:
         ops.linear(patches, P["conv1"], None, R=P["pos"], r_row_mod=N_PATCH, M=B * N_PATCH,
                    segs=[Seg(out=x3[:, 1:], ldo=WIDTH, rows_per_batch=N_PATCH, out_batch_stride=L * WIDTH)])
         ops.layernorm(xa, *P["ln_pre"], out=xb)
-        q3 = qkv.view(B, L, 3 * WIDTH)
-        for lp in P["layers"]:
-            ops.layernorm(xb, *lp["ln1"], out=h)
-            ops.linear(h, *lp["qkv"], out=qkv)
-            ops.attention(q3[:, :, :WIDTH], q3[:, :, WIDTH:2 * WIDTH], q3[:, :, 2 * WIDTH:], o.view(B, L, WIDTH), HEADS)
-            ops.linear(o, *lp["out"], R=xb, out=xa)
-            ops.layernorm(xa, *lp["ln2"], out=h)
-            ops.linear(h, *lp["fc"], act=ops.ACT_QUICKGELU, out=f)
-            ops.linear(f, *lp["pr"], R=xa, out=xb)
+        prenorm_blocks(P["layers"], xa, xb, h, qkv, o, f, B, L, HEADS, act=ops.ACT_QUICKGELU, eps=1e-5)
         assert xb.shape[0] == M
         ops.layernorm(xb.view(B, L, WIDTH)[:, :1], *P["ln_post"], out=ws["pooled"])
         return ops.linear(ws["pooled"], P["proj"], None, out=out)

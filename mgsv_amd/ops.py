@@ -871,3 +871,42 @@ def frames_preprocess(frames: Tensor, desc: Tensor, coef: Tensor, patches: Tenso
     check(lib().made_frames_preprocess(_p(frames), frames.numel(), _p(desc), n, _p(coef), coef.numel(), _p(patches), dt_of(patches),
                                        patches.stride(0), _p(crop), _stream()), "made_frames_preprocess")
     return patches
+
+
+def audio_resample(pcm: Tensor, desc: Tensor, taps: Tensor, out: Tensor) -> Tensor:
+    """made_audio_resample: every track of `desc` to 16 kHz in one launch (mgsv_amd/music.py builds the descriptors and taps).
+    pcm: f32 samples of every track (contiguous); desc: uint8 [n, 32] device rows laid out as MadeResampleDesc; taps: f32 [n_taps];
+    out: f32 [n, out_len] (contiguous): ceil(m n / o) resampled samples per row, zeros after."""
+    assert pcm.dtype == torch.float32 and pcm.is_contiguous() and taps.dtype == torch.float32 and taps.is_contiguous()
+    assert desc.is_contiguous() and desc.numel() * desc.element_size() % C.sizeof(_lib.MadeResampleDesc) == 0
+    n = desc.numel() * desc.element_size() // C.sizeof(_lib.MadeResampleDesc)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 2 and out.shape[0] == n
+    check(lib().made_audio_resample(_p(pcm), pcm.numel(), _p(desc), n, _p(taps), taps.numel(), _p(out), out.shape[1], _stream()),
+          "made_audio_resample")
+    return out
+
+
+def audio_fbank(pcm: Tensor, segs: Tensor, window: Tensor, twiddle: Tensor, mel: Tensor, spec: Tensor) -> Tensor:
+    """made_audio_fbank: the normalised Kaldi fbank [n, 1024, 128] f32 of every segment of `segs` (uint8 [n, 16] device rows laid out
+    as MadeAudioSegDesc, indices into the 16 kHz samples `pcm`); window [400], twiddle [512] and mel [128, mel_ld] f32 tables from
+    mgsv_amd/music.py fbank_tables.  spec: f32 [>= n, 1024, 128] (contiguous)."""
+    assert pcm.dtype == torch.float32 and pcm.is_contiguous()
+    assert segs.is_contiguous() and segs.numel() * segs.element_size() % C.sizeof(_lib.MadeAudioSegDesc) == 0
+    n = segs.numel() * segs.element_size() // C.sizeof(_lib.MadeAudioSegDesc)
+    for t in (window, twiddle, mel):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert window.numel() == 400 and twiddle.numel() == 512 and mel.dim() == 2 and mel.shape[0] == 128
+    assert spec.dtype == torch.float32 and spec.is_contiguous() and spec.shape[0] >= n and tuple(spec.shape[1:]) == (1024, 128)
+    check(lib().made_audio_fbank(_p(pcm), pcm.numel(), _p(segs), n, _p(window), _p(twiddle), _p(mel), mel.shape[1], _p(spec), _stream()),
+          "made_audio_fbank")
+    return spec
+
+
+def ast_patches(spec: Tensor, patches: Tensor, n: Optional[int] = None) -> Tensor:
+    """made_ast_patches: AST's patch-embedding operand [n * 1212, 256] (f32 or bf16, unit column stride) of the first n spectrograms
+    of spec [>= n, 1024, 128] f32 (contiguous)."""
+    n = spec.shape[0] if n is None else n
+    assert spec.dtype == torch.float32 and spec.is_contiguous() and tuple(spec.shape[1:]) == (1024, 128) and spec.shape[0] >= n
+    assert patches.dim() == 2 and patches.stride(1) == 1 and patches.shape[0] >= n * 1212 and patches.shape[1] >= 256
+    check(lib().made_ast_patches(_p(spec), n, _p(patches), dt_of(patches), patches.stride(0), _stream()), "made_ast_patches")
+    return patches

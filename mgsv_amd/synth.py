@@ -287,3 +287,28 @@ def make_clip_visual_state_dict(seed: int = 0, prefix: str = "visual.") -> "Orde
             t = (torch.rand(shape, generator=g) * 2 - 1) / fan_in[leaf] ** 0.5
         sd[prefix + k] = t.float()
     return sd
+
+
+def make_ast_state_dict(seed: int = 0, prefix: str = "module.v.") -> "OrderedDict[str, torch.Tensor]":
+    """Random f32 weights for AST's DeiT-base tower (mgsv_amd/music.py) under the checkpoint's `module.v.` names, at the scales timm
+    initialises DeiT with: cls / dist tokens, pos_embed and the Linears truncated normals of std 0.02, the patch Conv2d
+    U(+-1/sqrt(256)).  The LayerNorms and the biases (1 / 0 at initialisation) get small perturbations so that every parameter
+    matters.  Two head tensors are included, as the checkpoint has them, for the loader to ignore."""
+    import torch
+    from .music import ast_shapes
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    for k, shape in ast_shapes().items():
+        leaf = k.split(".", 2)[2] if k.startswith("blocks.") else k
+        if leaf.startswith(("norm", "norm1.", "norm2.")) and leaf.endswith(".weight"):
+            t = 1.0 + 0.1 * torch.randn(shape, generator=g)
+        elif leaf.endswith(".bias") and leaf != "patch_embed.proj.bias":
+            t = 0.02 * torch.randn(shape, generator=g)
+        elif leaf.startswith("patch_embed."):
+            t = (torch.rand(shape, generator=g) * 2 - 1) / 16.0
+        else:
+            t = torch.fmod(torch.randn(shape, generator=g), 2.0) * 0.02
+        sd[prefix + k] = t.float()
+    sd[prefix + "head.weight"] = torch.zeros(527, 768)
+    sd["module.mlp_head.1.weight" if prefix == "module.v." else "mlp_head.1.weight"] = torch.zeros(527, 768)
+    return sd
