@@ -373,6 +373,69 @@ typedef struct MadeWideAttnBwdArgs {
 int made_attention_wide_bwd(const MadeWideAttnBwdArgs* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Slice plan of the decoder's memory-space cross-attention: which key tiles (32 keys) every workgroup of made_attention_wide_planned /
+ * made_attention_wide_bwd_planned gets.  made_attention_wide(_bwd) cut every sample into n_split equal slices whatever its length, and
+ * a launch lasts as long as its longest workgroup; the plan deals the tiles of a padded batch by length instead:
+ *   tiles_b = ceil((last valid key of sample b + 1) / 32)      (0: no valid key)
+ *   n_b     = max(1, ceil(tiles_b / c))                        (slices of sample b; a sample without a valid key keeps ONE slice of zero
+ *                                                               tiles, so that a workgroup defines its outputs)
+ *   c       = the smallest cap >= 1 with sum_b n_b <= n_slots and max_b n_b <= max_slices      (made_wide_slice_cap below)
+ * and a sample's tiles are dealt evenly over its n_b slices (tiles_b / n_b each, the first tiles_b % n_b slices one more: none
+ * longer than c).  Slots are filled in batch_order (made_batch_order: longest first; NULL: sample order), a sample's slices
+ * consecutive.  The plan is made once per step on the device from the key mask (one workgroup, nothing read back) and serves every
+ * decoder layer, forward and backward.  Layout, int32 words:
+ *   [0..3]                    c, used slots, n_slots, max_slices
+ *   [4 + 4 b ..]              per sample: tiles_b, first slot, n_b, first valid key (0 when none)
+ *   [4 + 4 B + 16 w ..]       per slot w < n_slots (64 bytes): sample (-1: unused slot), first tile, tile count, slice index within the
+ *                             sample, first valid key, n_b, tiles_b, 0, then the valid-key bits of the slot's first 8 tiles (bit j of
+ *                             word i = key 32 (first tile + i) + j is attended to) -- a workgroup learns all it needs from one load */
+#define MADE_WIDE_PLAN_HEAD 4
+#define MADE_WIDE_PLAN_SAMPLE 4
+#define MADE_WIDE_PLAN_SLOT 16
+#define MADE_WIDE_PLAN_SLOT_BITS 8
+MADE_HOST_DEVICE static inline int64_t made_wide_plan_words(int64_t B, int64_t n_slots) {
+    return MADE_WIDE_PLAN_HEAD + MADE_WIDE_PLAN_SAMPLE * B + MADE_WIDE_PLAN_SLOT * n_slots;
+}
+/* slices the batch needs under cap c (tiles[b * stride]: the samples' tile counts), or -1 when a sample would need more than max_slices */
+MADE_HOST_DEVICE static inline int32_t made_wide_slice_count(const int32_t* tiles, int32_t stride, int32_t B, int32_t c, int32_t max_slices) {
+    int32_t total = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        const int32_t t = tiles[b * stride];
+        const int32_t n = t > c ? (t + c - 1) / c : 1;
+        if (n > max_slices) return -1;
+        total += n;
+    }
+    return total;
+}
+/* the cap: the smallest c >= 1 whose slices fit n_slots workgroups and max_slices partial rows per sample; 0: none (B > n_slots) */
+MADE_HOST_DEVICE static inline int32_t made_wide_slice_cap(const int32_t* tiles, int32_t stride, int32_t B, int32_t n_slots, int32_t max_slices) {
+    int32_t tmax = 1;
+    for (int32_t b = 0; b < B; ++b) tmax = tiles[b * stride] > tmax ? tiles[b * stride] : tmax;
+    for (int32_t c = 1; c <= tmax; ++c) {
+        const int32_t n = made_wide_slice_count(tiles, stride, B, c, max_slices);
+        if (n >= 0 && n <= n_slots) return c;
+    }
+    return 0;
+}
+/* slice s (< n) of a sample with `tiles` tiles in n slices: first tile and tile count */
+MADE_HOST_DEVICE static inline int32_t made_wide_slice_first(int32_t tiles, int32_t n, int32_t s) {
+    return s * (tiles / n) + (s < tiles % n ? s : tiles % n);
+}
+MADE_HOST_DEVICE static inline int32_t made_wide_slice_len(int32_t tiles, int32_t n, int32_t s) { return tiles / n + (s < tiles % n ? 1 : 0); }
+
+/* made_wide_slice_plan: key_mask [B, L] f32 -> plan (plan_bytes >= 4 * made_wide_plan_words(B, n_slots)).  One workgroup;
+ * B <= n_slots <= 1024, max_slices >= 1, L <= 32768.
+ * made_attention_wide_planned / _bwd_planned: made_attention_wide / _bwd on n_slots workgroups that follow the plan (made from the
+ * same key_mask with the same n_slots); args->n_split is the slice CAPACITY of part_o / part_ml / part_dq (>= the plan's max_slices),
+ * partial rows at [(b * capacity + slice) * NQ + q].  The merge launches sum a sample's slices 0 .. n_b - 1 in slice order: results
+ * are bitwise reproducible from launch to launch.  bf16, D in {256, 512}, no Kadd, a key mask, one query tile per sample
+ * (NQ1 * NQ2 <= 32 forward, NQ <= 8 backward); anything else is MADE_ERR_UNSUPPORTED and the caller keeps the unplanned call. */
+int made_wide_slice_plan(const float* key_mask, int64_t B, int64_t L, int32_t n_slots, int32_t max_slices,
+                         const int32_t* batch_order, void* plan, int64_t plan_bytes, void* stream);
+int made_attention_wide_planned(const MadeWideAttnArgs* args, const void* plan, int32_t n_slots, void* stream);
+int made_attention_wide_bwd_planned(const MadeWideAttnBwdArgs* args, const void* plan, int32_t n_slots, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Launch tape: record the library's launches of one training (or eval) step once, replay them from one C loop.
  * Between made_tape_begin() and made_tape_end() every kernel launch of the calling thread is executed as usual AND appended to the
  * tape (function, grid, block, LDS bytes, stream, argument bytes); made_stream_wait / made_memset_async / made_copy_async are the

@@ -30,6 +30,14 @@ GATE_NONE, GATE_RELU_OUT, GATE_GELU_Z, GATE_QUICKGELU_Z, GATE_SIGMOID_OUT = 0, 1
 
 vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int32, C.c_float
 
+# the slice plan of the decoder's cross-attention (include/made_hip.h MADE_WIDE_PLAN_*): int32 words of the header, per sample, per slot
+WIDE_PLAN_HEAD, WIDE_PLAN_SAMPLE, WIDE_PLAN_SLOT, WIDE_PLAN_SLOT_BITS = 4, 4, 16, 8
+
+
+def wide_plan_words(B: int, n_slots: int) -> int:
+    """made_wide_plan_words of include/made_hip.h"""
+    return WIDE_PLAN_HEAD + WIDE_PLAN_SAMPLE * B + WIDE_PLAN_SLOT * n_slots
+
 
 class MadeDropout(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("site", C.c_uint32), ("p", f32), ("seed_device", vp)]
@@ -231,6 +239,9 @@ SIGNATURES = {
     "made_attention": (C.c_int, [C.POINTER(MadeAttnArgs), vp]),
     "made_attention_wide": (C.c_int, [C.POINTER(MadeWideAttnArgs), vp]),
     "made_attention_wide_bwd": (C.c_int, [C.POINTER(MadeWideAttnBwdArgs), vp]),
+    "made_wide_slice_plan": (C.c_int, [vp, i64, i64, i32, i32, vp, vp, i64, vp]),
+    "made_attention_wide_planned": (C.c_int, [C.POINTER(MadeWideAttnArgs), vp, i32, vp]),
+    "made_attention_wide_bwd_planned": (C.c_int, [C.POINTER(MadeWideAttnBwdArgs), vp, i32, vp]),
     "made_layernorm": (C.c_int, [vp, i32, i64, i64, i64, vp, vp, vp, i32, i64, i64, i64, f32, vp, vp]),
     "made_layernorm_add": (C.c_int, [vp, i32, i64, vp, vp, vp, i32, i64, vp, i32, i64, vp, i64, i64, i64, f32, vp, vp]),
     "made_cast_mask_rows": (C.c_int, [vp, i64, vp, vp, i32, i64, i64, i64, vp]),

@@ -15,6 +15,15 @@
 // softmax redundantly (cheap) and accumulates ITS quarter of O^T += V^T P^T, reading the row-major V
 // tile as an MFMA A operand with ds_read_b64_tr_b16 (bf16) or plain ds_read_b32 (f32: lane = d).
 // Keys are consumed 32 at a time; K (+Kadd) and V tiles are staged global -> registers -> LDS.
+//
+// made_attention_wide_planned (the decoder in training): the same kernel body on a SLICE PLAN (made_wide_slice_plan, include/made_hip.h).
+// The unplanned launch cuts every sample into n_split equal slices whatever its length, one workgroup per CU, and lasts as long as its
+// longest workgroup (5 tiles on the benchmark's batch, 2.75 on average); the plan, made once per step on the device from the key
+// mask, deals the batch's tiles over one workgroup per CU by length (the smallest cap c of tiles per slice whose slices fit the
+// chip and the partial buffers: 3 on that batch).  A workgroup reads its slot -- sample, first tile, tile count, slice index, first
+// valid key, the valid-key bits of its tiles: 64 bytes -- in place of scanning the sample's key mask, runs the tile loop, and writes
+// its partial rows; attention_wide_combine_planned_kernel sums a sample's slices 0 .. n_b - 1 in slice order.  No workgroup waits for
+// another one: kernel boundaries only.
 #include "common.h"
 
 #include <type_traits>
@@ -33,8 +42,13 @@ template <> struct Frag<bf16_t> { typedef bf16x8 type; };
 // NSL = D slices per query tile: 4 -> one tile of 32 queries per workgroup, its four waves split D four ways; 2 -> two query
 // tiles per workgroup (waves 0-1 and 2-3), each split two ways: the K / V tiles staged through LDS then serve 64 queries, which
 // halves the staging per flop where a batch entry has 64 or more query rows (X-Pool: all videos against one track).
-template <typename TC, int D, bool DB, int NSL, bool X3 = false>      // X3 (f32 only): split-bf16 products (common.h, made_set_f32_products)
-__global__ __launch_bounds__(NTHREADS) void attention_wide_kernel(const MadeWideAttnArgs a) {
+// PLAN (made_attention_wide_planned: the two-stage bf16 variant with one query tile per sample): workgroup = one SLOT of the slice plan
+// (include/made_hip.h) instead of (sample, blockIdx.z-th equal slice): sample, first tile, tile count, slice index, the sample's first
+// valid key and the valid-key bits of its tiles arrive with one 64-byte load, so the scan of the sample's whole key mask (a dependent
+// global round trip, ballots and two barriers in front of the first tile) goes; a.n_split is the slice capacity of part_o / part_ml.
+template <typename TC, int D, bool DB, int NSL, bool X3 = false, bool PLAN = false>      // X3 (f32 only): split-bf16 products (common.h, made_set_f32_products)
+__global__ __launch_bounds__(NTHREADS) void attention_wide_kernel(const MadeWideAttnArgs a, const int32_t* __restrict__ plan) {
+    static_assert(!PLAN || (DB && sizeof(TC) == 2 && NSL == 4 && !X3), "the planned launch: LDS-DMA variant, one query tile");
     typedef typename Frag<TC>::type frag_t;
     constexpr int SZ = (int)sizeof(TC);
     constexpr bool IS_BF16 = SZ == 2;
@@ -65,13 +79,24 @@ __global__ __launch_bounds__(NTHREADS) void attention_wide_kernel(const MadeWide
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hh = lane >> 5;
     const int sl = wave % NSL, qt = wave / NSL;     // D slice and query tile of this wave
+    int32_t pl[MADE_WIDE_PLAN_SLOT] = {};           // (PLAN) this workgroup's slot
+    if constexpr (PLAN) {
+        const u32x4* sp = (const u32x4*)(plan + MADE_WIDE_PLAN_HEAD + MADE_WIDE_PLAN_SAMPLE * a.B + (int64_t)MADE_WIDE_PLAN_SLOT * blockIdx.x);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const u32x4 v = sp[i];
+            pl[4 * i] = (int32_t)v[0]; pl[4 * i + 1] = (int32_t)v[1]; pl[4 * i + 2] = (int32_t)v[2]; pl[4 * i + 3] = (int32_t)v[3];
+        }
+        if (pl[0] < 0 || pl[0] >= a.B || pl[3] < 0 || pl[3] >= a.n_split || pl[1] < 0 || pl[2] < 0 || (int64_t)(pl[1] + pl[2]) * WKEY >= a.L + WKEY ||
+            pl[4] < 0 || pl[4] >= a.L) return;                            // unused slot (or a plan that is not this call's: never out of bounds)
+    }
     // few query tiles per batch entry (in-batch X-Pool: 2): the batch index runs fastest, so the query tiles of one entry are
     // gridDim.x apart in dispatch order = on the same XCD when the batch is a multiple of 8, and share its K / V in that L2;
     // many query tiles (retrieval scale): the tiles of an entry are consecutive workgroups and share it in time instead
     const bool batch_fast = gridDim.x == (unsigned)a.B && (a.NQ1 * a.NQ2 + WQB - 1) / WQB != (int64_t)a.B;
-    const int64_t b = batch_fast ? blockIdx.x : blockIdx.y;
+    const int64_t b = PLAN ? (int64_t)pl[0] : (batch_fast ? blockIdx.x : blockIdx.y);
     const int64_t nq_total = a.NQ1 * a.NQ2;
-    const int64_t nq0 = (int64_t)(batch_fast ? blockIdx.y : blockIdx.x) * WQB + qt * WQ;
+    const int64_t nq0 = PLAN ? (int64_t)qt * WQ : (int64_t)(batch_fast ? blockIdx.y : blockIdx.x) * WQB + qt * WQ;
 
     const TC* Kg = (const TC*)a.K + b * a.k_bs;
     const TC* Ag = a.Kadd ? (const TC*)a.Kadd + b * a.kadd_bs : nullptr;
@@ -150,7 +175,25 @@ __global__ __launch_bounds__(NTHREADS) void attention_wide_kernel(const MadeWide
     // keys after the last valid one contribute exactly 0: stop there (padding is a suffix in the dataset's masks)
     int64_t l_eff = a.L;
     int first_valid = 0;
-    {
+    if constexpr (PLAN) {
+        first_valid = pl[4];
+        const int nt = pl[2];
+        if (nt <= MADE_WIDE_PLAN_SLOT_BITS) {                  // the bits came with the slot
+            uint32_t w = (uint32_t)pl[8];
+#pragma unroll
+            for (int i = 1; i < MADE_WIDE_PLAN_SLOT_BITS; ++i) w = tid == i ? (uint32_t)pl[8 + i] : w;
+            if (tid < MADE_WIDE_PLAN_SLOT_BITS) lds_mbits[tid] = w;
+        } else {                                               // a longer slice (few workgroups for the batch): bits of its own tiles from the mask
+            const int nk = nt * WKEY, k0 = pl[1] * WKEY;
+            for (int j = tid; j < ((nk + 63) & ~63); j += NTHREADS) {
+                const int key = k0 + j;
+                const float mv = maskg[key < (int)a.L ? key : (int)a.L - 1];
+                const unsigned long long bal = __ballot(j < nk && key < (int)a.L && mv != 0.f);
+                if (lane == 0) { lds_mbits[j / 32] = (uint32_t)bal; lds_mbits[j / 32 + 1] = (uint32_t)(bal >> 32); }
+            }
+        }
+        __syncthreads();
+    } else {
         const int lpad = (int)((a.L + 63) / 64) * 64;
         int last = -1, first = 0x7fffffff;
         for (int j = tid; j < lpad; j += NTHREADS) {
@@ -175,8 +218,10 @@ __global__ __launch_bounds__(NTHREADS) void attention_wide_kernel(const MadeWide
     const int64_t nsplit = a.n_split > 1 ? a.n_split : 1;
     const int64_t tiles_all = (l_eff + WKEY - 1) / WKEY;
     const int64_t tiles_per = (tiles_all + nsplit - 1) / nsplit;
-    const int64_t tile0 = (int64_t)blockIdx.z * tiles_per;
-    const int64_t ntiles = tile0 >= tiles_all ? 0 : (tile0 + tiles_per <= tiles_all ? tiles_per : tiles_all - tile0);
+    const int64_t tile0 = PLAN ? (int64_t)pl[1] : (int64_t)blockIdx.z * tiles_per;
+    const int64_t ntiles = PLAN ? (int64_t)pl[2] : (tile0 >= tiles_all ? 0 : (tile0 + tiles_per <= tiles_all ? tiles_per : tiles_all - tile0));
+    const int64_t mb0 = PLAN ? tile0 : 0;                      // lds_mbits[0] = the bits of this tile
+    const int64_t zslice = PLAN ? (int64_t)pl[3] : (int64_t)blockIdx.z;
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
     typedef const __attribute__((address_space(1))) void* glb_ptr_t;
     // (DMA) tile `key0` -> stage: this wave moves pieces wave, wave + 4, ... of both tiles (1 KB each: D = 512 one row, D = 256 two)
@@ -184,7 +229,7 @@ __global__ __launch_bounds__(NTHREADS) void attention_wide_kernel(const MadeWide
         constexpr int ROWS_PER_PIECE = DMA ? 1024 / (D * SZ) : 1;
         constexpr int NPIECE = WKEY / ROWS_PER_PIECE;
         constexpr int CPRW = D * SZ / 16;                          // chunks per row
-        const uint32_t bits = lds_mbits[key0 / WKEY];
+        const uint32_t bits = lds_mbits[key0 / WKEY - mb0];
         unsigned char* st = lds + stage * KV_STAGE;
         const unsigned char* Kb = (const unsigned char*)Kg;
         const unsigned char* Vb = (const unsigned char*)Vg;
@@ -215,7 +260,7 @@ __global__ __launch_bounds__(NTHREADS) void attention_wide_kernel(const MadeWide
         uint32_t tbits = 0xffffffffu;
         if constexpr (DMA) {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // tile t landed; the other stage is free
-            tbits = lds_mbits[t];
+            tbits = lds_mbits[t - mb0];
         } else if (NSTAGE == 2) {
             if (tt + 1 < ntiles) load_tile((t + 1) * WKEY);   // in flight during this tile's MFMAs; stored at the end of the tile
         } else {
@@ -387,14 +432,14 @@ __global__ __launch_bounds__(NTHREADS) void attention_wide_kernel(const MadeWide
     const float inv = 1.f / l_tot;
     const float sd_tot = sd_run + __shfl_xor(sd_run, 32);
     const bool live_q = my_q < nq_total;
-    if (nsplit == 1 && !live_q) return;
-    if (nsplit == 1 && sl == 0 && hh == 0) {
+    if (!PLAN && nsplit == 1 && !live_q) return;
+    if (!PLAN && nsplit == 1 && sl == 0 && hh == 0) {
         if (a.sum_out) a.sum_out[b * nq_total + my_q] = a.drop.p > 0.f ? sd_tot * inv : 1.f;
         if (a.lse_out) a.lse_out[b * nq_total + my_q] = m_run + logf(l_tot);
     }
-    if (nsplit > 1) {
+    if (PLAN || nsplit > 1) {
         // un-normalised partial result of this key slice
-        const int64_t prow = (b * nsplit + blockIdx.z) * nq_total + (live_q ? my_q : 0);
+        const int64_t prow = (b * nsplit + zslice) * nq_total + (live_q ? my_q : 0);
         if (live_q) {
             float* po = a.part_o + prow * D + sl * DS;
 #pragma unroll
@@ -544,8 +589,8 @@ int launch_wide(const MadeWideAttnArgs& a, hipStream_t st) {
     const int64_t qtiles = (nq + WQB - 1) / WQB;
     const bool batch_fast = qtiles > 1 && qtiles <= 8 && qtiles != a.B;       // see the kernel: which index runs fastest
     dim3 grid((unsigned)(batch_fast ? a.B : qtiles), (unsigned)(batch_fast ? qtiles : a.B), (unsigned)nsplit), block(NTHREADS);
-    if (SZ == 4 && g_made_f32_products) hipLaunchKernelGGL((attention_wide_kernel<TC, D, DB, NSL, SZ == 4>), grid, block, lds_bytes, st, a);
-    else hipLaunchKernelGGL((attention_wide_kernel<TC, D, DB, NSL>), grid, block, lds_bytes, st, a);
+    if (SZ == 4 && g_made_f32_products) hipLaunchKernelGGL((attention_wide_kernel<TC, D, DB, NSL, SZ == 4>), grid, block, lds_bytes, st, a, (const int32_t*)nullptr);
+    else hipLaunchKernelGGL((attention_wide_kernel<TC, D, DB, NSL>), grid, block, lds_bytes, st, a, (const int32_t*)nullptr);
     int rc = made_check_launch("made_attention_wide");
     if (rc != MADE_OK || nsplit == 1) return rc;
     const int64_t rows = a.B * nq;
@@ -553,7 +598,212 @@ int launch_wide(const MadeWideAttnArgs& a, hipStream_t st) {
     return made_check_launch("made_attention_wide(combine)");
 }
 
+// ---- the slice plan (include/made_hip.h) ------------------------------------------------------------------------------------------
+// One workgroup of 16 waves: (1) a wave per sample turns the mask row into valid-key bits (LDS) and finds the first / last valid
+// key; (2) thread t counts the slices the batch needs under cap t + 1 (made_wide_slice_count: the header's text, as the CPU test
+// compiles it) and the smallest cap that fits wins; (3) thread r deals the sample of rank r (batch_order) its slots.
+constexpr int PLAN_T = 1024;
+__global__ __launch_bounds__(PLAN_T) void wide_slice_plan_kernel(const float* __restrict__ mask, int B, int L, int n_slots, int max_slices,
+                                                                 const int32_t* __restrict__ order, int32_t* __restrict__ plan) {
+    __shared__ int32_t s_tiles[PLAN_T], s_first[PLAN_T], s_ord[PLAN_T];
+    __shared__ int32_t s_cap;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    uint32_t* s_bits = (uint32_t*)lds;                       // [B][wpr]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nch = (L + 63) / 64, wpr = 2 * nch;
+    if (tid == 0) s_cap = 0x7fffffff;
+    for (int b = wave; b < B; b += PLAN_T / 64) {
+        const float* m = mask + (int64_t)b * L;
+        int last = -1, first = -1;
+        for (int c0 = 0; c0 < nch; c0 += 8) {                // eight chunks of 64 keys travel together
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int i = (c0 + j) * 64 + lane;
+                v[j] = m[i < L ? i : L - 1];
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int i = (c0 + j) * 64 + lane;
+                const unsigned long long bal = __ballot(i < L && v[j] != 0.f);
+                if (c0 + j < nch) {
+                    if (lane == 0) { s_bits[b * wpr + 2 * (c0 + j)] = (uint32_t)bal; s_bits[b * wpr + 2 * (c0 + j) + 1] = (uint32_t)(bal >> 32); }
+                    if (bal) {
+                        last = (c0 + j) * 64 + 63 - __clzll(bal);
+                        if (first < 0) first = (c0 + j) * 64 + __ffsll(bal) - 1;
+                    }
+                }
+            }
+        }
+        if (lane == 0) { s_tiles[b] = (last + 1 + 31) / 32; s_first[b] = first < 0 ? 0 : first; }
+    }
+    if (tid < B) {
+        const int o = order ? order[tid] : tid;
+        s_ord[tid] = o >= 0 && o < B ? o : tid;
+    }
+    __syncthreads();
+    int tmax = 1;
+    for (int b = 0; b < B; ++b) tmax = max(tmax, s_tiles[b]);
+    for (int c = tid + 1; c <= tmax; c += PLAN_T) {
+        const int n = made_wide_slice_count(s_tiles, 1, B, c, max_slices);
+        if (n >= 0 && n <= n_slots) atomicMin(&s_cap, c);
+    }
+    __syncthreads();
+    const int cap = s_cap <= tmax ? s_cap : tmax;            // (B <= n_slots, max_slices >= 1: cap = tmax always fits)
+    int used = 0;
+    for (int r = 0; r < B; ++r) { const int t = s_tiles[s_ord[r]]; used += t > cap ? (t + cap - 1) / cap : 1; }
+    if (tid == 0) { plan[0] = cap; plan[1] = used; plan[2] = n_slots; plan[3] = max_slices; }
+    int32_t* slots = plan + MADE_WIDE_PLAN_HEAD + MADE_WIDE_PLAN_SAMPLE * B;
+    if (tid < B) {
+        int slot0 = 0;
+        for (int r = 0; r < tid; ++r) { const int t = s_tiles[s_ord[r]]; slot0 += t > cap ? (t + cap - 1) / cap : 1; }
+        const int b = s_ord[tid], t = s_tiles[b], fv = s_first[b];
+        const int n = t > cap ? (t + cap - 1) / cap : 1;
+        int32_t* sm = plan + MADE_WIDE_PLAN_HEAD + MADE_WIDE_PLAN_SAMPLE * b;
+        sm[0] = t; sm[1] = slot0; sm[2] = n; sm[3] = fv;
+        for (int s = 0; s < n && slot0 + s < n_slots; ++s) {
+            int32_t* sp = slots + (int64_t)MADE_WIDE_PLAN_SLOT * (slot0 + s);
+            const int t0 = made_wide_slice_first(t, n, s), tn = made_wide_slice_len(t, n, s);
+            sp[0] = b; sp[1] = t0; sp[2] = tn; sp[3] = s; sp[4] = fv; sp[5] = n; sp[6] = t; sp[7] = 0;
+            for (int i = 0; i < MADE_WIDE_PLAN_SLOT_BITS; ++i) sp[8 + i] = i < tn ? (int32_t)s_bits[b * wpr + t0 + i] : 0;
+        }
+    }
+    for (int w = used + tid; w < n_slots; w += PLAN_T) {
+        int32_t* sp = slots + (int64_t)MADE_WIDE_PLAN_SLOT * w;
+        sp[0] = -1;
+        for (int i = 1; i < MADE_WIDE_PLAN_SLOT; ++i) sp[i] = 0;
+    }
+}
+
+// merge of the planned launch: the sample's slice count comes from the plan; up to eight slices, all requested before the first use,
+// summed in slice order (the arithmetic of attention_wide_combine_kernel)
+__global__ __launch_bounds__(NTHREADS) void attention_wide_combine_planned_kernel(const MadeWideAttnArgs a, const int32_t* __restrict__ plan) {
+    constexpr int MAXS = 8;
+    const int lane = threadIdx.x & 63;
+    const int64_t nq_total = a.NQ1 * a.NQ2;
+    const int64_t row = (int64_t)blockIdx.x * (NTHREADS / 64) + (threadIdx.x >> 6);
+    if (row >= a.B * nq_total) return;
+    const int64_t b = row / nq_total, q = row % nq_total;
+    const int D = (int)a.D;
+    const int cap = (int)a.n_split;
+    int ns = plan[MADE_WIDE_PLAN_HEAD + MADE_WIDE_PLAN_SAMPLE * b + 2];
+    ns = ns < 1 ? 1 : (ns > MAXS ? MAXS : ns);
+    ns = ns > cap ? cap : ns;
+    float Lsum = 0.f, Dsum = 0.f;
+    f32x4 acc[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0.f; }
+    f32x4 t[MAXS][2];
+    float ml[MAXS][3];
+#pragma unroll
+    for (int sp = 0; sp < MAXS; ++sp) {
+        const int64_t pr = (b * cap + (sp < ns ? sp : ns - 1)) * nq_total + q;
+        ml[sp][0] = a.part_ml[pr * 4]; ml[sp][1] = a.part_ml[pr * 4 + 1]; ml[sp][2] = a.part_ml[pr * 4 + 2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            t[sp][i] = *(const f32x4*)(a.part_o + pr * D + (c < D ? c : 0));
+        }
+    }
+    float M = -INFINITY;
+#pragma unroll
+    for (int sp = 0; sp < MAXS; ++sp) if (sp < ns) M = fmaxf(M, ml[sp][0]);
+    const float Muse = (M == -INFINITY) ? 0.f : M;
+#pragma unroll
+    for (int sp = 0; sp < MAXS; ++sp) {
+        if (sp < ns) {
+            const float w = expf(ml[sp][0] - Muse);
+            Lsum += ml[sp][1] * w;
+            Dsum += ml[sp][2] * w;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] += t[sp][i][j] * w;
+        }
+    }
+    const float inv = 1.f / Lsum;
+    if (a.sum_out && lane == 0) a.sum_out[b * nq_total + q] = Dsum * inv;
+    if (a.lse_out && lane == 0) a.lse_out[b * nq_total + q] = Muse + logf(Lsum);
+    const int64_t obase = b * a.o_bs + (q / a.NQ2) * a.o_s1 + (q % a.NQ2) * a.o_s2;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        int c = (i * 64 + lane) * 4;
+        if (c < D) {
+            if (a.o_dtype == MADE_F32) {
+                f32x4 pk; pk[0] = acc[i][0] * inv; pk[1] = acc[i][1] * inv; pk[2] = acc[i][2] * inv; pk[3] = acc[i][3] * inv;
+                *(f32x4*)((float*)a.O + obase + c) = pk;
+            } else {
+                bf16x4 pk; pk[0] = (bf16_t)(acc[i][0] * inv); pk[1] = (bf16_t)(acc[i][1] * inv);
+                pk[2] = (bf16_t)(acc[i][2] * inv); pk[3] = (bf16_t)(acc[i][3] * inv);
+                *(bf16x4*)((bf16_t*)a.O + obase + c) = pk;
+            }
+        }
+    }
+}
+
+template <int D>
+int launch_wide_planned(const MadeWideAttnArgs& a, const int32_t* plan, int n_slots, hipStream_t st) {
+    constexpr size_t kBase = (size_t)2 * (WKEY * D * 2 + WKEY * D * 2) + 4 * 1024 * 4 + 2 * 32 * 4;       // (as launch_wide: two stages, DMA rows)
+    constexpr size_t kCap = kBase + 8192 < 160 * 1024 ? kBase + 8192 : 160 * 1024;
+    const size_t lds_bytes = kBase + (size_t)((a.L + 63) / 64 * 2 + 2) * 4;
+    if (lds_bytes > kCap) {
+        made_set_error("made_attention_wide_planned: L=%lld keys: the mask bit row does not fit in LDS beside the K / V stages", (long long)a.L);
+        return MADE_ERR_UNSUPPORTED;
+    }
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute((const void*)attention_wide_kernel<bf16_t, D, true, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCap);
+        if (e != hipSuccess) {
+            made_set_error("made_attention_wide_planned: cannot reserve %zu bytes of LDS: %s", kCap, hipGetErrorString(e));
+            return MADE_ERR_HIP;
+        }
+        attr_done = true;
+    }
+    hipLaunchKernelGGL((attention_wide_kernel<bf16_t, D, true, 4, false, true>), dim3((unsigned)n_slots), dim3(NTHREADS), lds_bytes, st, a, plan);
+    int rc = made_check_launch("made_attention_wide_planned");
+    if (rc != MADE_OK) return rc;
+    const int64_t rows = a.B * a.NQ1 * a.NQ2;
+    hipLaunchKernelGGL(attention_wide_combine_planned_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(NTHREADS), 0, st, a, plan);
+    return made_check_launch("made_attention_wide_planned(combine)");
+}
+
 }  // namespace
+
+extern "C" int made_wide_slice_plan(const float* key_mask, int64_t B, int64_t L, int32_t n_slots, int32_t max_slices,
+                                    const int32_t* batch_order, void* plan, int64_t plan_bytes, void* stream) {
+    MADE_REQUIRE(key_mask && plan && B > 0 && L > 0 && n_slots > 0 && max_slices > 0, "made_wide_slice_plan: bad arguments");
+    MADE_REQUIRE(plan_bytes >= 4 * made_wide_plan_words(B, n_slots), "made_wide_slice_plan: plan_bytes=%lld < %lld", (long long)plan_bytes,
+                 (long long)(4 * made_wide_plan_words(B, n_slots)));
+    MADE_REQUIRE(((uintptr_t)plan % 16) == 0, "made_wide_slice_plan: the plan must be 16-byte aligned");
+    MADE_UNSUPPORTED(B <= n_slots && n_slots <= PLAN_T, "made_wide_slice_plan: B=%lld samples need B <= n_slots=%d <= %d", (long long)B, n_slots, PLAN_T);
+    MADE_UNSUPPORTED(max_slices <= 8, "made_wide_slice_plan: max_slices=%d (the merges take at most 8 slices)", max_slices);
+    const int64_t bits_bytes = B * ((L + 63) / 64 * 2) * 4;
+    MADE_UNSUPPORTED(L <= 32768 && bits_bytes <= 40 * 1024, "made_wide_slice_plan: B=%lld x L=%lld: the valid-key bits do not fit one workgroup's LDS", (long long)B, (long long)L);
+    hipLaunchKernelGGL(wide_slice_plan_kernel, dim3(1), dim3(PLAN_T), (size_t)bits_bytes, (hipStream_t)stream, key_mask, (int)B, (int)L, (int)n_slots,
+                       (int)max_slices, batch_order, (int32_t*)plan);
+    return made_check_launch("made_wide_slice_plan");
+}
+
+extern "C" int made_attention_wide_planned(const MadeWideAttnArgs* args, const void* plan, int32_t n_slots, void* stream) {
+    MADE_REQUIRE(args != nullptr && plan != nullptr, "made_attention_wide_planned: null args / plan");
+    const MadeWideAttnArgs& a = *args;
+    MADE_REQUIRE(a.Q && a.K && a.V && a.O, "made_attention_wide_planned: null tensor");
+    MADE_REQUIRE(a.B >= 0 && a.NQ1 >= 0 && a.NQ2 > 0 && a.L > 0, "made_attention_wide_planned: bad dims");
+    MADE_REQUIRE(a.o_dtype == MADE_F32 || a.o_dtype == MADE_BF16, "made_attention_wide_planned: bad o_dtype %d", a.o_dtype);
+    MADE_UNSUPPORTED(a.dtype == MADE_BF16 && (a.D == 256 || a.D == 512) && a.Kadd == nullptr && a.key_mask != nullptr && a.NQ1 * a.NQ2 <= WQ,
+                     "made_attention_wide_planned: bf16, D in {256, 512}, no Kadd, a key mask and at most %d query rows per sample", WQ);
+    MADE_UNSUPPORTED(a.B <= n_slots && n_slots <= PLAN_T, "made_attention_wide_planned: B <= n_slots <= %d", PLAN_T);
+    MADE_UNSUPPORTED(a.q_bs % 8 == 0 && a.q_s1 % 8 == 0 && a.q_s2 % 8 == 0 && a.k_bs % 8 == 0 && a.ldk % 8 == 0 && a.v_bs % 8 == 0 && a.ldv % 8 == 0 &&
+                     a.o_bs % 4 == 0 && a.o_s1 % 4 == 0 && a.o_s2 % 4 == 0, "made_attention_wide_planned: strides must keep 16-byte alignment");
+    MADE_UNSUPPORTED(((uintptr_t)a.Q % 16) == 0 && ((uintptr_t)a.K % 16) == 0 && ((uintptr_t)a.V % 16) == 0 && ((uintptr_t)a.O % 16) == 0 &&
+                     ((uintptr_t)plan % 16) == 0, "made_attention_wide_planned: base pointers must be 16-byte aligned");
+    MADE_REQUIRE(a.drop.p >= 0.f && a.drop.p < 1.f, "made_attention_wide_planned: dropout p out of [0,1)");
+    MADE_REQUIRE(a.n_split >= 1 && a.n_split <= 8 && a.part_o != nullptr && a.part_ml != nullptr,
+                 "made_attention_wide_planned: n_split = the slice capacity of part_o / part_ml (1..8)");
+    if (a.B == 0 || a.NQ1 == 0) return MADE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    return a.D == 512 ? launch_wide_planned<512>(a, (const int32_t*)plan, n_slots, st) : launch_wide_planned<256>(a, (const int32_t*)plan, n_slots, st);
+}
 
 extern "C" int made_attention_wide(const MadeWideAttnArgs* args, void* stream) {
     MADE_REQUIRE(args != nullptr, "made_attention_wide: null args");

@@ -19,6 +19,12 @@
 //   * the key slices' partial dQ' meet in an f32 workspace and a small second launch sums them in slice order (summing them inside
 //     the launch behind a ticket was built and measured in round 3: +15-20 us per launch, the agent-scope fences cost more than the
 //     kernel boundary; profiles/r03_micro_merge_in_launch_vs_second_launch.txt).
+//
+// made_attention_wide_bwd_planned: the same body on the step's slice plan (made_wide_slice_plan; csrc/attention_wide.hip's header):
+// workgroup = one slot of the plan = one sample's run of at most c key tiles, dealt by length over one workgroup per CU instead of
+// n_split equal slices per sample; the slot's 64 bytes replace the scan of the key mask; the zero fill of the Pd / dS columns behind
+// the last valid key is dealt over the sample's slices (a sample without a valid key keeps one slice of zero tiles, which fills all
+// of them); wide_bwd_merge_planned_kernel sums the sample's n_b partial dQ' in slice order.
 #include "common.h"
 
 namespace {
@@ -30,8 +36,10 @@ constexpr int MAXQ = 8;       // query rows per sample (H * Q with one moment qu
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 
-template <int D>
-__global__ __launch_bounds__(NT) void attention_wide_bwd_kernel(const MadeWideAttnBwdArgs a) {
+// PLAN (made_attention_wide_bwd_planned): workgroup = one slot of the slice plan (include/made_hip.h) instead of (sample, blockIdx.z-th
+// equal slice); the slot's one 64-byte load replaces the scan of the sample's whole key mask, a.n_split is the slice capacity of part_dq.
+template <int D, bool PLAN = false>
+__global__ __launch_bounds__(NT) void attention_wide_bwd_kernel(const MadeWideAttnBwdArgs a, const int32_t* __restrict__ plan) {
     constexpr int DS = D / 4;                 // this wave's slice of D
     constexpr int NQF = DS / 16;              // 16-deep k-steps of the slice
     constexpr int NDT = DS / 32;              // 32-row tiles of the dQ'^T slice
@@ -46,7 +54,18 @@ __global__ __launch_bounds__(NT) void attention_wide_bwd_kernel(const MadeWideAt
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
     const int sl = wave;
-    const int64_t b = blockIdx.y;
+    int32_t pl[MADE_WIDE_PLAN_SLOT] = {};           // (PLAN) this workgroup's slot
+    if constexpr (PLAN) {
+        const u32x4* sp = (const u32x4*)(plan + MADE_WIDE_PLAN_HEAD + MADE_WIDE_PLAN_SAMPLE * a.B + (int64_t)MADE_WIDE_PLAN_SLOT * blockIdx.x);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const u32x4 v = sp[i];
+            pl[4 * i] = (int32_t)v[0]; pl[4 * i + 1] = (int32_t)v[1]; pl[4 * i + 2] = (int32_t)v[2]; pl[4 * i + 3] = (int32_t)v[3];
+        }
+        if (pl[0] < 0 || pl[0] >= a.B || pl[3] < 0 || pl[3] >= a.n_split || pl[1] < 0 || pl[2] < 0 || (int64_t)(pl[1] + pl[2]) * BK >= a.L + BK ||
+            pl[4] < 0 || pl[4] >= a.L) return;                            // unused slot (or a plan that is not this call's: never out of bounds)
+    }
+    const int64_t b = PLAN ? (int64_t)pl[0] : (int64_t)blockIdx.y;
     const int NQ = (int)a.NQ;
     const int rq = (r & 7) < NQ ? (r & 7) : NQ - 1;                 // this lane's query row (lanes r >= 8 duplicate, never stored)
     const bool live = r < NQ;
@@ -93,7 +112,25 @@ __global__ __launch_bounds__(NT) void attention_wide_bwd_kernel(const MadeWideAt
     // ---- mask bits; keys after the last valid one contribute nothing (padding is a suffix in the dataset's masks)
     int64_t l_eff = a.L;
     int first_valid = 0;
-    {
+    if constexpr (PLAN) {
+        first_valid = pl[4];
+        const int nt = pl[2];
+        if (nt <= MADE_WIDE_PLAN_SLOT_BITS) {                  // the bits came with the slot
+            uint32_t w = (uint32_t)pl[8];
+#pragma unroll
+            for (int i = 1; i < MADE_WIDE_PLAN_SLOT_BITS; ++i) w = tid == i ? (uint32_t)pl[8 + i] : w;
+            if (tid < MADE_WIDE_PLAN_SLOT_BITS) lds_mbits[tid] = w;
+        } else {                                               // a longer slice (few workgroups for the batch): bits of its own tiles from the mask
+            const int nk = nt * BK, k0 = pl[1] * BK;
+            for (int j = tid; j < ((nk + 63) & ~63); j += NT) {
+                const int key = k0 + j;
+                const float mv = maskg[key < (int)a.L ? key : (int)a.L - 1];
+                const unsigned long long bal = __ballot(j < nk && key < (int)a.L && mv != 0.f);
+                if (lane == 0) { lds_mbits[j / 32] = (uint32_t)bal; lds_mbits[j / 32 + 1] = (uint32_t)(bal >> 32); }
+            }
+        }
+        __syncthreads();                                       // (also: lds_q, written above)
+    } else {
         const int lpad = (int)((a.L + 63) / 64) * 64;
         int last = -1, first = 0x7fffffff;
         for (int j = tid; j < lpad; j += NT) {
@@ -117,17 +154,20 @@ __global__ __launch_bounds__(NT) void attention_wide_bwd_kernel(const MadeWideAt
     const float delta = ((lds_q[8 + rq] + lds_q[8 + MAXQ + rq]) + (lds_q[8 + 2 * MAXQ + rq] + lds_q[8 + 3 * MAXQ + rq])) + extra * ssum;
 
     const int64_t nsplit = a.n_split > 1 ? a.n_split : 1;
-    const int64_t tiles_all = (l_eff + BK - 1) / BK;
+    const int64_t tiles_all = PLAN ? (int64_t)pl[6] : (l_eff + BK - 1) / BK;
     const int64_t tiles_L = (a.L + BK - 1) / BK;
     const int64_t tiles_per = (tiles_all + nsplit - 1) / nsplit;
-    const int64_t tile0 = (int64_t)blockIdx.z * tiles_per;
-    const int64_t ntiles = tile0 >= tiles_all ? 0 : (tile0 + tiles_per <= tiles_all ? tiles_per : tiles_all - tile0);
+    const int64_t tile0 = PLAN ? (int64_t)pl[1] : (int64_t)blockIdx.z * tiles_per;
+    const int64_t ntiles = PLAN ? (int64_t)pl[2] : (tile0 >= tiles_all ? 0 : (tile0 + tiles_per <= tiles_all ? tiles_per : tiles_all - tile0));
+    const int64_t mb0 = PLAN ? tile0 : 0;                      // lds_mbits[0] = the bits of this tile
+    const int64_t zslice = PLAN ? (int64_t)pl[3] : (int64_t)blockIdx.z;      // this workgroup's slice of the sample ...
+    const int64_t zcount = PLAN ? (int64_t)(pl[5] > 0 ? pl[5] : 1) : nsplit; // ... of so many
 
     // tile `key0` -> stage: this wave moves pieces wave, wave + 4, ... of both tiles (1 KB each: D = 512 one row, D = 256 two)
     auto issue_tile = [&](int64_t key0, int stage) __attribute__((always_inline)) {
         constexpr int ROWS_PER_PIECE = 1024 / ROWB;
         constexpr int NPIECE = BK / ROWS_PER_PIECE;
-        const uint32_t bits = lds_mbits[key0 / BK];
+        const uint32_t bits = lds_mbits[key0 / BK - mb0];
         unsigned char* st = lds + stage * STAGE;
         const unsigned char* Kb = (const unsigned char*)Kg;
         const unsigned char* Vb = (const unsigned char*)Vg;
@@ -165,7 +205,7 @@ __global__ __launch_bounds__(NT) void attention_wide_bwd_kernel(const MadeWideAt
         const int64_t t = tile0 + tt;
         const int cur = (int)(tt & 1);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // tile t landed; the other stage is free
-        const uint32_t tbits = lds_mbits[t];
+        const uint32_t tbits = lds_mbits[t - mb0];
         const unsigned char* lds_k = lds + cur * STAGE;
         const unsigned char* lds_v = lds_k + BK * ROWB;
 
@@ -255,7 +295,7 @@ __global__ __launch_bounds__(NT) void attention_wide_bwd_kernel(const MadeWideAt
     }
     // ---- key tiles behind the last valid key: their Pd / dS columns are zero (the buffers are reused from batch to batch)
     if (wave < 2 && live) {
-        for (int64_t tz = tiles_all + blockIdx.z; tz < tiles_L; tz += nsplit) {
+        for (int64_t tz = tiles_all + zslice; tz < tiles_L; tz += zcount) {
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
                 const int64_t key0 = tz * BK + 8 * g4 + 4 * hh;
@@ -268,7 +308,7 @@ __global__ __launch_bounds__(NT) void attention_wide_bwd_kernel(const MadeWideAt
     }
 
     // ---- dQ': this slice's partial rows, merged over the key slices by the workgroup that finishes the sample last
-    if (nsplit == 1) {
+    if (!PLAN && nsplit == 1) {
         if (live) {
             bf16_t* dq = (bf16_t*)a.dQ + b * a.dq_bs + (int64_t)r * a.ld_dq + sl * DS;
 #pragma unroll
@@ -284,7 +324,7 @@ __global__ __launch_bounds__(NT) void attention_wide_bwd_kernel(const MadeWideAt
         return;
     }
     if (live) {
-        float* po = a.part_dq + ((b * nsplit + blockIdx.z) * NQ + r) * D + sl * DS;
+        float* po = a.part_dq + ((b * nsplit + zslice) * NQ + r) * D + sl * DS;
 #pragma unroll
         for (int d = 0; d < NDT; ++d)
 #pragma unroll
@@ -343,14 +383,104 @@ int launch_wide_bwd(const MadeWideAttnBwdArgs& a, hipStream_t st) {
         attr_done = true;
     }
     const int64_t nsplit = a.n_split > 1 ? a.n_split : 1;
-    hipLaunchKernelGGL((attention_wide_bwd_kernel<D>), dim3(1, (unsigned)a.B, (unsigned)nsplit), dim3(NT), lds_bytes, st, a);
+    hipLaunchKernelGGL((attention_wide_bwd_kernel<D>), dim3(1, (unsigned)a.B, (unsigned)nsplit), dim3(NT), lds_bytes, st, a, (const int32_t*)nullptr);
     int rc = made_check_launch("made_attention_wide_bwd");
     if (rc != MADE_OK || nsplit == 1) return rc;
     hipLaunchKernelGGL(wide_bwd_merge_kernel, dim3((unsigned)((a.B * a.NQ + 3) / 4)), dim3(NT), 0, st, a);
     return made_check_launch("made_attention_wide_bwd(merge)");
 }
 
+// merge of the planned launch: dQ[b, q, :] = sum of the sample's n_b slices (the plan's count) in slice order; up to eight slices, all
+// requested before the first use
+__global__ __launch_bounds__(NT) void wide_bwd_merge_planned_kernel(const MadeWideAttnBwdArgs a, const int32_t* __restrict__ plan) {
+    constexpr int MAXS = 8;
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= a.B * a.NQ) return;
+    const int64_t b = row / a.NQ, q = row % a.NQ;
+    const int D = (int)a.D;
+    const int per = D / 64;                                         // 8 or 4 columns per lane
+    const int cap = (int)a.n_split;
+    int ns = plan[MADE_WIDE_PLAN_HEAD + MADE_WIDE_PLAN_SAMPLE * b + 2];
+    ns = ns < 1 ? 1 : (ns > MAXS ? MAXS : ns);
+    ns = ns > cap ? cap : ns;
+    f32x4 t0[MAXS], t1[MAXS];
+#pragma unroll
+    for (int sp = 0; sp < MAXS; ++sp) {
+        const float* pp = a.part_dq + ((b * cap + (sp < ns ? sp : ns - 1)) * a.NQ + q) * D + lane * per;
+        t0[sp] = *(const f32x4*)pp;
+        t1[sp] = *(const f32x4*)(pp + (per == 8 ? 4 : 0));
+    }
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll
+    for (int sp = 0; sp < MAXS; ++sp) {
+        if (sp < ns) {
+            acc[0] += t0[sp][0]; acc[1] += t0[sp][1]; acc[2] += t0[sp][2]; acc[3] += t0[sp][3];
+            acc[4] += t1[sp][0]; acc[5] += t1[sp][1]; acc[6] += t1[sp][2]; acc[7] += t1[sp][3];
+        }
+    }
+    bf16_t* dq = (bf16_t*)a.dQ + b * a.dq_bs + q * a.ld_dq + lane * per;
+    bf16x4 p0; p0[0] = (bf16_t)acc[0]; p0[1] = (bf16_t)acc[1]; p0[2] = (bf16_t)acc[2]; p0[3] = (bf16_t)acc[3];
+    *(bf16x4*)dq = p0;
+    if (per == 8) {
+        bf16x4 p1; p1[0] = (bf16_t)acc[4]; p1[1] = (bf16_t)acc[5]; p1[2] = (bf16_t)acc[6]; p1[3] = (bf16_t)acc[7];
+        *(bf16x4*)(dq + 4) = p1;
+    }
+}
+
+template <int D>
+int launch_wide_bwd_planned(const MadeWideAttnBwdArgs& a, const int32_t* plan, int n_slots, hipStream_t st) {
+    constexpr size_t kBase = (size_t)2 * 2 * BK * D * 2 + (size_t)(4 * 2 * BK * MAXQ + 8 + 4 * MAXQ) * 4;
+    const size_t lds_bytes = kBase + (size_t)((a.L + 63) / 64 * 2 + 2) * 4;
+    if (lds_bytes > 160 * 1024) {
+        made_set_error("made_attention_wide_bwd_planned: L=%lld keys: the mask bit row does not fit in LDS beside the K / V stages", (long long)a.L);
+        return MADE_ERR_UNSUPPORTED;
+    }
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute((const void*)attention_wide_bwd_kernel<D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) {
+            made_set_error("made_attention_wide_bwd_planned: cannot reserve LDS: %s", hipGetErrorString(e));
+            return MADE_ERR_HIP;
+        }
+        attr_done = true;
+    }
+    hipLaunchKernelGGL((attention_wide_bwd_kernel<D, true>), dim3((unsigned)n_slots), dim3(NT), lds_bytes, st, a, plan);
+    int rc = made_check_launch("made_attention_wide_bwd_planned");
+    if (rc != MADE_OK) return rc;
+    hipLaunchKernelGGL(wide_bwd_merge_planned_kernel, dim3((unsigned)((a.B * a.NQ + 3) / 4)), dim3(NT), 0, st, a, plan);
+    return made_check_launch("made_attention_wide_bwd_planned(merge)");
+}
+
 }  // namespace
+
+extern "C" int made_attention_wide_bwd_planned(const MadeWideAttnBwdArgs* args, const void* plan, int32_t n_slots, void* stream) {
+    MADE_REQUIRE(args != nullptr && plan != nullptr, "made_attention_wide_bwd_planned: null args / plan");
+    const MadeWideAttnBwdArgs& a = *args;
+    MADE_REQUIRE(a.Q && a.dO && a.O && a.K && a.V && a.lse && a.Pd && a.dS && a.dQ, "made_attention_wide_bwd_planned: null tensor");
+    MADE_REQUIRE(a.B >= 0 && a.NQ > 0 && a.L > 0, "made_attention_wide_bwd_planned: bad dims");
+    MADE_UNSUPPORTED(a.NQ <= MAXQ && (a.D == 256 || a.D == 512) && a.key_mask != nullptr,
+                     "made_attention_wide_bwd_planned: NQ <= %d query rows per sample, D in {256, 512} and a key mask", MAXQ);
+    MADE_UNSUPPORTED(a.B <= n_slots && n_slots <= 1024, "made_attention_wide_bwd_planned: B <= n_slots <= 1024");
+    MADE_UNSUPPORTED(a.q_bs % 8 == 0 && a.ld_q % 8 == 0 && a.do_bs % 8 == 0 && a.ld_do % 8 == 0 && a.o_bs % 8 == 0 && a.ld_o % 8 == 0 &&
+                     a.k_bs % 8 == 0 && a.ldk % 8 == 0 && a.v_bs % 8 == 0 && a.ldv % 8 == 0 && a.p_bs % 4 == 0 && a.ld_p % 4 == 0 &&
+                     a.dq_bs % 4 == 0 && a.ld_dq % 4 == 0, "made_attention_wide_bwd_planned: strides must keep the rows aligned (16 bytes in, 8 bytes out)");
+    MADE_UNSUPPORTED(((uintptr_t)a.Q % 16) == 0 && ((uintptr_t)a.dO % 16) == 0 && ((uintptr_t)a.O % 16) == 0 && ((uintptr_t)a.K % 16) == 0 &&
+                     ((uintptr_t)a.V % 16) == 0 && ((uintptr_t)a.Pd % 8) == 0 && ((uintptr_t)a.dS % 8) == 0 && ((uintptr_t)a.dQ % 8) == 0 &&
+                     ((uintptr_t)plan % 16) == 0, "made_attention_wide_bwd_planned: base pointers must be aligned");
+    MADE_REQUIRE(a.ld_p >= a.L, "made_attention_wide_bwd_planned: ld_p < L");
+    MADE_REQUIRE(a.drop.p >= 0.f && a.drop.p < 1.f, "made_attention_wide_bwd_planned: dropout p out of [0,1)");
+    if (a.dattc && !a.extra) {
+        MADE_REQUIRE(a.vbias != nullptr && a.hd > 0 && a.hd % 8 == 0, "made_attention_wide_bwd_planned: dattc needs vbias and hd (a multiple of 8)");
+        MADE_UNSUPPORTED(a.hd * a.NQ == a.D, "made_attention_wide_bwd_planned: dattc needs the one-query layout NQ * hd == D; pass `extra` otherwise");
+    }
+    MADE_REQUIRE(a.n_split >= 1 && a.n_split <= 8 && a.part_dq != nullptr, "made_attention_wide_bwd_planned: n_split = the slice capacity of part_dq (1..8)");
+    if (a.B == 0) return MADE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    return a.D == 512 ? launch_wide_bwd_planned<512>(a, (const int32_t*)plan, n_slots, st) : launch_wide_bwd_planned<256>(a, (const int32_t*)plan, n_slots, st);
+}
 
 extern "C" int made_attention_wide_bwd(const MadeWideAttnBwdArgs* args, void* stream) {
     MADE_REQUIRE(args != nullptr, "made_attention_wide_bwd: null args");

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -428,12 +428,50 @@ def attention_bits_decode(bits: Tensor, B: int, H: int, Lq: int, Lk: int) -> Ten
     return b.permute(0, 1, 3, 2, 4).reshape(B, H, Lq, nkt * 32)[..., :Lk].bool()
 
 
+class WidePlan(NamedTuple):
+    """Slice plan of the decoder's memory-space cross-attention (made_wide_slice_plan): `plan=` of attention_wide / attention_wide_bwd."""
+    words: Tensor            # int32 [_lib.wide_plan_words(B, n_slots)]
+    B: int
+    L: int
+    n_slots: int             # workgroups of the planned launches
+    max_slices: int          # slices per sample at most: the capacity the partial buffers need
+
+    def header(self):
+        """(cap, used slots, n_slots, max_slices) -- reads the device (tests, tools)"""
+        return tuple(int(x) for x in self.words[:_lib.WIDE_PLAN_HEAD].tolist())
+
+    def samples(self) -> Tensor:
+        """int32 [B, 4]: tiles, first slot, slices, first valid key"""
+        return self.words[_lib.WIDE_PLAN_HEAD:_lib.WIDE_PLAN_HEAD + _lib.WIDE_PLAN_SAMPLE * self.B].view(self.B, _lib.WIDE_PLAN_SAMPLE)
+
+    def slots(self) -> Tensor:
+        """int32 [n_slots, 16]: sample, first tile, tiles, slice, first valid key, slices, sample's tiles, 0, 8 words of key bits"""
+        return self.words[_lib.WIDE_PLAN_HEAD + _lib.WIDE_PLAN_SAMPLE * self.B:][:_lib.WIDE_PLAN_SLOT * self.n_slots].view(self.n_slots, _lib.WIDE_PLAN_SLOT)
+
+
+def wide_slice_plan(key_mask: Tensor, *, n_slots: int, max_slices: int = 8, order: Optional[Tensor] = None, out: Optional[Tensor] = None) -> WidePlan:
+    """Deal the key tiles of a padded batch over n_slots workgroups by length (made_wide_slice_plan): once per step, for every decoder
+    layer's forward and backward.  key_mask [B, L] f32; order: batch_order(key_mask) or None."""
+    assert key_mask.dim() == 2
+    B, L = key_mask.shape
+    words = _lib.wide_plan_words(B, n_slots)
+    if out is None:
+        out = torch.empty(words, device=key_mask.device, dtype=torch.int32)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= words
+    if order is not None:
+        assert order.dtype == torch.int32 and order.numel() == B
+    check(lib().made_wide_slice_plan(_p(_f32(key_mask.contiguous(), "key_mask")), B, L, n_slots, max_slices, _p(order), _p(out), 4 * out.numel(),
+                                     _stream()), "made_wide_slice_plan")
+    return WidePlan(out, B, L, n_slots, max_slices)
+
+
 def attention_wide(Q: Tensor, K: Tensor, V: Tensor, O: Tensor, *, scale: float, Kadd: Optional[Tensor] = None,
                    key_mask: Optional[Tensor] = None, shared_q: bool = False, n_split: int = 1,
                    part_o: Optional[Tensor] = None, part_ml: Optional[Tensor] = None, drop=None,
-                   sum_out: Optional[Tensor] = None, lse_out: Optional[Tensor] = None) -> Tensor:
+                   sum_out: Optional[Tensor] = None, lse_out: Optional[Tensor] = None, plan: Optional[WidePlan] = None) -> Tensor:
     """Single-head attention with head dim = D.  Q [B|1, NQ1, NQ2, D], K/Kadd/V [B, L, D], O [B, NQ1, NQ2, D]
-    (strided views fine, unit inner stride).  shared_q: the same queries for every batch entry (Q.shape[0] == 1)."""
+    (strided views fine, unit inner stride).  shared_q: the same queries for every batch entry (Q.shape[0] == 1).
+    plan (wide_slice_plan of the same key_mask): the launch follows the plan and n_split is the slice capacity of part_o / part_ml."""
     assert Q.dim() == 4 and O.dim() == 4 and K.dim() == 3 and V.dim() == 3
     assert Q.stride(3) == 1 and O.stride(3) == 1 and K.stride(2) == 1 and V.stride(2) == 1
     assert Q.dtype == K.dtype == V.dtype
@@ -452,7 +490,9 @@ def attention_wide(Q: Tensor, K: Tensor, V: Tensor, O: Tensor, *, scale: float, 
     a.o_bs, a.o_s1, a.o_s2 = O.stride(0), O.stride(1), O.stride(2)
     a.scale = scale
     nq = a.NQ1 * a.NQ2
-    if n_split > 1:
+    if plan is not None:
+        assert key_mask is not None and (plan.B, plan.L) == (B, L) and n_split >= plan.max_slices, "the plan is not this call's"
+    if n_split > 1 or plan is not None:
         if part_o is None:
             part_o = torch.empty(B * n_split * nq * D, device=Q.device, dtype=torch.float32)
             part_ml = torch.empty(B * n_split * nq * 4, device=Q.device, dtype=torch.float32)
@@ -469,8 +509,9 @@ def attention_wide(Q: Tensor, K: Tensor, V: Tensor, O: Tensor, *, scale: float, 
     esz = 4 if a.dtype == F32 else 2
     _timed("attention_wide_" + ("f32" if a.dtype == F32 else "bf16"), 4.0 * B * nq * L * D,
            esz * B * (2 * L * D + 2 * nq * D),
-           lambda: check(lib().made_attention_wide(C.byref(a), _stream()), "made_attention_wide"),
-           f"B={B} NQ={nq} L={L} D={D} kadd={int(Kadd is not None)}")
+           (lambda: check(lib().made_attention_wide(C.byref(a), _stream()), "made_attention_wide")) if plan is None else
+           (lambda: check(lib().made_attention_wide_planned(C.byref(a), _p(plan.words), plan.n_slots, _stream()), "made_attention_wide_planned")),
+           f"B={B} NQ={nq} L={L} D={D} kadd={int(Kadd is not None)}" + (" planned" if plan is not None else ""))
     return O
 
 

@@ -349,9 +349,10 @@ def softmax_bwd(S: Tensor, dP: Tensor, mask: Optional[Tensor], rows_per_mask: in
 def attention_wide_bwd(Q: Tensor, dO: Tensor, O: Tensor, K: Tensor, V: Tensor, lse: Tensor, Pd: Tensor, dS: Tensor, dQ: Tensor, *, scale: float,
                        key_mask: Optional[Tensor] = None, ssum: Optional[Tensor] = None, extra: Optional[Tensor] = None,
                        dattc: Optional[Tensor] = None, vbias: Optional[Tensor] = None, hd: int = 0, drop=None, n_split: int = 1,
-                       part_dq: Optional[Tensor] = None) -> Tensor:
+                       part_dq: Optional[Tensor] = None, plan=None) -> Tensor:
     """Backward of the decoder's memory-space cross-attention in ONE launch (made_attention_wide_bwd).  Q / dO / O / dQ [B, NQ, D] bf16
-    (NQ <= 8), K / V [B, L, D] bf16, lse / ssum / extra [B, NQ] f32, Pd / dS [B, NQ, ld_p >= L] bf16 views."""
+    (NQ <= 8), K / V [B, L, D] bf16, lse / ssum / extra [B, NQ] f32, Pd / dS [B, NQ, ld_p >= L] bf16 views.
+    plan (ops.wide_slice_plan of the same key_mask): the launch follows the plan and n_split is the slice capacity of part_dq."""
     assert Q.dim() == 3 and dO.shape == Q.shape and O.shape == Q.shape and dQ.shape == Q.shape and K.dim() == 3 and V.shape == K.shape
     B, NQ, D = Q.shape
     L = K.shape[1]
@@ -370,13 +371,17 @@ def attention_wide_bwd(Q: Tensor, dO: Tensor, O: Tensor, K: Tensor, V: Tensor, l
     a.q_bs, a.ld_q, a.do_bs, a.ld_do, a.o_bs, a.ld_o = Q.stride(0), Q.stride(1), dO.stride(0), dO.stride(1), O.stride(0), O.stride(1)
     a.k_bs, a.ldk, a.v_bs, a.ldv = K.stride(0), K.stride(1), V.stride(0), V.stride(1)
     a.scale = float(scale)
-    if n_split > 1:
+    if plan is not None:
+        assert key_mask is not None and (plan.B, plan.L) == (B, L) and n_split >= plan.max_slices, "the plan is not this call's"
+    if n_split > 1 or plan is not None:
         assert part_dq is not None and part_dq.dtype == torch.float32 and part_dq.numel() >= B * n_split * NQ * D
         a.n_split, a.part_dq = n_split, _p(part_dq)
     if drop is not None and drop[2] > 0.0:
         set_drop(a.drop, drop)
     _timed("made_attention_wide_bwd", 6.0 * B * NQ * L * D, 2.0 * B * (2 * L * D + 4 * NQ * D + 2 * NQ * L),
-                lambda: check(lib().made_attention_wide_bwd(C.byref(a), _stream()), "made_attention_wide_bwd"), f"B={B} NQ={NQ} L={L} D={D}")
+                (lambda: check(lib().made_attention_wide_bwd(C.byref(a), _stream()), "made_attention_wide_bwd")) if plan is None else
+                (lambda: check(lib().made_attention_wide_bwd_planned(C.byref(a), _p(plan.words), plan.n_slots, _stream()), "made_attention_wide_bwd_planned")),
+                f"B={B} NQ={NQ} L={L} D={D}" + (" planned" if plan is not None else ""))
     return dQ
 
 

@@ -32,6 +32,8 @@ from .config import MadeConfig
 from .engine import MadeEngine
 from .ops import Seg, round_up
 
+WIDE_SLICES = 8          # slices per sample of the planned cross-attention at most = the capacity of the workspace's part_o / part_ml (engine.py)
+
 Tensor = torch.Tensor
 XA = "video_guided_to_music_pooling_cross_transformer"
 
@@ -533,6 +535,8 @@ class MadeTrainer(MadeEngine):
         i32 = torch.int32
         ws.update(rows_v=(E(B * Tv, dtype=i32), E(1, dtype=i32)), rows_a=(E(B * Ta, dtype=i32), E(1, dtype=i32)), rows_f=(E(rows, dtype=i32), E(1, dtype=i32)),
                   order_v=E(B, dtype=i32), order_a=E(B, dtype=i32), order_f=E(B, dtype=i32))
+        # slice plan of the decoder's cross-attention (one workgroup per CU, up to WIDE_SLICES slices per sample): made once per step
+        ws.update(wide_plan=E(_lib.wide_plan_words(B, self._wide_slots()), dtype=i32))
         # decoder: saved activations and per-layer output gradients as [nd, ...] stacks (uniform layer stride), so the weight
         # gradients of all 6 layers are a handful of layer-batched products after the loop instead of 60 tiny launches inside it
         BQ = B * Q
@@ -611,6 +615,10 @@ class MadeTrainer(MadeEngine):
             self._order[fm.data_ptr()] = ops.batch_order(fm, out=tw["order_v"])
             self._rows[fus_mask.data_ptr()] = ops.row_index(fus_mask, out=tw["rows_f"])
             self._order[fus_mask.data_ptr()] = ops.batch_order(fus_mask, out=tw["order_f"])
+            # the decoder's cross-attention (6 layers, forward and backward) deals its key tiles over the chip by the samples' lengths
+            self._wide_plan = (ops.wide_slice_plan(fus_mask, n_slots=self._wide_slots(), max_slices=WIDE_SLICES,
+                                                   order=self._order[fus_mask.data_ptr()], out=tw["wide_plan"])
+                               if "regression" not in c.mml_localization and self._wide_planned_ok(B, H * Q, D) else None)
             pos = ops.sine_pe(fus_mask, P["dim_t"], out=ws["pos"])
             self._encode_train(self._inputs[0], fm, "video", ws, tw, 0)
         self._encode_train(self._inputs[1], sm, "audio", ws, tw, Tv)
@@ -823,6 +831,11 @@ class MadeTrainer(MadeEngine):
         hs = ws["hs"]
         GQ = tw["GQ"]                                        # [B, 2, nd, H*Q, D]: part 1 holds the q' rows of every layer
         n_split = int(_lib.variant_env("MADE_WIDE_NSPLIT", "0")) or max(1, min(8, 256 // max(B, 1)))   # few queries, long memory: keys split over workgroups (knob for measurements)
+        # the planned launch (key tiles dealt by length, made_wide_slice_plan) unless the shape is not its own; MADE_WIDE_PLANNED=0 (read at
+        # every call, for same-process A/B runs): n_split equal slices per sample
+        wplan = self._wide_plan if _lib.variant_env("MADE_WIDE_PLANNED", "1") != "0" else None
+        if wplan is not None:
+            n_split = WIDE_SLICES
         t3_stack = tw["dstack"]["tgt"][1:]                   # [nd, B*Q, D]: slot l + 1 = layer l's output (t3)
         for l in range(nd):
             p, d = f"detr_transformer.decoder.layers.{l}", f"d.{l}"
@@ -839,7 +852,7 @@ class MadeTrainer(MadeEngine):
             ops.attention_wide(qprime.view(B, H, Q, D), mempos3, mem3, pooled.view(B, Q, H, D).permute(0, 2, 1, 3), scale=ca_scale,
                                key_mask=fus_mask, drop=self._drop(f"dec.{l}" + ".ca_attn", pd), sum_out=s_out,
                                n_split=n_split, part_o=ws["part_o"], part_ml=ws["part_ml"],
-                               lse_out=tw["ca_lse"][l] if stage else None)
+                               lse_out=tw["ca_lse"][l] if stage else None, plan=wplan)
             if Q > 1:
                 tw[d + ".s"].view(B, Q, H).copy_(s_out.view(B, H, Q).permute(0, 2, 1))
             attc = tw[d + ".attc"]
@@ -942,6 +955,16 @@ class MadeTrainer(MadeEngine):
         if st is None:
             st = self._opt_st = torch.cuda.Stream(device=self.device)
         return st
+
+    def _wide_slots(self) -> int:
+        """workgroups of the planned cross-attention launches: one per CU (two 64 KB K / V stages each)"""
+        if getattr(self, "_wide_slots_n", None) is None:
+            self._wide_slots_n = max(8, min(1024, _lib.device_info()[1]))
+        return self._wide_slots_n
+
+    def _wide_planned_ok(self, B: int, HQ: int, D: int) -> bool:
+        """shapes made_attention_wide_planned takes (include/made_hip.h); others keep made_attention_wide's equal slices"""
+        return self.tc == torch.bfloat16 and D in (256, 512) and HQ <= 32 and B <= self._wide_slots()
 
     def _dec_stage_chain(self) -> bool:
         """The training decoder's fused chain (made_dec_stage with the training options, in-launch merge of the memory-space attention,
@@ -1303,6 +1326,9 @@ class MadeTrainer(MadeEngine):
                 ops.linear(GQ[0, 1].reshape(nd * HQ, D), mempos3[0], None, M=nd * HQ, N=L, K=D, batch=B, a_z_stride=GQ.stride(0), w_z_stride=L * D,
                            segs=[Seg(out=S_all, ldo=Lp, rows_per_batch=HQ, out_batch_stride=B * HQ * Lp, out_z_stride=HQ * Lp)])
             n_split_b = int(_lib.variant_env("MADE_WIDE_NSPLIT", "0")) or max(1, min(8, 256 // max(B, 1)))
+            wplan = self._wide_plan if HQ <= 8 and _lib.variant_env("MADE_WIDE_PLANNED", "1") != "0" else None      # (as in forward_train)
+            if wplan is not None:
+                n_split_b = WIDE_SLICES
             if stage:
                 # the shared output norm's backward depends on the heads only: all layers in ONE launch ahead of the dependent chain
                 gN = tw["dgN"]
@@ -1373,7 +1399,7 @@ class MadeTrainer(MadeEngine):
                     tr.attention_wide_bwd(qprime, dpooled, tw[d + ".pooled"].view(B, HQ, D), mempos3, mem3, tw["ca_lse"][l].view(B, HQ),
                                           PdS[:, 0, l], PdS[:, 1, l], g_q, scale=ca_scale, key_mask=fus_mask, ssum=tw[d + ".s"].view(B, HQ),
                                           dattc=dattc, vbias=P[p + ".ca.in.b"][2 * D:], hd=hd, drop=self._drop(f"dec.{l}" + ".ca_attn", pd),
-                                          n_split=n_split_b, part_dq=ws["part_o"])
+                                          n_split=n_split_b, part_dq=ws["part_o"], plan=wplan)
                 else:
                     tr.head_bias_bwd(dattc, tw[d + ".s"], P[p + ".ca.in.b"][2 * D:], G[p + ".ca.in.b"][2 * D:], tw["d_ds"], H)
                     d_ds = tw["d_ds"]                                 # rows (b, q), columns h; the softmax backward numbers its rows (b, h, q)
