@@ -1032,6 +1032,41 @@ int made_gather_pairs(const int32_t* vi, const int32_t* mi, int64_t P, int64_t N
                       void* frame_out, int64_t frame_out_stride, void* seg_out, int64_t seg_out_stride,
                       float* fmask_out, float* smask_out, float* video_out, float* music_out, void* stream);
 
+/* made_gather_rows: dst[r, :] = src[index[r], :] for r < R, in one launch (a wave per row, 16-byte accesses): the unique AST
+ * feature rows of a library spread over the overlapping windows that share them (mgsv_amd/music.py encode_windows).  src [U, C]
+ * and dst [R, C] contiguous rows of `dtype` (MADE_F32 or MADE_BF16), index [R] device int32.  An index < 0 or >= U writes a zero
+ * row and reads nothing.  C * element size must be a multiple of 16 and both buffers 16-byte aligned. */
+int made_gather_rows(const void* src, int64_t U, const int32_t* index, int64_t R, int64_t C, void* dst, int32_t dtype, void* stream);
+
+/* made_group_topw: for every (row i, selected column sel[i, j]) of made_topk_groups' output the best w columns of that column's
+ * group in row i of sims [Nv, Nm] f32 (row stride ld >= Nm).  col_group [Nm] int32 is the group of every column (the array
+ * made_topk_groups selected with), start [n_groups + 1] / cols [n_cols] int32 the groups' members as a CSR built once on the host:
+ * group g holds cols[start[g] .. start[g + 1]); only those members are read, never the row.  idx_out / score_out [Nv, K, w], in
+ * made_topk_groups' total order and with its rules: score descending, then column ascending; NaN ranks below every number, -0
+ * equals +0 (and is reported as +0).  Position 0 is sel[i, j] itself (the group's representative column).  Positions past the
+ * group's size, and every position of a slot with sel < 0, hold -1 / -inf.  Members outside [0, Nm) and CSR ranges outside
+ * [0, n_cols] are ignored.  1 <= w <= 16. */
+int made_group_topw(const float* sims, int64_t ld, const int32_t* sel, const int32_t* col_group, const int32_t* start,
+                    const int32_t* cols, int64_t n_cols, int64_t Nv, int64_t Nm, int64_t n_groups, int64_t K, int64_t w,
+                    int32_t* idx_out, float* score_out, void* stream);
+
+/* made_merge_moments: the moments of P (video, track) entries on the track's own time axis from the moments of the track's w
+ * windows, one wave per entry, no atomics.  win_col / win_score [P, w] = made_group_topw's columns (-1: no window) and
+ * similarities; cand [P, w, Q, 3] f32 = every query's (start, end, foreground probability) in seconds on its window's axis,
+ * unclamped (made_span_iou's pred_out over single-query rows; Q = 1 and use_prob = 0 for the regression head, whose third value
+ * is ignored); offset / duration [Nm] f32 = every column's window offset and duration in seconds (duration may be NULL).
+ * A candidate's span is clamped to [0, min(max_m_duration, duration[col])], then offset[col] is added (f32).  Total order:
+ * window similarity descending, foreground probability descending (skipped when use_prob = 0), column ascending, query
+ * ascending; similarities and probabilities compare as in made_topk_groups (NaN lowest, -0 = +0).  Greedy suppression walks
+ * that order: a candidate is dropped when its IoU with one kept before it is > nms_iou, with (reference
+ * music_detr/span_utils.py:39-66 temporal_iou) inter = max(0, min(e1, e2) - max(s1, s2)), union = (e1 - s1) + (e2 - s2) - inter,
+ * iou = union > 0 ? inter / union : 0, f32 with one rounding per operation.  start_out / end_out / conf_out f32 and window_out
+ * int32 [P, n]: the first n kept candidates (conf = the probability, NaN when use_prob = 0; window = the candidate's column);
+ * slots past the number kept hold NaN / -1.  w * Q <= 256 (MADE_ERR_UNSUPPORTED otherwise); nms_iou >= 0. */
+int made_merge_moments(const float* cand, const int32_t* win_col, const float* win_score, const float* offset, const float* duration,
+                       int64_t P, int64_t Nm, int64_t w, int64_t Q, int32_t use_prob, float max_m_duration, float nms_iou, int64_t n,
+                       float* start_out, float* end_out, float* conf_out, int32_t* window_out, void* stream);
+
 /* ==========================================================================================
  * Frames: decoded video frames -> the input of the CLIP ViT-B/32 visual tower (mgsv_amd/frames.py).  The reference extracts its
  * frame features with OpenAI's clip package (model/model_Base.py:286-289,406-450) after torchvision preprocessing

@@ -304,6 +304,9 @@ SIGNATURES = {
     "made_topk_groups": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, i64, vp]),
     "made_gather_pairs": (C.c_int, [vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32,
                                     vp, i64, vp, i64, vp, vp, vp, vp, vp]),
+    "made_gather_rows": (C.c_int, [vp, i64, vp, i64, i64, vp, i32, vp]),
+    "made_group_topw": (C.c_int, [vp, i64, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp]),
+    "made_merge_moments": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, f32, f32, i64, vp, vp, vp, vp, vp]),
     "made_frames_preprocess": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i32, i64, vp, vp]),
     "made_audio_resample": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp]),
     "made_audio_fbank": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, i32, vp, vp]),

@@ -109,6 +109,20 @@ __device__ __forceinline__ void store_from_f32(void* p, int dtype, int64_t idx, 
     else ((bf16_t*)p)[idx] = (bf16_t)v;
 }
 
+// Order-preserving unsigned key of a score (made_topk_groups, made_group_topw, made_merge_moments): NaN -> 1 (below -inf), 0 is "no item" (fill), -0 is +0.  Finite values and the
+// infinities map to keys >= 0x007FFFFF, so the two reserved keys never collide with a number.
+__device__ __forceinline__ uint32_t score_key(float f) {
+    if (f != f) return 1u;
+    const uint32_t u = f == 0.f ? 0u : __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float key_score(uint32_t k) {
+    if (k == 0u) return -INFINITY;
+    if (k == 1u) return __uint_as_float(0x7FC00000u);
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
 // Slot of query q (0 .. 31 inside its group of 32) in the dropout bit cache of made_attention (MadeAttnArgs.keep_bits): register e of
 // a 32 x 32 MFMA accumulator tile holds row (e & 3) + 8 (e >> 2) + 4 hh, so the words at slots 2 e and 2 e + 1 are the two halves of
 // the 64-lane keep mask of register e.

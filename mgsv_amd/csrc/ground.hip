@@ -11,20 +11,6 @@ constexpr uint32_t SLOT_OUT = 0xFFFFFFFFu;
 constexpr uint32_t TIE = 0x40000000u;   // group table: TIE + (lowest column of the group at the threshold score)
 constexpr uint32_t TIE_NONE = 0x7FFFFFFFu;
 
-// Order-preserving unsigned key of a score: NaN -> 1 (below -inf), 0 is "no item" (fill), -0 is +0.  Finite values and the
-// infinities map to keys >= 0x007FFFFF, so the two reserved keys never collide with a number.
-__device__ __forceinline__ uint32_t score_key(float f) {
-    if (f != f) return 1u;
-    const uint32_t u = f == 0.f ? 0u : __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float key_score(uint32_t k) {
-    if (k == 0u) return -INFINITY;
-    if (k == 1u) return __uint_as_float(0x7FC00000u);
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
 struct TopkShared {
     int hist[256];
     uint32_t cand_key[256];

@@ -336,10 +336,12 @@ class Uni_model(nn.Module):
     # ---- grounding (mgsv_amd/grounding.py): each video's best k tracks and the moment in each
     @torch.no_grad()
     def ground(self, frame_feats, frame_masks, video_feats, segment_feats, segment_masks, music_feats, k: int, v_duration=None,
-               m_duration=None, sims=None, group_id=None, pair_batch: int = 64):
+               m_duration=None, sims=None, group_id=None, pair_batch: int = 64, windows=None, windows_per_track: int = 1,
+               moments: int = 1, nms_iou: float = 0.5):
         """Tower outputs as this module's forward returns them (feat_map["frame_feats"] / ["video_feats"] with mask_map["frame_masks"]
         for the videos, feat_map["segment_feats"] / ["music_feats"] with mask_map["segment_masks"] for the tracks; any device, f32 or
-        the compute dtype) -> grounding.Grounding with device tensors [N_v, k].  group_id [N_m]: columns sharing a music id."""
+        the compute dtype) -> grounding.Grounding with device tensors [N_v, k].  group_id [N_m]: columns sharing a music id.
+        windows (mgsv_amd.windows.Windows): the tracks are windows of longer tracks (grounding.ground)."""
         from ..engine import Encoded
         from ..grounding import ground
         eng = self._engine_ready()
@@ -350,5 +352,6 @@ class Uni_model(nn.Module):
                            duration=dur.to(dev, f32).contiguous() if torch.is_tensor(dur) else None)
 
         return ground(eng, rec(frame_feats, frame_masks, video_feats, v_duration), rec(segment_feats, segment_masks, music_feats, m_duration),
-                      k, sims=sims, group_id=group_id, pair_batch=pair_batch)
+                      k, sims=sims, group_id=group_id, pair_batch=pair_batch, windows=windows, windows_per_track=windows_per_track,
+                      moments=moments, nms_iou=nms_iou)
 

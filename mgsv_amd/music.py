@@ -359,11 +359,11 @@ class MusicEncoder:
         return ops.masked_mean(ws["y2"].view(B, 2, WIDTH), ws["ones"], out=out)     # (y[0] + y[1]) / 2
 
     # -------------------------------------------------------------------------------------------- audio -> spectrograms
-    def resample(self, tracks: Sequence, max_m_duration: float = 240) -> Tuple[Tensor, List[int]]:
+    def resample(self, tracks: Sequence, max_m_duration: float = 240, out_len: Optional[int] = None) -> Tuple[Tensor, List[int]]:
         """Channel 0 of every (waveform, sr) at 16 kHz, zero-padded / truncated: (f32 [N, int(16000 max_m_duration)], the resampled
-        lengths before padding)."""
+        lengths before padding).  out_len: that many samples per row instead (encode_windows: whole tracks)."""
         dev = self.device
-        total = int(SR * max_m_duration)
+        total = int(SR * max_m_duration) if out_len is None else int(out_len)
         chans = [_channel0(w) for w, _ in tracks]
         rates = [int(sr) for _, sr in tracks]
         n = len(chans)
@@ -467,3 +467,46 @@ class MusicEncoder:
             self.tower(ws["patches"], ws["feat"])
             flat[torch.from_numpy(sel[c0:c0 + m]).to(self.device)] = ws["feat"][:m]
         return feats, torch.from_numpy(masks).to(self.device), torch.tensor([n / SR for n in n16], dtype=torch.float64)
+
+    # -------------------------------------------------------------------------------------------- whole tracks -> windows
+    @torch.no_grad()
+    def encode_windows(self, tracks: Sequence, stride: float = 2.5, filter: float = 4.0, window: float = 240, hop: float = 120,
+                       group_samples: int = 1 << 26):
+        """(feats [Nw, S, 768] f32, mask [Nw, S] f32, Windows) of N whole tracks cut into overlapping windows of `window` seconds every
+        `hop` seconds (mgsv_amd/windows.py: window j of a track is what encode_tracks returns for its crop with max_m_duration =
+        window, bit for bit; a track no longer than the window gives its encode_tracks row).  Every track is resampled once, every
+        distinct (track, first sample, sample count) segment runs through the tower once (Windows.n_encoded rows; at hop = window / 2
+        about half of the windows' segments) and one made_gather_rows spreads the rows over the windows.  Tracks are resampled in
+        groups whose padded [n, longest] buffer holds at most group_samples floats (one track alone may exceed it)."""
+        from .windows import library_descriptors, window_table
+        S = len(segment_table(0, stride, filter, 0, window)[0])
+        self._set_products()
+        dev = self.device
+        chans = [_channel0(w) for w, _ in tracks]
+        n16 = [resampled_length(int(c.shape[0]), sr) for c, (_, sr) in zip(chans, tracks)]
+        win, masks, uniq, index = library_descriptors(n16, window, hop, stride, filter)
+        need = [int(SR * (window_table(n, window, hop, stride)[0][-1] + window)) for n in n16]     # samples the last window ends at
+        rows = torch.empty(max(len(uniq), 1), WIDTH, device=dev)
+        ws = self._workspace()
+        t0 = 0
+        while t0 < len(tracks):                                            # a group of consecutive tracks; `uniq` is track-major
+            t1, longest = t0 + 1, need[t0]
+            while t1 < len(tracks) and (t1 - t0 + 1) * max(longest, need[t1]) <= group_samples and t1 - t0 < TRACKS_MAX:
+                longest = max(longest, need[t1])
+                t1 += 1
+            pcm16, got = self.resample(tracks[t0:t1], out_len=longest)
+            assert got == n16[t0:t1]
+            u0, u1 = np.searchsorted(uniq[:, 0], [t0, t1])
+            d = np.zeros(u1 - u0, _SDESC)
+            d["first"] = (uniq[u0:u1, 0] - t0) * longest + uniq[u0:u1, 1]
+            d["count"] = uniq[u0:u1, 2]
+            for c0 in range(0, len(d), self.chunk):
+                m = min(self.chunk, len(d) - c0)
+                ops.audio_fbank(pcm16.view(-1), _desc_tensor(d[c0:c0 + m], dev), self.window, self.twiddle, self.mel, ws["spec"])
+                ops.ast_patches(ws["spec"], ws["patches"])
+                self.tower(ws["patches"], ws["feat"])
+                rows[u0 + c0:u0 + c0 + m].copy_(ws["feat"][:m])
+            t0 = t1
+        feats = torch.empty(len(win), S, WIDTH, device=dev)
+        ops.gather_rows(rows[:len(uniq)], torch.from_numpy(index).to(dev), feats.view(len(win) * S, WIDTH))
+        return feats, torch.from_numpy(masks).to(dev), win

@@ -951,3 +951,52 @@ def ast_patches(spec: Tensor, patches: Tensor, n: Optional[int] = None) -> Tenso
     assert patches.dim() == 2 and patches.stride(1) == 1 and patches.shape[0] >= n * 1212 and patches.shape[1] >= 256
     check(lib().made_ast_patches(_p(spec), n, _p(patches), dt_of(patches), patches.stride(0), _stream()), "made_ast_patches")
     return patches
+
+
+def gather_rows(src: Tensor, index: Tensor, dst: Tensor) -> Tensor:
+    """made_gather_rows: dst[r] = src[index[r]] (a zero row where the index is < 0 or >= len(src)), one launch.  src [U, C] and dst
+    [R, C] contiguous f32 or bf16 of one dtype, index [R] int32."""
+    assert src.dim() == 2 and dst.dim() == 2 and src.dtype == dst.dtype and src.is_contiguous() and dst.is_contiguous()
+    assert index.dtype == torch.int32 and index.is_contiguous() and index.numel() == dst.shape[0] and src.shape[1] == dst.shape[1]
+    check(lib().made_gather_rows(_p(src) if src.shape[0] else None, src.shape[0], _p(index), dst.shape[0], dst.shape[1], _p(dst),
+                                 dt_of(dst), _stream()), "made_gather_rows")
+    return dst
+
+
+def group_topw(sims: Tensor, sel: Tensor, col_group: Tensor, start: Tensor, cols: Tensor, w: int):
+    """made_group_topw: the best w columns of the group of every selected column sel [Nv, K] (topk_groups' idx) in its row of sims
+    [Nv, Nm] f32 -> (idx [Nv, K, w] int32, score [Nv, K, w] f32), score descending then column ascending, -1 / -inf past the group's
+    size.  col_group [Nm], start [G + 1] and cols int32: the column -> group map and the groups' members as a CSR."""
+    assert sims.dim() == 2 and sims.dtype == torch.float32 and sims.stride(1) == 1
+    Nv, Nm = sims.shape
+    for t in (sel, col_group, start, cols):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert sel.dim() == 2 and sel.shape[0] == Nv and col_group.numel() == Nm and start.numel() >= 2
+    K = sel.shape[1]
+    idx = torch.empty(Nv, K, w, device=sims.device, dtype=torch.int32)
+    score = torch.empty(Nv, K, w, device=sims.device, dtype=torch.float32)
+    check(lib().made_group_topw(_p(sims), sims.stride(0), _p(sel), _p(col_group), _p(start), _p(cols), cols.numel(), Nv, Nm,
+                                start.numel() - 1, K, w, _p(idx), _p(score), _stream()), "made_group_topw")
+    return idx, score
+
+
+def merge_moments(cand: Tensor, win_col: Tensor, win_score: Tensor, offset: Tensor, duration: Optional[Tensor], max_m_duration: float,
+                  nms_iou: float, n: int, use_prob: bool = True):
+    """made_merge_moments: cand [P, w, Q, 3] f32 (start, end, foreground probability per query, seconds on the window's axis),
+    win_col int32 / win_score f32 [P, w], offset / duration [Nm] f32 per column -> (start, end, confidence f32, window int32), each
+    [P, n]: the first n candidates the greedy suppression keeps, NaN / -1 past them."""
+    P, w, Q, three = cand.shape
+    assert three == 3 and cand.dtype == torch.float32 and cand.is_contiguous()
+    assert win_col.dtype == torch.int32 and win_col.is_contiguous() and tuple(win_col.shape) == (P, w)
+    assert win_score.dtype == torch.float32 and win_score.is_contiguous() and tuple(win_score.shape) == (P, w)
+    assert offset.dtype == torch.float32 and offset.is_contiguous()
+    Nm = offset.numel()
+    if duration is not None:
+        assert duration.dtype == torch.float32 and duration.is_contiguous() and duration.numel() == Nm
+    dev = cand.device
+    start, end, conf = (torch.empty(P, n, device=dev, dtype=torch.float32) for _ in range(3))
+    window = torch.empty(P, n, device=dev, dtype=torch.int32)
+    check(lib().made_merge_moments(_p(cand), _p(win_col), _p(win_score), _p(offset), _p(duration), P, Nm, w, Q, 1 if use_prob else 0,
+                                   float(max_m_duration), float(nms_iou), n, _p(start), _p(end), _p(conf), _p(window), _stream()),
+          "made_merge_moments")
+    return start, end, conf, window

@@ -8,6 +8,12 @@ reads WAVS/<music_id>.wav for every distinct music_id (WAV only: convert MP3 fir
 [max_snippet_num] f32 -- the files MGSV_EC_Dataset._features and the reference's feature loader read, so training, testing and
 --ground_topk run on them unchanged.  Rows past the track's end are zero (every consumer zeroes them anyway).  A host thread reads
 the next batch of WAVs while the GPU encodes this one.
+
+--window_hop H (seconds; 0 = off, the default): tracks longer than max_m_duration are also cut into overlapping windows of
+max_m_duration seconds every H seconds (mgsv_amd/windows.py; H a multiple of the stride) and get OUT/ast_windows/<music_id>.pt, a dict
+of feats [Nw, max_snippet_num, 768], mask [Nw, max_snippet_num], offset [Nw] and duration [Nw] (seconds) for
+ground(..., windows=...).  ast_feature / ast_mask stay what they are without the option -- window 0 -- so training and testing read
+them unchanged; segments that overlapping windows share are encoded once.
 """
 from __future__ import annotations
 
@@ -35,11 +41,13 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--tracks_per_batch", type=int, default=8)
     ap.add_argument("--skip_existing", type=int, default=0)
+    ap.add_argument("--window_hop", type=float, default=0, help="seconds between the windows of tracks longer than max_m_duration (0: off)")
     a = ap.parse_args(argv)
 
+    import numpy as np
     import pandas as pd
     import torch
-    from mgsv_amd.music import MusicEncoder, load_track, segment_table
+    from mgsv_amd.music import SR, MusicEncoder, load_track, resampled_length, segment_table
 
     segment_table(0, a.stride, a.filter, 0, a.max_m_duration)          # refuses a stride / filter the reference cannot run
     ids, seen = [], set()
@@ -52,6 +60,11 @@ def main(argv=None):
     fdir, mdir = os.path.join(a.out, "ast_feature"), os.path.join(a.out, "ast_mask")
     os.makedirs(fdir, exist_ok=True)
     os.makedirs(mdir, exist_ok=True)
+    wdir = os.path.join(a.out, "ast_windows")
+    if a.window_hop:
+        from mgsv_amd.windows import window_table
+        window_table(0, a.max_m_duration, a.window_hop, a.stride)      # refuses a hop that is not a multiple of the stride
+        os.makedirs(wdir, exist_ok=True)
     if a.skip_existing:
         ids = [i for i in ids if not (os.path.isfile(os.path.join(fdir, f"{i}.pt")) and os.path.isfile(os.path.join(mdir, f"{i}.pt")))]
     enc = MusicEncoder(a.ast_weights, device=a.device, dtype=a.dtype, chunk=a.chunk)
@@ -70,6 +83,16 @@ def main(argv=None):
         for j, mid in enumerate(batch):
             torch.save(feats[j].clone(), os.path.join(fdir, f"{mid}.pt"))
             torch.save(masks[j].clone(), os.path.join(mdir, f"{mid}.pt"))
+        if a.window_hop:                                               # the tracks longer than the window, whole
+            long = [j for j, (w, sr) in enumerate(tracks) if resampled_length(w.shape[-1], sr) > SR * a.max_m_duration]
+            if long:
+                wf, wm, win = enc.encode_windows([tracks[j] for j in long], stride=a.stride, filter=a.filter, window=a.max_m_duration,
+                                                 hop=a.window_hop)
+                wf, wm = wf.cpu(), wm.cpu()
+                for i, j in enumerate(long):
+                    sel = torch.from_numpy(np.flatnonzero(win.track == i))
+                    torch.save(dict(feats=wf[sel].clone(), mask=wm[sel].clone(), offset=torch.from_numpy(win.offset)[sel].clone(),
+                                    duration=torch.from_numpy(win.duration)[sel].clone()), os.path.join(wdir, f"{batch[j]}.pt"))
         print(f"[extract] {min((bi + 1) * a.tracks_per_batch, len(ids))}/{len(ids)} tracks", flush=True)
     ahead.shutdown()
 
