@@ -57,8 +57,8 @@ class MadeTrainer(MadeEngine):
         self.seed = 0
         self.training_dropout = True
         # bf16: the flash-attention forward stores its dropout decisions (one bit per score) and the two backward kernels test the bit
-        # instead of re-drawing it (made_attention's keep_bits; MADE_ATTN_BITS=0: re-draw, for A/B measurements)
-        self._bits = dtype == "bf16" and _lib.variant_env("MADE_ATTN_BITS", "1") != "0"
+        # instead of re-drawing it (made_attention's keep_bits: profiles/r04_i_attention_keep_bits.txt); f32 re-draws
+        self._bits = dtype == "bf16"
 
     # ------------------------------------------------------------------ support matrix
     def _check_train_supported(self):
@@ -494,9 +494,6 @@ class MadeTrainer(MadeEngine):
             # DETR encoder
             e_delta=E(B * H * L, dtype=f32), eg1=E(rows, D), eg2=E(rows, D), eg2b=E(rows, D), eg3=E(rows, D), eg3b=E(rows, D), eg3c=E(rows, D),
             egqkv=E(rows, 3 * D), egffn=E(rows, Fd),
-            # a second set of the four gradients a layer's weight-gradient launch reads: that launch runs on the second stream while
-            # the next layer's backward (odd / even layers alternate between the sets) already writes its own
-            eg2b_2=E(rows, D), eg3_2=E(rows, D), egqkv_2=E(rows, 3 * D), egffn_2=E(rows, Fd),
             dfus=E(rows, D),
             # decoder (rows = B*Q)
             s_raw=E(B * HQ, dtype=f32), dds_raw=E(B * HQ, dtype=f32), gq_raw=E(B, HQ, D),
@@ -505,7 +502,7 @@ class MadeTrainer(MadeEngine):
             dg1=E(B * Q, D), dg2=E(B * Q, D), dg3=E(B * Q, D), dg4=E(B * Q, D), dgqkv=E(B * Q, 3 * D), dgffn=E(B * Q, Fd),
             dgq=E(B, HQ, D), dtgt=E(B * Q, D), dhs=E(nd * B * Q, D), dgN=E(nd * B * Q, D),
             # the fused backward chain's hand-off rows (residual-stream gradients between its stages): a buffer of their own per layer and
-            # stage -- see backward()
+            # stage -- see _decoder_bwd()
             dchain=E(nd, 6, B * Q, D),
             # heads
             h1=E(nd * B * Q, D), h2=E(nd * B * Q, D), hg1=E(nd * B * Q, D), hg2=E(nd * B * Q, D),
@@ -731,13 +728,12 @@ class MadeTrainer(MadeEngine):
                 # streams join at the end of the forward)
                 _tape.zero_(self.flat_grad)
                 self._grads_zeroed = True
-            if (Q == 1 and not regression and c.moment_query_type != "xpool" and c.detr_enc_layers > 0
-                    and _lib.variant_env("MADE_DEC_EARLY", "1") != "0"):
+            if Q == 1 and not regression and c.moment_query_type != "xpool" and c.detr_enc_layers > 0:
                 # the query side of decoder layer 0 depends on the clip-level vector and the weights only: here, beside the DETR encoder,
                 # instead of at the head of the decoder's chain of dependent launches (as MadeEngine does for the eval path).
-                # (MADE_DEC_EARLY=0: at the head of the chain.  While the raw barriers of the LDS-DMA GEMM kernels lacked their
-                # lgkmcnt(0) -- csrc/linear.hip, linear_ring_kernel -- this placement made one stage of the chain come out a few ulps off in
-                # a fifth of the steps; 0 of 80 since: tools/race_probe3.py)
+                # (While the raw barriers of the LDS-DMA GEMM kernels lacked their lgkmcnt(0) -- csrc/linear.hip, linear_ring_kernel --
+                # this placement made one stage of the chain come out a few ulps off in a fifth of the steps; 0 of 80 since:
+                # tools/race_probe3.py)
                 dec_fill_tgt()
                 dec_query_side(0)
                 dec_early = torch.cuda.Event()
@@ -830,12 +826,7 @@ class MadeTrainer(MadeEngine):
             dec_fill_tgt()
         hs = ws["hs"]
         GQ = tw["GQ"]                                        # [B, 2, nd, H*Q, D]: part 1 holds the q' rows of every layer
-        n_split = int(_lib.variant_env("MADE_WIDE_NSPLIT", "0")) or max(1, min(8, 256 // max(B, 1)))   # few queries, long memory: keys split over workgroups (knob for measurements)
-        # the planned launch (key tiles dealt by length, made_wide_slice_plan) unless the shape is not its own; MADE_WIDE_PLANNED=0 (read at
-        # every call, for same-process A/B runs): n_split equal slices per sample
-        wplan = self._wide_plan if _lib.variant_env("MADE_WIDE_PLANNED", "1") != "0" else None
-        if wplan is not None:
-            n_split = WIDE_SLICES
+        n_split, wplan = self._wide_split(B)
         t3_stack = tw["dstack"]["tgt"][1:]                   # [nd, B*Q, D]: slot l + 1 = layer l's output (t3)
         for l in range(nd):
             p, d = f"detr_transformer.decoder.layers.{l}", f"d.{l}"
@@ -966,6 +957,18 @@ class MadeTrainer(MadeEngine):
         """shapes made_attention_wide_planned takes (include/made_hip.h); others keep made_attention_wide's equal slices"""
         return self.tc == torch.bfloat16 and D in (256, 512) and HQ <= 32 and B <= self._wide_slots()
 
+    def _wide_split(self, B: int, backward: bool = False):
+        """(n_split, plan) of the decoder's memory-space attention launches (few queries, long memory: the keys are split over
+        workgroups): WIDE_SLICES slices per sample dealt by the plan forward_train made (key tiles by length, made_wide_slice_plan)
+        where the shape is the planned launch's own -- in the backward up to 8 (head, query) rows -- else max(1, min(8, 256 // B))
+        equal slices (2 / 4 / 8 inside the step at B = 64: 5.06 / 4.89 / 4.96 ms, profiles/r06_ab_wide_nsplit.txt)."""
+        plan = self._wide_plan
+        if backward and self.cfg.detr_nheads * self.cfg.num_moment_queries > 8:
+            plan = None
+        if plan is not None:
+            return WIDE_SLICES, plan
+        return max(1, min(8, 256 // max(B, 1))), None
+
     def _dec_stage_chain(self) -> bool:
         """The training decoder's fused chain (made_dec_stage with the training options, in-launch merge of the memory-space attention,
         fused attention backward): bf16, one moment query, D = 256 / 512.  MADE_DEC_STAGE=0 keeps round 2's chain (A/B measurements);
@@ -1067,7 +1070,7 @@ class MadeTrainer(MadeEngine):
                 tw[pre + "xib_ws"] = torch.zeros(ops.xpool_inbatch_ws_bytes(B, S), device=self.device, dtype=torch.uint8)
             ops.xpool_inbatch(q, tw[pre + "k"].view(B, S, D), tw[pre + "u"].view(B, S, D), seg_mask, tw[pre + "o"].view(B, B, D),
                               scale=1.0 / math.sqrt(D), ws=tw[pre + "xib_ws"])
-        xsplit = int(_lib.variant_env("MADE_XPOOL_NSPLIT", "0")) or (max(1, min(4, 256 // max(B, 1), S // 64)) if (B <= 64 and self.tc == torch.bfloat16) else 1)
+        xsplit = max(1, min(4, 256 // max(B, 1), S // 64)) if (B <= 64 and self.tc == torch.bfloat16) else 1
         if inbatch:
             pass
         elif xsplit > 1:
@@ -1142,8 +1145,7 @@ class MadeTrainer(MadeEngine):
     # ================================================================== backward
     def _groupable(self, dz: Tensor, x: Tensor, gw: Tensor) -> bool:
         return (self.tc == torch.bfloat16 and dz.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and gw.shape[0] % 128 == 0
-                and gw.shape[1] % 128 == 0 and dz.stride(0) % 8 == 0 and x.stride(0) % 8 == 0 and dz.shape[0] >= 256
-                and not getattr(self, "no_grouped_dw", False))
+                and gw.shape[1] % 128 == 0 and dz.stride(0) % 8 == 0 and x.stride(0) % 8 == 0 and dz.shape[0] >= 256)
 
     def _flush_dw(self, pending: list, row_mask: Optional[Tensor]) -> None:
         """The weight gradients a layer's backward has queued (they reduce over the same rows) in one launch (made_gemm_tn_grouped)."""
@@ -1200,373 +1202,426 @@ class MadeTrainer(MadeEngine):
         buffer) is final -- data-parallel training starts that part's all-reduce there, under the encoders' backward.
         early_opt(): called at the same point on a THIRD stream that waits for everything queued so far on the two others (neither
         of them waits for it until the end of the backward pass): optimizer_step(part="early") there applies the matching + detection
-        groups' update under the temporal encoders' backward, which reads none of their weights (opt-in, see _early_opt_ok)."""
+        groups' update under the temporal encoders' backward, which reads none of their weights (opt-in, see _early_opt_ok).
+        This function is the schedule only -- which stage runs on which stream and who waits for whom; the launches are the stages'."""
         self._set_products()
-        c, P, G = self.cfg, self.P, self.G
+        c = self.cfg
         B, Tv, Ta = self._shape
         ws, tw = self._buffers(B, Tv, Ta), self._train_buffers(B, Tv, Ta)
-        feats_v, feats_a, fm, sm, tg = self._inputs
-        concat = "concat" in c.mml_fusion
-        D, L, Q, nd, ne, H = c.D, (Tv + Ta if concat else Ta), c.num_moment_queries, c.detr_dec_layers, c.detr_enc_layers, c.detr_nheads
-        hd, HQ = D // H, H * Q
-        pd = float(c.detr_dropout)
-        inv_keep = 1.0 / (1.0 - pd) if (self.training_dropout and pd > 0) else 1.0
-        fus, fus_mask = ws["fus"], ws["fus_mask"]
-        fskip = fus_mask.view(-1)
-        qskip = fus_mask
         regression = "regression" in c.mml_localization
-        if regression:
-            fskip = qskip = None
-        rows = B * L
+        xq = c.moment_query_type == "xpool" and not regression
         if zero_grad and not getattr(self, "_grads_zeroed", False):
             _tape.zero_(self.flat_grad)
         self._grads_zeroed = False
-        dvideo, dmusic = tw["dvideo"], tw["dmusic"]
         _tape.zero_(tw["dclip"])                              # dvideo, dmusic and the contrastive head's dvid_sum in one fill
-        video, music = ws["video"], ws["music"]
-        frame, seg_view = self._views
         # the X-Pool / similarity branch is independent of the DETR stack until the temporal encoders: its (latency-bound)
         # backward runs on the second stream beside the decoder's
         cur, side = torch.cuda.current_stream(), self._side_stream()
-        xq = c.moment_query_type == "xpool" and not regression
         side.wait_stream(cur)
-        ret_done = None
-        ret_gen = None
-        if not xq:                                           # (with an xpool query it follows the decoder's backward: see below)
-            # MADE_RET_BWD_MAIN=1: on the main stream, in front of the heads and the decoder's chain (tools/race_probe3.py: beside the
-            # first decoder layers of the backward chain these launches are what makes one element of a chain product come out one
-            # bf16 ulp off in ~15 % of the first steps -- 0 of 60 with them on the main stream or with one stream only; DESIGN.md 3c-3)
-            ret_main = _lib.variant_env("MADE_RET_BWD_MAIN", "0") == "1"
-            # MADE_RET_SPLIT (default 1): the branch's backward is issued in two parts -- up to the X-Pool tower's batched score / dP
-            # products now, those and everything behind them on the second stream BEHIND the decoder's chain (see below)
-            ret_split = (_lib.variant_env("MADE_RET_SPLIT", "1") != "0" and not ret_main and not regression
-                         and _lib.variant_env("MADE_RET_HANDOFF", "") == "" and _lib.variant_env("MADE_RET_HANDOFF_REV", "") == "")
-            with torch.cuda.stream(cur if ret_main else side):
-                self._ret_main_stream = cur
-                try:
-                    self._ret_ck(0)
-                    if ret_split:
-                        ret_gen = self._retrieval_bwd_gen(ws, tw, g_ret, B, Ta, sm)
-                        if next(ret_gen, "done") == "done":          # (a configuration without the tower: nothing left for later)
-                            ret_gen = None
-                    else:
-                        self._retrieval_bwd(ws, tw, g_ret, B, Ta, sm)
-                    on_main = torch.cuda.current_stream() == cur
-                finally:
-                    self._ret_main_stream = None
+        ret_gen = ret_done = None
+        if not xq:                                           # (with an xpool query it follows the decoder's backward: _merge_clip_grads)
+            with torch.cuda.stream(side):
+                ret_gen = self._retrieval_bwd_first(ws, tw, g_ret)
                 if ret_gen is None:
                     ret_done = torch.cuda.Event()
-                    ret_done.record(cur if on_main else side)
+                    ret_done.record(side)
 
         if regression:
-            dmem, dtgt0 = self._regression_bwd(ws, tw, g_loc, B, L), None
+            dmem, dtgt0 = self._regression_bwd(ws, tw, g_loc, B, self._fused_len()), None
         else:
-            # ---------------- criterion + heads
-            logits, spans = ws["logits"], ws["spans"]
-            pi, ti, cnt = self._match
-            pq = ws["pq"] if c.contrastive_align_loss else None
-            vid_sum = ws["vid_sum"] if c.contrastive_align_loss else None
-            tr.set_criterion_bwd(logits, spans, tg, pi, ti, cnt, pq, vid_sum, P["empty_weight"], c.foreground_label, P["crit_weights"], g_loc,
-                                 tw["dlog"], tw["dsp"], tw["dpq"] if pq is not None else None, tw["dvid_sum"] if pq is not None else None,
-                                 ld_out=HEAD_PAD, through_sigmoid=True)
-            hs2 = ws["hs"].view(nd * B * Q, D)
-            dhs = tw["dhs"]
-            dlog, dsp = tw["dlog"], tw["dsp"]
-            if self.tc != torch.float32:                          # same dtype as the activations for the A^T B products
-                tr.add3(tw["dlogsp_c"], tw["dlogsp"])             # both casts in one launch
-                dlog, dsp = tw["dlog_c"], tw["dsp_c"]
-            # the heads' weight gradients wait for nobody on the main stream: they are launched with the decoder's (second stream,
-            # after the loop below); their operands (dlog / dsp / hg1 / hg2 / h1 / h2 / hs) are not touched in between
-            heads_dw: list = []
-            heads_dw.append(lambda: tr.gemm_tn(dlog[:, :2], hs2, G["class_embed.w"], accumulate=True, colsum=G["class_embed.b"]))
-            ops.linear(dlog, P["class_embed.wt"], None, out=dhs)
-            n_span = 1 if c.predict_center == 1 else 2             # predict_center: the width column is a constant, its gradient is dropped
-            heads_dw.append(lambda: tr.gemm_tn(dsp[:, :n_span], tw["h2"], G["span_embed.2.w"], accumulate=True, colsum=G["span_embed.2.b"]))
-            dz2 = ops.linear(dsp, P["span_embed.2.wt"], None, out=tw["hg1"], gate=_lib.GATE_RELU_OUT, G=tw["h2"])
-            dz1 = self._lin_bwd(dz2, tw["h1"], "span_embed.1", dx_out=tw["hg2"], gate=_lib.GATE_RELU_OUT, G=tw["h1"], later=heads_dw)
-            self._lin_bwd(dz1, hs2, "span_embed.0", dx_out=dhs, R=dhs, later=heads_dw)
-            if c.contrastive_align_loss:
-                Dc = pq.shape[-1]
-                dn = tw["dpq"]
-                if c.audio_short_cut:                             # back through normalize(. + music), aux layers twice; music collects the sums
-                    if c.aux_loss and nd > 1:
-                        n_aux = (nd - 1) * B * Q
-                        ds2 = tw["dpq_s2"][:n_aux]
-                        tr.l2norm_bwd(tw["pq_s2"][:n_aux], dn[:n_aux], dx=ds2)
-                        dmusic.add_(ds2.view(nd - 1, B, Q, D).sum((0, 2)))
-                        dn[:n_aux].copy_(ds2)
-                    tr.l2norm_bwd(tw["pq_s1"], dn, dx=tw["dpq_s"])
-                    dmusic.add_(tw["dpq_s"].view(nd, B, Q, D).sum((0, 2)))
-                    dn = tw["dpq_s"]
-                tr.l2norm_bwd(ws["pq_raw"], dn, dx_alt=tw["dpq_raw"])
-                self._lin_bwd(tw["dpq_raw"], hs2, "proj_q", dx_out=dhs, R=dhs, later=heads_dw)
-                # proj_vid_mem: every frame (padded ones too) receives d vid_sum (reference loss_detr.py:118)
-                tr.l2norm_bwd(ws["pv_raw"], tw["dvid_sum"], dx_alt=tw["dpv_raw"], dy_rows_per=Tv)
-                # (its weight gradient is nobody's input: with the heads' other weight gradients on the second stream, after the decoder's
-                #  chain -- it was 52 us at the head of the main stream's backward)
-                heads_dw.append(lambda: tr.gemm_tn(tw["dpv_raw"][:Tv], frame[0], G["proj_v.w"], accumulate=True, colsum=G["proj_v.b"], batch=(B, 1),
-                                                   a_zs=(Tv * Dc, 0), b_zs=(frame.stride(0), 0), colsum_zs=(0, 0)))
-                ops.linear(tw["dpv_raw"], P["proj_v.wt"], None, out=tw["dframe_x"])
-
-            # ---------------- decoder, last layer first.  Inside the loop only the data-gradient chain runs; every output gradient a
-            # weight gradient needs is kept per layer (the g_* stacks) and the weight-gradient products of all layers are batched after it.
-            qp = P["query_embed"]
-            mem3, mempos3 = tw["mem"].view(B, L, D), tw["mempos"].view(B, L, D)
-            Lp = tw["PdS"].shape[-1]
-            GQ, PdS = tw["GQ"], tw["PdS"]
-            ca_scale = 1.0 / math.sqrt(hd)
-            st = tw["dstack"]
-            dtgt = None
-            # the scores of every layer's memory-space attention depend on forward values only (q', memory + pos): ONE batched
-            # product for all layers ([nd, B, H*Q, L] rows) ahead of the dependent chain instead of one launch inside every layer
-            stage = self._dec_stage_chain()                    # fused chain: see forward_train
-            pre = bool(c.detr_pre_norm)                        # pre-norm layers (reference music_detr/transformer.py:246-271): separate launches
-            S_all = tw["dS_S"]
-            if not stage:
-                ops.linear(GQ[0, 1].reshape(nd * HQ, D), mempos3[0], None, M=nd * HQ, N=L, K=D, batch=B, a_z_stride=GQ.stride(0), w_z_stride=L * D,
-                           segs=[Seg(out=S_all, ldo=Lp, rows_per_batch=HQ, out_batch_stride=B * HQ * Lp, out_z_stride=HQ * Lp)])
-            n_split_b = int(_lib.variant_env("MADE_WIDE_NSPLIT", "0")) or max(1, min(8, 256 // max(B, 1)))
-            wplan = self._wide_plan if HQ <= 8 and _lib.variant_env("MADE_WIDE_PLANNED", "1") != "0" else None      # (as in forward_train)
-            if wplan is not None:
-                n_split_b = WIDE_SLICES
-            if stage:
-                # the shared output norm's backward depends on the heads only: all layers in ONE launch ahead of the dependent chain
-                gN = tw["dgN"]
-                tr.layernorm_bwd(tw["dstack"]["tgt"][1:].reshape(nd * B * Q, D), P["dec.norm.g"], dhs, gN, dgamma=G["dec.norm.g"], dbeta=G["dec.norm.b"])
-            for l in range(nd - 1, -1, -1):
-                p, d = f"detr_transformer.decoder.layers.{l}", f"d.{l}"
-                g1, g2, g4 = tw["dg1"], tw["dg2"], tw["dg4"]
-                if stage and _lib.variant_env("MADE_CHAIN_BUFS", "1") != "0":
-                    # every hand-off of the chain gets rows of its own instead of three scratch buffers rewritten and re-read a few launches
-                    # apart (MADE_CHAIN_BUFS=0: the shared buffers) -- a leftover of the hunt for the chain's one-ulp deviation, which
-                    # turned out to need two launches of the retrieval branch beside the chain (MADE_RET_SPLIT above, DESIGN.md 3c-3);
-                    # kept: tools/race_probe3.py reads the hand-offs from here
-                    ch = tw["dchain"][l]
-                    g1a, g1b, g2a, g2b, g2c, dt_out = ch[0], ch[1], ch[2], ch[3], ch[4], ch[5]
-                else:
-                    g1a = g1b = g1
-                    g2a = g2b = g2c = g2
-                    dt_out = tw["dtgt"]
-                Win, Wt = P[p + ".ca.in.w"], P[p + ".ca.in.wt"]
-                g_ffn, g_z, g_ca, g_attc, g_q, g_qc, g_sa, gqkv = (st[k][l] for k in ("g_ffn", "g_z", "g_ca", "g_attc", "g_q", "g_qc", "g_sa", "g_qkv"))
-                if stage:
-                    # hs_l = dec.norm(t3) (its backward: one launch for all layers ahead of the chain), t3 = LN3(t2 + drop3(ffn)) also feeds
-                    # the next layer: norm 3's backward of (d hs_l through the output norm + d tgt_{l+1}) in the prologue of the FFN's second
-                    # dX product
-                    tr.dec_stage_bwd(tw[d + ".t_c"], P[p + ".ln3.g"], gN[l * B * Q:(l + 1) * B * Q], P[p + ".ff2.wt"], g_z,
-                                     dgamma_a=G[p + ".ln3.g"], dbeta_a=G[p + ".ln3.b"], add=dtgt, dx_out=g2a, a_out=g_ffn,
-                                     drop_a=self._drop(f"dec.{l}" + ".drop3", pd), G=tw[d + ".h"], gate_scale=inv_keep)
-                elif pre:
-                    # hs_l = dec.norm(stream); the stream (slot l + 1 of the tgt stack) also feeds the next layer: g1 = d stream
-                    tr.layernorm_bwd(tw[d + ".t3"], P["dec.norm.g"], dhs[l * B * Q:(l + 1) * B * Q], g1, dgamma=G["dec.norm.g"], dbeta=G["dec.norm.b"], add=dtgt)
-                    # stream = t_b + drop3(ffn(LN3(t_b)))
-                    tr.gate_rows(g1, g_ffn, drop=self._drop(f"dec.{l}" + ".drop3", pd))
-                else:
-                    # hs_l = dec.norm(t3); t3 also feeds the next layer
-                    tr.layernorm_bwd(tw[d + ".t3"], P["dec.norm.g"], dhs[l * B * Q:(l + 1) * B * Q], g1, dgamma=G["dec.norm.g"], dbeta=G["dec.norm.b"], add=dtgt)
-                    # t3 = LN3(t2 + drop3(ffn))
-                    tr.layernorm_bwd(tw[d + ".t_c"], P[p + ".ln3.g"], g1, g2, dgamma=G[p + ".ln3.g"], dbeta=G[p + ".ln3.b"],
-                                     dx_drop=g_ffn, drop=self._drop(f"dec.{l}" + ".drop3", pd))
-                if not stage:
-                    ops.linear(g_ffn, P[p + ".ff2.wt"], None, out=g_z, gate=_lib.GATE_RELU_OUT, G=tw[d + ".h"], gate_scale=inv_keep)
-                if pre:
-                    dn3 = ops.linear(g_z, P[p + ".ff1.wt"], None, out=g4)
-                    # t_b = t_a + drop2(cross-attention): d t_b = LN3'(dn3) + d stream -> g2; its dropped copy feeds the out-projection
-                    tr.layernorm_bwd(tw[d + ".t_b"], P[p + ".ln3.g"], dn3, g2, dgamma=G[p + ".ln3.g"], dbeta=G[p + ".ln3.b"], add=g1,
-                                     dx_drop=g_ca, drop=self._drop(f"dec.{l}" + ".drop2", pd))
-                    dattc = ops.linear(g_ca, P[p + ".ca.out.wt"], None, out=g_attc)
-                else:
-                    dt2 = ops.linear(g_z, P[p + ".ff1.wt"], None, out=g1a, R=g2a)
-                # t2 = LN2(t1 + drop2(cross-attention))
-                if pre:
-                    pass
-                elif stage:                                       # norm 2's backward in the prologue of the out-projection's dX product
-                    dattc = tr.dec_stage_bwd(tw[d + ".t_b"], P[p + ".ln2.g"], dt2, P[p + ".ca.out.wt"], g_attc, dgamma_a=G[p + ".ln2.g"],
-                                             dbeta_a=G[p + ".ln2.b"], dx_out=g2b, a_out=g_ca, drop_a=self._drop(f"dec.{l}" + ".drop2", pd))
-                else:
-                    tr.layernorm_bwd(tw[d + ".t_b"], P[p + ".ln2.g"], dt2, g2, dgamma=G[p + ".ln2.g"], dbeta=G[p + ".ln2.b"],
-                                     dx_drop=g_ca, drop=self._drop(f"dec.{l}" + ".drop2", pd))
-                    dattc = ops.linear(g_ca, P[p + ".ca.out.wt"], None, out=g_attc)
-                dpooled = GQ[:, 0, l]                             # [B, H*Q, D] slice of the concatenated buffer
-                qprime = GQ[:, 1, l]
-                if stage:
-                    # v_h = W_v,h pooled_h : dpooled_h = dattc_h W_v,h
-                    ops.linear(dattc[:, :hd], Wt[:, 2 * D:2 * D + hd], None, M=B * Q, N=D, K=hd, batch=H, a_z_stride=hd, w_z_stride=hd,
-                               segs=[Seg(out=dpooled, ldo=D, rows_per_batch=Q, out_batch_stride=dpooled.stride(0), out_z_stride=Q * D)])
-                    # the memory-space attention's backward in ONE launch: scores and probabilities recomputed from the saved lse, the
-                    # value-bias term reduced from dattc, Pd / dS written for the memory-gradient product after the loop, dq' = dS (mem + pos)
-                    # (the value bias' own gradient needs nothing of the chain: after the loop, second stream)
-                    tr.attention_wide_bwd(qprime, dpooled, tw[d + ".pooled"].view(B, HQ, D), mempos3, mem3, tw["ca_lse"][l].view(B, HQ),
-                                          PdS[:, 0, l], PdS[:, 1, l], g_q, scale=ca_scale, key_mask=fus_mask, ssum=tw[d + ".s"].view(B, HQ),
-                                          dattc=dattc, vbias=P[p + ".ca.in.b"][2 * D:], hd=hd, drop=self._drop(f"dec.{l}" + ".ca_attn", pd),
-                                          n_split=n_split_b, part_dq=ws["part_o"], plan=wplan)
-                else:
-                    tr.head_bias_bwd(dattc, tw[d + ".s"], P[p + ".ca.in.b"][2 * D:], G[p + ".ca.in.b"][2 * D:], tw["d_ds"], H)
-                    d_ds = tw["d_ds"]                                 # rows (b, q), columns h; the softmax backward numbers its rows (b, h, q)
-                    if Q > 1:
-                        tw["dds_raw"].view(B, H, Q).copy_(d_ds.view(B, Q, H).permute(0, 2, 1))
-                        d_ds = tw["dds_raw"]
-                    # v_h = W_v,h pooled_h : dpooled_h = dattc_h W_v,h
-                    ops.linear(dattc[:, :hd], Wt[:, 2 * D:2 * D + hd], None, M=B * Q, N=D, K=hd, batch=H, a_z_stride=hd, w_z_stride=hd,
-                               segs=[Seg(out=dpooled, ldo=D, rows_per_batch=Q, out_batch_stride=dpooled.stride(0), out_z_stride=Q * D)])
-                    # scores and dPd of the memory-space attention (few rows per sample: materialised)
-                    S, dP = S_all[l], tw["dS_dP"]
-                    ops.linear(dpooled[0], mem3[0], None, M=HQ, N=L, K=D, batch=B, a_z_stride=dpooled.stride(0), w_z_stride=L * D,
-                               segs=[Seg(out=dP, ldo=Lp, out_z_stride=HQ * Lp)])
-                    tr.softmax_bwd(S, dP, fus_mask, HQ, ca_scale, PdS[:, 0, l], PdS[:, 1, l], tw["dSt"], HQ, L, extra=d_ds.view(-1),
-                                   drop=self._drop(f"dec.{l}" + ".ca_attn", pd), ldo=Lp, ldt=HQ, out_batch_stride=PdS.stride(0))
-                    # dq'[b] = dS[b] (mem + pos)[b]
-                    gq_out = g_q if Q == 1 else tw["gq_raw"]         # [B, (h, q), D] out of the product; [B, (q, h), D] for the Linears
-                    tr.gemm_tn(tw["dSt"][0], mempos3[0], gq_out[0], batch=(B, 1), a_zs=(L * HQ, 0), b_zs=(L * D, 0), c_zs=(HQ * D, 0),
-                               row_mask=fus_mask, mask_zs=(L, 0))
-                    if Q > 1:
-                        g_q.view(B, Q, H, D).copy_(gq_out.view(B, H, Q, D).permute(0, 2, 1, 3))
-                # q'_h = W_k,h^T qc_h : dqc_h = dq'_h W_k,h^T
-                dq2 = g_q.view(B * Q, H * D)
-                ops.linear(dq2[:, :D], Win[D:D + hd], None, M=B * Q, N=hd, K=D, batch=H, a_z_stride=D, w_z_stride=hd * D,
-                           segs=[Seg(out=g_qc, ldo=D, out_z_stride=hd)])
-                # qc = W_q (t1 + qp) + b_q
-                # dt1 = residual path + query path in the Linear's epilogue; the query path alone (the pre-residual value) is kept for
-                # the query embedding's gradient
-                dt1q = st["dt1q"][l]                               # (summed over the batch into the query embedding's gradient after the loop)
-                if pre:
-                    # qc = W_q (LN2(t_a) + qp) + b_q: d (LN2(t_a) + qp) -> dt1q; d t_a = LN2'(dt1q) + d t_b -> g1, its dropped copy feeds the
-                    # self-attention's out-projection
-                    ops.linear(g_qc, Wt[:, :D], None, out=dt1q)
-                    tr.layernorm_bwd(tw[d + ".t_a"], P[p + ".ln2.g"], dt1q, g1, dgamma=G[p + ".ln2.g"], dbeta=G[p + ".ln2.b"], add=g2,
-                                     dx_drop=g_sa, drop=self._drop(f"dec.{l}" + ".drop1", pd))
-                    if Q == 1:                                    # value path only (see the forward)
-                        ops.linear(g_sa, P[p + ".sa.out.wt"], None, segs=[Seg(out=gqkv[:, 2 * D:], ldo=gqkv.stride(0))],
-                                   drop=self._drop(f"dec.{l}" + ".sa_attn", pd), drop_ld=H, drop_col_div=hd)
-                        dn1 = ops.linear(gqkv[:, 2 * D:], P[p + ".sa.in.wt"][:, 2 * D:], None, out=g4)
-                    else:
-                        datt = ops.linear(g_sa, P[p + ".sa.out.wt"], None, out=g4)
-                        qkv = tw[d + ".qkv"]
-                        q3, g3v = qkv.view(B, Q, 3 * D), gqkv.view(B, Q, 3 * D)
-                        tr.attention_bwd(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], tw[d + ".att"].view(B, Q, D), datt.view(B, Q, D),
-                                         g3v[:, :, :D], g3v[:, :, D:2 * D], g3v[:, :, 2 * D:], tw[d + ".lse"], tw["d_delta"], H,
-                                         drop=self._drop(f"dec.{l}" + ".sa_attn", pd))
-                        dn1 = ops.linear(gqkv, P[p + ".sa.in.wt"], None, out=g2)       # q, k and v all read n1 (+ qp)
-                        dqk = ops.linear(gqkv[:, :2 * D], P[p + ".sa.in.wt"][:, :2 * D], None, out=g4)
-                        tr.colsum(dqk.view(B, Q * D), G["query_embed"].view(-1))        # the query embedding enters through q, k
-                    # n1 = LN1(tgt): d tgt = LN1'(dn1) + d t_a
-                    dtgt = tr.layernorm_bwd(tw[d + ".tgt"], P[p + ".ln1.g"], dn1, tw["dtgt"], dgamma=G[p + ".ln1.g"], dbeta=G[p + ".ln1.b"], add=g1)
-                    continue
-                ops.linear(g_qc, Wt[:, :D], None, out=g1b, R=g2b, Zout=dt1q)
-                # t1 = LN1(tgt + drop1(self-attention))
-                if stage:
-                    # norm 1's backward in the prologue of the self-attention out-projection's dX product (value path only: dv = datt under
-                    # the same per-head mask, drawn in the epilogue)
-                    tr.dec_stage_bwd(tw[d + ".t_a"], P[p + ".ln1.g"], g1b, P[p + ".sa.out.wt"], gqkv[:, 2 * D:], dgamma_a=G[p + ".ln1.g"],
-                                     dbeta_a=G[p + ".ln1.b"], dx_out=g2c, a_out=g_sa, drop_a=self._drop(f"dec.{l}" + ".drop1", pd),
-                                     drop_o=self._drop(f"dec.{l}" + ".sa_attn", pd), drop_o_ld=H, drop_o_col_div=hd)
-                    dtgt = ops.linear(gqkv[:, 2 * D:], P[p + ".sa.in.wt"][:, 2 * D:], None, R=g2c, out=dt_out)
-                    continue
-                tr.layernorm_bwd(tw[d + ".t_a"], P[p + ".ln1.g"], g1, g2, dgamma=G[p + ".ln1.g"], dbeta=G[p + ".ln1.b"],
-                                 dx_drop=g_sa, drop=self._drop(f"dec.{l}" + ".drop1", pd))
-                if Q == 1:                                        # value path only (see the forward): dv = datt under the same per-head mask,
-                    ops.linear(g_sa, P[p + ".sa.out.wt"], None, segs=[Seg(out=gqkv[:, 2 * D:], ldo=gqkv.stride(0))],       # drawn in the epilogue
-                               drop=self._drop(f"dec.{l}" + ".sa_attn", pd), drop_ld=H, drop_col_div=hd)
-                    dtgt = ops.linear(gqkv[:, 2 * D:], P[p + ".sa.in.wt"][:, 2 * D:], None, R=g2, out=tw["dtgt"])
-                else:
-                    datt = ops.linear(g_sa, P[p + ".sa.out.wt"], None, out=g4)
-                    qkv = tw[d + ".qkv"]
-                    q3, g3v = qkv.view(B, Q, 3 * D), gqkv.view(B, Q, 3 * D)
-                    tr.attention_bwd(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], tw[d + ".att"].view(B, Q, D), datt.view(B, Q, D),
-                                     g3v[:, :, :D], g3v[:, :, D:2 * D], g3v[:, :, 2 * D:], tw[d + ".lse"], tw["d_delta"], H,
-                                     drop=self._drop(f"dec.{l}" + ".sa_attn", pd))
-                    dtgt = ops.linear(gqkv, P[p + ".sa.in.wt"], None, R=g2, out=tw["dtgt"])
-                    # the query embedding also enters through q,k of the self-attention
-                    dqk = ops.linear(gqkv[:, :2 * D], P[p + ".sa.in.wt"][:, :2 * D], None, out=g4)
-                    tr.colsum(dqk.view(B, Q * D), G["query_embed"].view(-1))
-            dtgt0 = dtgt                                          # gradient of the decoder's content query = the clip-level vector
-            # gradient of the memory: values path (Pd^T dpooled) + keys path (dS^T q'), all layers in one product per sample -- the
-            # one thing the DETR encoder's backward waits for
-            dmem = tw["eg1"]
-            tr.gemm_tn(PdS.view(B, 2 * nd * HQ, Lp)[0, :, :L], GQ.view(B, 2 * nd * HQ, D)[0], dmem.view(B, L, D)[0], batch=(B, 1),
-                       a_zs=(PdS.stride(0), 0), b_zs=(GQ.stride(0), 0), c_zs=(L * D, 0))
-
-            # ---- weight gradients of all decoder layers: one layer-batched product per parameter (the layers' parameters, and
-            # the [nd, ...] stacks, are equally spaced).  Nothing on the main stream needs them before the optimizer: they go to the
+            heads_dw = self._heads_bwd(ws, tw, g_loc)
+            dmem, dtgt0 = self._decoder_bwd(ws, tw)
+            # Nothing on the main stream needs the decoder's and the heads' weight gradients before the optimizer: they go to the
             # second stream (a dozen launches of modest size, ~0.35 ms of kernel time) and run beside the DETR encoder's backward;
             # the join in front of grad_sync below covers them.
-            dw_side = _lib.variant_env("MADE_DEC_DW_SIDE", "1") != "0"       # (knob for A/B measurements)
-            if dw_side:
-                side.wait_stream(cur)
+            side.wait_stream(cur)
             if ret_gen is not None:
                 # second part of the retrieval branch's backward: behind the chain (second stream), in front of the weight gradients
-                side.wait_stream(cur)
+                side.wait_stream(cur)                        # (repeats the wait above: a candidate for removal, with a measurement)
                 with torch.cuda.stream(side):
                     for _ in ret_gen:
                         pass
                     ret_done = torch.cuda.Event()
                     ret_done.record(side)
-                ret_gen = None
-            dec_dw = torch.cuda.stream(side if dw_side else cur)
-            dec_dw.__enter__()
-            for launch in heads_dw:
-                launch()
-            tr.colsum(st["dt1q"].view(nd * B, Q * D), G["query_embed"].view(-1))     # every layer's query path at once
-            if stage:                                          # the value bias' gradient d b_v,h = sum_b s[b, h] dattc[b, h] of every layer
-                for l in range(nd):
-                    pl = f"detr_transformer.decoder.layers.{l}"
-                    tr.head_bias_bwd(st["g_attc"][l], tw[f"d.{l}.s"], P[pl + ".ca.in.b"][2 * D:], G[pl + ".ca.in.b"][2 * D:], tw["d_ds"], H)
-            p0, p1 = "detr_transformer.decoder.layers.0", "detr_transformer.decoder.layers.1"
-            BQ = B * Q
+            with torch.cuda.stream(side):
+                self._decoder_dw(tw, heads_dw)
 
-            def lstride(key):
-                return (G[p1 + key].data_ptr() - G[p0 + key].data_ptr()) // 4 if nd > 1 else 0
+        dl_v, dl_a = self._detr_encoder_bwd(ws, tw, dmem)
 
-            def batched(a_stack, b_stack, wkey, bkey, a_cols=None, b_cols=None, w_rows=None):
-                A, Bm = a_stack[0], b_stack[0]
-                if a_cols is not None:
-                    A = A[:, a_cols[0]:a_cols[1]]
-                if b_cols is not None:
-                    Bm = Bm[:, b_cols[0]:b_cols[1]]
-                gw, gb = G[p0 + wkey], (G[p0 + bkey] if bkey is not None else None)
-                if w_rows is not None:
-                    gw = gw[w_rows[0]:w_rows[1]]
-                    gb = gb[w_rows[0]:w_rows[1]] if gb is not None else None
-                tr.gemm_tn(A, Bm, gw, accumulate=True, colsum=gb, batch=(nd, 1), a_zs=(a_stack.stride(0), 0), b_zs=(b_stack.stride(0), 0),
-                           c_zs=(lstride(wkey), 0), colsum_zs=(lstride(bkey) if bkey is not None else 0, 0))
+        # join the X-Pool / similarity branch
+        # (one process: the main stream needs the retrieval branch's results here, not the weight-gradient products queued behind it on
+        #  the second stream -- joining the whole stream left it idle behind them, 0.2 ms per step;
+        #  data-parallel jobs start their first all-reduce below and need every gradient of its range complete)
+        if ret_done is not None and grad_sync is None:
+            cur.wait_event(ret_done)
+        else:
+            cur.wait_stream(side)
+        self._merge_clip_grads(ws, tw, g_ret, dtgt0)
 
-            batched(st["g_ffn"], st["h"], ".ff2.w", ".ff2.b")
-            batched(st["g_z"], st["t2"], ".ff1.w", ".ff1.b")
-            batched(st["g_ca"], st["attc"], ".ca.out.w", ".ca.out.b")
-            batched(st["g_qc"], st["t1q"], ".ca.in.w", ".ca.in.b", w_rows=(0, D))
-            batched(st["g_sa"], st["att"], ".sa.out.w", ".sa.out.b")
-            if Q > 1:                                             # (a single query's q / k projections get no gradient)
-                batched(st["g_qkv"], st["tq"], ".sa.in.w", ".sa.in.b", a_cols=(0, 2 * D), w_rows=(0, 2 * D))
-            batched(st["g_qkv"], st["n1"] if pre else st["tgt"], ".sa.in.w", ".sa.in.b", a_cols=(2 * D, 3 * D), w_rows=(2 * D, 3 * D))
-            # per-head products of the memory-space cross-attention, batched over (layer, head)
-            gWin0 = G[p0 + ".ca.in.w"]
-            ls = lstride(".ca.in.w")
-            # v_h = W_v,h pooled_h : dW_v,h += dattc_h^T pooled_h
-            tr.gemm_tn(st["g_attc"][0][:, :hd], st["pooled"][0][:, :D], gWin0[2 * D:2 * D + hd], accumulate=True, batch=(nd, H),
-                       a_zs=(st["g_attc"].stride(0), hd), b_zs=(st["pooled"].stride(0), D), c_zs=(ls, hd * D))
-            # q'_h = W_k,h^T qc_h : dW_k,h += qc_h^T dq'_h
-            gq2 = st["g_q"].view(nd, BQ, H * D)
-            tr.gemm_tn(st["qc"][0][:, :hd], gq2[0][:, :D], gWin0[D:D + hd], accumulate=True, batch=(nd, H),
-                       a_zs=(st["qc"].stride(0), hd), b_zs=(gq2.stride(0), D), c_zs=(ls, hd * D))
-            dec_dw.__exit__(None, None, None)
+        if grad_sync is not None:
+            grad_sync()
+        opt_st = None
+        if early_opt is not None:
+            opt_st = self._opt_stream()
+            e_main, e_side = torch.cuda.Event(), torch.cuda.Event()
+            e_main.record(cur); e_side.record(side)            # (the decoder's weight-gradient launches sit on the second stream)
+            opt_st.wait_event(e_main); opt_st.wait_event(e_side)
+            with torch.cuda.stream(opt_st):
+                early_opt()
+        # temporal encoders: video on the second stream.  The audio tower's weight-gradient products stay on the main stream, which
+        # idles at the end of the step while the second stream is still in the video tower's chain (profiles/r06_ab_dw_side.txt)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            self._tower_bwd("video", ws, tw, dl_v)
+        self._tower_bwd("audio", ws, tw, dl_a)
+        cur.wait_stream(side)
+        if opt_st is not None:
+            cur.wait_stream(opt_st)
 
+    def _retrieval_bwd_first(self, ws, tw, g_ret: Optional[Tensor]):
+        """First part of the retrieval branch's backward: up to the X-Pool tower's batched score / dP products.  Returns the generator
+        whose exhaustion issues those and everything behind them -- backward() does that BEHIND the decoder's chain: two launches of this
+        branch beside the chain's first layers made one element of a chain product come out one bf16 ulp off -- or None
+        when nothing is left (regression, a configuration without the tower, MADE_RET_SPLIT=0: the whole branch at once, the reference
+        of tests/test_corun_determinism_gpu.py)."""
+        B, _, Ta = self._shape
+        sm = self._inputs[3]
+        if _lib.variant_env("MADE_RET_SPLIT", "1") == "0" or "regression" in self.cfg.mml_localization:
+            self._retrieval_bwd(ws, tw, g_ret, B, Ta, sm)
+            return None
+        gen = self._retrieval_bwd_gen(ws, tw, g_ret, B, Ta, sm)
+        return None if next(gen, "done") == "done" else gen
 
-        # ---------------- DETR encoder
+    def _heads_bwd(self, ws, tw, g_loc: Optional[Tensor]) -> list:
+        """Criterion and heads: the gradient of every decoder layer's output into tw["dhs"].  Returns the heads' weight-gradient launches
+        as closures: they wait for nobody on the main stream and are launched with the decoder's (_decoder_dw: second stream, after the
+        chain); their operands (dlog / dsp / hg1 / hg2 / h1 / h2 / hs) are not touched in between."""
+        c, P, G = self.cfg, self.P, self.G
+        B, Tv, _ = self._shape
+        D, Q, nd = c.D, c.num_moment_queries, c.detr_dec_layers
+        tg, frame, dmusic = self._inputs[4], self._views[0], tw["dmusic"]
+        logits, spans = ws["logits"], ws["spans"]
+        pi, ti, cnt = self._match
+        pq = ws["pq"] if c.contrastive_align_loss else None
+        vid_sum = ws["vid_sum"] if c.contrastive_align_loss else None
+        tr.set_criterion_bwd(logits, spans, tg, pi, ti, cnt, pq, vid_sum, P["empty_weight"], c.foreground_label, P["crit_weights"], g_loc,
+                             tw["dlog"], tw["dsp"], tw["dpq"] if pq is not None else None, tw["dvid_sum"] if pq is not None else None,
+                             ld_out=HEAD_PAD, through_sigmoid=True)
+        hs2 = ws["hs"].view(nd * B * Q, D)
+        dhs = tw["dhs"]
+        dlog, dsp = tw["dlog"], tw["dsp"]
+        if self.tc != torch.float32:                          # same dtype as the activations for the A^T B products
+            tr.add3(tw["dlogsp_c"], tw["dlogsp"])             # both casts in one launch
+            dlog, dsp = tw["dlog_c"], tw["dsp_c"]
+        heads_dw: list = []
+        heads_dw.append(lambda: tr.gemm_tn(dlog[:, :2], hs2, G["class_embed.w"], accumulate=True, colsum=G["class_embed.b"]))
+        ops.linear(dlog, P["class_embed.wt"], None, out=dhs)
+        n_span = 1 if c.predict_center == 1 else 2             # predict_center: the width column is a constant, its gradient is dropped
+        heads_dw.append(lambda: tr.gemm_tn(dsp[:, :n_span], tw["h2"], G["span_embed.2.w"], accumulate=True, colsum=G["span_embed.2.b"]))
+        dz2 = ops.linear(dsp, P["span_embed.2.wt"], None, out=tw["hg1"], gate=_lib.GATE_RELU_OUT, G=tw["h2"])
+        dz1 = self._lin_bwd(dz2, tw["h1"], "span_embed.1", dx_out=tw["hg2"], gate=_lib.GATE_RELU_OUT, G=tw["h1"], later=heads_dw)
+        self._lin_bwd(dz1, hs2, "span_embed.0", dx_out=dhs, R=dhs, later=heads_dw)
+        if c.contrastive_align_loss:
+            Dc = pq.shape[-1]
+            dn = tw["dpq"]
+            if c.audio_short_cut:                             # back through normalize(. + music), aux layers twice; music collects the sums
+                if c.aux_loss and nd > 1:
+                    n_aux = (nd - 1) * B * Q
+                    ds2 = tw["dpq_s2"][:n_aux]
+                    tr.l2norm_bwd(tw["pq_s2"][:n_aux], dn[:n_aux], dx=ds2)
+                    dmusic.add_(ds2.view(nd - 1, B, Q, D).sum((0, 2)))
+                    dn[:n_aux].copy_(ds2)
+                tr.l2norm_bwd(tw["pq_s1"], dn, dx=tw["dpq_s"])
+                dmusic.add_(tw["dpq_s"].view(nd, B, Q, D).sum((0, 2)))
+                dn = tw["dpq_s"]
+            tr.l2norm_bwd(ws["pq_raw"], dn, dx_alt=tw["dpq_raw"])
+            self._lin_bwd(tw["dpq_raw"], hs2, "proj_q", dx_out=dhs, R=dhs, later=heads_dw)
+            # proj_vid_mem: every frame (padded ones too) receives d vid_sum (reference loss_detr.py:118)
+            tr.l2norm_bwd(ws["pv_raw"], tw["dvid_sum"], dx_alt=tw["dpv_raw"], dy_rows_per=Tv)
+            # (its weight gradient is nobody's input: with the heads' other weight gradients on the second stream, after the decoder's
+            #  chain -- it was 52 us at the head of the main stream's backward)
+            heads_dw.append(lambda: tr.gemm_tn(tw["dpv_raw"][:Tv], frame[0], G["proj_v.w"], accumulate=True, colsum=G["proj_v.b"], batch=(B, 1),
+                                               a_zs=(Tv * Dc, 0), b_zs=(frame.stride(0), 0), colsum_zs=(0, 0)))
+            ops.linear(tw["dpv_raw"], P["proj_v.wt"], None, out=tw["dframe_x"])
+        return heads_dw
+
+    def _fused_len(self) -> int:
+        """length of the fused sequence the DETR stack runs on"""
+        _, Tv, Ta = self._shape
+        return Tv + Ta if "concat" in self.cfg.mml_fusion else Ta
+
+    def _dec_self_attn_bwd(self, tw, l: int, g_sa: Tensor, gqkv: Tensor, g4: Tensor, dx_out: Tensor, R: Optional[Tensor] = None) -> Tensor:
+        """A decoder layer's self-attention backward with more than one moment query: out-projection, attention, in-projection (q, k
+        and v all read the layer's input + query embedding; dX (+ R) -> dx_out, returned), and the query embedding's share through q, k."""
+        c, P, G = self.cfg, self.P, self.G
+        B, D, Q, H = self._shape[0], c.D, c.num_moment_queries, c.detr_nheads
+        p, d = f"detr_transformer.decoder.layers.{l}", f"d.{l}"
+        datt = ops.linear(g_sa, P[p + ".sa.out.wt"], None, out=g4)
+        q3, g3v = tw[d + ".qkv"].view(B, Q, 3 * D), gqkv.view(B, Q, 3 * D)
+        tr.attention_bwd(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], tw[d + ".att"].view(B, Q, D), datt.view(B, Q, D),
+                         g3v[:, :, :D], g3v[:, :, D:2 * D], g3v[:, :, 2 * D:], tw[d + ".lse"], tw["d_delta"], H,
+                         drop=self._drop(f"dec.{l}" + ".sa_attn", float(c.detr_dropout)))
+        dx = ops.linear(gqkv, P[p + ".sa.in.wt"], None, R=R, out=dx_out)
+        dqk = ops.linear(gqkv[:, :2 * D], P[p + ".sa.in.wt"][:, :2 * D], None, out=g4)
+        tr.colsum(dqk.view(B, Q * D), G["query_embed"].view(-1))
+        return dx
+
+    def _decoder_bwd(self, ws, tw) -> Tuple[Tensor, Tensor]:
+        """Decoder, last layer first: the data-gradient chain from tw["dhs"].  Inside the loop only that chain runs; every output gradient
+        a weight gradient needs is kept per layer (the g_* stacks) and the weight-gradient products of all layers are batched after it
+        (_decoder_dw).  Returns (dmem, dtgt0): the gradients of the encoder memory and of the decoder's content query."""
+        c, P, G = self.cfg, self.P, self.G
+        B, L = self._shape[0], self._fused_len()
+        D, Q, nd, H = c.D, c.num_moment_queries, c.detr_dec_layers, c.detr_nheads
+        hd, HQ = D // H, H * Q
+        pd = float(c.detr_dropout)
+        inv_keep = 1.0 / (1.0 - pd) if (self.training_dropout and pd > 0) else 1.0
+        fus_mask, dhs = ws["fus_mask"], tw["dhs"]
+        mem3, mempos3 = tw["mem"].view(B, L, D), tw["mempos"].view(B, L, D)
+        Lp = tw["PdS"].shape[-1]
+        GQ, PdS = tw["GQ"], tw["PdS"]
+        ca_scale = 1.0 / math.sqrt(hd)
+        st = tw["dstack"]
+        dtgt = None
+        stage = self._dec_stage_chain()                    # fused chain: see forward_train
+        pre = bool(c.detr_pre_norm)                        # pre-norm layers (reference music_detr/transformer.py:246-271): separate launches
+        if stage:
+            n_split, wplan = self._wide_split(B, backward=True)
+            # the shared output norm's backward depends on the heads only: all layers in ONE launch ahead of the dependent chain
+            gN = tw["dgN"]
+            tr.layernorm_bwd(st["tgt"][1:].reshape(nd * B * Q, D), P["dec.norm.g"], dhs, gN, dgamma=G["dec.norm.g"], dbeta=G["dec.norm.b"])
+        else:
+            # the scores of every layer's memory-space attention depend on forward values only (q', memory + pos): ONE batched
+            # product for all layers ([nd, B, H*Q, L] rows) ahead of the dependent chain instead of one launch inside every layer
+            S_all = tw["dS_S"]
+            ops.linear(GQ[0, 1].reshape(nd * HQ, D), mempos3[0], None, M=nd * HQ, N=L, K=D, batch=B, a_z_stride=GQ.stride(0), w_z_stride=L * D,
+                       segs=[Seg(out=S_all, ldo=Lp, rows_per_batch=HQ, out_batch_stride=B * HQ * Lp, out_z_stride=HQ * Lp)])
+        for l in range(nd - 1, -1, -1):
+            p, d = f"detr_transformer.decoder.layers.{l}", f"d.{l}"
+            g1, g2, g4 = tw["dg1"], tw["dg2"], tw["dg4"]
+            if stage:
+                # every hand-off of the fused chain has rows of its own (tools/race_probe3.py and the co-run test read them from here)
+                ch = tw["dchain"][l]
+                g1a, g1b, g2a, g2b, g2c, dt_out = ch[0], ch[1], ch[2], ch[3], ch[4], ch[5]
+            else:
+                g1a = g1b = g1
+                g2a = g2b = g2
+            Win, Wt = P[p + ".ca.in.w"], P[p + ".ca.in.wt"]
+            g_ffn, g_z, g_ca, g_attc, g_q, g_qc, g_sa, gqkv = (st[k][l] for k in ("g_ffn", "g_z", "g_ca", "g_attc", "g_q", "g_qc", "g_sa", "g_qkv"))
+            if stage:
+                # hs_l = dec.norm(t3) (its backward: one launch for all layers ahead of the chain), t3 = LN3(t2 + drop3(ffn)) also feeds
+                # the next layer: norm 3's backward of (d hs_l through the output norm + d tgt_{l+1}) in the prologue of the FFN's second
+                # dX product
+                tr.dec_stage_bwd(tw[d + ".t_c"], P[p + ".ln3.g"], gN[l * B * Q:(l + 1) * B * Q], P[p + ".ff2.wt"], g_z,
+                                 dgamma_a=G[p + ".ln3.g"], dbeta_a=G[p + ".ln3.b"], add=dtgt, dx_out=g2a, a_out=g_ffn,
+                                 drop_a=self._drop(f"dec.{l}" + ".drop3", pd), G=tw[d + ".h"], gate_scale=inv_keep)
+            elif pre:
+                # hs_l = dec.norm(stream); the stream (slot l + 1 of the tgt stack) also feeds the next layer: g1 = d stream
+                tr.layernorm_bwd(tw[d + ".t3"], P["dec.norm.g"], dhs[l * B * Q:(l + 1) * B * Q], g1, dgamma=G["dec.norm.g"], dbeta=G["dec.norm.b"], add=dtgt)
+                # stream = t_b + drop3(ffn(LN3(t_b)))
+                tr.gate_rows(g1, g_ffn, drop=self._drop(f"dec.{l}" + ".drop3", pd))
+            else:
+                # hs_l = dec.norm(t3); t3 also feeds the next layer
+                tr.layernorm_bwd(tw[d + ".t3"], P["dec.norm.g"], dhs[l * B * Q:(l + 1) * B * Q], g1, dgamma=G["dec.norm.g"], dbeta=G["dec.norm.b"], add=dtgt)
+                # t3 = LN3(t2 + drop3(ffn))
+                tr.layernorm_bwd(tw[d + ".t_c"], P[p + ".ln3.g"], g1, g2, dgamma=G[p + ".ln3.g"], dbeta=G[p + ".ln3.b"],
+                                 dx_drop=g_ffn, drop=self._drop(f"dec.{l}" + ".drop3", pd))
+            if not stage:
+                ops.linear(g_ffn, P[p + ".ff2.wt"], None, out=g_z, gate=_lib.GATE_RELU_OUT, G=tw[d + ".h"], gate_scale=inv_keep)
+            if pre:
+                dn3 = ops.linear(g_z, P[p + ".ff1.wt"], None, out=g4)
+                # t_b = t_a + drop2(cross-attention): d t_b = LN3'(dn3) + d stream -> g2; its dropped copy feeds the out-projection
+                tr.layernorm_bwd(tw[d + ".t_b"], P[p + ".ln3.g"], dn3, g2, dgamma=G[p + ".ln3.g"], dbeta=G[p + ".ln3.b"], add=g1,
+                                 dx_drop=g_ca, drop=self._drop(f"dec.{l}" + ".drop2", pd))
+                dattc = ops.linear(g_ca, P[p + ".ca.out.wt"], None, out=g_attc)
+            else:
+                dt2 = ops.linear(g_z, P[p + ".ff1.wt"], None, out=g1a, R=g2a)
+            # t2 = LN2(t1 + drop2(cross-attention))
+            if pre:
+                pass
+            elif stage:                                       # norm 2's backward in the prologue of the out-projection's dX product
+                dattc = tr.dec_stage_bwd(tw[d + ".t_b"], P[p + ".ln2.g"], dt2, P[p + ".ca.out.wt"], g_attc, dgamma_a=G[p + ".ln2.g"],
+                                         dbeta_a=G[p + ".ln2.b"], dx_out=g2b, a_out=g_ca, drop_a=self._drop(f"dec.{l}" + ".drop2", pd))
+            else:
+                tr.layernorm_bwd(tw[d + ".t_b"], P[p + ".ln2.g"], dt2, g2, dgamma=G[p + ".ln2.g"], dbeta=G[p + ".ln2.b"],
+                                 dx_drop=g_ca, drop=self._drop(f"dec.{l}" + ".drop2", pd))
+                dattc = ops.linear(g_ca, P[p + ".ca.out.wt"], None, out=g_attc)
+            dpooled = GQ[:, 0, l]                             # [B, H*Q, D] slice of the concatenated buffer
+            qprime = GQ[:, 1, l]
+            if stage:
+                # v_h = W_v,h pooled_h : dpooled_h = dattc_h W_v,h
+                ops.linear(dattc[:, :hd], Wt[:, 2 * D:2 * D + hd], None, M=B * Q, N=D, K=hd, batch=H, a_z_stride=hd, w_z_stride=hd,
+                           segs=[Seg(out=dpooled, ldo=D, rows_per_batch=Q, out_batch_stride=dpooled.stride(0), out_z_stride=Q * D)])
+                # the memory-space attention's backward in ONE launch: scores and probabilities recomputed from the saved lse, the
+                # value-bias term reduced from dattc, Pd / dS written for the memory-gradient product after the loop, dq' = dS (mem + pos)
+                # (the value bias' own gradient needs nothing of the chain: after the loop, second stream)
+                tr.attention_wide_bwd(qprime, dpooled, tw[d + ".pooled"].view(B, HQ, D), mempos3, mem3, tw["ca_lse"][l].view(B, HQ),
+                                      PdS[:, 0, l], PdS[:, 1, l], g_q, scale=ca_scale, key_mask=fus_mask, ssum=tw[d + ".s"].view(B, HQ),
+                                      dattc=dattc, vbias=P[p + ".ca.in.b"][2 * D:], hd=hd, drop=self._drop(f"dec.{l}" + ".ca_attn", pd),
+                                      n_split=n_split, part_dq=ws["part_o"], plan=wplan)
+            else:
+                tr.head_bias_bwd(dattc, tw[d + ".s"], P[p + ".ca.in.b"][2 * D:], G[p + ".ca.in.b"][2 * D:], tw["d_ds"], H)
+                d_ds = tw["d_ds"]                                 # rows (b, q), columns h; the softmax backward numbers its rows (b, h, q)
+                if Q > 1:
+                    tw["dds_raw"].view(B, H, Q).copy_(d_ds.view(B, Q, H).permute(0, 2, 1))
+                    d_ds = tw["dds_raw"]
+                # v_h = W_v,h pooled_h : dpooled_h = dattc_h W_v,h
+                ops.linear(dattc[:, :hd], Wt[:, 2 * D:2 * D + hd], None, M=B * Q, N=D, K=hd, batch=H, a_z_stride=hd, w_z_stride=hd,
+                           segs=[Seg(out=dpooled, ldo=D, rows_per_batch=Q, out_batch_stride=dpooled.stride(0), out_z_stride=Q * D)])
+                # scores and dPd of the memory-space attention (few rows per sample: materialised)
+                S, dP = S_all[l], tw["dS_dP"]
+                ops.linear(dpooled[0], mem3[0], None, M=HQ, N=L, K=D, batch=B, a_z_stride=dpooled.stride(0), w_z_stride=L * D,
+                           segs=[Seg(out=dP, ldo=Lp, out_z_stride=HQ * Lp)])
+                tr.softmax_bwd(S, dP, fus_mask, HQ, ca_scale, PdS[:, 0, l], PdS[:, 1, l], tw["dSt"], HQ, L, extra=d_ds.view(-1),
+                               drop=self._drop(f"dec.{l}" + ".ca_attn", pd), ldo=Lp, ldt=HQ, out_batch_stride=PdS.stride(0))
+                # dq'[b] = dS[b] (mem + pos)[b]
+                gq_out = g_q if Q == 1 else tw["gq_raw"]         # [B, (h, q), D] out of the product; [B, (q, h), D] for the Linears
+                tr.gemm_tn(tw["dSt"][0], mempos3[0], gq_out[0], batch=(B, 1), a_zs=(L * HQ, 0), b_zs=(L * D, 0), c_zs=(HQ * D, 0),
+                           row_mask=fus_mask, mask_zs=(L, 0))
+                if Q > 1:
+                    g_q.view(B, Q, H, D).copy_(gq_out.view(B, H, Q, D).permute(0, 2, 1, 3))
+            # q'_h = W_k,h^T qc_h : dqc_h = dq'_h W_k,h^T
+            dq2 = g_q.view(B * Q, H * D)
+            ops.linear(dq2[:, :D], Win[D:D + hd], None, M=B * Q, N=hd, K=D, batch=H, a_z_stride=D, w_z_stride=hd * D,
+                       segs=[Seg(out=g_qc, ldo=D, out_z_stride=hd)])
+            # qc = W_q (t1 + qp) + b_q
+            # dt1 = residual path + query path in the Linear's epilogue; the query path alone (the pre-residual value) is kept for
+            # the query embedding's gradient
+            dt1q = st["dt1q"][l]                               # (summed over the batch into the query embedding's gradient after the loop)
+            if pre:
+                # qc = W_q (LN2(t_a) + qp) + b_q: d (LN2(t_a) + qp) -> dt1q; d t_a = LN2'(dt1q) + d t_b -> g1, its dropped copy feeds the
+                # self-attention's out-projection
+                ops.linear(g_qc, Wt[:, :D], None, out=dt1q)
+                tr.layernorm_bwd(tw[d + ".t_a"], P[p + ".ln2.g"], dt1q, g1, dgamma=G[p + ".ln2.g"], dbeta=G[p + ".ln2.b"], add=g2,
+                                 dx_drop=g_sa, drop=self._drop(f"dec.{l}" + ".drop1", pd))
+                if Q == 1:                                    # value path only (see the forward)
+                    ops.linear(g_sa, P[p + ".sa.out.wt"], None, segs=[Seg(out=gqkv[:, 2 * D:], ldo=gqkv.stride(0))],
+                               drop=self._drop(f"dec.{l}" + ".sa_attn", pd), drop_ld=H, drop_col_div=hd)
+                    dn1 = ops.linear(gqkv[:, 2 * D:], P[p + ".sa.in.wt"][:, 2 * D:], None, out=g4)
+                else:
+                    dn1 = self._dec_self_attn_bwd(tw, l, g_sa, gqkv, g4, dx_out=g2)
+                # n1 = LN1(tgt): d tgt = LN1'(dn1) + d t_a
+                dtgt = tr.layernorm_bwd(tw[d + ".tgt"], P[p + ".ln1.g"], dn1, tw["dtgt"], dgamma=G[p + ".ln1.g"], dbeta=G[p + ".ln1.b"], add=g1)
+                continue
+            ops.linear(g_qc, Wt[:, :D], None, out=g1b, R=g2b, Zout=dt1q)
+            # t1 = LN1(tgt + drop1(self-attention))
+            if stage:
+                # norm 1's backward in the prologue of the self-attention out-projection's dX product (value path only: dv = datt under
+                # the same per-head mask, drawn in the epilogue)
+                tr.dec_stage_bwd(tw[d + ".t_a"], P[p + ".ln1.g"], g1b, P[p + ".sa.out.wt"], gqkv[:, 2 * D:], dgamma_a=G[p + ".ln1.g"],
+                                 dbeta_a=G[p + ".ln1.b"], dx_out=g2c, a_out=g_sa, drop_a=self._drop(f"dec.{l}" + ".drop1", pd),
+                                 drop_o=self._drop(f"dec.{l}" + ".sa_attn", pd), drop_o_ld=H, drop_o_col_div=hd)
+                dtgt = ops.linear(gqkv[:, 2 * D:], P[p + ".sa.in.wt"][:, 2 * D:], None, R=g2c, out=dt_out)
+                continue
+            tr.layernorm_bwd(tw[d + ".t_a"], P[p + ".ln1.g"], g1, g2, dgamma=G[p + ".ln1.g"], dbeta=G[p + ".ln1.b"],
+                             dx_drop=g_sa, drop=self._drop(f"dec.{l}" + ".drop1", pd))
+            if Q == 1:                                        # value path only (see the forward): dv = datt under the same per-head mask,
+                ops.linear(g_sa, P[p + ".sa.out.wt"], None, segs=[Seg(out=gqkv[:, 2 * D:], ldo=gqkv.stride(0))],       # drawn in the epilogue
+                           drop=self._drop(f"dec.{l}" + ".sa_attn", pd), drop_ld=H, drop_col_div=hd)
+                dtgt = ops.linear(gqkv[:, 2 * D:], P[p + ".sa.in.wt"][:, 2 * D:], None, R=g2, out=tw["dtgt"])
+            else:
+                dtgt = self._dec_self_attn_bwd(tw, l, g_sa, gqkv, g4, dx_out=tw["dtgt"], R=g2)
+        # gradient of the memory: values path (Pd^T dpooled) + keys path (dS^T q'), all layers in one product per sample -- the
+        # one thing the DETR encoder's backward waits for
+        dmem = tw["eg1"]
+        tr.gemm_tn(PdS.view(B, 2 * nd * HQ, Lp)[0, :, :L], GQ.view(B, 2 * nd * HQ, D)[0], dmem.view(B, L, D)[0], batch=(B, 1),
+                   a_zs=(PdS.stride(0), 0), b_zs=(GQ.stride(0), 0), c_zs=(L * D, 0))
+        return dmem, dtgt                                     # (d tgt of layer 0 = the gradient of the clip-level vector)
+
+    def _decoder_dw(self, tw, heads_dw: list) -> None:
+        """Weight gradients of the heads (the closures of _heads_bwd) and of all decoder layers: one layer-batched product per parameter
+        (the layers' parameters, and the [nd, ...] stacks, are equally spaced)."""
+        c, P, G = self.cfg, self.P, self.G
+        B, D, Q, nd, H = self._shape[0], c.D, c.num_moment_queries, c.detr_dec_layers, c.detr_nheads
+        hd, BQ = D // H, B * Q
+        st = tw["dstack"]
+        for launch in heads_dw:
+            launch()
+        tr.colsum(st["dt1q"].view(nd * B, Q * D), G["query_embed"].view(-1))     # every layer's query path at once
+        if self._dec_stage_chain():                        # the value bias' gradient d b_v,h = sum_b s[b, h] dattc[b, h] of every layer
+            for l in range(nd):
+                pl = f"detr_transformer.decoder.layers.{l}"
+                tr.head_bias_bwd(st["g_attc"][l], tw[f"d.{l}.s"], P[pl + ".ca.in.b"][2 * D:], G[pl + ".ca.in.b"][2 * D:], tw["d_ds"], H)
+        p0, p1 = "detr_transformer.decoder.layers.0", "detr_transformer.decoder.layers.1"
+
+        def lstride(key):
+            return (G[p1 + key].data_ptr() - G[p0 + key].data_ptr()) // 4 if nd > 1 else 0
+
+        def batched(a_stack, b_stack, wkey, bkey, a_cols=None, b_cols=None, w_rows=None):
+            A, Bm = a_stack[0], b_stack[0]
+            if a_cols is not None:
+                A = A[:, a_cols[0]:a_cols[1]]
+            if b_cols is not None:
+                Bm = Bm[:, b_cols[0]:b_cols[1]]
+            gw, gb = G[p0 + wkey], (G[p0 + bkey] if bkey is not None else None)
+            if w_rows is not None:
+                gw = gw[w_rows[0]:w_rows[1]]
+                gb = gb[w_rows[0]:w_rows[1]] if gb is not None else None
+            tr.gemm_tn(A, Bm, gw, accumulate=True, colsum=gb, batch=(nd, 1), a_zs=(a_stack.stride(0), 0), b_zs=(b_stack.stride(0), 0),
+                       c_zs=(lstride(wkey), 0), colsum_zs=(lstride(bkey) if bkey is not None else 0, 0))
+
+        batched(st["g_ffn"], st["h"], ".ff2.w", ".ff2.b")
+        batched(st["g_z"], st["t2"], ".ff1.w", ".ff1.b")
+        batched(st["g_ca"], st["attc"], ".ca.out.w", ".ca.out.b")
+        batched(st["g_qc"], st["t1q"], ".ca.in.w", ".ca.in.b", w_rows=(0, D))
+        batched(st["g_sa"], st["att"], ".sa.out.w", ".sa.out.b")
+        if Q > 1:                                             # (a single query's q / k projections get no gradient)
+            batched(st["g_qkv"], st["tq"], ".sa.in.w", ".sa.in.b", a_cols=(0, 2 * D), w_rows=(0, 2 * D))
+        batched(st["g_qkv"], st["n1"] if c.detr_pre_norm else st["tgt"], ".sa.in.w", ".sa.in.b", a_cols=(2 * D, 3 * D), w_rows=(2 * D, 3 * D))
+        # per-head products of the memory-space cross-attention, batched over (layer, head)
+        gWin0 = G[p0 + ".ca.in.w"]
+        ls = lstride(".ca.in.w")
+        # v_h = W_v,h pooled_h : dW_v,h += dattc_h^T pooled_h
+        tr.gemm_tn(st["g_attc"][0][:, :hd], st["pooled"][0][:, :D], gWin0[2 * D:2 * D + hd], accumulate=True, batch=(nd, H),
+                   a_zs=(st["g_attc"].stride(0), hd), b_zs=(st["pooled"].stride(0), D), c_zs=(ls, hd * D))
+        # q'_h = W_k,h^T qc_h : dW_k,h += qc_h^T dq'_h
+        gq2 = st["g_q"].view(nd, BQ, H * D)
+        tr.gemm_tn(st["qc"][0][:, :hd], gq2[0][:, :D], gWin0[D:D + hd], accumulate=True, batch=(nd, H),
+                   a_zs=(st["qc"].stride(0), hd), b_zs=(gq2.stride(0), D), c_zs=(ls, hd * D))
+
+    def _enc_attn_bwd(self, ws, tw, l: int, datt: Tensor, gq: Tensor, x_qk: Tensor, x_v: Tensor, pend: list) -> None:
+        """Tail of a DETR-encoder layer's backward, shared by the pre- and post-norm forms (they differ in which saved activations fed
+        q / k -- x_qk -- and v -- x_v): the attention's backward into gq, then the in-projection's weight gradients, queued on `pend` for
+        the layer's grouped launch where that takes them."""
+        c, G = self.cfg, self.G
+        B, L, D, H = self._shape[0], self._fused_len(), c.D, c.detr_nheads
+        p, e = f"detr_transformer.encoder.layers.{l}", f"e.{l}"
+        fus_mask = ws["fus_mask"]
+        regression = "regression" in c.mml_localization      # (every position computed, keys stay masked: see _detr_encoder_bwd)
+        fskip, qskip = (None, None) if regression else (fus_mask.view(-1), fus_mask)
+        q3, gq3 = tw[e + ".qkv"].view(B, L, 3 * D), gq.view(B, L, 3 * D)
+        tr.attention_bwd(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], tw[e + ".att"].view(B, L, D), datt.view(B, L, D),
+                         gq3[:, :, :D], gq3[:, :, D:2 * D], gq3[:, :, 2 * D:], tw[e + ".lse"], tw["e_delta"], H,
+                         key_mask=fus_mask, q_skip_mask=qskip, drop=self._drop(f"enc.{l}" + ".attn", float(c.detr_dropout)),
+                         order=self._order[fus_mask.data_ptr()], keep_bits=tw[e + ".kbits"] if self._bits else None)
+        gW, gb = G[p + ".in.w"], G[p + ".in.b"]
+        if self._groupable(gq, x_qk, gW[:2 * D]) and self._rw(fskip) is not None:
+            pend.append((gq[:, :2 * D], x_qk, gW[:2 * D], gb[:2 * D]))
+            pend.append((gq[:, 2 * D:], x_v, gW[2 * D:], gb[2 * D:]))
+        else:
+            tr.gemm_tn(gq[:, :2 * D], x_qk, gW[:2 * D], accumulate=True, colsum=gb[:2 * D], rows=self._rw(fskip))
+            tr.gemm_tn(gq[:, 2 * D:], x_v, gW[2 * D:], accumulate=True, colsum=gb[2 * D:], rows=self._rw(fskip))
+
+    def _detr_encoder_bwd(self, ws, tw, dmem: Tensor) -> Tuple[Tensor, Tensor]:
+        """DETR encoder, last layer first, from the gradient of its memory, then back through the fusion to the two temporal towers'
+        outputs.  Returns their gradients (dl_v [B, T_v, D], dl_a [B, T_a, D]).
+        Each layer's weight gradients are one grouped launch behind its data chain, on the same stream (the single-pass attention
+        backward shortened the main stream's chain; inside the step 4.80 against 4.88 ms with these and the audio tower's on the main
+        stream instead of the second: profiles/r06_ab_dw_side.txt)."""
+        c, P, G = self.cfg, self.P, self.G
+        B, Tv, Ta = self._shape
+        D, L, ne = c.D, self._fused_len(), c.detr_enc_layers
+        rows = B * L
+        pd = float(c.detr_dropout)
+        inv_keep = 1.0 / (1.0 - pd) if (self.training_dropout and pd > 0) else 1.0
+        fus, fus_mask = ws["fus"], ws["fus_mask"]
+        # the regression head sums the memory over ALL positions: the encoder computed the padded ones too (forward_train)
+        fskip = None if "regression" in c.mml_localization else fus_mask.view(-1)
         dsrc = dmem
-        # the encoder layers' grouped weight-gradient launches: on the main stream since round 6 (the single-pass attention backward shortened the
-        # main stream's chain; inside the step 4.80 against 4.88 ms with these and the audio tower's on the main stream: gpurun_out/ab_dw_side.txt,
-        # profiles/r06_ab_dw_side.txt).  MADE_ENC_DW_SIDE=1 (measurement knob): on the second stream, as rounds 3-5 had them
-        enc_dw_side = _lib.variant_env("MADE_ENC_DW_SIDE", "0") != "0"
-        enc_dw_done = [None, None]
         for l in range(ne - 1, -1, -1):
             p, e = f"detr_transformer.encoder.layers.{l}", f"e.{l}"
             # (every gradient that feeds a weight-gradient product keeps a buffer of its own until the layer's grouped launch)
             g2, g2b, g3, g3b, g3c, gq, gf = tw["eg2"], tw["eg2b"], tw["eg3"], tw["eg3b"], tw["eg3c"], tw["egqkv"], tw["egffn"]
-            if enc_dw_side:
-                if l & 1:
-                    g2b, g3, gq, gf = tw["eg2b_2"], tw["eg3_2"], tw["egqkv_2"], tw["egffn_2"]
-                if enc_dw_done[l & 1] is not None:               # (more than two layers: the set's previous weight-gradient launch)
-                    cur.wait_event(enc_dw_done[l & 1])
             pend: list = []
             if c.detr_pre_norm:
                 # reference music_detr/transformer.py:170-189 (forward_pre), backwards.  dsrc = gradient of the layer's output stream x2.
@@ -1584,119 +1639,69 @@ class MadeTrainer(MadeEngine):
                 tr.layernorm_bwd(tw[e + ".x"], P[p + ".ln2.g"], dn2, dx, dgamma=G[p + ".ln2.g"], dbeta=G[p + ".ln2.b"], add=dsrc, dx_drop=g2b,
                                  drop=self._drop(f"enc.{l}" + ".drop1", pd), row_skip=fskip)
                 datt = self._lin_bwd(g2b, tw[e + ".att"], p + ".out", dx_out=g3c, row_mask=fskip, skip=fskip, defer=pend)
-                qkv = tw[e + ".qkv"]
-                q3, gq3 = qkv.view(B, L, 3 * D), gq.view(B, L, 3 * D)
-                tr.attention_bwd(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], tw[e + ".att"].view(B, L, D), datt.view(B, L, D),
-                                 gq3[:, :, :D], gq3[:, :, D:2 * D], gq3[:, :, 2 * D:], tw[e + ".lse"], tw["e_delta"], H,
-                                 key_mask=fus_mask, q_skip_mask=qskip, drop=self._drop(f"enc.{l}" + ".attn", pd),
-                                 order=self._order[fus_mask.data_ptr()], keep_bits=tw[e + ".kbits"] if self._bits else None)
-                gW, gb = G[p + ".in.w"], G[p + ".in.b"]
-                if self._groupable(gq, n1pos, gW[:2 * D]) and self._rw(fskip) is not None:
-                    pend.append((gq[:, :2 * D], n1pos, gW[:2 * D], gb[:2 * D]))
-                    pend.append((gq[:, 2 * D:], n1, gW[2 * D:], gb[2 * D:]))
-                else:
-                    tr.gemm_tn(gq[:, :2 * D], n1pos, gW[:2 * D], accumulate=True, colsum=gb[:2 * D], rows=self._rw(fskip))
-                    tr.gemm_tn(gq[:, 2 * D:], n1, gW[2 * D:], accumulate=True, colsum=gb[2 * D:], rows=self._rw(fskip))
+                self._enc_attn_bwd(ws, tw, l, datt, gq, n1pos, n1, pend)
                 dn1 = ops.linear(gq, P[p + ".in.wt"], None, out=g2, rows=self._rw(fskip))      # q, k and v all read LN1(x_in) (+ pos)
                 nxt = tw["dfus"] if dx is tw["eg1"] else tw["eg1"]
                 dsrc = tr.layernorm_bwd(xin, P[p + ".ln1.g"], dn1, nxt, dgamma=G[p + ".ln1.g"], dbeta=G[p + ".ln1.b"], add=dx, row_skip=fskip)
-                if enc_dw_side:
-                    side.wait_stream(cur)
-                    with torch.cuda.stream(side):
-                        self._flush_dw(pend, fskip)
-                        enc_dw_done[l & 1] = torch.cuda.Event()
-                        enc_dw_done[l & 1].record(side)
-                else:
-                    self._flush_dw(pend, fskip)
-                continue
-            src = fus.view(rows, D) if l == 0 else tw[e + ".src"]
-            srcpos = tw[e + ".srcpos"]
-            # src_{l+1} = LN2(s1 + drop2(ffn))
-            tr.layernorm_bwd(tw[e + ".x2"], P[p + ".ln2.g"], dsrc, g2, dgamma=G[p + ".ln2.g"], dbeta=G[p + ".ln2.b"], dx_drop=g3,
-                             drop=self._drop(f"enc.{l}" + ".drop2", pd), row_skip=fskip)
-            dz = self._lin_bwd(g3, tw[e + ".h"], p + ".ff2", dx_out=gf, row_mask=fskip, skip=fskip, gate=_lib.GATE_RELU_OUT, G=tw[e + ".h"],
-                               gate_scale=inv_keep, defer=pend)
-            ds1 = self._lin_bwd(dz, tw[e + ".s1"], p + ".ff1", dx_out=g3b, row_mask=fskip, skip=fskip, R=g2, defer=pend)
-            # s1 = LN1(src + drop1(attention))
-            dx = tw["eg1"] if dsrc is not tw["eg1"] else tw["dfus"]
-            tr.layernorm_bwd(tw[e + ".x"], P[p + ".ln1.g"], ds1, dx, dgamma=G[p + ".ln1.g"], dbeta=G[p + ".ln1.b"], dx_drop=g2b,
-                             drop=self._drop(f"enc.{l}" + ".drop1", pd), row_skip=fskip)
-            datt = self._lin_bwd(g2b, tw[e + ".att"], p + ".out", dx_out=g3c, row_mask=fskip, skip=fskip, defer=pend)
-            qkv = tw[e + ".qkv"]
-            q3, gq3 = qkv.view(B, L, 3 * D), gq.view(B, L, 3 * D)
-            tr.attention_bwd(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], tw[e + ".att"].view(B, L, D), datt.view(B, L, D),
-                             gq3[:, :, :D], gq3[:, :, D:2 * D], gq3[:, :, 2 * D:], tw[e + ".lse"], tw["e_delta"], H,
-                             key_mask=fus_mask, q_skip_mask=qskip, drop=self._drop(f"enc.{l}" + ".attn", pd),
-                             order=self._order[fus_mask.data_ptr()], keep_bits=tw[e + ".kbits"] if self._bits else None)
-            gW, gb = G[p + ".in.w"], G[p + ".in.b"]
-            if self._groupable(gq, srcpos, gW[:2 * D]) and self._rw(fskip) is not None:
-                pend.append((gq[:, :2 * D], srcpos, gW[:2 * D], gb[:2 * D]))
-                pend.append((gq[:, 2 * D:], src, gW[2 * D:], gb[2 * D:]))
             else:
-                tr.gemm_tn(gq[:, :2 * D], srcpos, gW[:2 * D], accumulate=True, colsum=gb[:2 * D], rows=self._rw(fskip))
-                tr.gemm_tn(gq[:, 2 * D:], src, gW[2 * D:], accumulate=True, colsum=gb[2 * D:], rows=self._rw(fskip))
-            nxt = tw["dfus"] if dx is tw["eg1"] else tw["eg1"]
-            dsrc = ops.linear(gq, P[p + ".in.wt"], None, R=dx, out=nxt, rows=self._rw(fskip))
-            if enc_dw_side:
-                # the layer's grouped weight-gradient launch (~170 us of MFMA work) needs nothing but this layer's gradients and
-                # nobody on the main stream needs it: second stream, beside the next layer's (bandwidth- and VALU-heavy) data chain
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    self._flush_dw(pend, fskip)
-                    enc_dw_done[l & 1] = torch.cuda.Event()
-                    enc_dw_done[l & 1].record(side)
-            else:
-                self._flush_dw(pend, fskip)
+                src = fus.view(rows, D) if l == 0 else tw[e + ".src"]
+                srcpos = tw[e + ".srcpos"]
+                # src_{l+1} = LN2(s1 + drop2(ffn))
+                tr.layernorm_bwd(tw[e + ".x2"], P[p + ".ln2.g"], dsrc, g2, dgamma=G[p + ".ln2.g"], dbeta=G[p + ".ln2.b"], dx_drop=g3,
+                                 drop=self._drop(f"enc.{l}" + ".drop2", pd), row_skip=fskip)
+                dz = self._lin_bwd(g3, tw[e + ".h"], p + ".ff2", dx_out=gf, row_mask=fskip, skip=fskip, gate=_lib.GATE_RELU_OUT, G=tw[e + ".h"],
+                                   gate_scale=inv_keep, defer=pend)
+                ds1 = self._lin_bwd(dz, tw[e + ".s1"], p + ".ff1", dx_out=g3b, row_mask=fskip, skip=fskip, R=g2, defer=pend)
+                # s1 = LN1(src + drop1(attention))
+                dx = tw["eg1"] if dsrc is not tw["eg1"] else tw["dfus"]
+                tr.layernorm_bwd(tw[e + ".x"], P[p + ".ln1.g"], ds1, dx, dgamma=G[p + ".ln1.g"], dbeta=G[p + ".ln1.b"], dx_drop=g2b,
+                                 drop=self._drop(f"enc.{l}" + ".drop1", pd), row_skip=fskip)
+                datt = self._lin_bwd(g2b, tw[e + ".att"], p + ".out", dx_out=g3c, row_mask=fskip, skip=fskip, defer=pend)
+                self._enc_attn_bwd(ws, tw, l, datt, gq, srcpos, src, pend)
+                nxt = tw["dfus"] if dx is tw["eg1"] else tw["eg1"]
+                dsrc = ops.linear(gq, P[p + ".in.wt"], None, R=dx, out=nxt, rows=self._rw(fskip))
+            self._flush_dw(pend, fskip)
         dfus = dsrc.view(B, L, D)
-        if concat:
-            dl_v, dl_a = dfus[:, :Tv], dfus[:, Tv:]
-        else:                                                 # through the CA fusion block back to the two encoders' outputs
-            self._ca_fusion_bwd(ws, tw, dsrc, frame, seg_view, fm, sm, B, Tv, Ta)
-            dl_v, dl_a = tw["c_dframe"].view(B, Tv, D), tw["c_dseg"].view(B, Ta, D)
+        if "concat" in c.mml_fusion:
+            return dfus[:, :Tv], dfus[:, Tv:]
+        # through the CA fusion block back to the two encoders' outputs
+        frame, seg_view = self._views
+        self._ca_fusion_bwd(ws, tw, dsrc, frame, seg_view, self._inputs[2], self._inputs[3], B, Tv, Ta)
+        return tw["c_dframe"].view(B, Tv, D), tw["c_dseg"].view(B, Ta, D)
 
-        # ---------------- join the X-Pool / similarity branch, merge the gradients of the clip-level vectors
-        # (one process: the main stream needs the retrieval branch's results here, not the weight-gradient products queued behind it on
-        #  the second stream -- joining the whole stream left it idle behind the last DETR layer's grouped product, 0.2 ms per step;
-        #  data-parallel jobs start their first all-reduce below and need every gradient of its range complete)
-        if ret_done is not None and grad_sync is None and _lib.variant_env("MADE_BWD_EVENT_JOIN", "1") != "0":
-            cur.wait_event(ret_done)
-        else:
-            cur.wait_stream(side)
-        if xq:
+    def _merge_clip_grads(self, ws, tw, g_ret: Optional[Tensor], dtgt0: Optional[Tensor]) -> None:
+        """The decoder's content query was a clip-level vector: its gradient (dtgt0) joins that vector's.  With an xpool query the
+        retrieval branch's whole backward runs here, behind the decoder's."""
+        c = self.cfg
+        B, _, Ta = self._shape
+        D, Q = c.D, c.num_moment_queries
+        if "regression" in c.mml_localization:               # (no decoder, no content query)
+            return
+        if c.moment_query_type == "xpool":
             # the decoder's content query was the mean over the videos of each track's pooled vectors: its gradient enters the
             # X-Pool tail as dpool[m] / N_v for every video n
             dq = tw["dxpool_q"]
             tr.add3(dq, dtgt0.view(B, D) if Q == 1 else dtgt0.view(B, Q, D).float().sum(dim=1).contiguous())
-            self._retrieval_bwd(ws, tw, g_ret, B, Ta, sm, dpool=dq)
-        if c.moment_query_type in ("video", "music") and not regression:       # (a zero content query has no gradient to hand on)
-            dq_vec = dvideo if c.moment_query_type == "video" else dmusic
+            self._retrieval_bwd(ws, tw, g_ret, B, Ta, self._inputs[3], dpool=dq)
+        if c.moment_query_type in ("video", "music"):        # (a zero content query has no gradient to hand on)
+            dq_vec = tw["dvideo"] if c.moment_query_type == "video" else tw["dmusic"]
             tr.add3(dq_vec, dq_vec, dtgt0.view(B, D) if Q == 1 else dtgt0.view(B, Q, D).float().sum(dim=1))    # the vector was repeated Q times
 
-        if grad_sync is not None:
-            grad_sync()
-        opt_st = None
-        if early_opt is not None:
-            opt_st = self._opt_stream()
-            e_main, e_side = torch.cuda.Event(), torch.cuda.Event()
-            e_main.record(cur); e_side.record(side)            # (the last DETR layer's weight-gradient launch sits on the second stream)
-            opt_st.wait_event(e_main); opt_st.wait_event(e_side)
-            with torch.cuda.stream(opt_st):
-                early_opt()
-        # ---------------- temporal encoders (video on the second stream)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            # extra gradients of the frame features: the contrastive-align projection and the second X-Pool tower's pooled sequences
-            dxv = tw["dframe_x"] if (c.contrastive_align_loss and not regression) else None
-            if "video" in c.vmr_fusion:
-                dxv = tw["ydseg"] if dxv is None else tr.add3(tw["dframe_sum"], dxv, tw["ydseg"])
-            self._encode_bwd("video", ws, tw, dl_v, dxv.view(B, Tv, D) if dxv is not None else None, dvideo, fm, feats_v)
-        # (the audio tower's weight-gradient products stay on the main stream since round 6 -- it idles at the end of the step while the second
-        # stream is still in the video tower's chain; MADE_AUDIO_DW_SIDE=1: behind the video tower on the second stream, as before)
-        self._encode_bwd("audio", ws, tw, dl_a, tw["xdseg"].view(B, Ta, D), dmusic, sm, feats_a,
-                         dw_stream=side if _lib.variant_env("MADE_AUDIO_DW_SIDE", "0") != "0" else None)
-        cur.wait_stream(side)
-        if opt_st is not None:
-            cur.wait_stream(opt_st)
+    def _tower_bwd(self, which: str, ws, tw, d_local: Tensor) -> None:
+        """One temporal tower's backward from the gradient of its local output (d_local), the gradient of its clip-level vector and the
+        extra gradients of its sequence that the other branches left."""
+        c = self.cfg
+        B, Tv, Ta = self._shape
+        D = c.D
+        feats_v, feats_a, fm, sm, _ = self._inputs
+        if which == "audio":
+            self._encode_bwd("audio", ws, tw, d_local, tw["xdseg"].view(B, Ta, D), tw["dmusic"], sm, feats_a)
+            return
+        # extra gradients of the frame features: the contrastive-align projection and the second X-Pool tower's pooled sequences
+        dxv = tw["dframe_x"] if (c.contrastive_align_loss and "regression" not in c.mml_localization) else None
+        if "video" in c.vmr_fusion:
+            dxv = tw["ydseg"] if dxv is None else tr.add3(tw["dframe_sum"], dxv, tw["ydseg"])
+        self._encode_bwd("video", ws, tw, d_local, dxv.view(B, Tv, D) if dxv is not None else None, tw["dvideo"], fm, feats_v)
 
     def _regression_train(self, out, ws, tw, mem3: Tensor, fus_mask: Tensor, v_duration, cur, side) -> Dict[str, Tensor]:
         """reference model/model_Uni.py:228-232,290-300 in train mode: memory summed over all L positions / number of valid ones ->
@@ -1794,32 +1799,11 @@ class MadeTrainer(MadeEngine):
                 self._xpool_bwd(tw, "xav", "y", ds_st, music, dmusic, frame, self._inputs[2] if c.fusion_mask == 1 else None, B, frame.shape[1])
             else:
                 _tape.zero_(tw["ydseg"])
-        self._ret_ck(9)
         if dual:
             tr.gemm_tn(ds_dt, tw["mn"], tw["dvn"])            # d vhat = dsims mhat
             tr.gemm_tn(ds_d, tw["vn"], tw["dmn"])             # d mhat = dsims^T vhat
             tr.l2norm_bwd(video, tw["dvn"], dvideo, accumulate=True)
             tr.l2norm_bwd(music, tw["dmn"], dmusic, accumulate=True)
-
-    def _ret_ck(self, i: int) -> None:
-        """measurement knob (MADE_RET_HANDOFF=i): from checkpoint i of the retrieval branch's backward on, its launches go to the MAIN
-        stream (the ones before stay on the second stream) -- which of them disturbs the decoder's backward chain"""
-        if getattr(self, "_ret_main_stream", None) is None:
-            return
-        main = self._ret_main_stream
-        if _lib.variant_env("MADE_RET_HANDOFF", "") == str(i) and torch.cuda.current_stream() != main:
-            main.wait_stream(torch.cuda.current_stream())
-            torch.cuda.set_stream(main)
-        # MADE_RET_HANDOFF_REV=i: the other way round -- the launches in front of checkpoint i on the main stream, the rest on the second
-        rev = _lib.variant_env("MADE_RET_HANDOFF_REV", "")
-        if rev != "":
-            side = self._side_stream()
-            if i == 0 and int(rev) > 0 and torch.cuda.current_stream() != main:
-                main.wait_stream(torch.cuda.current_stream())
-                torch.cuda.set_stream(main)
-            elif i == int(rev) and i > 0 and torch.cuda.current_stream() == main:
-                side.wait_stream(main)
-                torch.cuda.set_stream(side)
 
     def _xpool_bwd(self, *a, **k) -> None:
         for _ in self._xpool_bwd_gen(*a, **k):
@@ -1844,32 +1828,24 @@ class MadeTrainer(MadeEngine):
         else:
             tr.xpool_tail_bwd(tw[pre + "y"], P[key + ".ln3.g"], P[key + ".ln3.b"], qvec, ds, g1, B, B, dy_drop=g2, drop=self._drop("xa.linear_out", dr.P_XPOOL),
                               dgamma=G[key + ".ln3.g"], dbeta=G[key + ".ln3.b"], dvideo=dqvec, dpool=dpool, dpool_scale=1.0 / B)
-        self._ret_ck(1)
         da3 = self._lin_bwd(g2, tw[pre + "a3"], key + ".lin", dx_out=g3, R=g1)
         tr.layernorm_bwd(tw[pre + "a2"], P[key + ".ln2.g"], da3, g1, dgamma=G[key + ".ln2.g"], dbeta=G[key + ".ln2.b"])
-        self._ret_ck(2)
         do = self._lin_bwd(g1, tw[pre + "o"], key + ".out", dx_out=g2)
         Sp = tw[pre + "S"].shape[1]
         yield
-        self._ret_ck(3)
         xk, xu, q = tw[pre + "k"], tw[pre + "u"], tw[pre + "q"]
         ops.linear(q, xk[:S], None, M=B, N=S, K=D, batch=B, a_z_stride=0, w_z_stride=S * D, segs=[Seg(out=tw[pre + "S"], ldo=Sp, out_z_stride=B * Sp)])
         ops.linear(do[:B], xu[:S], None, M=B, N=S, K=D, batch=B, a_z_stride=B * D, w_z_stride=S * D, segs=[Seg(out=tw[pre + "dP"], ldo=Sp, out_z_stride=B * Sp)])
-        self._ret_ck(4)
         tr.softmax_bwd(tw[pre + "S"], tw[pre + "dP"], seg_mask, B, 1.0 / math.sqrt(D), tw[pre + "P"], tw[pre + "dS"], tw[pre + "dSt"], B, S, ldo=Sp, ldt=B)
         dkv = tw[pre + "dkv"]
-        self._ret_ck(5)
         # dU[m] = P[m]^T dO[m];  dK[m] = dS[m]^T q;  dq = sum_m dS[m] K[m]
         tr.gemm_tn(tw[pre + "P"][:B, :S], do[:B], dkv[:S, D:], batch=(B, 1), a_zs=(B * Sp, 0), b_zs=(B * D, 0), c_zs=(S * 2 * D, 0))
         tr.gemm_tn(tw[pre + "dS"][:B, :S], q, dkv[:S, :D], batch=(B, 1), a_zs=(B * Sp, 0), b_zs=(0, 0), c_zs=(S * 2 * D, 0))
         _tape.zero_(tw[pre + "dq32"])
         tr.gemm_tn(tw[pre + "dSt"][0], xk[:S], tw[pre + "dq32"], batch=(B, 1), a_zs=(S * B, 0), b_zs=(S * D, 0), c_zs=(0, 0), accumulate=True,
                    row_mask=seg_mask, mask_zs=(S, 0))
-        self._ret_ck(6)
         ds1 = self._lin_bwd(dkv, tw[pre + "s1"], key + ".kv", dx_out=tw[pre + "ds1"], row_mask=skip, skip=skip)
-        self._ret_ck(7)
         tr.layernorm_bwd(seg, P[key + ".ln1.g"], ds1, tw[pre + "dseg"], dgamma=G[key + ".ln1.g"], dbeta=G[key + ".ln1.b"], row_skip=skip)
-        self._ret_ck(8)
         dq = tr.add3(tw[pre + "dq"], tw[pre + "dq32"])
         dv1 = self._lin_bwd(dq, tw[pre + "v1"], key + ".q", dx_out=tw[pre + "dv1"])
         tr.layernorm_bwd(qvec, P[key + ".ln1.g"], dv1, dqvec, dgamma=G[key + ".ln1.g"], dbeta=G[key + ".ln1.b"], add=dqvec)
@@ -1943,10 +1919,7 @@ class MadeTrainer(MadeEngine):
         tr.gemm_tn(dx, xin, G[proj + ".w"], accumulate=True, rows=self._rw(mflat))
         tr.colsum(dx, G[proj + ".b"])
 
-    def _encode_bwd(self, which: str, ws, tw, d_local: Tensor, d_extra: Optional[Tensor], dvec: Tensor, mask: Tensor, feats: Tensor,
-                    dw_stream=None) -> None:
-        """dw_stream: run the weight-gradient products there instead of on the current stream (a one-layer block only: a deeper stack
-        reuses the gradient buffers they read from layer to layer)."""
+    def _encode_bwd(self, which: str, ws, tw, d_local: Tensor, d_extra: Optional[Tensor], dvec: Tensor, mask: Tensor, feats: Tensor) -> None:
         c, P, G = self.cfg, self.P, self.G
         if c.agg_module == "mlp":
             return self._encode_bwd_mlp(which, ws, tw, d_local, d_extra, dvec, mask, feats)
@@ -2006,14 +1979,6 @@ class MadeTrainer(MadeEngine):
                 # instead of a launch of its own (round 6: 63 us at the very end of the main stream for the audio tower)
                 pend.append((dx, tw[tag + ".xin"], G[proj + ".w"], G[proj + ".b"]))
                 proj_grouped = True
-            if dw_stream is not None and depth == 1 and not cls and not c.with_act_after_proj:
-                dw_stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(dw_stream):
-                    self._flush_dw(pend, mflat)
-                    if not proj_grouped:
-                        xin_ = tw[tag + ".xin"] if self.tc == torch.bfloat16 else feats.view(rows, Kin)
-                        tr.gemm_tn(dx, xin_, G[proj + ".w"], accumulate=True, colsum=G[proj + ".b"], rows=self._rw(mflat0))
-                return
             self._flush_dw(pend, mflat)
         if proj_grouped:
             return
