@@ -1050,6 +1050,21 @@ int made_group_topw(const float* sims, int64_t ld, const int32_t* sel, const int
                     const int32_t* cols, int64_t n_cols, int64_t Nv, int64_t Nm, int64_t n_groups, int64_t K, int64_t w,
                     int32_t* idx_out, float* score_out, void* stream);
 
+/* made_topk_merge: a running selection merged with the selection of one more chunk of columns, for every row (a selection
+ * decomposes over column chunks that hold whole groups: mgsv_amd/library.py, grounding.ground_library).  An entry is a selected
+ * group with the w best columns of that group, in made_group_topw's form: col [.., w] int32 (-1: none) and score [.., w] f32
+ * (-inf: none), sorted inside the entry; the entry's key is (score[0], col[0]), an entry with col[0] == -1 is empty.  Both lists
+ * -- a [Nv, Ka, w] and b [Nv, Kb, w], whose columns are local to the chunk -- are sorted by key in made_topk_groups' total order
+ * (score descending through the same order-preserving key, so NaN ranks lowest and -0 equals +0; then column ascending), empty
+ * entries last.  out [Nv, K, w] receives the first K entries of the union in that order, payload unchanged except that
+ * col_offset is added to every column >= 0 of b (also before b's keys are compared); the rest is filled with -1 / -inf.  No group
+ * may occur in both lists and no column twice (nothing is deduplicated); keys that are equal all the same rank in entry order, a
+ * before b.  One workgroup per row, no atomics, no workspace; 16-byte accesses when w % 4 == 0 and every buffer is 16-byte
+ * aligned.  1 <= K <= 256, 0 <= Ka, Kb <= 256 (an empty list's pointers may be NULL), 1 <= w <= 16, 0 <= col_offset < 2^31; the
+ * outputs must not overlap the inputs or each other. */
+int made_topk_merge(const int32_t* a_col, const float* a_score, int64_t Ka, const int32_t* b_col, const float* b_score, int64_t Kb,
+                    int64_t col_offset, int64_t Nv, int64_t w, int64_t K, int32_t* out_col, float* out_score, void* stream);
+
 /* made_merge_moments: the moments of P (video, track) entries on the track's own time axis from the moments of the track's w
  * windows, one wave per entry, no atomics.  win_col / win_score [P, w] = made_group_topw's columns (-1: no window) and
  * similarities; cand [P, w, Q, 3] f32 = every query's (start, end, foreground probability) in seconds on its window's axis,

@@ -238,9 +238,97 @@ __global__ __launch_bounds__(256) void gather_pairs_kernel(const int32_t* vi, co
     }
 }
 
+constexpr int MERGE_K = 256;            // entries of one list at most (made_topk_groups' K limit)
+
+struct MergeListShared {
+    uint64_t key[2 * MERGE_K];          // (score key, 0x7FFFFFFF - column) of an entry's best column; 0 = an empty entry
+    int src[MERGE_K];                   // output slot -> entry (a: 0 .. Ka-1, b: Ka .. Ka+Kb-1)
+};
+
+// One workgroup per row merges two sorted lists of entries (made_topk_merge).  Rank by counting over the Ka + Kb <= 512 keys in
+// LDS (every thread reads the same key: a broadcast), then the payload of the first K entries is copied slot by slot, so the
+// stores of a row are contiguous.  Equal keys (empty entries; lists that break the disjoint-columns contract) rank in entry
+// order: the ranks are a permutation of 0 .. Ka+Kb-1 whatever the input, and every output slot is written exactly once.
+template <int V>                        // V = 4: 16-byte accesses (w % 4 == 0, every buffer 16-byte aligned); V = 1: 4-byte
+__global__ __launch_bounds__(GT) void topk_merge_kernel(const int32_t* a_col, const float* a_score, int Ka, const int32_t* b_col,
+                                                        const float* b_score, int Kb, int32_t col_offset, int w, int K,
+                                                        int32_t* out_col, float* out_score) {
+    __shared__ MergeListShared sh;
+    const int64_t row = blockIdx.x;
+    const int n = Ka + Kb;
+    const int32_t* ac = a_col + row * Ka * w;
+    const float* as = a_score + row * Ka * w;
+    const int32_t* bc = b_col + row * Kb * w;
+    const float* bs = b_score + row * Kb * w;
+    for (int i = threadIdx.x; i < n; i += GT) {
+        const bool isb = i >= Ka;
+        const int64_t e = (int64_t)(isb ? i - Ka : i) * w;
+        const int c = isb ? bc[e] : ac[e];
+        uint64_t k = 0ull;
+        if (c >= 0) {
+            const float s = isb ? bs[e] : as[e];
+            const uint32_t col = (uint32_t)c + (isb ? (uint32_t)col_offset : 0u);
+            k = ((uint64_t)score_key(s) << 32) | (uint32_t)(0x7FFFFFFFu - col);
+        }
+        sh.key[i] = k;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += GT) {
+        const uint64_t k = sh.key[i];
+        int r = 0;
+        for (int q = 0; q < n; ++q) {
+            const uint64_t kq = sh.key[q];
+            r += (kq > k || (kq == k && q < i)) ? 1 : 0;
+        }
+        if (r < K) sh.src[r] = i;
+    }
+    __syncthreads();
+    const int filled = min(n, K);
+    const int wv = w / V;                                        // payload vectors per entry
+    const int64_t o = row * K * w;
+    for (int x = threadIdx.x; x < K * wv; x += GT) {
+        const int r = x / wv, j = (x - r * wv) * V;
+        int32_t c[V];
+        float s[V];
+#pragma unroll
+        for (int t = 0; t < V; ++t) { c[t] = -1; s[t] = -INFINITY; }
+        const int i = r < filled ? sh.src[r] : -1;
+        if (i >= 0 && sh.key[i] != 0ull) {
+            const bool isb = i >= Ka;
+            const int64_t e = (int64_t)(isb ? i - Ka : i) * w + j;
+            const int32_t* pc = isb ? bc + e : ac + e;
+            const float* ps = isb ? bs + e : as + e;
+            if constexpr (V == 4) {
+                const int4 cv = *(const int4*)pc;
+                const float4 sv = *(const float4*)ps;
+                c[0] = cv.x; c[1] = cv.y; c[2] = cv.z; c[3] = cv.w;
+                s[0] = sv.x; s[1] = sv.y; s[2] = sv.z; s[3] = sv.w;
+            } else {
+                c[0] = *pc; s[0] = *ps;
+            }
+            if (isb) {
+#pragma unroll
+                for (int t = 0; t < V; ++t) c[t] = c[t] >= 0 ? (int32_t)((uint32_t)c[t] + (uint32_t)col_offset) : c[t];
+            }
+        }
+        if constexpr (V == 4) {
+            *(int4*)(out_col + o + (int64_t)r * w + j) = make_int4(c[0], c[1], c[2], c[3]);
+            *(float4*)(out_score + o + (int64_t)r * w + j) = make_float4(s[0], s[1], s[2], s[3]);
+        } else {
+            out_col[o + (int64_t)r * w + j] = c[0];
+            out_score[o + (int64_t)r * w + j] = s[0];
+        }
+    }
+}
+
 int64_t topk_blocks(int64_t Nm) { return (Nm + CAP - 1) / CAP; }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+bool overlaps(const void* p, int64_t pn, const void* q, int64_t qn) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && pn > 0 && qn > 0 && a < b + (uintptr_t)qn && b < a + (uintptr_t)pn;
+}
 
 }  // namespace
 
@@ -308,6 +396,35 @@ extern "C" int made_topk_groups(const float* sims, int64_t ld, const int32_t* gr
         cur ^= 1;
     }
     return made_check_launch("made_topk_groups");
+}
+
+extern "C" int made_topk_merge(const int32_t* a_col, const float* a_score, int64_t Ka, const int32_t* b_col, const float* b_score,
+                               int64_t Kb, int64_t col_offset, int64_t Nv, int64_t w, int64_t K, int32_t* out_col, float* out_score,
+                               void* stream) {
+    MADE_REQUIRE(out_col && out_score, "made_topk_merge: null output pointer");
+    MADE_REQUIRE(K >= 1 && K <= MERGE_K, "made_topk_merge: K must lie in [1, 256]");
+    MADE_REQUIRE(Ka >= 0 && Ka <= MERGE_K && Kb >= 0 && Kb <= MERGE_K, "made_topk_merge: Ka and Kb must lie in [0, 256]");
+    MADE_REQUIRE(w >= 1 && w <= 16, "made_topk_merge: w must lie in [1, 16]");
+    MADE_REQUIRE(Nv >= 0 && Nv < (1LL << 31), "made_topk_merge: bad dims (0 <= Nv < 2^31)");
+    MADE_REQUIRE(col_offset >= 0 && col_offset < (1LL << 31), "made_topk_merge: col_offset must lie in [0, 2^31)");
+    MADE_REQUIRE((Ka == 0 || (a_col && a_score)) && (Kb == 0 || (b_col && b_score)), "made_topk_merge: null pointer (a list that is not empty)");
+    const int64_t na = Nv * Ka * w * 4, nb = Nv * Kb * w * 4, no = Nv * K * w * 4;
+    MADE_REQUIRE((const void*)out_col != (const void*)out_score && !overlaps(out_col, no, out_score, no) &&
+                 !overlaps(out_col, no, a_col, na) && !overlaps(out_col, no, a_score, na) && !overlaps(out_col, no, b_col, nb) &&
+                 !overlaps(out_col, no, b_score, nb) && !overlaps(out_score, no, a_col, na) && !overlaps(out_score, no, a_score, na) &&
+                 !overlaps(out_score, no, b_col, nb) && !overlaps(out_score, no, b_score, nb),
+                 "made_topk_merge: the outputs must not alias the inputs or each other");
+    if (Nv == 0) return MADE_OK;
+    const bool v4 = w % 4 == 0 && aligned16(a_col) && aligned16(a_score) && aligned16(b_col) && aligned16(b_score) &&
+                    aligned16(out_col) && aligned16(out_score);
+    const hipStream_t st = (hipStream_t)stream;
+    if (v4)
+        hipLaunchKernelGGL(topk_merge_kernel<4>, dim3((unsigned)Nv), dim3(GT), 0, st, a_col, a_score, (int)Ka, b_col, b_score, (int)Kb,
+                           (int32_t)col_offset, (int)w, (int)K, out_col, out_score);
+    else
+        hipLaunchKernelGGL(topk_merge_kernel<1>, dim3((unsigned)Nv), dim3(GT), 0, st, a_col, a_score, (int)Ka, b_col, b_score, (int)Kb,
+                           (int32_t)col_offset, (int)w, (int)K, out_col, out_score);
+    return made_check_launch("made_topk_merge");
 }
 
 extern "C" int made_gather_pairs(const int32_t* vi, const int32_t* mi, int64_t P, int64_t Nv, int64_t Nm,

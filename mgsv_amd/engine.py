@@ -591,12 +591,14 @@ class MadeEngine:
             _lib.check(_lib.lib().made_set_f32_products(self._f32_products), "made_set_f32_products")
 
     def retrieval_sim_matrix(self, video_embeds: Tensor, segment_embeds: Tensor, segment_masks: Tensor,
-                             music_embeds: Tensor, chunk_m: Optional[int] = None) -> Tensor:
-        """reference test-MaDe.py:386-403: sim[Nv, Nm] = single (X-Pool) + dual (cosine)."""
+                             music_embeds: Tensor, chunk_m: Optional[int] = None, out: Optional[Tensor] = None,
+                             single_out: Optional[Tensor] = None) -> Tensor:
+        """reference test-MaDe.py:386-403: sim[Nv, Nm] = single (X-Pool) + dual (cosine).  out / single_out: [Nv, Nm] f32 views
+        (two different buffers) that receive the sum / the X-Pool term instead of new tensors."""
         self._set_products()
         seg = segment_embeds.to(self.tc) if segment_embeds.dtype != self.tc else segment_embeds
-        single = self.xpool_sims(video_embeds, seg, segment_masks if self.cfg.fusion_mask == 1 else None, chunk_m=chunk_m)
-        return self.dual_sims(video_embeds, music_embeds, add=single)
+        single = self.xpool_sims(video_embeds, seg, segment_masks if self.cfg.fusion_mask == 1 else None, sims_out=single_out, chunk_m=chunk_m)
+        return self.dual_sims(video_embeds, music_embeds, out=out, add=single)
 
     # ------------------------------------------------------------------ full forward
     @torch.no_grad()

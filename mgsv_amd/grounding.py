@@ -98,20 +98,22 @@ class Grounding:
         return out
 
 
-def similarity_matrix(engine: MadeEngine, video: Tensor, seg: Tensor, seg_mask: Tensor, music: Tensor) -> Tensor:
+def similarity_matrix(engine: MadeEngine, video: Tensor, seg: Tensor, seg_mask: Tensor, music: Tensor, out: Optional[Tensor] = None,
+                      single_out: Optional[Tensor] = None) -> Tensor:
     """[N_v, N_m] f32 similarities by the configuration's vmr loss, the branch the evaluation ranks with (reference
     test-MaDe.py:386-408): cosine only for "dual" (or no X-Pool tower), X-Pool only for "single", X-Pool + cosine otherwise.
-    seg [N_m, S, D] may be a strided view (the sharded retrieval's packed records)."""
+    seg [N_m, S, D] may be a strided view (the sharded retrieval's packed records).  out / single_out: [N_v, N_m] f32 views (unit
+    column stride) to write the result / the X-Pool term of the sum into instead of new tensors (ground_library's reused block)."""
     c = engine.cfg
     dev = engine.device
     video = video.to(dev, torch.float32).contiguous()
     music = music.to(dev, torch.float32).contiguous()
     seg_mask = seg_mask.to(dev, torch.float32).contiguous()
     if "XA" not in c.vmr_fusion or c.vmr_loss == "dual":
-        return engine.dual_sims(video, music)
+        return engine.dual_sims(video, music, out=out)
     if c.vmr_loss == "single":
-        return engine.xpool_sims(video, seg.to(engine.tc), seg_mask if c.fusion_mask == 1 else None)
-    return engine.retrieval_sim_matrix(video, seg.to(dev), seg_mask, music)
+        return engine.xpool_sims(video, seg.to(engine.tc), seg_mask if c.fusion_mask == 1 else None, sims_out=out)
+    return engine.retrieval_sim_matrix(video, seg.to(dev), seg_mask, music, out=out, single_out=single_out)
 
 
 def _group_tensor(group_id, Nm: int, dev):
@@ -130,7 +132,6 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     windows: the columns of `music` are windows of tracks (music.duration = the windows' durations, group_id one entry per TRACK):
     each track's best `windows_per_track` windows are localized and their queries merged into up to `moments` moments per track on
     the track's time axis, a candidate being dropped when its IoU with a better one kept exceeds nms_iou."""
-    c = engine.cfg
     dev = engine.device
     Nv, Nm = len(videos), len(music)
     if sims is None:
@@ -144,10 +145,31 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     gid, G = _group_tensor(group_id, Nm, dev)
     kk = max(1, min(int(k), G))
     track, score = ops.topk_groups(sims, kk, gid, G)
-    P = Nv * kk
     vi = torch.arange(Nv, device=dev, dtype=torch.int32).repeat_interleave(kk)
     mi = track.reshape(-1)
     mi = torch.where(mi < 0, torch.zeros_like(mi), mi)             # (no track: localized against track 0, reported as -1 / NaN)
+    start, end, conf = _pair_moments(engine, videos, music, vi, mi, track.reshape(-1) < 0, pair_batch)
+    return Grounding(track=track, score=score, start=start.view(Nv, kk), end=end.view(Nv, kk), confidence=conf.view(Nv, kk))
+
+
+def _pad_pairs(vi: Tensor, mi: Tensor, min_pairs: int):
+    """The pair list with copies of its last pair appended up to min_pairs entries: `_localize_chunks` then forms the batches of a
+    longer list (pairs are independent, but the batch size picks the decoder's split-K shape, and with it the rounding)."""
+    pad = min_pairs - vi.numel()
+    if pad <= 0 or vi.numel() == 0:
+        return vi, mi
+    return torch.cat([vi, vi[-1:].expand(pad)]).contiguous(), torch.cat([mi, mi[-1:].expand(pad)]).contiguous()
+
+
+def _pair_moments(engine: MadeEngine, videos: Encoded, music: Encoded, vi: Tensor, mi: Tensor, none: Tensor, pair_batch: int,
+                  min_pairs: int = 0):
+    """(start, end, confidence) f32 [P] of the pairs (vi[p], mi[p]): the top query's span in seconds clamped to
+    [0, min(max_m_duration, the track's duration)]; NaN where none[p].  The tail of `ground` without windows."""
+    c = engine.cfg
+    dev = engine.device
+    n_pairs = vi.numel()
+    vi, mi = _pad_pairs(vi, mi, min_pairs)
+    P = vi.numel()
     pred = torch.empty(P, 3, device=dev, dtype=torch.float32)      # start, end (seconds, unclamped), confidence
     regression = "regression" in c.mml_localization
     mx = float(c.max_m_duration)
@@ -165,17 +187,17 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
         _lib.check(_lib.lib().made_span_iou(out["pred_logits"].data_ptr(), out["pred_spans"].data_ptr(), scratch[0].data_ptr(),
                                             scratch[1].data_ptr(), n, Q, int(c.foreground_label), mx, scratch[2].data_ptr(),
                                             pred[p0:p0 + n].data_ptr(), torch.cuda.current_stream().cuda_stream), "made_span_iou")
+    pred, mi, P = pred[:n_pairs], mi[:n_pairs], n_pairs
     hi = torch.full((P,), mx, device=dev, dtype=torch.float32)
     if music.duration is not None:
         hi = torch.minimum(hi, music.duration.to(dev, torch.float32)[mi.long()])
     start = torch.minimum(pred[:, 0].clamp(min=0), hi)
     end = torch.minimum(pred[:, 1].clamp(min=0), hi)
     conf = pred[:, 2].clone()
-    none = track.reshape(-1) < 0
     if bool(none.any()):
         nan = torch.full_like(start, float("nan"))
         start, end, conf = torch.where(none, nan, start), torch.where(none, nan, end), torch.where(none, nan, conf)
-    return Grounding(track=track, score=score, start=start.view(Nv, kk), end=end.view(Nv, kk), confidence=conf.view(Nv, kk))
+    return start, end, conf
 
 
 def _pair_candidates(engine: MadeEngine, videos: Encoded, music: Encoded, vi: Tensor, mi: Tensor, pair_batch: int) -> Tensor:
@@ -209,7 +231,6 @@ def _pair_candidates(engine: MadeEngine, videos: Encoded, music: Encoded, vi: Te
 
 def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Tensor, group_id, pair_batch: int,
                     windows: Windows, w: int, n: int, nms_iou: float) -> Grounding:
-    c = engine.cfg
     dev = engine.device
     Nv, Nm = len(videos), len(music)
     if len(windows) != Nm:
@@ -234,15 +255,287 @@ def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int,
     vi = torch.arange(Nv, device=dev, dtype=torch.int32).repeat_interleave(kk * w)
     mi = wcol.reshape(-1)
     mi = torch.where(mi < 0, torch.zeros_like(mi), mi)             # (no window: localized against column 0, left out by the merge)
-    cand = _pair_candidates(engine, videos, music, vi, mi, pair_batch)
-    Q = cand.shape[1]
     duration = music.duration.to(dev, torch.float32).contiguous() if music.duration is not None else None
-    st, en, cf, wi = ops.merge_moments(cand.view(Nv * kk, w, Q, 3), wcol.view(Nv * kk, w), wscore.view(Nv * kk, w), as_dev(windows.offset),
-                                       duration, float(c.max_m_duration), nms_iou, n, use_prob="regression" not in c.mml_localization)
-    track = torch.where(rep < 0, rep, as_dev(windows.track)[rep.clamp(min=0).long()])
+    st, en, cf, wi = _window_moments(engine, videos, music, vi, mi, wcol, wscore, as_dev(windows.offset), duration, n, nms_iou, pair_batch)
+    track = _window_tracks(rep, as_dev(windows.track))
     shape = (Nv, kk) if n == 1 else (Nv, kk, n)
     return Grounding(track=track, score=score, start=st.view(shape), end=en.view(shape), confidence=cf.view(shape), window=wi.view(shape),
                      windows=windows)
+
+
+def _window_moments(engine: MadeEngine, videos: Encoded, music: Encoded, vi: Tensor, mi: Tensor, wcol: Tensor, wscore: Tensor,
+                    offset: Tensor, duration: Optional[Tensor], n: int, nms_iou: float, pair_batch: int, min_pairs: int = 0):
+    """(start, end, confidence f32, window int32), each [entries, n]: the moments of every (video, track) entry from the
+    localization of its w windows -- pairs (vi[p], mi[p]), mi indexing `music`, p = entry * w + window -- merged on the track's
+    axis.  wcol / wscore [.., w] name the windows by the column that `offset` / `duration` (one entry per column) are indexed by.
+    The tail of `ground` over windows."""
+    c = engine.cfg
+    w = wcol.shape[-1]
+    E = wcol.numel() // w
+    vi, mi = _pad_pairs(vi, mi, min_pairs)
+    cand = _pair_candidates(engine, videos, music, vi, mi, pair_batch)[:E * w]
+    Q = cand.shape[1]
+    return ops.merge_moments(cand.view(E, w, Q, 3), wcol.view(E, w), wscore.view(E, w), offset, duration, float(c.max_m_duration), nms_iou, n,
+                             use_prob="regression" not in c.mml_localization)
+
+
+def _window_tracks(rep: Tensor, track_of_col: Tensor) -> Tensor:
+    """the track of every selected representative column (-1 stays -1)"""
+    return torch.where(rep < 0, rep, track_of_col[rep.clamp(min=0).long()])
+
+
+# ---------------------------------------------------------------------------------------------- a stored library, streamed
+def _as_device(a, dev, dtype) -> Tensor:
+    if isinstance(a, Tensor):
+        return a.to(dev, dtype).contiguous()
+    return torch.from_numpy(np.array(a)).to(dev, dtype).contiguous()
+
+
+def _host_view(t: Tensor) -> np.ndarray:
+    """a numpy view of a host tensor (bf16 as its uint16 patterns, the form a host library stores)"""
+    return t.view(torch.int16).numpy().view(np.uint16) if t.dtype == torch.bfloat16 else t.numpy()
+
+
+class _Staging:
+    """`sets` pinned host sets and as many device sets of (tokens, mask, vec, duration) for `rows` columns, a copy stream and the
+    events that order them.  Kept on the library, so that later calls reuse the pinned memory."""
+
+    def __init__(self, library, rows: int, dev, sets: int):
+        S, D = library.S, library.D
+        tc = torch.bfloat16 if library.dtype == "bf16" else torch.float32
+        shapes = (((rows, S, D), tc), ((rows, S), torch.float32), ((rows, D), torch.float32), ((rows,), torch.float32))
+        self.rows = rows
+        self.host = [[torch.empty(s, dtype=t, pin_memory=True) for s, t in shapes] for _ in range(sets)]
+        self.dev = [[torch.empty(s, dtype=t, device=dev) for s, t in shapes] for _ in range(sets)]
+        self.copy = torch.cuda.Stream(device=dev)
+        self.copy.wait_stream(torch.cuda.current_stream(dev))      # (the device sets may reuse memory that queued kernels still read)
+        self.uploaded = [torch.cuda.Event() for _ in range(sets)]                    # the upload into device set j has finished
+        self.consumed = [torch.cuda.Event() for _ in range(sets)]                    # the kernels reading device set j have finished
+
+    def fill(self, j: int, library, rows) -> int:
+        """Host: the library's rows (a slice, or an index array) into pinned set j, once the upload that last read it has finished."""
+        self.uploaded[j].synchronize()
+        n = 0
+        for dst, src in zip(self.host[j], (library.tokens, library.mask, library.vec, library.duration)):
+            if src is None:
+                continue
+            if isinstance(src, Tensor):
+                part = src[rows] if isinstance(rows, slice) else src[torch.from_numpy(rows)]
+                n = part.shape[0]
+                dst[:n].copy_(part)
+            else:
+                view = _host_view(dst)
+                if isinstance(rows, slice):
+                    n = rows.stop - rows.start
+                    np.copyto(view[:n], src[rows])
+                else:
+                    n = len(rows)
+                    np.take(src, rows, axis=0, out=view[:n])
+        return n
+
+    def upload(self, j: int, n: int, has_duration: bool, src=None) -> Encoded:
+        """Copy stream: pinned set j (or the pinned tensors `src`) -> device set j, after the kernels that last read device set j."""
+        self.copy.wait_event(self.consumed[j])
+        with torch.cuda.stream(self.copy):
+            for k, (dst, s) in enumerate(zip(self.dev[j], self.host[j] if src is None else src)):
+                if k < 3 or has_duration:
+                    dst[:n].copy_(s[:n], non_blocking=True)
+            self.uploaded[j].record(self.copy)
+        tok, mask, vec, dur = (t[:n] for t in self.dev[j])
+        return Encoded(tokens=tok, mask=mask, vec=vec, duration=dur if has_duration else None)
+
+
+def _staging(library, name: str, rows: int, dev, sets: int) -> _Staging:
+    st = library._stages.get(name)
+    if st is None or st.rows < rows or st.dev[0][0].device != dev:
+        grown = min(len(library), 3 * st.rows // 2) if st is not None else 0      # (pinned allocations are slow: grow in steps)
+        st = library._stages[name] = _Staging(library, max(rows, grown, 1), dev, sets)
+    return st
+
+
+def _plan_tables(plan: dict, dev):
+    """the plan's group tables on the device, uploaded once per (plan, device): local group ids [N], the chunks' CSR starts, and the
+    CSR's column list 0, 1, 2, ... (groups are contiguous)"""
+    key = str(dev)
+    if key not in plan["device"]:
+        longest = max((b - a for a, b in plan["chunks"]), default=0)
+        plan["device"][key] = (torch.from_numpy(plan["gid"]).to(dev), torch.from_numpy(plan["start"]).to(dev),
+                               torch.arange(longest, device=dev, dtype=torch.int32))
+    return plan["device"][key]
+
+
+def _select_streamed(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, chunk_cols: int, sims_fn, timings: Optional[dict]):
+    """(wcol int32, wscore f32) [N_v, kk, w]: every video's best kk groups of the library and the best w columns of each, library
+    column numbers -- what made_topk_groups + made_group_topw give on the whole similarity matrix, folded over the chunk plan."""
+    dev = engine.device
+    Nv = len(videos)
+    plan = library._plan(chunk_cols)
+    chunks = plan["chunks"]
+    grouped = library.grouped
+    gid_all = start_all = cols_all = None
+    if grouped:
+        gid_all, start_all, cols_all = _plan_tables(plan, dev)
+    longest = max(b - a for a, b in chunks)
+    cur = torch.cuda.current_stream()
+    resident = library.on_device
+    stage = None if resident else _staging(library, "chunks", longest, dev, 2)
+    has_dur = library.duration is not None
+    video = videos.vec.to(dev, torch.float32).contiguous()
+    sims_buf = single_buf = None
+    if sims_fn is None:
+        sims_buf = torch.empty(Nv, longest, device=dev, dtype=torch.float32)
+        single_buf = torch.empty(Nv, longest, device=dev, dtype=torch.float32)
+    state = [(torch.empty(Nv, kk, w, device=dev, dtype=torch.int32), torch.empty(Nv, kk, w, device=dev, dtype=torch.float32))
+             for _ in range(2)]
+    run = (torch.empty(Nv, 0, w, device=dev, dtype=torch.int32), torch.empty(Nv, 0, w, device=dev, dtype=torch.float32))
+    marks = []                                                      # (compute stream reaches the wait, sims start, sims end, merge end) per chunk
+
+    def chunk_encoded(i: int) -> Encoded:
+        c0, c1 = chunks[i]
+        if resident:
+            return Encoded(tokens=library.tokens[c0:c1], mask=library.mask[c0:c1], vec=library.vec[c0:c1],
+                           duration=library.duration[c0:c1] if has_dur else None)
+        if library.pinned:                                          # pinned already: no staging copy
+            return stage.upload(i % 2, c1 - c0, has_dur, src=[None if a is None else a[c0:c1] for a in
+                                                              (library.tokens, library.mask, library.vec, library.duration)])
+        n = stage.fill(i % 2, library, slice(c0, c1))
+        return stage.upload(i % 2, n, has_dur)
+
+    nxt = chunk_encoded(0)
+    for i, (c0, c1) in enumerate(chunks):
+        chunk, n = nxt, c1 - c0
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timings is not None else None
+        if ev:
+            ev[0].record(cur)
+        if not resident:
+            cur.wait_event(stage.uploaded[i % 2])
+        if ev:
+            ev[1].record(cur)
+        if sims_fn is not None:
+            sims = sims_fn(chunk, c0, c1).to(dev, torch.float32)
+            if sims.stride(1) != 1:
+                sims = sims.contiguous()
+            assert tuple(sims.shape) == (Nv, n), "sims_fn must return [N_v, c1 - c0]"
+        else:
+            sims = similarity_matrix(engine, video, chunk.tokens, chunk.mask, chunk.vec, out=sims_buf[:, :n], single_out=single_buf[:, :n])
+        if ev:
+            ev[2].record(cur)
+        if grouped:
+            gid = gid_all[c0:c1]
+            ng = plan["n_groups"][i]
+            rep, score = ops.topk_groups(sims, kk, gid, ng)
+            if w > 1:
+                s0 = plan["start_at"][i]
+                bcol, bscore = ops.group_topw(sims, rep, gid, start_all[s0:s0 + ng + 1], cols_all[:n], w)
+            else:
+                bcol, bscore = rep.view(Nv, kk, 1), score.view(Nv, kk, 1)
+        else:
+            rep, score = ops.topk_groups(sims, kk)
+            bcol, bscore = rep.view(Nv, kk, 1), score.view(Nv, kk, 1)
+        out = state[i % 2]
+        ops.topk_merge(run[0], run[1], bcol, bscore, kk, col_offset=c0, out_col=out[0], out_score=out[1])
+        run = out
+        if not resident:
+            stage.consumed[i % 2].record(cur)
+        if ev:
+            ev[3].record(cur)
+            marks.append(ev)
+        if i + 1 < len(chunks):                                     # the host copies chunk i + 1 under the kernels of chunk i
+            nxt = chunk_encoded(i + 1)
+    if timings is not None:
+        torch.cuda.synchronize()
+        timings["chunks"] = len(chunks)
+        timings["similarities_ms"] = sum(e[1].elapsed_time(e[2]) for e in marks)
+        timings["selection_merge_ms"] = sum(e[2].elapsed_time(e[3]) for e in marks)
+        timings["upload_wait_ms"] = sum(max(0.0, e[0].elapsed_time(e[1])) for e in marks)      # the compute stream's stalls on uploads
+        timings["upload_wait_max_ms"] = max(max(0.0, e[0].elapsed_time(e[1])) for e in marks)
+    return run
+
+
+@torch.no_grad()
+def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_batch: int = 64, windows_per_track: int = 1,
+                   moments: int = 1, nms_iou: float = 0.5, chunk_cols: int = 4096, video_batch: int = 1024, sims_fn=None,
+                   timings: Optional[dict] = None) -> Grounding:
+    """`ground()` for a stored library (mgsv_amd.library.MusicLibrary: host arrays, a memory-mapped directory, or device tensors):
+    the same Grounding, bit for bit, as
+        ground(engine, videos, library.as_encoded(dev), k, group_id=library.group_id, windows=library.windows, ...)
+    on the same similarities, without the [N_v, N] similarity matrix, the resident library or the limit of 32 768 groups.
+    Selection walks library.chunk_plan(chunk_cols): per chunk the similarities of its columns (sims_fn(chunk, c0, c1) -> [N_v, c1 - c0]
+    if given, else `similarity_matrix` on the chunk), made_topk_groups / made_group_topw over the chunk's groups, and made_topk_merge
+    into the running list; a host library's chunks are uploaded through two pinned staging sets on a copy stream, under the kernels
+    of the chunk before.  Localization runs per video_batch videos on the distinct selected columns only.  track: the library
+    column without windows, the track's index with windows; `to_records` takes library.ids.  timings: a dict that receives the
+    phases' milliseconds (this synchronises the device; for measurements)."""
+    c = engine.cfg
+    dev = engine.device
+    if c.moment_query_type == "xpool":
+        raise NotImplementedError("moment_query_type=xpool: the decoder query is the track's pooled vector averaged over the videos of "
+                                  "the batch (reference model/model_Uni.py:222-223), a property of the batch with no per-pair meaning")
+    library.check_engine(engine)
+    Nv, N = len(videos), len(library)
+    if N == 0:
+        raise ValueError("the library is empty")
+    windows = library.windows
+    w, n = 1, 1
+    if windows is not None:
+        w, n = int(windows_per_track), int(moments)
+        if not 1 <= w <= 16:
+            raise ValueError(f"windows_per_track = {w}: must lie in [1, 16]")
+        if n < 1:
+            raise ValueError(f"moments = {n}: must be >= 1")
+    kk = max(1, min(int(k), library.n_groups))
+    video_batch = max(1, int(video_batch))
+    t0 = torch.cuda.Event(enable_timing=True) if timings is not None else None
+    wcol, wscore = _select_streamed(engine, videos, library, kk, w, int(chunk_cols), sims_fn, timings)
+    if t0 is not None:
+        t0.record()
+    rep, score = wcol[:, :, 0].contiguous(), wscore[:, :, 0].contiguous()
+    resident = library.on_device
+    if resident:
+        music_all = library.as_encoded(dev)
+    offset = track_of_col = duration = None
+    if windows is not None:
+        offset = _as_device(windows.offset, dev, torch.float32)
+        track_of_col = _as_device(windows.track, dev, torch.int32)
+        duration = _as_device(library.duration, dev, torch.float32) if library.duration is not None else None
+    min_pairs = min(int(pair_batch), Nv * kk * w)                   # the batch size `ground` localizes all N_v * kk * w pairs with
+    parts = []
+    for v0 in range(0, Nv, video_batch):
+        v1 = min(Nv, v0 + video_batch)
+        B = v1 - v0
+        cols = wcol[v0:v1].reshape(-1)
+        mi = torch.where(cols < 0, torch.zeros_like(cols), cols)   # (nothing there: localized against column 0, as in `ground`)
+        vi = torch.arange(v0, v1, device=dev, dtype=torch.int32).repeat_interleave(kk * w)
+        if resident:
+            music = music_all
+        else:                                                       # the distinct columns of this batch, uploaded as a compact Encoded
+            uniq, inv = torch.unique(mi, return_inverse=True)
+            rows = uniq.cpu().numpy().astype(np.int64)
+            stage = _staging(library, "columns", len(rows), dev, 1)
+            nrows = stage.fill(0, library, rows)
+            music = stage.upload(0, nrows, library.duration is not None)
+            torch.cuda.current_stream().wait_event(stage.uploaded[0])
+            mi = inv.to(torch.int32).contiguous()
+        if windows is None:
+            st, en, cf = _pair_moments(engine, videos, music, vi, mi, cols < 0, pair_batch, min_pairs=min_pairs)
+            parts.append((st.view(B, kk), en.view(B, kk), cf.view(B, kk), None))
+        else:
+            st, en, cf, wi = _window_moments(engine, videos, music, vi, mi, wcol[v0:v1], wscore[v0:v1], offset, duration, n, nms_iou, pair_batch,
+                                             min_pairs=min_pairs)
+            shape = (B, kk) if n == 1 else (B, kk, n)
+            parts.append((st.view(shape), en.view(shape), cf.view(shape), wi.view(shape)))
+        if not resident:
+            stage.consumed[0].record(torch.cuda.current_stream())
+    start, end, conf = (torch.cat([p[j] for p in parts]) for j in range(3))
+    if timings is not None:
+        t1 = torch.cuda.Event(enable_timing=True)
+        t1.record()
+        torch.cuda.synchronize()
+        timings["localization_ms"] = t0.elapsed_time(t1)
+    if windows is None:
+        return Grounding(track=rep, score=score, start=start, end=end, confidence=conf)
+    return Grounding(track=_window_tracks(rep, track_of_col), score=score, start=start, end=end, confidence=conf,
+                     window=torch.cat([p[3] for p in parts]), windows=windows)
 
 
 def moment_iou(start: Tensor, end: Tensor, gt_moment: Tensor, m_duration: Tensor, max_m_duration: float) -> Tensor:

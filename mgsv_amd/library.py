@@ -1,0 +1,442 @@
+"""A stored music library: the music side of `ground()` kept on the host (or on disk), grounded chunk by chunk.
+
+`ground()` needs the library's tower outputs in one device `Encoded`, the whole [N_v, N_m] similarity matrix and one LDS slot per
+group (at most 32 768 groups).  Selection is a maximum, so it decomposes exactly over chunks of columns that hold whole groups:
+`grounding.ground_library` walks `MusicLibrary.chunk_plan`, selects inside every chunk with the calls `ground()` makes and folds the
+per-chunk lists with made_topk_merge.  This module is the host side of that: the arrays in *library order* (the columns of every
+group contiguous), their directory format, a writer that builds a library batch by batch, and the chunk plan.
+
+Directory format (version 1): manifest.json {format, version, dtype, N, S, D, duration, windows, ids, grouped, n_tracks} and .npy
+arrays tokens [N, S, D] (float32, or uint16 holding bf16 bit patterns), mask [N, S] f32, vec [N, D] f32, col_group [N] int32,
+source [N] int64, optionally duration [N] f32, win_track int32 / win_offset f32 / win_duration f32 [N], track_group [n_tracks]
+int32, and ids.json.
+"""
+from __future__ import annotations
+
+import json
+import os
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .engine import Encoded
+from .windows import Windows
+
+Tensor = torch.Tensor
+
+FORMAT = "mgsv_amd.music_library"
+VERSION = 1
+MAX_GROUPED_CHUNK = 32768               # made_topk_groups: one LDS slot per group, and a chunk has at most as many groups as columns
+MAX_CHUNK = 1 << 24                     # made_topk_groups: columns of one call
+_NPY_HEADER = 128                       # the writer's fixed-size .npy header, rewritten with the final shape on close()
+
+
+def _dtype_name(t: torch.dtype) -> str:
+    if t == torch.bfloat16:
+        return "bf16"
+    if t == torch.float32:
+        return "f32"
+    raise ValueError(f"a library holds f32 or bf16 tokens, not {t}")
+
+
+def _tokens_to_host(t: Tensor) -> np.ndarray:
+    """tokens as a numpy array: float32, or uint16 holding the bf16 bit patterns"""
+    t = t.detach().cpu().contiguous()
+    if t.dtype == torch.bfloat16:
+        return t.view(torch.int16).numpy().view(np.uint16)
+    return t.numpy()
+
+
+def _host(a, dtype) -> np.ndarray:
+    if isinstance(a, Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _tokens_tensor(a: np.ndarray, dtype: str) -> Tensor:
+    """a host tensor of the compute dtype over (a copy of, if it is not writable) the host array"""
+    a = np.ascontiguousarray(a)
+    if not a.flags.writeable:
+        a = a.copy()
+    if dtype == "bf16":
+        return torch.from_numpy(a.view(np.int16)).view(torch.bfloat16)
+    return torch.from_numpy(a)
+
+
+def _runs(col_group: np.ndarray) -> np.ndarray:
+    """starts of the runs of equal values, with N appended: int64 [R + 1]"""
+    n = len(col_group)
+    if n == 0:
+        return np.zeros(1, np.int64)
+    cut = np.flatnonzero(col_group[1:] != col_group[:-1]) + 1
+    return np.concatenate([[0], cut, [n]]).astype(np.int64)
+
+
+def contiguous_order(col_group: np.ndarray) -> np.ndarray:
+    """int64 [N]: the columns in library order -- groups by their first appearance (a stable sort), column order kept inside a
+    group.  The identity when every group's columns are contiguous already."""
+    g = np.asarray(col_group).reshape(-1)
+    _, first, inv = np.unique(g, return_index=True, return_inverse=True)
+    return np.argsort(first[inv.reshape(-1)], kind="stable").astype(np.int64)
+
+
+class MusicLibrary:
+    """The music side of `ground()` in library order.  Host libraries hold numpy arrays (possibly memory-mapped, tokens as float32
+    or as uint16 bf16 patterns); `to(device)` gives a library whose tokens / mask / vec / duration are device tensors, which
+    `ground_library` slices in place.  group_id / windows: the arguments that make
+    `ground(engine, videos, lib.as_encoded(dev), k, group_id=lib.group_id, windows=lib.windows, ...)` the resident counterpart of
+    `ground_library(engine, videos, lib, k, ...)`."""
+
+    def __init__(self, tokens, mask, vec, col_group, source, dtype: str, duration=None, windows: Optional[Windows] = None,
+                 ids: Optional[Sequence] = None, group_id=None):
+        if dtype not in ("f32", "bf16"):
+            raise ValueError(f"dtype = {dtype!r}: a library holds f32 or bf16 tokens")
+        self.tokens, self.mask, self.vec, self.duration = tokens, mask, vec, duration
+        self.dtype = dtype
+        self.col_group = np.ascontiguousarray(col_group, dtype=np.int32).reshape(-1)
+        self.source = np.ascontiguousarray(source, dtype=np.int64).reshape(-1)
+        self.windows = windows
+        self.ids = list(ids) if ids is not None else None
+        self.group_id = None if group_id is None else np.ascontiguousarray(group_id, dtype=np.int32).reshape(-1)
+        if len(self.tokens.shape) != 3:
+            raise ValueError("tokens must be [N, S, D]")
+        N = int(self.tokens.shape[0])
+        if tuple(self.mask.shape) != (N, self.S) or tuple(self.vec.shape) != (N, self.D):
+            raise ValueError(f"mask must be [N, S] and vec [N, D] for tokens {tuple(self.tokens.shape)}")
+        if len(self.col_group) != N or len(self.source) != N or (duration is not None and tuple(duration.shape) != (N,)):
+            raise ValueError("col_group, source and duration need one entry per column")
+        if windows is not None and len(windows) != N:
+            raise ValueError(f"windows describes {len(windows)} columns, the library has {N}")
+        if N and self.col_group.min() < 0:
+            raise ValueError("group ids must be >= 0")
+        self._run_start = _runs(self.col_group)
+        if len(self._run_start) - 1 != len(np.unique(self.col_group)):
+            raise ValueError("the columns of every group must be contiguous (MusicLibrary.build reorders them)")
+        self._plans: Dict[int, dict] = {}
+        self._stages: Dict[str, object] = {}                       # ground_library's pinned staging sets, reused across calls
+
+    # ------------------------------------------------------------------ shape
+    def __len__(self) -> int:
+        return int(self.tokens.shape[0])
+
+    @property
+    def S(self) -> int:
+        return int(self.tokens.shape[1])
+
+    @property
+    def D(self) -> int:
+        return int(self.tokens.shape[2])
+
+    @property
+    def on_device(self) -> bool:
+        return isinstance(self.tokens, Tensor) and self.tokens.is_cuda
+
+    @property
+    def grouped(self) -> bool:
+        """whether selection goes by group (a group_id was given, or the columns are windows of tracks)"""
+        return self.group_id is not None or self.windows is not None
+
+    @property
+    def n_groups(self) -> int:
+        """the number `ground()` clamps k to: the largest group id + 1 (ids that no column has count)"""
+        if self.windows is not None and self.group_id is None:
+            return int(self.windows.n_tracks)
+        if self.group_id is not None:
+            return int(self.group_id.max()) + 1
+        return len(self)
+
+    # ------------------------------------------------------------------ construction
+    @classmethod
+    def build(cls, music: Encoded, group_id=None, windows: Optional[Windows] = None, ids: Optional[Sequence] = None) -> "MusicLibrary":
+        """A host library of an `Encoded` (device or host tensors).  group_id: one entry per column, or per TRACK with windows.
+        Columns are reordered only if a group's columns are not contiguous: groups by first appearance, stable inside a group.
+        The Windows keep their track numbering; only the per-column arrays are permuted (and `ids`, one per column, without
+        windows)."""
+        N = len(music)
+        gid = None if group_id is None else _host(group_id, np.int32).reshape(-1)
+        if windows is not None:
+            if len(windows) != N:
+                raise ValueError(f"windows describes {len(windows)} columns, the library has {N}")
+            if gid is not None and gid.size != windows.n_tracks:
+                raise ValueError("with windows, group_id needs one entry per track")
+            col_group = windows.track.astype(np.int32) if gid is None else gid[windows.track]
+        else:
+            if gid is not None and gid.size != N:
+                raise ValueError("group_id needs one entry per track")
+            col_group = np.arange(N, dtype=np.int32) if gid is None else gid
+        if ids is not None and len(ids) != (windows.n_tracks if windows is not None else N):
+            raise ValueError("ids needs one entry per track")
+        order = contiguous_order(col_group)
+        same = bool((order == np.arange(N)).all())
+        take = (lambda a: a) if same else (lambda a: np.ascontiguousarray(a[order]))
+        dur = None if music.duration is None else take(_host(music.duration, np.float32).reshape(-1))
+        win = windows
+        if windows is not None and not same:
+            win = Windows(track=windows.track[order], offset=windows.offset[order], duration=windows.duration[order],
+                          n_tracks=windows.n_tracks, n_encoded=windows.n_encoded)
+        if windows is None:
+            if ids is not None and not same:
+                ids = [ids[i] for i in order]
+            gid = None if gid is None else take(gid)
+        return cls(take(_tokens_to_host(music.tokens)), take(_host(music.mask, np.float32)), take(_host(music.vec, np.float32)),
+                   take(col_group), order, _dtype_name(music.tokens.dtype), duration=dur, windows=win, ids=ids, group_id=gid)
+
+    def to(self, device) -> "MusicLibrary":
+        """The same library with tokens / mask / vec / duration as tensors on `device` (the host tables stay on the host)."""
+        dev = torch.device(device)
+        up = lambda a: (a if isinstance(a, Tensor) else torch.from_numpy(np.array(a))).to(dev)
+        tok = self.tokens.to(dev) if isinstance(self.tokens, Tensor) else _tokens_tensor(self.tokens, self.dtype).to(dev)
+        return MusicLibrary(tok, up(self.mask), up(self.vec), self.col_group, self.source, self.dtype,
+                            duration=None if self.duration is None else up(self.duration), windows=self.windows, ids=self.ids,
+                            group_id=self.group_id)
+
+    def pin(self) -> "MusicLibrary":
+        """The same library with tokens / mask / vec / duration copied into pinned host tensors: `ground_library` uploads its
+        chunks straight from them, without the staging copy."""
+        pin = lambda a: (a.cpu() if isinstance(a, Tensor) else torch.from_numpy(np.array(a))).pin_memory()
+        tok = self.tokens.cpu() if isinstance(self.tokens, Tensor) else _tokens_tensor(self.tokens, self.dtype)
+        return MusicLibrary(tok.pin_memory(), pin(self.mask), pin(self.vec), self.col_group, self.source, self.dtype,
+                            duration=None if self.duration is None else pin(self.duration), windows=self.windows, ids=self.ids,
+                            group_id=self.group_id)
+
+    @property
+    def pinned(self) -> bool:
+        return isinstance(self.tokens, Tensor) and not self.tokens.is_cuda and self.tokens.is_pinned()
+
+    def as_encoded(self, device) -> Encoded:
+        """The whole library as a resident `Encoded`, in library order."""
+        lib = self if self.on_device and self.tokens.device == torch.device(device) else self.to(device)
+        return Encoded(tokens=lib.tokens, mask=lib.mask, vec=lib.vec, duration=lib.duration)
+
+    def check_engine(self, engine) -> None:
+        """ValueError unless the stored tower outputs are this engine's: compute dtype and width (nothing is cast)."""
+        want = _dtype_name(engine.tc)
+        if self.dtype != want:
+            raise ValueError(f"the library holds {self.dtype} tokens, the engine computes in {want}")
+        if self.D != int(engine.cfg.D):
+            raise ValueError(f"the library's D = {self.D}, the engine's {int(engine.cfg.D)}")
+        if self.S < 1:
+            raise ValueError(f"the library's S = {self.S}: must be >= 1")
+
+    # ------------------------------------------------------------------ directory format
+    def save(self, path: str) -> None:
+        if self.on_device:
+            raise ValueError("save() writes a host library")
+        os.makedirs(path, exist_ok=True)
+        sv = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        sv("tokens", self.tokens)
+        sv("mask", self.mask)
+        sv("vec", self.vec)
+        sv("col_group", self.col_group)
+        sv("source", self.source)
+        if self.duration is not None:
+            sv("duration", self.duration)
+        _write_tables(path, self.windows, self.group_id, self.ids)
+        _write_manifest(path, self.dtype, len(self), self.S, self.D, self.duration is not None, self.windows, self.ids is not None,
+                        self.group_id is not None)
+
+    @classmethod
+    def load(cls, path: str, mmap: bool = True) -> "MusicLibrary":
+        with open(os.path.join(path, "manifest.json")) as f:
+            man = json.load(f)
+        if man.get("format") != FORMAT or man.get("version") != VERSION:
+            raise ValueError(f"{path}: not a music library of format version {VERSION}")
+        ld = lambda name: np.load(os.path.join(path, name + ".npy"), mmap_mode="r" if mmap else None)
+        tokens, mask, vec = ld("tokens"), ld("mask"), ld("vec")
+        N, S, D = int(man["N"]), int(man["S"]), int(man["D"])
+        want = np.dtype(np.uint16) if man["dtype"] == "bf16" else np.dtype(np.float32)
+        if man["dtype"] not in ("f32", "bf16") or tokens.dtype != want or tuple(tokens.shape) != (N, S, D):
+            raise ValueError(f"{path}: the manifest says {man['dtype']} tokens [{N}, {S}, {D}], tokens.npy holds {tokens.dtype} "
+                             f"{tuple(tokens.shape)}")
+        windows = None
+        if man["windows"]:
+            windows = Windows(track=np.load(os.path.join(path, "win_track.npy")), offset=np.load(os.path.join(path, "win_offset.npy")),
+                              duration=np.load(os.path.join(path, "win_duration.npy")), n_tracks=int(man["n_tracks"]))
+        col_group = np.load(os.path.join(path, "col_group.npy"))
+        group_id = None
+        if man["grouped"]:
+            group_id = np.load(os.path.join(path, "track_group.npy")) if windows is not None else col_group
+        ids = None
+        if man["ids"]:
+            with open(os.path.join(path, "ids.json")) as f:
+                ids = json.load(f)
+        return cls(tokens, mask, vec, col_group, np.load(os.path.join(path, "source.npy")), man["dtype"],
+                   duration=ld("duration") if man["duration"] else None, windows=windows, ids=ids, group_id=group_id)
+
+    # ------------------------------------------------------------------ the chunk plan
+    def chunk_plan(self, chunk_cols: int) -> List[Tuple[int, int]]:
+        """[(c0, c1), ...]: contiguous chunks of at most chunk_cols columns that cover [0, N) once, in order, every group whole and
+        no chunk empty.  ValueError for a group of more than chunk_cols columns."""
+        return self._plan(chunk_cols)["chunks"]
+
+    def _plan(self, chunk_cols: int) -> dict:
+        """The plan and its group tables, computed once: chunks; gid int32 [N] (every column's group, dense inside its chunk, in
+        order of appearance); start int32 (the chunks' CSR starts, one after the other) and start_at (each chunk's first entry
+        in it).  The CSR's column list of every chunk is 0, 1, 2, ...: groups are contiguous and numbered in order."""
+        chunk_cols = int(chunk_cols)
+        if chunk_cols < 1:
+            raise ValueError(f"chunk_cols = {chunk_cols}: must be >= 1")
+        if chunk_cols > (MAX_GROUPED_CHUNK if self.grouped else MAX_CHUNK):
+            raise ValueError(f"chunk_cols = {chunk_cols}: at most {MAX_GROUPED_CHUNK} columns per chunk when columns are selected by "
+                             f"group (one LDS slot per group), {MAX_CHUNK} otherwise")
+        if chunk_cols in self._plans:
+            return self._plans[chunk_cols]
+        rs, N = self._run_start, len(self)
+        chunks, runs = [], []                                                        # runs: (first run, one past the last) of a chunk
+        r0 = 0
+        while r0 < len(rs) - 1:
+            c0 = int(rs[r0])
+            r1 = int(np.searchsorted(rs, c0 + chunk_cols, side="right")) - 1         # the last run boundary within reach
+            if r1 == r0:
+                raise ValueError(f"group {int(self.col_group[c0])} has {int(rs[r0 + 1] - c0)} columns, more than chunk_cols = {chunk_cols}")
+            chunks.append((c0, int(rs[r1])))
+            runs.append((r0, r1))
+            r0 = r1
+        run_of = np.repeat(np.arange(len(rs) - 1, dtype=np.int64), np.diff(rs))      # dense group number in library order
+        gid = np.empty(N, np.int32)
+        start, start_at = [], []
+        at = 0
+        for (a, b), (r0, r1) in zip(chunks, runs):
+            gid[a:b] = run_of[a:b] - r0
+            start_at.append(at)
+            start.append(rs[r0:r1 + 1] - a)
+            at += r1 - r0 + 1
+        plan = dict(chunks=chunks, gid=gid, start=np.concatenate(start).astype(np.int32) if start else np.zeros(0, np.int32),
+                    start_at=start_at, n_groups=[r1 - r0 for r0, r1 in runs], device={})
+        self._plans[chunk_cols] = plan
+        return plan
+
+
+def _write_tables(path: str, windows: Optional[Windows], group_id, ids) -> None:
+    if windows is not None:
+        np.save(os.path.join(path, "win_track.npy"), windows.track)
+        np.save(os.path.join(path, "win_offset.npy"), windows.offset)
+        np.save(os.path.join(path, "win_duration.npy"), windows.duration)
+        if group_id is not None:
+            np.save(os.path.join(path, "track_group.npy"), np.ascontiguousarray(group_id, dtype=np.int32))
+    if ids is not None:
+        with open(os.path.join(path, "ids.json"), "w") as f:
+            json.dump(list(ids), f)
+
+
+def _write_manifest(path: str, dtype: str, N: int, S: int, D: int, duration: bool, windows: Optional[Windows], ids: bool,
+                    grouped: bool) -> None:
+    man = dict(format=FORMAT, version=VERSION, dtype=dtype, N=int(N), S=int(S), D=int(D), duration=bool(duration),
+               windows=windows is not None, ids=bool(ids), grouped=bool(grouped),
+               n_tracks=int(windows.n_tracks) if windows is not None else None)
+    with open(os.path.join(path, "manifest.json"), "w") as f:
+        json.dump(man, f, indent=1)
+        f.write("\n")
+
+
+def _npy_header(dtype: np.dtype, shape: Tuple[int, ...]) -> bytes:
+    """a version-1.0 .npy header of exactly _NPY_HEADER bytes (the writer rewrites it in place once N is known)"""
+    d = "{'descr': %r, 'fortran_order': False, 'shape': %r, }" % (np.dtype(dtype).str, tuple(int(x) for x in shape))
+    pad = _NPY_HEADER - 10 - len(d) - 1
+    assert pad >= 0, "shape too long for the fixed header"
+    return b"\x93NUMPY\x01\x00" + (_NPY_HEADER - 10).to_bytes(2, "little") + (d + " " * pad + "\n").encode("latin1")
+
+
+class MusicLibraryWriter:
+    """Builds a library larger than the device, batch by batch: every `add` appends whole groups to the arrays on disk (nothing
+    already written is ever permuted), `close()` writes the tables and the manifest and returns the library, memory-mapped.
+        add(music, col_group, duration=None, windows_rows=None, ids=None)
+    col_group [n]: the group of every added column, contiguous inside the batch, none seen in an earlier add.  windows_rows: a
+    `Windows` (or a (track, offset, duration) triple) for the added columns with the LIBRARY's track numbers -- then ids holds one
+    entry per new track, else one per column.  duration defaults to music.duration."""
+
+    def __init__(self, path: str, S: int, D: int, dtype: str):
+        if dtype not in ("f32", "bf16"):
+            raise ValueError(f"dtype = {dtype!r}: a library holds f32 or bf16 tokens")
+        self.path, self.S, self.D, self.dtype = path, int(S), int(D), dtype
+        os.makedirs(path, exist_ok=True)
+        self._tok_dtype = np.dtype(np.uint16) if dtype == "bf16" else np.dtype(np.float32)
+        self._files = {}
+        for name, dt, tail in (("tokens", self._tok_dtype, (self.S, self.D)), ("mask", np.float32, (self.S,)), ("vec", np.float32, (self.D,))):
+            f = open(os.path.join(path, name + ".npy"), "wb")
+            f.write(_npy_header(dt, (0,) + tail))
+            self._files[name] = (f, np.dtype(dt), tail)
+        self.N = 0
+        self._seen = set()
+        self._col_group: List[np.ndarray] = []
+        self._duration: List[np.ndarray] = []
+        self._win: List[Tuple[np.ndarray, np.ndarray, np.ndarray]] = []
+        self._ids: Optional[list] = None
+        self._closed = False
+
+    def add(self, music: Encoded, col_group, duration=None, windows_rows=None, ids: Optional[Sequence] = None) -> None:
+        if self._closed:
+            raise ValueError("the writer is closed")
+        n = len(music)
+        g = _host(col_group, np.int32).reshape(-1)
+        if _dtype_name(music.tokens.dtype) != self.dtype or tuple(music.tokens.shape[1:]) != (self.S, self.D):
+            raise ValueError(f"the writer takes {self.dtype} tokens [n, {self.S}, {self.D}], not {music.tokens.dtype} {tuple(music.tokens.shape)}")
+        if g.size != n:
+            raise ValueError("col_group needs one entry per added column")
+        if n == 0:
+            return
+        if g.min() < 0:
+            raise ValueError("group ids must be >= 0")
+        new = np.unique(g)
+        if len(_runs(g)) - 1 != len(new):
+            raise ValueError("the columns of every group must be contiguous inside an add (MusicLibrary.build reorders a batch)")
+        again = [int(x) for x in new if int(x) in self._seen]
+        if again:
+            raise ValueError(f"group {again[0]} appeared in an earlier add: every add must hold whole groups")
+        duration = music.duration if duration is None else duration
+        if (duration is None) != (not self._duration) and self.N:
+            raise ValueError("either every add carries durations or none does")
+        if (windows_rows is None) != (not self._win) and self.N:
+            raise ValueError("either every add carries windows or none does")
+        if (ids is None) != (self._ids is None) and self.N:
+            raise ValueError("either every add carries ids or none does")
+        if windows_rows is not None:
+            tr, off, dur = ((windows_rows.track, windows_rows.offset, windows_rows.duration) if isinstance(windows_rows, Windows)
+                            else windows_rows)
+            tr, off, dur = _host(tr, np.int32).reshape(-1), _host(off, np.float32).reshape(-1), _host(dur, np.float32).reshape(-1)
+            if not (len(tr) == len(off) == len(dur) == n):
+                raise ValueError("windows_rows needs one entry per added column")
+            self._win.append((tr, off, dur))
+        elif ids is not None and len(ids) != n:
+            raise ValueError("ids needs one entry per added column")
+        for name, a in (("tokens", _tokens_to_host(music.tokens)), ("mask", _host(music.mask, np.float32)), ("vec", _host(music.vec, np.float32))):
+            f, dt, tail = self._files[name]
+            assert a.dtype == dt and tuple(a.shape) == (n,) + tail, (name, a.dtype, a.shape)
+            f.write(a.tobytes())
+        self._seen.update(int(x) for x in new)
+        self._col_group.append(g)
+        if duration is not None:
+            self._duration.append(_host(duration, np.float32).reshape(-1))
+        if ids is not None:
+            self._ids = (self._ids or []) + list(ids)
+        self.N += n
+
+    def close(self) -> MusicLibrary:
+        if self._closed:
+            raise ValueError("the writer is closed")
+        self._closed = True
+        for name, (f, dt, tail) in self._files.items():
+            f.seek(0)
+            f.write(_npy_header(dt, (self.N,) + tail))
+            f.close()
+        cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)
+        col_group = cat(self._col_group, np.int32)
+        np.save(os.path.join(self.path, "col_group.npy"), col_group)
+        np.save(os.path.join(self.path, "source.npy"), np.arange(self.N, dtype=np.int64))
+        if self._duration:
+            np.save(os.path.join(self.path, "duration.npy"), cat(self._duration, np.float32))
+        windows, track_group = None, None
+        if self._win:
+            tr = cat([w[0] for w in self._win], np.int32)
+            windows = Windows(track=tr, offset=cat([w[1] for w in self._win], np.float32), duration=cat([w[2] for w in self._win], np.float32),
+                              n_tracks=int(tr.max()) + 1)
+            track_group = np.zeros(windows.n_tracks, np.int32)
+            track_group[tr] = col_group                            # (col_group = group_id[track]: every window of a track agrees)
+            if not np.array_equal(track_group[tr], col_group):
+                raise ValueError("the windows of one track were given different groups")
+        if self._ids is not None and len(self._ids) != (windows.n_tracks if windows is not None else self.N):
+            raise ValueError("ids needs one entry per track")
+        _write_tables(self.path, windows, track_group, self._ids)
+        _write_manifest(self.path, self.dtype, self.N, self.S, self.D, bool(self._duration), windows, self._ids is not None, True)
+        return MusicLibrary.load(self.path, mmap=True)

@@ -980,6 +980,29 @@ def group_topw(sims: Tensor, sel: Tensor, col_group: Tensor, start: Tensor, cols
     return idx, score
 
 
+def topk_merge(a_col: Tensor, a_score: Tensor, b_col: Tensor, b_score: Tensor, K: int, col_offset: int = 0,
+               out_col: Optional[Tensor] = None, out_score: Optional[Tensor] = None):
+    """made_topk_merge: the first K entries of the union of two sorted per-row lists of selected groups, a [Nv, Ka, w] (running) and
+    b [Nv, Kb, w] (one chunk, columns local to it: col_offset is added), each entry the group_topw payload of a group (col int32,
+    score f32) -> (col [Nv, K, w], score [Nv, K, w]), -1 / -inf past the union.  The outputs must not alias the inputs."""
+    for c, s in ((a_col, a_score), (b_col, b_score)):
+        assert c.dim() == 3 and c.dtype == torch.int32 and s.dtype == torch.float32 and c.shape == s.shape
+        assert c.is_contiguous() and s.is_contiguous()
+    Nv, Ka, w = a_col.shape
+    assert b_col.shape[0] == Nv and b_col.shape[2] == w
+    Kb = b_col.shape[1]
+    if out_col is None:
+        out_col = torch.empty(Nv, K, w, device=a_col.device, dtype=torch.int32)
+    if out_score is None:
+        out_score = torch.empty(Nv, K, w, device=a_col.device, dtype=torch.float32)
+    assert out_col.dtype == torch.int32 and out_score.dtype == torch.float32 and out_col.is_contiguous() and out_score.is_contiguous()
+    assert tuple(out_col.shape) == (Nv, K, w) and tuple(out_score.shape) == (Nv, K, w)
+    check(lib().made_topk_merge(_p(a_col) if Ka else None, _p(a_score) if Ka else None, Ka, _p(b_col) if Kb else None,
+                                _p(b_score) if Kb else None, Kb, int(col_offset), Nv, w, K, _p(out_col), _p(out_score), _stream()),
+          "made_topk_merge")
+    return out_col, out_score
+
+
 def merge_moments(cand: Tensor, win_col: Tensor, win_score: Tensor, offset: Tensor, duration: Optional[Tensor], max_m_duration: float,
                   nms_iou: float, n: int, use_prob: bool = True):
     """made_merge_moments: cand [P, w, Q, 3] f32 (start, end, foreground probability per query, seconds on the window's axis),
