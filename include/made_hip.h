@@ -1016,6 +1016,33 @@ int64_t made_topk_groups_ws_bytes(int64_t Nv, int64_t Nm, int64_t K);
 int made_topk_groups(const float* sims, int64_t ld, const int32_t* group_id, int64_t Nv, int64_t Nm, int64_t n_groups,
                      int64_t K, int32_t* idx_out, float* score_out, void* ws, int64_t ws_bytes, void* stream);
 
+/* made_eligibility: which columns of a library each video may be grounded in -- per-video constraints on per-column attributes,
+ * as a bit matrix for made_topk_groups_masked / made_group_topw_masked.  Column attributes (any may be NULL: that test is off for
+ * every row): col_tags [Nm] int64 (64 free bits, compared as unsigned patterns), col_length [Nm] f32 seconds, col_key [Nm] int32
+ * (the column's track index, the unit exclusion lists name).  Row constraints: row_all / row_any / row_forbid [Nv] int64 (each may
+ * be NULL = 0), row_min / row_max [Nv] f32 (NULL: not tested), ex_start [Nv + 1] int32 and ex_keys [n_ex_keys] int32 a CSR of
+ * excluded keys, ascending inside each row (ex_start may be NULL: no lists; ranges are clamped to [0, n_ex_keys]).  Column c
+ * (tags T, length L, key t) is eligible for row i iff (T & all_i) == all_i, and any_i == 0 or (T & any_i) != 0, and
+ * (T & forbid_i) == 0, and L >= min_i, and L <= max_i (plain f32 comparisons: a NaN length fails a bound that is tested), and t
+ * is not in row i's list (binary search; an empty list is not searched).  Outputs, either may be NULL but not both:
+ * bits_out [Nv, ld_words] uint32, column c = bit c & 31 of word c >> 5, the bits past Nm of the last word 0, words
+ * ceil(Nm / 32) .. ld_words-1 of a row untouched; col_any_out [ceil(Nm / 32)] uint32, the OR over the rows, accumulated with
+ * atomicOr: the caller zeroes it.  Refused: a row pattern without col_tags, a bound without col_length, lists without col_key.
+ * One thread per column keeps the attributes in registers over a strip of rows; 64 tests are one ballot. */
+int made_eligibility(const int64_t* col_tags, const float* col_length, const int32_t* col_key, const int64_t* row_all,
+                     const int64_t* row_any, const int64_t* row_forbid, const float* row_min, const float* row_max,
+                     const int32_t* ex_start, const int32_t* ex_keys, int64_t n_ex_keys, int64_t Nv, int64_t Nm, uint32_t* bits_out,
+                     int64_t ld_words, uint32_t* col_any_out, void* stream);
+
+/* made_topk_groups_masked: made_topk_groups on every row with its ineligible columns removed.  bits [Nv, bits_ld] uint32 is
+ * made_eligibility's bits_out (bits_ld >= ceil(Nm / 32)): a column whose bit is clear adds to no group's maximum, represents no
+ * group and breaks no tie; a group without an eligible column is absent, and positions past the eligible groups hold -1 / -inf.
+ * An eligible -inf or NaN column is still an item.  Everything else -- order, limits, the long-row path and its workspace of
+ * made_topk_groups_ws_bytes -- is made_topk_groups'; bits == NULL is that call. */
+int made_topk_groups_masked(const float* sims, int64_t ld, const int32_t* group_id, const uint32_t* bits, int64_t bits_ld, int64_t Nv,
+                            int64_t Nm, int64_t n_groups, int64_t K, int32_t* idx_out, float* score_out, void* ws, int64_t ws_bytes,
+                            void* stream);
+
 /* made_gather_pairs: the localization batch of P (video, track) pairs vi[P], mi[P] (device int32) from per-item tower outputs, in
  * one launch -- what the temporal encoders of a forward over those pairs leave behind.  Video side: frame tokens [Nv, Tv, D]
  * (`dtype`, item stride v_tok_stride elements, rows contiguous), frame mask [Nv, Tv] f32, clip vector [Nv, D] f32; music side
@@ -1049,6 +1076,13 @@ int made_gather_rows(const void* src, int64_t U, const int32_t* index, int64_t R
 int made_group_topw(const float* sims, int64_t ld, const int32_t* sel, const int32_t* col_group, const int32_t* start,
                     const int32_t* cols, int64_t n_cols, int64_t Nv, int64_t Nm, int64_t n_groups, int64_t K, int64_t w,
                     int32_t* idx_out, float* score_out, void* stream);
+
+/* made_group_topw_masked: made_group_topw with the ineligible members of every group skipped (bits [Nv, bits_ld] uint32 as in
+ * made_topk_groups_masked, whose output sel is): a member whose bit is clear fills no slot, so a group left with fewer than w
+ * eligible members ends in -1 / -inf.  bits == NULL is made_group_topw. */
+int made_group_topw_masked(const float* sims, int64_t ld, const uint32_t* bits, int64_t bits_ld, const int32_t* sel,
+                           const int32_t* col_group, const int32_t* start, const int32_t* cols, int64_t n_cols, int64_t Nv, int64_t Nm,
+                           int64_t n_groups, int64_t K, int64_t w, int32_t* idx_out, float* score_out, void* stream);
 
 /* made_topk_merge: a running selection merged with the selection of one more chunk of columns, for every row (a selection
  * decomposes over column chunks that hold whole groups: mgsv_amd/library.py, grounding.ground_library).  An entry is a selected

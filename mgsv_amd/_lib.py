@@ -302,10 +302,13 @@ SIGNATURES = {
     "made_set_criterion": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, f32, vp, vp, vp, vp]),
     "made_topk_groups_ws_bytes": (C.c_int64, [i64, i64, i64]),
     "made_topk_groups": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, vp, i64, vp]),
+    "made_eligibility": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, vp]),
+    "made_topk_groups_masked": (C.c_int, [vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp]),
     "made_gather_pairs": (C.c_int, [vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, i32,
                                     vp, i64, vp, i64, vp, vp, vp, vp, vp]),
     "made_gather_rows": (C.c_int, [vp, i64, vp, i64, i64, vp, i32, vp]),
     "made_group_topw": (C.c_int, [vp, i64, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp]),
+    "made_group_topw_masked": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp]),
     "made_topk_merge": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp]),
     "made_merge_moments": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, f32, f32, i64, vp, vp, vp, vp, vp]),
     "made_frames_preprocess": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i32, i64, vp, vp]),

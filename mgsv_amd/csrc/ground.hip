@@ -1,5 +1,6 @@
-// Grounding: the best K tracks of every video row of the similarity matrix (made_topk_groups) and the localization batch of
-// arbitrary (video, track) pairs assembled from per-item tower outputs (made_gather_pairs).  Neither has a counterpart in the
+// Grounding: the best K tracks of every video row of the similarity matrix (made_topk_groups; made_topk_groups_masked under the
+// per-video eligibility bits of made_eligibility) and the localization batch of arbitrary (video, track) pairs assembled from
+// per-item tower outputs (made_gather_pairs).  Neither has a counterpart in the
 // reference, which predicts a moment only in the ground-truth track.
 #include "common.h"
 
@@ -95,12 +96,25 @@ __device__ __forceinline__ int block_excl_count(bool flag, TopkShared& sh, int* 
     return off + pre;
 }
 
+// Key of column j of a row under an eligibility mask (made_eligibility's layout: bit j & 31 of word j >> 5): 0, "no item", when the
+// bit is clear.  Every read of a score in the masked instantiations goes through here; the unmasked ones read the score alone.
+template <bool MASKED>
+__device__ __forceinline__ uint32_t column_key(const float* s, const uint32_t* bits, int j) {
+    if constexpr (MASKED) {
+        if (!((bits[j >> 5] >> (j & 31)) & 1u)) return 0u;
+    }
+    return score_key(s[j]);
+}
+
 // One workgroup selects the best K of one row's items and writes them sorted (score descending, column ascending).
 //   mode 0: columns [c0, c0 + n) of the row, one item each;
 //   mode 1: groups -- item g = group g, key = the group's best column, column = the lowest column attaining it;
 //   mode 2: the sorted candidate lists of a previous pass (key, column), item order ascending in column among equal keys.
 // Workgroup x: row = x / nblk, block b = x % nblk.  final_out: idx / score [row, K]; else key / column candidates [row, nblk, K].
-__global__ __launch_bounds__(GT) void topk_kernel(const float* sims, int64_t ld, const int32_t* gid, int Nm, int G,
+// MASKED: columns whose bit of mask [row, mask_ld words] is clear are no items (modes 0 and 1; mode 2 sees candidate lists only).
+template <bool MASKED>
+__global__ __launch_bounds__(GT) void topk_kernel(const float* sims, int64_t ld, const uint32_t* mask, int64_t mask_ld,
+                                                  const int32_t* gid, int Nm, int G,
                                                   const uint32_t* ckey_in, const int32_t* ccol_in, int n_in, int per_block,
                                                   int K, int mode, int nblk, int32_t* idx_out, float* score_out,
                                                   uint32_t* ckey_out, int32_t* ccol_out) {
@@ -109,18 +123,19 @@ __global__ __launch_bounds__(GT) void topk_kernel(const float* sims, int64_t ld,
     const int64_t row = blockIdx.x / nblk;
     const int b = blockIdx.x % nblk;
     const float* s = sims ? sims + row * ld : nullptr;
+    const uint32_t* mb = MASKED ? mask + row * mask_ld : nullptr;
     int n, i0 = 0;
     if (mode == 0) {
         i0 = b * per_block;
         n = min(per_block, Nm - i0);
-        for (int i = threadIdx.x; i < n; i += GT) v[i] = score_key(s[i0 + i]);
+        for (int i = threadIdx.x; i < n; i += GT) v[i] = column_key<MASKED>(s, mb, i0 + i);
     } else if (mode == 1) {
         n = G;
         for (int g = threadIdx.x; g < G; g += GT) v[g] = 0u;
         __syncthreads();
         for (int j = threadIdx.x; j < Nm; j += GT) {
             const int g = gid[j];
-            if ((unsigned)g < (unsigned)G) atomicMax(&v[g], score_key(s[j]));
+            if ((unsigned)g < (unsigned)G) atomicMax(&v[g], column_key<MASKED>(s, mb, j));
         }
     } else {
         i0 = b * per_block;
@@ -152,7 +167,7 @@ __global__ __launch_bounds__(GT) void topk_kernel(const float* sims, int64_t ld,
             if ((unsigned)g >= (unsigned)G) continue;
             const uint32_t e = v[g];
             if (e == SLOT_OUT) continue;
-            const uint32_t k = score_key(s[j]);
+            const uint32_t k = column_key<MASKED>(s, mb, j);
             if (e < 256u) { if (k == sh.cand_key[e]) atomicMin(&sh.cand_col[e], j); }
             else if (k == t) atomicMin(&v[g], TIE + (uint32_t)j);
         }
@@ -340,8 +355,13 @@ extern "C" int64_t made_topk_groups_ws_bytes(int64_t Nv, int64_t Nm, int64_t K) 
     return (nb0 + nb1) * Nv * K * 8;
 }
 
-extern "C" int made_topk_groups(const float* sims, int64_t ld, const int32_t* group_id, int64_t Nv, int64_t Nm, int64_t n_groups,
-                                int64_t K, int32_t* idx_out, float* score_out, void* ws, int64_t ws_bytes, void* stream) {
+namespace {
+
+// made_topk_groups and made_topk_groups_masked: the same launches, of the unmasked or the masked instantiation
+template <bool MASKED>
+int topk_groups_launch(const float* sims, int64_t ld, const int32_t* group_id, const uint32_t* bits, int64_t bits_ld, int64_t Nv,
+                       int64_t Nm, int64_t n_groups, int64_t K, int32_t* idx_out, float* score_out, void* ws, int64_t ws_bytes,
+                       void* stream) {
     MADE_REQUIRE(sims && idx_out && score_out, "made_topk_groups: null pointer");
     MADE_REQUIRE(Nv >= 0 && Nm > 0 && ld >= Nm, "made_topk_groups: bad dims (Nv >= 0, Nm > 0, ld >= Nm)");
     MADE_REQUIRE(K >= 1 && K <= 256, "made_topk_groups: K must lie in [1, 256]");
@@ -350,21 +370,23 @@ extern "C" int made_topk_groups(const float* sims, int64_t ld, const int32_t* gr
     const int64_t need = group_id ? 0 : made_topk_groups_ws_bytes(Nv, Nm, K);
     MADE_REQUIRE(need == 0 || (ws && ws_bytes >= need), "made_topk_groups: workspace of %lld bytes needed", (long long)need);
     MADE_REQUIRE(Nv * topk_blocks(Nm) < (1LL << 31), "made_topk_groups: too many rows");
+    if (MASKED) MADE_REQUIRE(bits_ld >= (Nm + 31) / 32, "made_topk_groups_masked: bits_ld must be >= ceil(Nm / 32) words");
     if (Nv == 0) return MADE_OK;
-    static bool attr_done = false;
+    static bool attr_done = false;                               // (one per instantiation; the later passes are unmasked)
     if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * 4);
+        (void)hipFuncSetAttribute((const void*)topk_kernel<MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * 4);
+        if (MASKED) (void)hipFuncSetAttribute((const void*)topk_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, CAP * 4);
         attr_done = true;
     }
     const hipStream_t st = (hipStream_t)stream;
     if (group_id) {
-        hipLaunchKernelGGL(topk_kernel, dim3((unsigned)Nv), dim3(GT), (size_t)n_groups * 4, st, sims, ld, group_id, (int)Nm, (int)n_groups,
+        hipLaunchKernelGGL(topk_kernel<MASKED>, dim3((unsigned)Nv), dim3(GT), (size_t)n_groups * 4, st, sims, ld, bits, bits_ld, group_id, (int)Nm, (int)n_groups,
                            (const uint32_t*)nullptr, (const int32_t*)nullptr, 0, 0, (int)K, 1, 1, idx_out, score_out, (uint32_t*)nullptr,
                            (int32_t*)nullptr);
         return made_check_launch("made_topk_groups");
     }
     if (Nm <= CAP) {
-        hipLaunchKernelGGL(topk_kernel, dim3((unsigned)Nv), dim3(GT), (size_t)Nm * 4, st, sims, ld, (const int32_t*)nullptr, (int)Nm, 0,
+        hipLaunchKernelGGL(topk_kernel<MASKED>, dim3((unsigned)Nv), dim3(GT), (size_t)Nm * 4, st, sims, ld, bits, bits_ld, (const int32_t*)nullptr, (int)Nm, 0,
                            (const uint32_t*)nullptr, (const int32_t*)nullptr, 0, (int)Nm, (int)K, 0, 1, idx_out, score_out,
                            (uint32_t*)nullptr, (int32_t*)nullptr);
         return made_check_launch("made_topk_groups");
@@ -378,7 +400,7 @@ extern "C" int made_topk_groups(const float* sims, int64_t ld, const int32_t* gr
     char* base = (char*)ws;
     uint32_t* keys[2] = {(uint32_t*)base, (uint32_t*)(base + nb0 * Nv * K * 8)};
     int32_t* cols[2] = {(int32_t*)(base + nb0 * Nv * K * 4), (int32_t*)(base + nb0 * Nv * K * 8 + nb1 * Nv * K * 4)};
-    hipLaunchKernelGGL(topk_kernel, dim3((unsigned)(Nv * nb0)), dim3(GT), (size_t)CAP * 4, st, sims, ld, (const int32_t*)nullptr, (int)Nm, 0,
+    hipLaunchKernelGGL(topk_kernel<MASKED>, dim3((unsigned)(Nv * nb0)), dim3(GT), (size_t)CAP * 4, st, sims, ld, bits, bits_ld, (const int32_t*)nullptr, (int)Nm, 0,
                        (const uint32_t*)nullptr, (const int32_t*)nullptr, 0, CAP, (int)K, 0, (int)nb0, (int32_t*)nullptr, (float*)nullptr,
                        keys[0], cols[0]);
     int64_t nb = nb0;
@@ -387,8 +409,8 @@ extern "C" int made_topk_groups(const float* sims, int64_t ld, const int32_t* gr
         const int64_t n_in = nb * K;
         const int64_t nxt = (n_in + fan - 1) / fan;
         const bool last = nxt == 1;
-        hipLaunchKernelGGL(topk_kernel, dim3((unsigned)(Nv * nxt)), dim3(GT), (size_t)min(n_in, fan) * 4, st, (const float*)nullptr, ld,
-                           (const int32_t*)nullptr, (int)Nm, 0, (const uint32_t*)keys[cur], (const int32_t*)cols[cur], (int)n_in, (int)fan,
+        hipLaunchKernelGGL(topk_kernel<false>, dim3((unsigned)(Nv * nxt)), dim3(GT), (size_t)min(n_in, fan) * 4, st, (const float*)nullptr, ld,
+                           (const uint32_t*)nullptr, (int64_t)0, (const int32_t*)nullptr, (int)Nm, 0, (const uint32_t*)keys[cur], (const int32_t*)cols[cur], (int)n_in, (int)fan,
                            (int)K, 2, (int)nxt, last ? idx_out : (int32_t*)nullptr, last ? score_out : (float*)nullptr,
                            last ? (uint32_t*)nullptr : keys[cur ^ 1], last ? (int32_t*)nullptr : cols[cur ^ 1]);
         if (last) break;
@@ -396,6 +418,97 @@ extern "C" int made_topk_groups(const float* sims, int64_t ld, const int32_t* gr
         cur ^= 1;
     }
     return made_check_launch("made_topk_groups");
+}
+
+}  // namespace
+
+extern "C" int made_topk_groups(const float* sims, int64_t ld, const int32_t* group_id, int64_t Nv, int64_t Nm, int64_t n_groups,
+                                int64_t K, int32_t* idx_out, float* score_out, void* ws, int64_t ws_bytes, void* stream) {
+    return topk_groups_launch<false>(sims, ld, group_id, nullptr, 0, Nv, Nm, n_groups, K, idx_out, score_out, ws, ws_bytes, stream);
+}
+
+extern "C" int made_topk_groups_masked(const float* sims, int64_t ld, const int32_t* group_id, const uint32_t* bits, int64_t bits_ld,
+                                       int64_t Nv, int64_t Nm, int64_t n_groups, int64_t K, int32_t* idx_out, float* score_out,
+                                       void* ws, int64_t ws_bytes, void* stream) {
+    if (!bits) return topk_groups_launch<false>(sims, ld, group_id, nullptr, 0, Nv, Nm, n_groups, K, idx_out, score_out, ws, ws_bytes, stream);
+    return topk_groups_launch<true>(sims, ld, group_id, bits, bits_ld, Nv, Nm, n_groups, K, idx_out, score_out, ws, ws_bytes, stream);
+}
+
+namespace {
+
+constexpr int ET = 256;                 // columns of one workgroup of made_eligibility: one per thread, 2 words of 32 per wave
+constexpr int E_BLOCKS = 2048;          // workgroups aimed at: the rows are dealt over as many as the column tiles leave room for
+
+// Workgroup (x, y): columns [256 x, 256 x + 256), rows y, y + gridDim.y, ...  A thread keeps its column's attributes in registers
+// for every row; a row's constraints are uniform loads.  A wave's 64 tests of a row are one ballot = two words of bits_out; the
+// OR over the workgroup's rows stays in registers and costs one atomicOr per word at the end.
+__global__ __launch_bounds__(ET) void eligibility_kernel(const int64_t* col_tags, const float* col_length, const int32_t* col_key,
+                                                         const int64_t* row_all, const int64_t* row_any, const int64_t* row_forbid,
+                                                         const float* row_min, const float* row_max, const int32_t* ex_start,
+                                                         const int32_t* ex_keys, int n_ex, int Nv, int Nm, uint32_t* bits_out,
+                                                         int64_t ld_words, uint32_t* col_any_out) {
+    const int c = blockIdx.x * ET + threadIdx.x;
+    const bool there = c < Nm;
+    const int lane = threadIdx.x & 63;
+    const uint64_t tags = there && col_tags ? (uint64_t)col_tags[c] : 0ull;
+    const float len = there && col_length ? col_length[c] : 0.f;
+    const int key = there && col_key ? col_key[c] : 0;
+    const int word = (blockIdx.x * ET + (threadIdx.x & ~63)) / 32 + (lane >> 5);      // the word lanes 0 and 32 of this wave write
+    const bool writer = (lane & 31) == 0 && word < (Nm + 31) / 32;
+    unsigned long long any = 0ull;
+    for (int i = blockIdx.y; i < Nv; i += gridDim.y) {
+        bool ok = there;
+        if (col_tags) {
+            const uint64_t all = row_all ? (uint64_t)row_all[i] : 0ull;
+            const uint64_t some = row_any ? (uint64_t)row_any[i] : 0ull;
+            const uint64_t none = row_forbid ? (uint64_t)row_forbid[i] : 0ull;
+            ok = ok && (tags & all) == all && (some == 0ull || (tags & some) != 0ull) && (tags & none) == 0ull;
+        }
+        if (row_min) ok = ok && len >= row_min[i];               // (a NaN length fails a bound that is tested)
+        if (row_max) ok = ok && len <= row_max[i];
+        if (ex_start) {
+            int a = min(max(ex_start[i], 0), n_ex);              // uniform: an empty list costs nothing more
+            const int end = min(max(ex_start[i + 1], a), n_ex);
+            if (a < end && ok) {
+                int b = end;
+                while (a < b) {                                  // first position whose key is >= key
+                    const int m = a + ((b - a) >> 1);
+                    if (ex_keys[m] < key) a = m + 1; else b = m;
+                }
+                ok = !(a < end && ex_keys[a] == key);
+            }
+        }
+        const unsigned long long bal = __ballot(ok);
+        any |= bal;
+        if (bits_out && writer) bits_out[(int64_t)i * ld_words + word] = (uint32_t)(bal >> (lane & 32));
+    }
+    if (col_any_out && writer) {
+        const uint32_t wd = (uint32_t)(any >> (lane & 32));
+        if (wd) atomicOr(&col_any_out[word], wd);
+    }
+}
+
+}  // namespace
+
+extern "C" int made_eligibility(const int64_t* col_tags, const float* col_length, const int32_t* col_key, const int64_t* row_all,
+                                const int64_t* row_any, const int64_t* row_forbid, const float* row_min, const float* row_max,
+                                const int32_t* ex_start, const int32_t* ex_keys, int64_t n_ex_keys, int64_t Nv, int64_t Nm,
+                                uint32_t* bits_out, int64_t ld_words, uint32_t* col_any_out, void* stream) {
+    MADE_REQUIRE(Nv >= 0 && Nm > 0 && Nv < (1LL << 31) && Nm < (1LL << 31) - 256, "made_eligibility: bad dims (0 <= Nv < 2^31, 0 < Nm < 2^31 - 256)");
+    MADE_REQUIRE(bits_out || col_any_out, "made_eligibility: no output (bits_out and col_any_out are both null)");
+    MADE_REQUIRE(!bits_out || ld_words >= (Nm + 31) / 32, "made_eligibility: ld_words must be >= ceil(Nm / 32)");
+    MADE_REQUIRE(col_length || (!row_min && !row_max), "made_eligibility: a length bound (row_min / row_max) needs col_length");
+    MADE_REQUIRE(col_key || !ex_start, "made_eligibility: exclusion lists (ex_start) need col_key");
+    MADE_REQUIRE(col_tags || (!row_all && !row_any && !row_forbid), "made_eligibility: a tag pattern (row_all / row_any / row_forbid) needs col_tags");
+    MADE_REQUIRE(!ex_start || (n_ex_keys >= 0 && n_ex_keys < (1LL << 31) && (ex_keys || n_ex_keys == 0)),
+                 "made_eligibility: ex_start needs ex_keys [n_ex_keys], 0 <= n_ex_keys < 2^31");
+    if (Nv == 0) return MADE_OK;
+    const int64_t tiles = (Nm + ET - 1) / ET;
+    const int64_t ny = max((int64_t)1, min(min(Nv, (int64_t)65535), E_BLOCKS / tiles));
+    hipLaunchKernelGGL(eligibility_kernel, dim3((unsigned)tiles, (unsigned)ny), dim3(ET), 0, (hipStream_t)stream, col_tags, col_length,
+                       col_key, row_all, row_any, row_forbid, row_min, row_max, ex_start, ex_keys, (int)(ex_start ? n_ex_keys : 0), (int)Nv,
+                       (int)Nm, bits_out, ld_words, col_any_out);
+    return made_check_launch("made_eligibility");
 }
 
 extern "C" int made_topk_merge(const int32_t* a_col, const float* a_score, int64_t Ka, const int32_t* b_col, const float* b_score,

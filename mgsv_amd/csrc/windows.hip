@@ -1,6 +1,6 @@
 // Windows: grounding in tracks longer than max_m_duration through overlapping windows (mgsv_amd/windows.py, grounding.py).  The
 // unique AST feature rows spread over the windows that share them (made_gather_rows), the best w windows of every selected track
-// (made_group_topw) and the windows' moments merged on the track's own time axis (made_merge_moments).  The reference has no
+// (made_group_topw; made_group_topw_masked under made_eligibility's bits) and the windows' moments merged on the track's own time axis (made_merge_moments).  The reference has no
 // counterpart: its dataset is cut to max_m_duration (dataloaders/dataloader_MGSV_EC_rawdata.py:95-158).
 // Compiled with -ffp-contract=off (csrc/Makefile): made_merge_moments' f32 arithmetic is one rounding per operation, so that a
 // numpy f32 restatement is bit-exact.
@@ -36,14 +36,18 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
 }
 
 // One wave per (video, selected group): w rounds, each taking the largest (score key, lowest column) of the group's members that
-// lies strictly below the previous round's pick -- the members come from the CSR, the row is never scanned.
-__global__ __launch_bounds__(256) void group_topw_kernel(const float* sims, int64_t ld, const int32_t* sel, const int32_t* col_group,
+// lies strictly below the previous round's pick -- the members come from the CSR, the row is never scanned.  MASKED: a member whose
+// bit of mask [row, mask_ld words] (made_eligibility's layout) is clear is skipped: it fills no slot.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void group_topw_kernel(const float* sims, int64_t ld, const uint32_t* mask, int64_t mask_ld,
+                                                         const int32_t* sel, const int32_t* col_group,
                                                          const int32_t* start, const int32_t* cols, int n_cols, int64_t NK, int K, int Nm,
                                                          int G, int w, int32_t* idx_out, float* score_out) {
     const int64_t e = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (e >= NK) return;
     const int lane = threadIdx.x & 63;
     const float* s = sims + (e / K) * ld;
+    const uint32_t* mb = MASKED ? mask + (e / K) * mask_ld : nullptr;
     const int c0 = sel[e];
     int a = 0, b = 0;
     if (c0 >= 0 && c0 < Nm) {
@@ -59,6 +63,9 @@ __global__ __launch_bounds__(256) void group_topw_kernel(const float* sims, int6
         for (int i = a + lane; i < b; i += 64) {
             const int c = cols[i];
             if ((unsigned)c >= (unsigned)Nm) continue;
+            if constexpr (MASKED) {
+                if (!((mb[c >> 5] >> (c & 31)) & 1u)) continue;
+            }
             const uint64_t v = ((uint64_t)score_key(s[c]) << 32) | (uint32_t)(0x7FFFFFFF - c);
             if (v < bound && v > best) best = v;
         }
@@ -177,18 +184,37 @@ extern "C" int made_gather_rows(const void* src, int64_t U, const int32_t* index
     return made_check_launch("made_gather_rows");
 }
 
-extern "C" int made_group_topw(const float* sims, int64_t ld, const int32_t* sel, const int32_t* col_group, const int32_t* start,
-                               const int32_t* cols, int64_t n_cols, int64_t Nv, int64_t Nm, int64_t n_groups, int64_t K, int64_t w,
-                               int32_t* idx_out, float* score_out, void* stream) {
+namespace {
+
+template <bool MASKED>
+int group_topw_launch(const float* sims, int64_t ld, const uint32_t* bits, int64_t bits_ld, const int32_t* sel, const int32_t* col_group,
+                      const int32_t* start, const int32_t* cols, int64_t n_cols, int64_t Nv, int64_t Nm, int64_t n_groups, int64_t K,
+                      int64_t w, int32_t* idx_out, float* score_out, void* stream) {
     MADE_REQUIRE(sims && sel && col_group && start && cols && idx_out && score_out, "made_group_topw: null pointer");
     MADE_REQUIRE(Nv >= 0 && Nm > 0 && ld >= Nm && Nm < (1LL << 31), "made_group_topw: bad dims (Nv >= 0, Nm > 0, ld >= Nm)");
     MADE_REQUIRE(K >= 1 && n_groups >= 1 && n_groups < (1LL << 31) && n_cols >= 0 && n_cols < (1LL << 31), "made_group_topw: bad dims");
     MADE_REQUIRE(w >= 1 && w <= 16, "made_group_topw: w must lie in [1, 16]");
     MADE_REQUIRE(Nv * K < (1LL << 32), "made_group_topw: too many (video, group) entries");
+    if (MASKED) MADE_REQUIRE(bits_ld >= (Nm + 31) / 32, "made_group_topw_masked: bits_ld must be >= ceil(Nm / 32) words");
     if (Nv == 0) return MADE_OK;
-    hipLaunchKernelGGL(group_topw_kernel, dim3((unsigned)((Nv * K + 3) / 4)), dim3(256), 0, (hipStream_t)stream, sims, ld, sel, col_group,
-                       start, cols, (int)n_cols, Nv * K, (int)K, (int)Nm, (int)n_groups, (int)w, idx_out, score_out);
+    hipLaunchKernelGGL(group_topw_kernel<MASKED>, dim3((unsigned)((Nv * K + 3) / 4)), dim3(256), 0, (hipStream_t)stream, sims, ld, bits,
+                       bits_ld, sel, col_group, start, cols, (int)n_cols, Nv * K, (int)K, (int)Nm, (int)n_groups, (int)w, idx_out, score_out);
     return made_check_launch("made_group_topw");
+}
+
+}  // namespace
+
+extern "C" int made_group_topw(const float* sims, int64_t ld, const int32_t* sel, const int32_t* col_group, const int32_t* start,
+                               const int32_t* cols, int64_t n_cols, int64_t Nv, int64_t Nm, int64_t n_groups, int64_t K, int64_t w,
+                               int32_t* idx_out, float* score_out, void* stream) {
+    return group_topw_launch<false>(sims, ld, nullptr, 0, sel, col_group, start, cols, n_cols, Nv, Nm, n_groups, K, w, idx_out, score_out, stream);
+}
+
+extern "C" int made_group_topw_masked(const float* sims, int64_t ld, const uint32_t* bits, int64_t bits_ld, const int32_t* sel,
+                                      const int32_t* col_group, const int32_t* start, const int32_t* cols, int64_t n_cols, int64_t Nv,
+                                      int64_t Nm, int64_t n_groups, int64_t K, int64_t w, int32_t* idx_out, float* score_out, void* stream) {
+    if (!bits) return group_topw_launch<false>(sims, ld, nullptr, 0, sel, col_group, start, cols, n_cols, Nv, Nm, n_groups, K, w, idx_out, score_out, stream);
+    return group_topw_launch<true>(sims, ld, bits, bits_ld, sel, col_group, start, cols, n_cols, Nv, Nm, n_groups, K, w, idx_out, score_out, stream);
 }
 
 extern "C" int made_merge_moments(const float* cand, const int32_t* win_col, const float* win_score, const float* offset,

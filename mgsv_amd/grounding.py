@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -98,6 +98,162 @@ class Grounding:
         return out
 
 
+# ---------------------------------------------------------------------------------------------- per-video constraints
+class NormalizedConstraints(NamedTuple):
+    """`Constraints.normalized`: one entry per video.  require_all / require_any / forbid int64 [N_v] (the bit patterns), min_length /
+    max_length f32 [N_v] or None (not tested), start int32 [N_v + 1] / keys int32 the exclusion lists as a CSR, ascending and unique
+    inside each row (None / None when there is no list)."""
+    require_all: np.ndarray
+    require_any: np.ndarray
+    forbid: np.ndarray
+    min_length: Optional[np.ndarray]
+    max_length: Optional[np.ndarray]
+    start: Optional[np.ndarray]
+    keys: Optional[np.ndarray]
+
+    @property
+    def uses_tags(self) -> bool:
+        return bool(self.require_all.any() or self.require_any.any() or self.forbid.any())
+
+    @property
+    def uses_length(self) -> bool:
+        return self.min_length is not None or self.max_length is not None
+
+
+def _patterns(x, Nv: int, name: str) -> np.ndarray:
+    """int64 [N_v] holding the 64-bit patterns of ints in [-2^63, 2^64) (bit 63 set = a negative int64)"""
+    if x is None:
+        return np.zeros(Nv, np.int64)
+    if isinstance(x, Tensor):
+        x = x.cpu().numpy()
+    if isinstance(x, np.ndarray) and x.dtype == np.uint64:
+        x = x.view(np.int64)
+    vals = [x] * Nv if np.ndim(x) == 0 else list(x)
+    if len(vals) != Nv:
+        raise ValueError(f"{name} needs one entry per video ({Nv}), got {len(vals)}")
+    out = np.empty(Nv, np.uint64)
+    for i, v in enumerate(vals):
+        v = int(v)
+        if not -(1 << 63) <= v < (1 << 64):
+            raise ValueError(f"{name}[{i}] = {v}: not a 64-bit pattern")
+        out[i] = v & 0xFFFFFFFFFFFFFFFF
+    return out.view(np.int64)
+
+
+def tag_array(tags) -> np.ndarray:
+    """int64 [n]: the tracks' tag patterns from an int64 / uint64 array or tensor, or a sequence of ints in [-2^63, 2^64)"""
+    if isinstance(tags, Tensor):
+        tags = tags.cpu().numpy()
+    a = tags if isinstance(tags, np.ndarray) else None
+    if a is not None and a.dtype in (np.int64, np.uint64):
+        return np.ascontiguousarray(a.reshape(-1)).view(np.int64)
+    vals = list(np.asarray(tags, dtype=object).reshape(-1))
+    return _patterns(vals, len(vals), "tags")
+
+
+def _seconds(x, Nv: int, name: str) -> Optional[np.ndarray]:
+    if x is None:
+        return None
+    if isinstance(x, Tensor):
+        x = x.cpu().numpy()
+    a = np.asarray(x, dtype=np.float32)
+    if a.ndim == 0:
+        return np.full(Nv, a, np.float32)
+    if a.shape != (Nv,):
+        raise ValueError(f"{name} needs one entry per video ({Nv}), got shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+@dataclass
+class Constraints:
+    """What each video may be grounded in.  Every field is None (no test), a scalar (every video), or one entry per video.
+    require_all / require_any / forbid: ints, bit patterns over a track's 64 tag bits -- a track is eligible when it carries every
+    bit of require_all, at least one of require_any (if any is asked for) and none of forbid.  min_length / max_length: seconds,
+    inclusive bounds on the track's length.  exclude: one sequence of track indices per video (`Grounding.track`'s numbering);
+    indices that exist nowhere and duplicates are harmless."""
+    require_all: object = None
+    require_any: object = None
+    forbid: object = None
+    min_length: object = None
+    max_length: object = None
+    exclude: Optional[Sequence] = None
+
+    def normalized(self, Nv: int) -> NormalizedConstraints:
+        start = keys = None
+        if self.exclude is not None:
+            rows = list(self.exclude)
+            if len(rows) != Nv:
+                raise ValueError(f"exclude needs one sequence of track indices per video ({Nv}), got {len(rows)}")
+            lists = []
+            for i, r in enumerate(rows):
+                a = np.asarray(r.cpu() if isinstance(r, Tensor) else ([] if r is None else r), dtype=np.int64).reshape(-1)
+                a = np.unique(a)                                   # ascending, duplicates dropped
+                lists.append(a[(a >= -(1 << 31)) & (a < (1 << 31))].astype(np.int32))      # (no track has another index)
+            start = np.zeros(Nv + 1, np.int64)
+            np.cumsum([len(a) for a in lists], out=start[1:])
+            if start[-1] >= (1 << 31):
+                raise ValueError("the exclusion lists hold 2^31 entries or more")
+            start = start.astype(np.int32)
+            keys = np.concatenate(lists).astype(np.int32) if lists else np.zeros(0, np.int32)
+        return NormalizedConstraints(_patterns(self.require_all, Nv, "require_all"), _patterns(self.require_any, Nv, "require_any"),
+                                     _patterns(self.forbid, Nv, "forbid"), _seconds(self.min_length, Nv, "min_length"),
+                                     _seconds(self.max_length, Nv, "max_length"), start, keys)
+
+
+def default_length(duration, windows: Optional[Windows]) -> Optional[np.ndarray]:
+    """A track's length when none is given, f32 [tracks]: the column's duration without windows; with windows the maximum over the
+    track's windows of float64(offset) + float64(duration), rounded once to f32 (NaN for a track without a window).  None when
+    there is neither."""
+    if windows is not None:
+        end = windows.offset.astype(np.float64) + windows.duration.astype(np.float64)
+        out = np.full(windows.n_tracks, -np.inf, np.float64)
+        np.maximum.at(out, windows.track, end)
+        out[np.isneginf(out)] = np.nan
+        return out.astype(np.float32)
+    if duration is None:
+        return None
+    if isinstance(duration, Tensor):
+        duration = duration.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(duration, dtype=np.float32).reshape(-1))
+
+
+def track_attributes(nc: NormalizedConstraints, n_tracks: int, tags, length, duration, windows: Optional[Windows]):
+    """(tags int64 [tracks] or None, length f32 [tracks] or None): the attributes the constraints `nc` test, validated; an attribute
+    nothing tests is None.  ValueError when tags are tested and none were given, or a length bound is asked for and there is
+    neither a length nor a duration."""
+    t = l = None
+    if nc.uses_tags:
+        if tags is None:
+            raise ValueError("the constraints test tags, but the tracks have none (tags=...)")
+        t = tag_array(tags)
+        if t.size != n_tracks:
+            raise ValueError(f"tags needs one entry per track ({n_tracks}), got {t.size}")
+    if nc.uses_length:
+        l = default_length(duration, windows) if length is None else np.ascontiguousarray(
+            (length.cpu().numpy() if isinstance(length, Tensor) else np.asarray(length)).astype(np.float32).reshape(-1))
+        if l is None:
+            raise ValueError("a length bound needs the tracks' length: pass length=..., or durations")
+        if l.size != n_tracks:
+            raise ValueError(f"length needs one entry per track ({n_tracks}), got {l.size}")
+    return t, l
+
+
+class _RowConstraints:
+    """the per-video side of made_eligibility on the device"""
+
+    def __init__(self, nc: NormalizedConstraints, dev):
+        up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        tags = nc.uses_tags
+        self.all, self.any, self.forbid = (up(a) if tags else None for a in (nc.require_all, nc.require_any, nc.forbid))
+        self.min, self.max = up(nc.min_length), up(nc.max_length)
+        self.start, self.keys = up(nc.start), up(nc.keys)
+
+    def bits(self, Nv: int, Nm: int, col_tags, col_length, col_key, bits=True, col_any=None, device=None):
+        return ops.eligibility(Nv, Nm, col_tags if self.all is not None else None, col_length if self.min is not None or self.max is not None else None,
+                               col_key if self.start is not None else None, self.all, self.any, self.forbid, self.min, self.max,
+                               self.start, self.keys, bits=bits, col_any=col_any, device=device)
+
+
 def similarity_matrix(engine: MadeEngine, video: Tensor, seg: Tensor, seg_mask: Tensor, music: Tensor, out: Optional[Tensor] = None,
                       single_out: Optional[Tensor] = None) -> Tensor:
     """[N_v, N_m] f32 similarities by the configuration's vmr loss, the branch the evaluation ranks with (reference
@@ -127,8 +283,11 @@ def _group_tensor(group_id, Nm: int, dev):
 @torch.no_grad()
 def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Optional[Tensor] = None, group_id=None,
            pair_batch: int = 64, windows: Optional[Windows] = None, windows_per_track: int = 1, moments: int = 1,
-           nms_iou: float = 0.5) -> Grounding:
+           nms_iou: float = 0.5, constraints: Optional[Constraints] = None, tags=None, length=None) -> Grounding:
     """Each video's best k tracks (groups of columns sharing a music id when group_id [N_m] is given) and the moment in each.
+    constraints: per-video `Constraints` on the tracks' `tags` (int64 [tracks]) and `length` (f32 seconds [tracks]; default: the
+    durations) -- the selection then runs on every row with its ineligible columns removed (made_eligibility, then the masked
+    kernels): an ineligible column gives no group its score, represents none and fills no window slot.
     windows: the columns of `music` are windows of tracks (music.duration = the windows' durations, group_id one entry per TRACK):
     each track's best `windows_per_track` windows are localized and their queries merged into up to `moments` moments per track on
     the track's time axis, a candidate being dropped when its IoU with a better one kept exceeds nms_iou."""
@@ -139,12 +298,21 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     sims = sims.to(dev, torch.float32)
     if sims.stride(1) != 1:
         sims = sims.contiguous()
+    bits = None
+    if constraints is not None:
+        nc = constraints.normalized(Nv)
+        n_tracks = windows.n_tracks if windows is not None else Nm
+        t, l = track_attributes(nc, n_tracks, tags, length, music.duration, windows)
+        col = (lambda a: a) if windows is None else (lambda a: a[windows.track])      # track attributes -> columns
+        up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(col(a), dtype=dt)).to(dev)
+        key = np.arange(Nm, dtype=np.int32) if windows is None else windows.track.astype(np.int32)
+        bits = _RowConstraints(nc, dev).bits(Nv, Nm, up(t, np.int64), up(l, np.float32), torch.from_numpy(key).to(dev), device=dev)
     if windows is not None:
         return _ground_windows(engine, videos, music, k, sims, group_id, pair_batch, windows, int(windows_per_track), int(moments),
-                               float(nms_iou))
+                               float(nms_iou), bits)
     gid, G = _group_tensor(group_id, Nm, dev)
     kk = max(1, min(int(k), G))
-    track, score = ops.topk_groups(sims, kk, gid, G)
+    track, score = ops.topk_groups(sims, kk, gid, G) if bits is None else ops.topk_groups_masked(sims, bits, kk, gid, G)
     vi = torch.arange(Nv, device=dev, dtype=torch.int32).repeat_interleave(kk)
     mi = track.reshape(-1)
     mi = torch.where(mi < 0, torch.zeros_like(mi), mi)             # (no track: localized against track 0, reported as -1 / NaN)
@@ -230,7 +398,7 @@ def _pair_candidates(engine: MadeEngine, videos: Encoded, music: Encoded, vi: Te
 
 
 def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Tensor, group_id, pair_batch: int,
-                    windows: Windows, w: int, n: int, nms_iou: float) -> Grounding:
+                    windows: Windows, w: int, n: int, nms_iou: float, bits: Optional[Tensor] = None) -> Grounding:
     dev = engine.device
     Nv, Nm = len(videos), len(music)
     if len(windows) != Nm:
@@ -250,8 +418,12 @@ def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int,
     as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     gid = as_dev(col_group)
     kk = max(1, min(int(k), G))
-    rep, score = ops.topk_groups(sims, kk, gid, G)                 # a track's score: its best window's similarity
-    wcol, wscore = ops.group_topw(sims, rep, gid, as_dev(start), as_dev(cols), w)
+    if bits is None:
+        rep, score = ops.topk_groups(sims, kk, gid, G)             # a track's score: its best window's similarity
+        wcol, wscore = ops.group_topw(sims, rep, gid, as_dev(start), as_dev(cols), w)
+    else:                                                          # ... its best ELIGIBLE window's
+        rep, score = ops.topk_groups_masked(sims, bits, kk, gid, G)
+        wcol, wscore = ops.group_topw_masked(sims, bits, rep, gid, as_dev(start), as_dev(cols), w)
     vi = torch.arange(Nv, device=dev, dtype=torch.int32).repeat_interleave(kk * w)
     mi = wcol.reshape(-1)
     mi = torch.where(mi < 0, torch.zeros_like(mi), mi)             # (no window: localized against column 0, left out by the merge)
@@ -452,10 +624,178 @@ def _select_streamed(engine: MadeEngine, videos: Encoded, library, kk: int, w: i
     return run
 
 
+def _library_attributes(library, dev, want_tags: bool, want_length: bool):
+    """the library's column attributes (tags int64, length f32, track int32; [N] each, None where not wanted) on the device,
+    uploaded once per device"""
+    key = (str(dev), bool(want_tags), bool(want_length))
+    if key not in library._device_attrs:
+        up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        library._device_attrs[key] = tuple(up(a) for a in library.column_attributes(want_tags, want_length))
+    return library._device_attrs[key]
+
+
+def _gather_device(t: Tensor, idx32: Tensor, idx64: Tensor) -> Tensor:
+    """t[idx] along dim 0 on the device: made_gather_rows where its alignment rule holds, index_select otherwise"""
+    n = idx32.numel()
+    flat = t.reshape(t.shape[0], -1) if t.is_contiguous() else None
+    if flat is not None and t.dtype in (torch.float32, torch.bfloat16) and (flat.shape[1] * t.element_size()) % 16 == 0 \
+            and t.data_ptr() % 16 == 0:
+        out = torch.empty((n,) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype)
+        if out.data_ptr() % 16 == 0:
+            ops.gather_rows(flat, idx32, out.view(n, -1))
+            return out
+    return t.index_select(0, idx64)
+
+
+def _kept_columns(library, col_any: Tensor) -> np.ndarray:
+    """bool [N]: the columns of the KEPT groups -- those with at least one column in made_eligibility's col_any (eligible for some
+    video).  Dropping the other groups changes no row."""
+    N = len(library)
+    words = np.ascontiguousarray(col_any.cpu().numpy()).view(np.uint32)
+    some = np.unpackbits(words.astype("<u4").view(np.uint8), bitorder="little")[:N].astype(bool)
+    rs = library._run_start
+    return np.repeat(np.logical_or.reduceat(some, rs[:-1]), np.diff(rs))
+
+
+def _select_constrained(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, chunk_cols: int, sims_fn, timings: Optional[dict],
+                        constraints: Constraints, compact: Optional[bool]):
+    """`_select_streamed` under per-video constraints: what made_topk_groups_masked + made_group_topw_masked give on the whole
+    similarity matrix under made_eligibility's bits.  A union pass over all columns names the kept groups; with compact False the
+    chunk plan is walked and chunks without a kept column are skipped, with compact True a restricted plan holds the kept groups
+    only and every chunk is gathered by its list of library columns (a pinned library then takes the staging copy)."""
+    from .library import restricted_plan
+    dev = engine.device
+    Nv, N = len(videos), len(library)
+    nc = constraints.normalized(Nv)
+    rc = _RowConstraints(nc, dev)
+    col_tags, col_length, col_key = _library_attributes(library, dev, nc.uses_tags, nc.uses_length)
+    cur = torch.cuda.current_stream()
+    tu = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timings is not None else None
+    if tu:
+        tu[0].record(cur)
+    col_any = torch.zeros((N + 31) // 32, device=dev, dtype=torch.int32)
+    rc.bits(Nv, N, col_tags, col_length, col_key, bits=None, col_any=col_any, device=dev)
+    keep = _kept_columns(library, col_any)                         # (one host read: the walk is planned from it)
+    if tu:
+        tu[1].record(cur)
+    n_kept = int(keep.sum())
+    if compact is None:                                            # a hook written for (chunk, c0, c1) keeps working
+        compact = False if sims_fn is not None else 2 * n_kept <= N
+    grouped = library.grouped
+    items = []                                                     # (rows: slice or int64 array, n, gid, n_groups, start, col_offset, cols int32 / int64 on the device)
+    if compact:
+        up = lambda a: torch.from_numpy(a).to(dev)
+        for ch in restricted_plan(library, chunk_cols, keep):
+            c64 = up(ch["cols"])
+            items.append((ch["cols"], len(ch["cols"]), up(ch["gid"]) if grouped else None, ch["n_groups"], up(ch["start"]) if grouped else None,
+                          0, (c64.to(torch.int32), c64)))
+        skipped = 0
+    else:
+        plan = library._plan(chunk_cols)
+        gid_all = start_all = None
+        if grouped:
+            gid_all, start_all, _ = _plan_tables(plan, dev)
+        for i, (c0, c1) in enumerate(plan["chunks"]):
+            if not keep[c0:c1].any():
+                continue
+            ng, s0 = plan["n_groups"][i], plan["start_at"][i]
+            items.append((slice(c0, c1), c1 - c0, gid_all[c0:c1] if grouped else None, ng, start_all[s0:s0 + ng + 1] if grouped else None,
+                          c0, None))
+        skipped = len(plan["chunks"]) - len(items)
+    longest = max((it[1] for it in items), default=1)
+    cols_all = torch.arange(longest, device=dev, dtype=torch.int32)
+    resident = library.on_device
+    stage = None if resident else _staging(library, "chunks", longest, dev, 2)
+    has_dur = library.duration is not None
+    video = videos.vec.to(dev, torch.float32).contiguous()
+    sims_buf = single_buf = None
+    if sims_fn is None:
+        sims_buf = torch.empty(Nv, longest, device=dev, dtype=torch.float32)
+        single_buf = torch.empty(Nv, longest, device=dev, dtype=torch.float32)
+    bits_buf = torch.empty(Nv, (longest + 31) // 32, device=dev, dtype=torch.int32)
+    state = [(torch.empty(Nv, kk, w, device=dev, dtype=torch.int32), torch.empty(Nv, kk, w, device=dev, dtype=torch.float32))
+             for _ in range(2)]
+    run = (torch.empty(Nv, 0, w, device=dev, dtype=torch.int32), torch.empty(Nv, 0, w, device=dev, dtype=torch.float32))
+    marks = []                                                      # (reaches the wait, sims start, sims end, eligibility end, merge end) per chunk
+
+    def chunk_encoded(i: int) -> Encoded:
+        rows, n, cols = items[i][0], items[i][1], items[i][6]
+        arrays = (library.tokens, library.mask, library.vec, library.duration if has_dur else None)
+        if resident:
+            part = [None if a is None else (a[rows] if cols is None else _gather_device(a, cols[0], cols[1])) for a in arrays]
+            return Encoded(tokens=part[0], mask=part[1], vec=part[2], duration=part[3])
+        if library.pinned and cols is None:                         # pinned already: no staging copy for a contiguous chunk
+            return stage.upload(i % 2, n, has_dur, src=[None if a is None else a[rows] for a in
+                                                        (library.tokens, library.mask, library.vec, library.duration)])
+        got = stage.fill(i % 2, library, rows)
+        return stage.upload(i % 2, got, has_dur)
+
+    nxt = chunk_encoded(0) if items else None
+    for i, (rows, n, gid, ng, start, c0, cols) in enumerate(items):
+        chunk = nxt
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timings is not None else None
+        if ev:
+            ev[0].record(cur)
+        if not resident:
+            cur.wait_event(stage.uploaded[i % 2])
+        if ev:
+            ev[1].record(cur)
+        if sims_fn is not None:
+            sims = (sims_fn(chunk, c0, c0 + n) if cols is None else sims_fn(chunk, cols[1], None)).to(dev, torch.float32)
+            if sims.stride(1) != 1:
+                sims = sims.contiguous()
+            assert tuple(sims.shape) == (Nv, n), "sims_fn must return one column per column of the chunk"
+        else:
+            sims = similarity_matrix(engine, video, chunk.tokens, chunk.mask, chunk.vec, out=sims_buf[:, :n], single_out=single_buf[:, :n])
+        if ev:
+            ev[2].record(cur)
+        part = lambda a: None if a is None else (a[rows] if cols is None else a.index_select(0, cols[1]))
+        bits = rc.bits(Nv, n, part(col_tags), part(col_length), part(col_key), bits=bits_buf[:, :(n + 31) // 32], device=dev)
+        if ev:
+            ev[3].record(cur)
+        if grouped:
+            rep, score = ops.topk_groups_masked(sims, bits, kk, gid, ng)
+            if w > 1:
+                bcol, bscore = ops.group_topw_masked(sims, bits, rep, gid, start, cols_all[:n], w)
+            else:
+                bcol, bscore = rep.view(Nv, kk, 1), score.view(Nv, kk, 1)
+        else:
+            rep, score = ops.topk_groups_masked(sims, bits, kk)
+            bcol, bscore = rep.view(Nv, kk, 1), score.view(Nv, kk, 1)
+        if cols is not None:                                        # local -> library columns (ascending lists keep the tie order)
+            bcol = torch.where(bcol < 0, bcol, cols[0][bcol.clamp(min=0).long()]).contiguous()
+        out = state[i % 2]
+        ops.topk_merge(run[0], run[1], bcol, bscore, kk, col_offset=c0, out_col=out[0], out_score=out[1])
+        run = out
+        if not resident:
+            stage.consumed[i % 2].record(cur)
+        if ev:
+            ev[4].record(cur)
+            marks.append(ev)
+        if i + 1 < len(items):
+            nxt = chunk_encoded(i + 1)
+    if not items:                                                   # nothing is eligible for anyone: every slot empty
+        run = ops.topk_merge(run[0], run[1], run[0], run[1], kk)
+    if timings is not None:
+        torch.cuda.synchronize()
+        wait = [max(0.0, e[0].elapsed_time(e[1])) for e in marks]
+        timings["chunks"] = len(items)
+        timings["chunks_skipped"] = skipped
+        timings["columns_scored"] = sum(it[1] for it in items)
+        timings["compact"] = bool(compact)
+        timings["union_ms"] = tu[0].elapsed_time(tu[1])
+        timings["similarities_ms"] = sum(e[1].elapsed_time(e[2]) for e in marks)
+        timings["eligibility_ms"] = sum(e[2].elapsed_time(e[3]) for e in marks)
+        timings["selection_merge_ms"] = sum(e[3].elapsed_time(e[4]) for e in marks)
+        timings["upload_wait_ms"] = sum(wait)
+        timings["upload_wait_max_ms"] = max(wait, default=0.0)
+    return run
+
+
 @torch.no_grad()
 def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_batch: int = 64, windows_per_track: int = 1,
                    moments: int = 1, nms_iou: float = 0.5, chunk_cols: int = 4096, video_batch: int = 1024, sims_fn=None,
-                   timings: Optional[dict] = None) -> Grounding:
+                   timings: Optional[dict] = None, constraints: Optional[Constraints] = None, compact: Optional[bool] = None) -> Grounding:
     """`ground()` for a stored library (mgsv_amd.library.MusicLibrary: host arrays, a memory-mapped directory, or device tensors):
     the same Grounding, bit for bit, as
         ground(engine, videos, library.as_encoded(dev), k, group_id=library.group_id, windows=library.windows, ...)
@@ -465,7 +805,13 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     into the running list; a host library's chunks are uploaded through two pinned staging sets on a copy stream, under the kernels
     of the chunk before.  Localization runs per video_batch videos on the distinct selected columns only.  track: the library
     column without windows, the track's index with windows; `to_records` takes library.ids.  timings: a dict that receives the
-    phases' milliseconds (this synchronises the device; for measurements)."""
+    phases' milliseconds, and columns_scored / chunks_skipped (this synchronises the device; for measurements).
+    constraints: per-video `Constraints` on the library's tags / length and exclusion lists of tracks -- the same Grounding as
+    `ground(..., constraints=constraints, tags=library.tags, length=library.length)`.  Groups in which no video has an eligible
+    column are never uploaded or scored: with compact False the plan's chunks without such a group are skipped; with compact True
+    a plan over the kept groups alone is walked, every chunk gathered by its ascending list of library columns (an explicit hook is
+    then called as sims_fn(chunk, cols, None), cols the int64 device tensor of those columns).  compact None: False with a hook,
+    else True iff the kept columns are at most half of the library."""
     c = engine.cfg
     dev = engine.device
     if c.moment_query_type == "xpool":
@@ -486,7 +832,12 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     kk = max(1, min(int(k), library.n_groups))
     video_batch = max(1, int(video_batch))
     t0 = torch.cuda.Event(enable_timing=True) if timings is not None else None
-    wcol, wscore = _select_streamed(engine, videos, library, kk, w, int(chunk_cols), sims_fn, timings)
+    if constraints is None:
+        wcol, wscore = _select_streamed(engine, videos, library, kk, w, int(chunk_cols), sims_fn, timings)
+        if timings is not None:
+            timings["columns_scored"], timings["chunks_skipped"] = N, 0
+    else:
+        wcol, wscore = _select_constrained(engine, videos, library, kk, w, int(chunk_cols), sims_fn, timings, constraints, compact)
     if t0 is not None:
         t0.record()
     rep, score = wcol[:, :, 0].contiguous(), wscore[:, :, 0].contiguous()

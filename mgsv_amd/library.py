@@ -9,7 +9,8 @@ group contiguous), their directory format, a writer that builds a library batch 
 Directory format (version 1): manifest.json {format, version, dtype, N, S, D, duration, windows, ids, grouped, n_tracks} and .npy
 arrays tokens [N, S, D] (float32, or uint16 holding bf16 bit patterns), mask [N, S] f32, vec [N, D] f32, col_group [N] int32,
 source [N] int64, optionally duration [N] f32, win_track int32 / win_offset f32 / win_duration f32 [N], track_group [n_tracks]
-int32, and ids.json.
+int32, and ids.json.  Optional track attributes for `ground_library(..., constraints=...)`: tags.npy int64 and length.npy f32, one
+entry per track, named by the manifest's "attributes" {tags, length, tag_names}; a manifest without that entry has none.
 """
 from __future__ import annotations
 
@@ -54,6 +55,14 @@ def _host(a, dtype) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+def _tags_host(a) -> np.ndarray:
+    """int64 [n] tag patterns of an int64 / uint64 array (bit 63 = the sign bit)"""
+    a = np.asarray(a.detach().cpu().numpy() if isinstance(a, Tensor) else a)
+    if a.dtype == np.uint64:
+        a = a.view(np.int64)
+    return np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+
+
 def _tokens_tensor(a: np.ndarray, dtype: str) -> Tensor:
     """a host tensor of the compute dtype over (a copy of, if it is not writable) the host array"""
     a = np.ascontiguousarray(a)
@@ -89,7 +98,7 @@ class MusicLibrary:
     `ground_library(engine, videos, lib, k, ...)`."""
 
     def __init__(self, tokens, mask, vec, col_group, source, dtype: str, duration=None, windows: Optional[Windows] = None,
-                 ids: Optional[Sequence] = None, group_id=None):
+                 ids: Optional[Sequence] = None, group_id=None, tags=None, length=None, tag_names: Optional[Sequence[str]] = None):
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"dtype = {dtype!r}: a library holds f32 or bf16 tokens")
         self.tokens, self.mask, self.vec, self.duration = tokens, mask, vec, duration
@@ -113,6 +122,16 @@ class MusicLibrary:
         self._run_start = _runs(self.col_group)
         if len(self._run_start) - 1 != len(np.unique(self.col_group)):
             raise ValueError("the columns of every group must be contiguous (MusicLibrary.build reorders them)")
+        # track attributes (the unit of `Grounding.track` and `ids`: the column without windows, the track with windows)
+        self.tags = None if tags is None else _tags_host(tags)
+        self.length = None if length is None else np.ascontiguousarray(length, dtype=np.float32).reshape(-1)
+        self.tag_names = None if tag_names is None else [str(x) for x in tag_names]
+        for name, a in (("tags", self.tags), ("length", self.length)):
+            if a is not None and len(a) != self.n_tracks:
+                raise ValueError(f"{name} needs one entry per track ({self.n_tracks}), got {len(a)}")
+        if self.tag_names is not None and (len(self.tag_names) > 64 or len(set(self.tag_names)) != len(self.tag_names)):
+            raise ValueError("tag_names: at most 64 distinct names, bit i <-> tag_names[i]")
+        self._device_attrs: Dict[str, tuple] = {}                  # ground_library's column attributes, uploaded once per device
         self._plans: Dict[int, dict] = {}
         self._stages: Dict[str, object] = {}                       # ground_library's pinned staging sets, reused across calls
 
@@ -138,6 +157,45 @@ class MusicLibrary:
         return self.group_id is not None or self.windows is not None
 
     @property
+    def n_tracks(self) -> int:
+        """the tracks `Grounding.track`, `ids`, `tags` and `length` are numbered by: columns without windows"""
+        return int(self.windows.n_tracks) if self.windows is not None else len(self)
+
+    def tag_mask(self, names) -> int:
+        """the bit pattern of the named tags (a name or a sequence of names); KeyError for a name the library does not have"""
+        names = [names] if isinstance(names, str) else list(names)
+        table = {n: i for i, n in enumerate(self.tag_names or [])}
+        out = 0
+        for n in names:
+            if n not in table:
+                raise KeyError(n)
+            out |= 1 << table[n]
+        return out
+
+    def track_length(self) -> Optional[np.ndarray]:
+        """f32 [tracks]: `length`, or by default the column's duration / the end of the track's last window (None: neither)"""
+        if self.length is not None:
+            return self.length
+        from .grounding import default_length
+        return default_length(self.duration, self.windows)
+
+    def column_attributes(self, want_tags: bool, want_length: bool):
+        """(tags int64 [N] or None, length f32 [N] or None, key int32 [N]): the track attributes per column, and every column's
+        track.  ValueError when an attribute is wanted that the library does not have."""
+        key = np.arange(len(self), dtype=np.int32) if self.windows is None else self.windows.track.astype(np.int32)
+        t = l = None
+        if want_tags:
+            if self.tags is None:
+                raise ValueError("the constraints test tags, but the library has none")
+            t = np.ascontiguousarray(self.tags[key])
+        if want_length:
+            l = self.track_length()
+            if l is None:
+                raise ValueError("a length bound needs the tracks' length: the library has neither length nor durations")
+            l = np.ascontiguousarray(l[key])
+        return t, l, key
+
+    @property
     def n_groups(self) -> int:
         """the number `ground()` clamps k to: the largest group id + 1 (ids that no column has count)"""
         if self.windows is not None and self.group_id is None:
@@ -148,11 +206,12 @@ class MusicLibrary:
 
     # ------------------------------------------------------------------ construction
     @classmethod
-    def build(cls, music: Encoded, group_id=None, windows: Optional[Windows] = None, ids: Optional[Sequence] = None) -> "MusicLibrary":
+    def build(cls, music: Encoded, group_id=None, windows: Optional[Windows] = None, ids: Optional[Sequence] = None, tags=None,
+              length=None, tag_names: Optional[Sequence[str]] = None) -> "MusicLibrary":
         """A host library of an `Encoded` (device or host tensors).  group_id: one entry per column, or per TRACK with windows.
         Columns are reordered only if a group's columns are not contiguous: groups by first appearance, stable inside a group.
         The Windows keep their track numbering; only the per-column arrays are permuted (and `ids`, one per column, without
-        windows)."""
+        windows).  tags (int64) / length (f32 seconds): one entry per track, permuted like `ids`."""
         N = len(music)
         gid = None if group_id is None else _host(group_id, np.int32).reshape(-1)
         if windows is not None:
@@ -175,12 +234,21 @@ class MusicLibrary:
         if windows is not None and not same:
             win = Windows(track=windows.track[order], offset=windows.offset[order], duration=windows.duration[order],
                           n_tracks=windows.n_tracks, n_encoded=windows.n_encoded)
+        from .grounding import tag_array
+        tags = None if tags is None else tag_array(tags)
+        length = None if length is None else _host(length, np.float32).reshape(-1)
+        for name, a in (("tags", tags), ("length", length)):
+            if a is not None and len(a) != (windows.n_tracks if windows is not None else N):
+                raise ValueError(f"{name} needs one entry per track")
         if windows is None:
             if ids is not None and not same:
                 ids = [ids[i] for i in order]
             gid = None if gid is None else take(gid)
+            tags = None if tags is None else take(tags)
+            length = None if length is None else take(length)
         return cls(take(_tokens_to_host(music.tokens)), take(_host(music.mask, np.float32)), take(_host(music.vec, np.float32)),
-                   take(col_group), order, _dtype_name(music.tokens.dtype), duration=dur, windows=win, ids=ids, group_id=gid)
+                   take(col_group), order, _dtype_name(music.tokens.dtype), duration=dur, windows=win, ids=ids, group_id=gid,
+                   tags=tags, length=length, tag_names=tag_names)
 
     def to(self, device) -> "MusicLibrary":
         """The same library with tokens / mask / vec / duration as tensors on `device` (the host tables stay on the host)."""
@@ -189,7 +257,7 @@ class MusicLibrary:
         tok = self.tokens.to(dev) if isinstance(self.tokens, Tensor) else _tokens_tensor(self.tokens, self.dtype).to(dev)
         return MusicLibrary(tok, up(self.mask), up(self.vec), self.col_group, self.source, self.dtype,
                             duration=None if self.duration is None else up(self.duration), windows=self.windows, ids=self.ids,
-                            group_id=self.group_id)
+                            group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names)
 
     def pin(self) -> "MusicLibrary":
         """The same library with tokens / mask / vec / duration copied into pinned host tensors: `ground_library` uploads its
@@ -198,7 +266,7 @@ class MusicLibrary:
         tok = self.tokens.cpu() if isinstance(self.tokens, Tensor) else _tokens_tensor(self.tokens, self.dtype)
         return MusicLibrary(tok.pin_memory(), pin(self.mask), pin(self.vec), self.col_group, self.source, self.dtype,
                             duration=None if self.duration is None else pin(self.duration), windows=self.windows, ids=self.ids,
-                            group_id=self.group_id)
+                            group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names)
 
     @property
     def pinned(self) -> bool:
@@ -234,7 +302,7 @@ class MusicLibrary:
             sv("duration", self.duration)
         _write_tables(path, self.windows, self.group_id, self.ids)
         _write_manifest(path, self.dtype, len(self), self.S, self.D, self.duration is not None, self.windows, self.ids is not None,
-                        self.group_id is not None)
+                        self.group_id is not None, _write_attributes(path, self.tags, self.length, self.tag_names))
 
     @classmethod
     def load(cls, path: str, mmap: bool = True) -> "MusicLibrary":
@@ -261,8 +329,11 @@ class MusicLibrary:
         if man["ids"]:
             with open(os.path.join(path, "ids.json")) as f:
                 ids = json.load(f)
+        attr = man.get("attributes") or {}
         return cls(tokens, mask, vec, col_group, np.load(os.path.join(path, "source.npy")), man["dtype"],
-                   duration=ld("duration") if man["duration"] else None, windows=windows, ids=ids, group_id=group_id)
+                   duration=ld("duration") if man["duration"] else None, windows=windows, ids=ids, group_id=group_id,
+                   tags=np.load(os.path.join(path, "tags.npy")) if attr.get("tags") else None,
+                   length=np.load(os.path.join(path, "length.npy")) if attr.get("length") else None, tag_names=attr.get("tag_names"))
 
     # ------------------------------------------------------------------ the chunk plan
     def chunk_plan(self, chunk_cols: int) -> List[Tuple[int, int]]:
@@ -308,6 +379,45 @@ class MusicLibrary:
         return plan
 
 
+def restricted_plan(library: MusicLibrary, chunk_cols: int, keep: np.ndarray) -> List[dict]:
+    """The chunk plan over the KEPT groups only -- those with at least one column in keep (bool [N]) -- for one constrained call
+    (nothing is cached).  Chunks of at most chunk_cols columns of whole kept groups, in library order; per chunk: cols int64
+    (ascending library columns), gid int32 (every column's group, dense inside the chunk), start int32 (the groups' CSR starts;
+    the column list is 0, 1, 2, ...), n_groups.  ValueError for a kept group of more than chunk_cols columns, and for a chunk_cols
+    the full plan refuses."""
+    chunk_cols = int(chunk_cols)
+    if chunk_cols < 1:
+        raise ValueError(f"chunk_cols = {chunk_cols}: must be >= 1")
+    if chunk_cols > (MAX_GROUPED_CHUNK if library.grouped else MAX_CHUNK):
+        raise ValueError(f"chunk_cols = {chunk_cols}: at most {MAX_GROUPED_CHUNK} columns per chunk when columns are selected by "
+                         f"group (one LDS slot per group), {MAX_CHUNK} otherwise")
+    rs = library._run_start
+    keep = np.asarray(keep, dtype=bool).reshape(-1)
+    if len(keep) != len(library):
+        raise ValueError("keep needs one entry per column")
+    if len(rs) < 2:
+        return []
+    kept_runs = np.flatnonzero(np.logical_or.reduceat(keep, rs[:-1]))
+    sizes = (rs[kept_runs + 1] - rs[kept_runs]).astype(np.int64)
+    big = np.flatnonzero(sizes > chunk_cols)
+    if len(big):
+        r = int(kept_runs[big[0]])
+        raise ValueError(f"group {int(library.col_group[rs[r]])} has {int(sizes[big[0]])} columns, more than chunk_cols = {chunk_cols}")
+    out = []
+    i = 0
+    ends = np.cumsum(sizes)
+    while i < len(kept_runs):
+        base = int(ends[i - 1]) if i else 0
+        j = int(np.searchsorted(ends, base + chunk_cols, side="right"))             # kept runs i .. j-1 fit
+        runs, sz = kept_runs[i:j], sizes[i:j]
+        start = np.concatenate([[0], np.cumsum(sz)])
+        cols = np.repeat(rs[runs] - start[:-1], sz) + np.arange(start[-1])
+        out.append(dict(cols=cols.astype(np.int64), gid=np.repeat(np.arange(len(runs)), sz).astype(np.int32),
+                        start=start.astype(np.int32), n_groups=len(runs)))
+        i = j
+    return out
+
+
 def _write_tables(path: str, windows: Optional[Windows], group_id, ids) -> None:
     if windows is not None:
         np.save(os.path.join(path, "win_track.npy"), windows.track)
@@ -320,11 +430,24 @@ def _write_tables(path: str, windows: Optional[Windows], group_id, ids) -> None:
             json.dump(list(ids), f)
 
 
+def _write_attributes(path: str, tags, length, tag_names) -> Optional[dict]:
+    """tags.npy / length.npy and the manifest's "attributes" entry (None, and no entry, for a library without attributes)"""
+    if tags is None and length is None and tag_names is None:
+        return None
+    if tags is not None:
+        np.save(os.path.join(path, "tags.npy"), np.ascontiguousarray(tags, dtype=np.int64))
+    if length is not None:
+        np.save(os.path.join(path, "length.npy"), np.ascontiguousarray(length, dtype=np.float32))
+    return dict(tags=tags is not None, length=length is not None, tag_names=None if tag_names is None else list(tag_names))
+
+
 def _write_manifest(path: str, dtype: str, N: int, S: int, D: int, duration: bool, windows: Optional[Windows], ids: bool,
-                    grouped: bool) -> None:
+                    grouped: bool, attributes: Optional[dict] = None) -> None:
     man = dict(format=FORMAT, version=VERSION, dtype=dtype, N=int(N), S=int(S), D=int(D), duration=bool(duration),
                windows=windows is not None, ids=bool(ids), grouped=bool(grouped),
                n_tracks=int(windows.n_tracks) if windows is not None else None)
+    if attributes is not None:
+        man["attributes"] = attributes
     with open(os.path.join(path, "manifest.json"), "w") as f:
         json.dump(man, f, indent=1)
         f.write("\n")
@@ -344,9 +467,10 @@ class MusicLibraryWriter:
         add(music, col_group, duration=None, windows_rows=None, ids=None)
     col_group [n]: the group of every added column, contiguous inside the batch, none seen in an earlier add.  windows_rows: a
     `Windows` (or a (track, offset, duration) triple) for the added columns with the LIBRARY's track numbers -- then ids holds one
-    entry per new track, else one per column.  duration defaults to music.duration."""
+    entry per new track, else one per column; tags (int64) / length (f32 seconds) go like ids, one entry per new track, and every
+    add carries them or none does.  duration defaults to music.duration.  tag_names: the library's names of the tag bits."""
 
-    def __init__(self, path: str, S: int, D: int, dtype: str):
+    def __init__(self, path: str, S: int, D: int, dtype: str, tag_names: Optional[Sequence[str]] = None):
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"dtype = {dtype!r}: a library holds f32 or bf16 tokens")
         self.path, self.S, self.D, self.dtype = path, int(S), int(D), dtype
@@ -363,9 +487,15 @@ class MusicLibraryWriter:
         self._duration: List[np.ndarray] = []
         self._win: List[Tuple[np.ndarray, np.ndarray, np.ndarray]] = []
         self._ids: Optional[list] = None
+        self._tags: List[np.ndarray] = []
+        self._length: List[np.ndarray] = []
+        self._tag_names = None if tag_names is None else [str(x) for x in tag_names]
+        if self._tag_names is not None and (len(self._tag_names) > 64 or len(set(self._tag_names)) != len(self._tag_names)):
+            raise ValueError("tag_names: at most 64 distinct names, bit i <-> tag_names[i]")
         self._closed = False
 
-    def add(self, music: Encoded, col_group, duration=None, windows_rows=None, ids: Optional[Sequence] = None) -> None:
+    def add(self, music: Encoded, col_group, duration=None, windows_rows=None, ids: Optional[Sequence] = None, tags=None,
+            length=None) -> None:
         if self._closed:
             raise ValueError("the writer is closed")
         n = len(music)
@@ -391,6 +521,17 @@ class MusicLibraryWriter:
             raise ValueError("either every add carries windows or none does")
         if (ids is None) != (self._ids is None) and self.N:
             raise ValueError("either every add carries ids or none does")
+        if ((tags is None) != (not self._tags) or (length is None) != (not self._length)) and self.N:
+            raise ValueError("either every add carries tags / length or none does")
+        if tags is not None:
+            from .grounding import tag_array
+            tags = tag_array(tags)
+        if length is not None:
+            length = _host(length, np.float32).reshape(-1)
+        if windows_rows is None:
+            for name, a in (("tags", tags), ("length", length)):
+                if a is not None and len(a) != n:
+                    raise ValueError(f"{name} needs one entry per added column")
         if windows_rows is not None:
             tr, off, dur = ((windows_rows.track, windows_rows.offset, windows_rows.duration) if isinstance(windows_rows, Windows)
                             else windows_rows)
@@ -410,6 +551,10 @@ class MusicLibraryWriter:
             self._duration.append(_host(duration, np.float32).reshape(-1))
         if ids is not None:
             self._ids = (self._ids or []) + list(ids)
+        if tags is not None:
+            self._tags.append(tags)
+        if length is not None:
+            self._length.append(length)
         self.N += n
 
     def close(self) -> MusicLibrary:
@@ -437,6 +582,13 @@ class MusicLibraryWriter:
                 raise ValueError("the windows of one track were given different groups")
         if self._ids is not None and len(self._ids) != (windows.n_tracks if windows is not None else self.N):
             raise ValueError("ids needs one entry per track")
+        n_tracks = windows.n_tracks if windows is not None else self.N
+        tags = cat(self._tags, np.int64) if self._tags else None
+        length = cat(self._length, np.float32) if self._length else None
+        for name, a in (("tags", tags), ("length", length)):
+            if a is not None and len(a) != n_tracks:
+                raise ValueError(f"{name} needs one entry per track ({n_tracks}), got {len(a)}")
         _write_tables(self.path, windows, track_group, self._ids)
-        _write_manifest(self.path, self.dtype, self.N, self.S, self.D, bool(self._duration), windows, self._ids is not None, True)
+        _write_manifest(self.path, self.dtype, self.N, self.S, self.D, bool(self._duration), windows, self._ids is not None, True,
+                        _write_attributes(self.path, tags, length, self._tag_names))
         return MusicLibrary.load(self.path, mmap=True)

@@ -875,6 +875,70 @@ def topk_groups(sims: Tensor, K: int, group_id: Optional[Tensor] = None, n_group
     return idx, score
 
 
+def eligibility(Nv: int, Nm: int, col_tags: Optional[Tensor] = None, col_length: Optional[Tensor] = None, col_key: Optional[Tensor] = None,
+                row_all: Optional[Tensor] = None, row_any: Optional[Tensor] = None, row_forbid: Optional[Tensor] = None,
+                row_min: Optional[Tensor] = None, row_max: Optional[Tensor] = None, ex_start: Optional[Tensor] = None,
+                ex_keys: Optional[Tensor] = None, bits: object = True, col_any: Optional[Tensor] = None, device=None):
+    """made_eligibility: per-video constraints (row_* [Nv], the exclusion CSR ex_start [Nv + 1] / ex_keys) tested on per-column
+    attributes (col_tags int64, col_length f32, col_key int32, [Nm] each; None: that test is off) -> bits uint32
+    [Nv, ceil(Nm / 32)], column c = bit c & 31 of word c >> 5.  bits: True allocates, a tensor [Nv, >= ceil(Nm / 32)] is written in
+    place, None leaves the matrix out (the union pass).  col_any uint32 [ceil(Nm / 32)], zeroed by the caller, receives the OR over
+    the rows.  Returns bits (or None)."""
+    words = (Nm + 31) // 32
+    for t, dt, n in ((col_tags, torch.int64, Nm), (col_length, torch.float32, Nm), (col_key, torch.int32, Nm), (row_all, torch.int64, Nv),
+                     (row_any, torch.int64, Nv), (row_forbid, torch.int64, Nv), (row_min, torch.float32, Nv), (row_max, torch.float32, Nv),
+                     (ex_start, torch.int32, Nv + 1)):
+        if t is not None:
+            assert t.dtype == dt and t.is_contiguous() and t.numel() == n, (dt, n, t.dtype, tuple(t.shape))
+            device = t.device
+    n_ex = 0
+    if ex_start is not None:
+        assert ex_keys is not None and ex_keys.dtype == torch.int32 and ex_keys.is_contiguous()
+        n_ex = ex_keys.numel()
+    if bits is True:
+        bits = torch.empty(Nv, words, device=device, dtype=torch.int32)
+    ld = 0
+    if bits is not None:
+        assert bits.dim() == 2 and bits.dtype == torch.int32 and bits.stride(1) == 1 and bits.shape[0] == Nv and bits.shape[1] >= words
+        ld = bits.stride(0) if Nv > 1 else bits.shape[1]
+    if col_any is not None:
+        assert col_any.dtype == torch.int32 and col_any.is_contiguous() and col_any.numel() >= words
+    check(lib().made_eligibility(_p(col_tags), _p(col_length), _p(col_key), _p(row_all), _p(row_any), _p(row_forbid), _p(row_min),
+                                 _p(row_max), _p(ex_start), _p(ex_keys) if n_ex else None, n_ex, Nv, Nm, _p(bits), ld, _p(col_any),
+                                 _stream()), "made_eligibility")
+    return bits
+
+
+def _mask_ld(bits: Tensor, Nv: int, Nm: int) -> int:
+    assert bits.dim() == 2 and bits.dtype == torch.int32 and bits.stride(1) == 1 and bits.shape[0] == Nv and bits.shape[1] >= (Nm + 31) // 32
+    return bits.stride(0) if Nv > 1 else bits.shape[1]
+
+
+def topk_groups_masked(sims: Tensor, bits: Optional[Tensor], K: int, group_id: Optional[Tensor] = None, n_groups: Optional[int] = None,
+                       idx: Optional[Tensor] = None, score: Optional[Tensor] = None, ws: Optional[Tensor] = None):
+    """made_topk_groups_masked: `topk_groups` on every row with the columns removed whose bit of bits [Nv, >= ceil(Nm / 32)]
+    (`eligibility`'s output, uint32 words held as int32) is clear.  bits None: the unmasked selection."""
+    assert sims.dim() == 2 and sims.dtype == torch.float32 and sims.stride(1) == 1
+    Nv, Nm = sims.shape
+    dev = sims.device
+    G = 0
+    if group_id is not None:
+        assert group_id.dtype == torch.int32 and group_id.is_contiguous() and group_id.numel() == Nm
+        G = int(group_id.max()) + 1 if n_groups is None else int(n_groups)
+    if idx is None:
+        idx = torch.empty(Nv, K, device=dev, dtype=torch.int32)
+    if score is None:
+        score = torch.empty(Nv, K, device=dev, dtype=torch.float32)
+    assert idx.is_contiguous() and score.is_contiguous() and idx.shape == (Nv, K) and score.shape == (Nv, K)
+    need = topk_groups_ws_bytes(Nv, Nm, K) if group_id is None and 1 <= K <= 256 else 0
+    if need and (ws is None or ws.numel() * ws.element_size() < need):
+        ws = torch.empty(need, device=dev, dtype=torch.uint8)
+    ld = _mask_ld(bits, Nv, Nm) if bits is not None else 0
+    check(lib().made_topk_groups_masked(_p(sims), sims.stride(0), _p(group_id), _p(bits), ld, Nv, Nm, G, K, _p(idx), _p(score),
+                                        _p(ws) if need else None, need, _stream()), "made_topk_groups_masked")
+    return idx, score
+
+
 def gather_pairs(vi: Tensor, mi: Tensor, v_tok: Tensor, v_mask: Tensor, v_vec: Tensor, m_tok: Tensor, m_mask: Tensor, m_vec: Tensor,
                  frame_out: Tensor, seg_out: Tensor, fmask_out: Tensor, smask_out: Tensor, video_out: Tensor, music_out: Tensor) -> None:
     """made_gather_pairs: the localization batch of the pairs (vi[p], mi[p]) from per-item tower outputs.  v_tok [Nv, Tv, D] / m_tok
@@ -977,6 +1041,23 @@ def group_topw(sims: Tensor, sel: Tensor, col_group: Tensor, start: Tensor, cols
     score = torch.empty(Nv, K, w, device=sims.device, dtype=torch.float32)
     check(lib().made_group_topw(_p(sims), sims.stride(0), _p(sel), _p(col_group), _p(start), _p(cols), cols.numel(), Nv, Nm,
                                 start.numel() - 1, K, w, _p(idx), _p(score), _stream()), "made_group_topw")
+    return idx, score
+
+
+def group_topw_masked(sims: Tensor, bits: Optional[Tensor], sel: Tensor, col_group: Tensor, start: Tensor, cols: Tensor, w: int):
+    """made_group_topw_masked: `group_topw` with the members skipped whose bit of bits (`eligibility`'s output) is clear; sel is
+    `topk_groups_masked`'s idx under the same bits.  bits None: the unmasked call."""
+    assert sims.dim() == 2 and sims.dtype == torch.float32 and sims.stride(1) == 1
+    Nv, Nm = sims.shape
+    for t in (sel, col_group, start, cols):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert sel.dim() == 2 and sel.shape[0] == Nv and col_group.numel() == Nm and start.numel() >= 2
+    K = sel.shape[1]
+    idx = torch.empty(Nv, K, w, device=sims.device, dtype=torch.int32)
+    score = torch.empty(Nv, K, w, device=sims.device, dtype=torch.float32)
+    ld = _mask_ld(bits, Nv, Nm) if bits is not None else 0
+    check(lib().made_group_topw_masked(_p(sims), sims.stride(0), _p(bits), ld, _p(sel), _p(col_group), _p(start), _p(cols), cols.numel(),
+                                       Nv, Nm, start.numel() - 1, K, w, _p(idx), _p(score), _stream()), "made_group_topw_masked")
     return idx, score
 
 
