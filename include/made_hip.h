@@ -618,6 +618,31 @@ typedef struct MadeXpoolSimsArgs {
 int     made_xpool_sims(const MadeXpoolSimsArgs* args, void* stream);
 int64_t made_xpool_sims_ws_bytes(int64_t Nv, int64_t Nm, int64_t D);
 
+/* made_xpool_sims_pairs: made_xpool_sims for LISTED pairs (the second stage of `ground(..., shortlist=R)`: bf16, D = 256, S <= 96).  The pairs are
+ * a CSR over U tracks: pair p in [start[u], start[u + 1]) is (video[p], track u), start [U + 1] ascending, the videos of a track in any order
+ * (the caller lists them ascending); score [P] f32 receives the X-Pool similarity of every pair.  K [U, S, D], UU [U, S, 2 D] = u | u'',
+ * key_mask [U, S] or NULL, av, bv, ln3_g, ln3_b, vn and Q as for made_xpool_sims -- the same arithmetic: scores by MFMA, masked softmax in f32,
+ * probabilities rounded to bf16 before the two P.V products, y = k1 z + k2 Bv + Av, LayerNorm3 and the cosine through the six sums in f32;
+ * rounding points differ from made_xpool_sims (z and g3 vn stay f32), results agree to the bf16 bound, not bit for bit.  One workgroup per
+ * track and tile of 32 listed videos; the track's value rows go through LDS once per workgroup, Q rows and vn rows are gathered by video
+ * index; no workspace, no preparation launch, no atomics.  A pair's result does not depend on the other pairs of the launch or of its tile.
+ * A track without a valid segment gives NaN; a video index outside [0, Nv) gives NaN and nothing is read for it; an empty range is legal;
+ * start values are clamped to [0, P].  max_count: the longest range (sizes the grid; 0 or an underestimate only costs speed). */
+typedef struct MadeXpoolPairsArgs {
+    const void* Q; int64_t ldq;
+    const void* K; const void* UU; int64_t k_bs, ldk, u_bs, ldu;
+    const float* key_mask;
+    const float* av; const float* bv;
+    const float* ln3_g; const float* ln3_b;
+    const float* vn; int64_t ldvn;
+    const int32_t* start; const int32_t* video;
+    float* score;
+    int64_t Nv, U, P, S, D, max_count;
+    float scale, eps;
+} MadeXpoolPairsArgs;
+
+int     made_xpool_sims_pairs(const MadeXpoolPairsArgs* args, void* stream);
+
 /* made_xpool_inbatch: the in-batch X-Pool contraction for a batch of at most 64 videos -- out[m, n, :] = softmax_s(scale q_n . k_{m,s} + mask) U_m
  * (reference modules/transformer.py:110-119, out projection hoisted onto the values; the north-star contraction).  Two launches of one
  * workgroup per CU -- scores per (track, 128 segments) with the tile-local softmax pieces, then P.V per (track, 128 value columns) -- with only
@@ -1098,6 +1123,17 @@ int made_group_topw_masked(const float* sims, int64_t ld, const uint32_t* bits, 
  * outputs must not overlap the inputs or each other. */
 int made_topk_merge(const int32_t* a_col, const float* a_score, int64_t Ka, const int32_t* b_col, const float* b_score, int64_t Kb,
                     int64_t col_offset, int64_t Nv, int64_t w, int64_t K, int32_t* out_col, float* out_score, void* stream);
+
+/* made_topk_candidates: the selection of a row that is known only at R <= 256 candidate columns (`ground(..., shortlist=R)`).
+ * cand_col [Nv, R] int32 (-1 or >= N: no candidate; the columns of a row distinct) and cand_score [Nv, R] f32; col_group [N] int32
+ * with ids in [0, n_groups), or NULL (every column its own group).  out_col / out_score [Nv, K, w]: bit for bit what
+ * made_topk_groups_masked followed by made_group_topw_masked give on a dense row that holds the candidates' scores at their
+ * columns with every other eligibility bit clear -- groups by their best candidate (score descending through the order-preserving
+ * key, so NaN ranks lowest and -0 is +0; then column ascending), inside a group its best w candidates in the same order, -1 / -inf
+ * past the groups and past a group's candidates.  One workgroup per row, keys in LDS, rank by counting: comparisons only, no
+ * float arithmetic, no atomics.  1 <= K <= 256, 1 <= w <= 16; the outputs must not overlap the inputs or each other. */
+int made_topk_candidates(const int32_t* cand_col, const float* cand_score, int64_t Nv, int64_t R, const int32_t* col_group, int64_t N,
+                         int64_t n_groups, int64_t K, int64_t w, int32_t* out_col, float* out_score, void* stream);
 
 /* made_merge_moments: the moments of P (video, track) entries on the track's own time axis from the moments of the track's w
  * windows, one wave per entry, no atomics.  win_col / win_score [P, w] = made_group_topw's columns (-1: no window) and

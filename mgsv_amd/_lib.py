@@ -141,6 +141,13 @@ class MadeXpoolSimsArgs(C.Structure):
                 ("scale", f32), ("eps", f32), ("ws", vp), ("prepare_ws", i32), ("_pad", i32)]
 
 
+class MadeXpoolPairsArgs(C.Structure):
+    _fields_ = [("Q", vp), ("ldq", i64), ("K", vp), ("UU", vp), ("k_bs", i64), ("ldk", i64), ("u_bs", i64), ("ldu", i64),
+                ("key_mask", vp), ("av", vp), ("bv", vp), ("ln3_g", vp), ("ln3_b", vp), ("vn", vp), ("ldvn", i64),
+                ("start", vp), ("video", vp), ("score", vp), ("Nv", i64), ("U", i64), ("P", i64), ("S", i64), ("D", i64),
+                ("max_count", i64), ("scale", f32), ("eps", f32)]
+
+
 class MadeXpoolInbatchArgs(C.Structure):
     _fields_ = [("Q", vp), ("ldq", i64), ("K", vp), ("U", vp), ("k_bs", i64), ("ldk", i64), ("u_bs", i64), ("ldu", i64),
                 ("key_mask", vp), ("out", vp), ("out_dtype", i32), ("_pad", i32), ("o_bs", i64), ("ldo", i64),
@@ -285,6 +292,7 @@ SIGNATURES = {
     "made_xpool_attention": (C.c_int, [C.POINTER(MadeXpoolAttnArgs), vp]),
     "made_xpool_sims": (C.c_int, [C.POINTER(MadeXpoolSimsArgs), vp]),
     "made_xpool_sims_ws_bytes": (C.c_int64, [i64, i64, i64]),
+    "made_xpool_sims_pairs": (C.c_int, [C.POINTER(MadeXpoolPairsArgs), vp]),
     "made_xpool_inbatch": (C.c_int, [C.POINTER(MadeXpoolInbatchArgs), vp]),
     "made_xpool_inbatch_ws_bytes": (C.c_int64, [i64, i64]),
     "made_batch_order": (C.c_int, [vp, i64, i64, vp, vp]),
@@ -310,6 +318,7 @@ SIGNATURES = {
     "made_group_topw": (C.c_int, [vp, i64, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp]),
     "made_group_topw_masked": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp]),
     "made_topk_merge": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp]),
+    "made_topk_candidates": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i64, i64, vp, vp, vp]),
     "made_merge_moments": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, f32, f32, i64, vp, vp, vp, vp, vp]),
     "made_frames_preprocess": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i32, i64, vp, vp]),
     "made_audio_resample": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp]),

@@ -540,6 +540,95 @@ extern "C" int made_topk_merge(const int32_t* a_col, const float* a_score, int64
     return made_check_launch("made_topk_merge");
 }
 
+namespace {
+
+struct CandShared {
+    uint64_t key[GT];                   // (score key, 0x7FFFFFFF - column) of a candidate; 0 = none
+    int grp[GT];                        // its group
+    int lead[GT];                       // the candidate that represents its group (itself: a leader)
+    int rank[GT];                       // a leader's rank among the leaders = the group's output slot
+};
+
+// One workgroup per row, one thread per candidate, rank by counting as made_topk_merge does (comparisons only).  A candidate's key
+// is what made_group_topw compares -- (score key, lowest column first) -- so the best member of a group is its representative, the
+// leaders in descending key order are made_topk_groups_masked's groups, and a member's rank inside its group is its window slot.
+// The output row is assembled in LDS (the -1 / -inf fill first), then stored with contiguous writes.
+__global__ __launch_bounds__(GT) void topk_candidates_kernel(const int32_t* cand_col, const float* cand_score, int R, const int32_t* col_group,
+                                                             int N, int G, int K, int w, int32_t* out_col, float* out_score) {
+    extern __shared__ uint32_t v[];                              // [K * w] columns, then [K * w] score bits
+    __shared__ CandShared sh;
+    const int64_t row = blockIdx.x;
+    const int i = threadIdx.x;
+    const int KW = K * w;
+    uint64_t k = 0ull;
+    int g = -1, c = -1;
+    if (i < R) {
+        c = cand_col[row * R + i];
+        if (c >= 0 && c < N) {
+            g = col_group ? col_group[c] : c;
+            if (col_group && (unsigned)g >= (unsigned)G) g = -1;   // (a column of no group is no item, as in made_topk_groups)
+            else k = ((uint64_t)score_key(cand_score[row * R + i]) << 32) | (uint32_t)(0x7FFFFFFF - c);
+        }
+    }
+    sh.key[i] = k; sh.grp[i] = g;
+    for (int x = i; x < KW; x += GT) { v[x] = 0xFFFFFFFFu; v[KW + x] = 0xFF800000u; }
+    __syncthreads();
+    int wr = 0, lead = i;
+    if (k != 0ull) {
+        uint64_t bk = k;
+        for (int q = 0; q < R; ++q) {
+            const uint64_t kq = sh.key[q];
+            if (kq == 0ull || sh.grp[q] != g) continue;
+            wr += (kq > k || (kq == k && q < i)) ? 1 : 0;         // (equal keys -- a column listed twice -- rank in list order)
+            if (kq > bk || (kq == bk && q < lead)) { bk = kq; lead = q; }
+        }
+    }
+    sh.lead[i] = lead;
+    __syncthreads();
+    if (k != 0ull && lead == i) {
+        int rk = 0;
+        for (int q = 0; q < R; ++q) {
+            const uint64_t kq = sh.key[q];
+            if (kq == 0ull || sh.lead[q] != q) continue;
+            rk += (kq > k || (kq == k && q < i)) ? 1 : 0;
+        }
+        sh.rank[i] = rk;
+    }
+    __syncthreads();
+    if (k != 0ull) {
+        const int slot = sh.rank[lead];
+        if (slot < K && wr < w) {
+            v[slot * w + wr] = (uint32_t)c;
+            v[KW + slot * w + wr] = __float_as_uint(key_score((uint32_t)(k >> 32)));
+        }
+    }
+    __syncthreads();
+    for (int x = i; x < KW; x += GT) {
+        out_col[row * KW + x] = (int32_t)v[x];
+        out_score[row * KW + x] = __uint_as_float(v[KW + x]);
+    }
+}
+
+}  // namespace
+
+extern "C" int made_topk_candidates(const int32_t* cand_col, const float* cand_score, int64_t Nv, int64_t R, const int32_t* col_group,
+                                    int64_t N, int64_t n_groups, int64_t K, int64_t w, int32_t* out_col, float* out_score, void* stream) {
+    MADE_REQUIRE(cand_col && cand_score && out_col && out_score, "made_topk_candidates: null pointer");
+    MADE_REQUIRE(R >= 1 && R <= GT, "made_topk_candidates: R must lie in [1, 256]");
+    MADE_REQUIRE(K >= 1 && K <= 256, "made_topk_candidates: K must lie in [1, 256]");
+    MADE_REQUIRE(w >= 1 && w <= 16, "made_topk_candidates: w must lie in [1, 16]");
+    MADE_REQUIRE(Nv >= 0 && Nv < (1LL << 31) && N > 0 && N < (1LL << 31), "made_topk_candidates: bad dims (0 <= Nv < 2^31, 0 < N < 2^31)");
+    if (col_group) MADE_REQUIRE(n_groups >= 1 && n_groups < (1LL << 31), "made_topk_candidates: n_groups must lie in [1, 2^31)");
+    const int64_t nc = Nv * R * 4, no = Nv * K * w * 4;
+    MADE_REQUIRE((const void*)out_col != (const void*)out_score && !overlaps(out_col, no, out_score, no) && !overlaps(out_col, no, cand_col, nc) &&
+                 !overlaps(out_col, no, cand_score, nc) && !overlaps(out_score, no, cand_col, nc) && !overlaps(out_score, no, cand_score, nc),
+                 "made_topk_candidates: the outputs must not alias the inputs or each other");
+    if (Nv == 0) return MADE_OK;
+    hipLaunchKernelGGL(topk_candidates_kernel, dim3((unsigned)Nv), dim3(GT), (size_t)(K * w * 8), (hipStream_t)stream, cand_col, cand_score, (int)R,
+                       col_group, (int)N, (int)n_groups, (int)K, (int)w, out_col, out_score);
+    return made_check_launch("made_topk_candidates");
+}
+
 extern "C" int made_gather_pairs(const int32_t* vi, const int32_t* mi, int64_t P, int64_t Nv, int64_t Nm,
                                  const void* v_tok, int64_t v_tok_stride, const float* v_mask, int64_t v_mask_stride,
                                  const float* v_vec, int64_t v_vec_stride,

@@ -570,12 +570,46 @@ class MadeEngine:
                            pooled_out=pooled_out[m0 * Nv:(m0 + n) * Nv] if pooled_out is not None else None)
         return sims_out
 
-    def dual_sims(self, video: Tensor, music: Tensor, out: Optional[Tensor] = None, add: Optional[Tensor] = None) -> Tensor:
-        """cos(v, m) (reference modules/loss.py:52-56), always with the exact-f32 MFMA; `add` is summed in."""
+    def xpool_pair_sims(self, video: Tensor, seg: Tensor, seg_mask: Optional[Tensor], start: Tensor, vidx: Tensor, max_count: int = 0,
+                        cache: Optional[dict] = None, tower: str = "xa") -> Tensor:
+        """The X-Pool similarity of listed pairs, f32 [P]: pair p in [start[u], start[u + 1]) is (video vidx[p], track u of seg) -- `xpool_sims`'
+        value for that pair.  video [Nv, D] f32; seg [U, S, D] compute dtype; seg_mask [U, S] or None; start [U + 1] / vidx [P] int32.
+        bf16, D = 256, S <= 96: the projections of `xpool_sims`' default path on the U tracks, then one made_xpool_sims_pairs launch (work
+        proportional to P).  Everything else: `xpool_sims(video, seg)` -- every video against the U tracks -- and a gather of the listed
+        entries: correct everywhere, cheap only when there are few videos.  cache: a dict that keeps the per-video operands between calls
+        on the same videos."""
+        P, tc, dev = self.P, self.tc, self.device
+        Nv, D = video.shape
+        U, S, _ = seg.shape
+        if not (tc == torch.bfloat16 and D == 256 and S <= 96):
+            sims = self.xpool_sims(video, seg, seg_mask, tower=tower)
+            col = torch.repeat_interleave(torch.arange(U, device=dev), (start[1:] - start[:-1]).long())
+            return sims[vidx.long(), col]
+        cache = {} if cache is None else cache
+        if "q" not in cache:
+            v1 = ops.layernorm(video, P[tower + ".ln1.g"], P[tower + ".ln1.b"], out_dtype=tc)
+            cache["q"] = ops.linear(v1, P[tower + ".q.w"], P[tower + ".q.b"])
+            cache["vn"] = ops.l2norm_rows(video)
+        skip = seg_mask.reshape(-1) if seg_mask is not None else None
+        s1 = torch.empty(U * S, D, device=dev, dtype=tc)
+        kbuf = torch.empty(U * S, D, device=dev, dtype=tc)
+        ubuf = torch.empty(U * S, D, device=dev, dtype=tc)
+        uu = torch.empty(U * S, 2 * D, device=dev, dtype=tc)
+        ops.layernorm(seg, P[tower + ".ln1.g"], P[tower + ".ln1.b"], out=s1, row_skip=skip)
+        ops.linear(s1, P[tower + ".kv.w"], P[tower + ".kv.b"], tile_skip_mask=skip, segs=[Seg(out=kbuf, col_begin=0), Seg(out=ubuf, col_begin=D)])
+        ops.linear(ubuf, P[tower + ".out.w"], P[tower + ".out.b"], out=uu[:, :D], tile_skip_mask=skip)
+        ops.linear(uu[:, :D], P[tower + ".linf.w"], None, out=uu[:, D:], tile_skip_mask=skip)
+        return ops.xpool_sims_pairs(cache["q"], kbuf.view(U, S, D), uu.view(U, S, 2 * D), seg_mask, P[tower + ".linf.b"], P[tower + ".linf.rs"],
+                                    (P[tower + ".ln3.g"], P[tower + ".ln3.b"]), cache["vn"], start, vidx, scale=1.0 / math.sqrt(D),
+                                    max_count=max_count)
+
+    def dual_sims(self, video: Tensor, music: Tensor, out: Optional[Tensor] = None, add: Optional[Tensor] = None, splitk: bool = True) -> Tensor:
+        """cos(v, m) (reference modules/loss.py:52-56), always with the exact-f32 MFMA; `add` is summed in.  splitk False: never the
+        in-batch split-K form, whose sums are ordered differently (the shortlist's cosines, which must not depend on the chunking)."""
         vn = ops.l2norm_rows(video)
         mn = ops.l2norm_rows(music)
         Nv, Nm, D = vn.shape[0], mn.shape[0], vn.shape[1]
-        if Nv <= 256 and Nm <= 256 and Nm % 4 == 0 and (add is None or add.stride(0) % 4 == 0):   # in-batch: one output tile -> split K over workgroups
+        if splitk and Nv <= 256 and Nm <= 256 and Nm % 4 == 0 and (add is None or add.stride(0) % 4 == 0):   # in-batch: one output tile -> split K over workgroups
             if out is None:
                 out = torch.empty(Nv, Nm, device=vn.device, dtype=torch.float32)
             split = max(2, min(16, D // 32))

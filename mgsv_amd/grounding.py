@@ -49,6 +49,8 @@ class Grounding:
     confidence: Tensor
     window: Optional[Tensor] = None
     windows: Optional[Windows] = None
+    cand_col: Optional[Tensor] = None      # grounded with a shortlist: [N_v, R] int32, the library columns that were scored (-1: none) ...
+    cand_score: Optional[Tensor] = None    # ... and their exact scores, f32 (NaN where there is no candidate)
 
     @property
     def k(self) -> int:
@@ -280,24 +282,116 @@ def _group_tensor(group_id, Nm: int, dev):
     return g.to(dev).contiguous(), int(g.max()) + 1
 
 
+# ---------------------------------------------------------------------------------------------- the cosine shortlist
+SHORTLIST_MAX = 256                     # made_topk_groups' K limit, made_topk_candidates' R limit
+
+
+def check_shortlist(cfg, shortlist, explicit_sims: bool) -> Optional[int]:
+    """`shortlist` as an int in [1, 256] (None stays None).  ValueError for a value outside that range, for a shortlist together with
+    similarities of the caller's, and for a configuration whose score is not cosine + X-Pool."""
+    if shortlist is None:
+        return None
+    R = int(shortlist)
+    if R != shortlist or not 1 <= R <= SHORTLIST_MAX:
+        raise ValueError(f"shortlist = {shortlist!r}: must be an integer in [1, {SHORTLIST_MAX}]")
+    if explicit_sims:
+        raise ValueError("shortlist pre-selects with the model's own cosine and scores the survivors with its own X-Pool: it cannot be "
+                         "combined with sims= / sims_fn=")
+    if "XA" not in cfg.vmr_fusion or cfg.vmr_loss == "dual":
+        raise ValueError("shortlist: this configuration's score is the cosine alone (vmr_loss = 'dual', or no X-Pool tower): there is "
+                         "nothing to re-score, ground without a shortlist")
+    if cfg.vmr_loss == "single":
+        raise ValueError("shortlist: vmr_loss = 'single' scores with X-Pool alone: the score has no cosine term to pre-select with")
+    return R
+
+
+def pair_csr(cand_col: Tensor):
+    """The pairs (video i, column cand_col[i, j] >= 0) of a candidate table [N_v, R] (an integer tensor, on any device), sorted by
+    column: (cols int64 [U] the distinct columns ascending, start int32 [U + 1], video int32 [P] ascending inside a column, slot
+    int64 [P] = i * R + j of every pair), tensors on the table's device."""
+    Nv, R = cand_col.shape
+    n = Nv * R
+    flat = cand_col.reshape(-1).to(torch.int64)
+    there = flat >= 0
+    key = torch.where(there, flat, torch.full_like(flat, 1 << 31)) * max(n, 1) + torch.arange(n, device=flat.device)
+    key = torch.sort(key).values[:int(there.sum())]                # (column, slot): slots ascend with the video inside a column
+    slot = key % max(n, 1)
+    cols, counts = torch.unique_consecutive(key // max(n, 1), return_counts=True)
+    start = torch.zeros(cols.numel() + 1, device=flat.device, dtype=torch.int64)
+    start[1:] = torch.cumsum(counts, 0)
+    return cols, start.to(torch.int32), (slot // max(R, 1)).to(torch.int32), slot
+
+
+def _shortlist_fold(engine: MadeEngine, video: Tensor, vec: Tensor, bits: Optional[Tensor], R: int, c0: int, run, out):
+    """one chunk of stage 1: the cosines of its columns, their best R per row, merged into the running list"""
+    Nv, n = video.shape[0], vec.shape[0]
+    cos = engine.dual_sims(video, vec, splitk=False)
+    kk = min(R, n)
+    idx, sc = ops.topk_groups(cos, kk) if bits is None else ops.topk_groups_masked(cos, bits, kk)
+    return ops.topk_merge(run[0], run[1], idx.view(Nv, kk, 1), sc.view(Nv, kk, 1), R, col_offset=c0, out_col=out[0], out_score=out[1])
+
+
+def _score_candidates(engine: MadeEngine, video: Tensor, cand_col: Tensor, cand_cos: Tensor, fetch, chunk_cols: int, stats: Optional[dict] = None):
+    """Stage 2: cand_score [N_v, R] f32 = cosine + X-Pool of every candidate (NaN where there is none).  The pairs are sorted by
+    column; the distinct columns are walked in chunks of at most chunk_cols, each fetched by fetch(cols int64 numpy) -> (tokens
+    [n, S, D], mask [n, S], done()) and scored by `MadeEngine.xpool_pair_sims`."""
+    dev = engine.device
+    Nv, R = cand_col.shape
+    cols_d, start_d, vidx_d, slot_d = pair_csr(cand_col)
+    cols, start = cols_d.cpu().numpy(), start_d.cpu().numpy().astype(np.int64)      # (one host read: the walk is planned from it)
+    xp = torch.full((Nv * R,), float("nan"), device=dev, dtype=torch.float32)
+    cache = {}
+    use_mask = engine.cfg.fusion_mask == 1
+    chunk_cols = max(1, int(chunk_cols))
+    for u0 in range(0, len(cols), chunk_cols):
+        u1 = min(len(cols), u0 + chunk_cols)
+        p0, p1 = int(start[u0]), int(start[u1])
+        st = (start_d[u0:u1 + 1] - start_d[u0]).contiguous()
+        tokens, mask, done = fetch(cols[u0:u1])
+        sc = engine.xpool_pair_sims(video, tokens, mask if use_mask else None, st, vidx_d[p0:p1].contiguous(),
+                                    max_count=int(np.diff(start[u0:u1 + 1]).max()), cache=cache)
+        xp[slot_d[p0:p1]] = sc
+        done()
+    if stats is not None:
+        stats["pairs_scored"], stats["columns_projected"] = int(slot_d.numel()), int(len(cols))
+    return cand_cos + xp.view(Nv, R)                               # (one f32 add; NaN where cand_col is -1)
+
+
+def _device_fetch(tokens: Tensor, mask: Tensor):
+    """`_score_candidates`' fetch from resident tensors: made_gather_rows of the listed columns"""
+    dev = tokens.device
+    def fetch(cols: np.ndarray):
+        i64 = torch.from_numpy(cols).to(dev)
+        i32 = i64.to(torch.int32)
+        return _gather_device(tokens, i32, i64), _gather_device(mask, i32, i64), (lambda: None)
+    return fetch
+
+
 @torch.no_grad()
 def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Optional[Tensor] = None, group_id=None,
            pair_batch: int = 64, windows: Optional[Windows] = None, windows_per_track: int = 1, moments: int = 1,
-           nms_iou: float = 0.5, constraints: Optional[Constraints] = None, tags=None, length=None) -> Grounding:
+           nms_iou: float = 0.5, constraints: Optional[Constraints] = None, tags=None, length=None,
+           shortlist: Optional[int] = None) -> Grounding:
     """Each video's best k tracks (groups of columns sharing a music id when group_id [N_m] is given) and the moment in each.
     constraints: per-video `Constraints` on the tracks' `tags` (int64 [tracks]) and `length` (f32 seconds [tracks]; default: the
     durations) -- the selection then runs on every row with its ineligible columns removed (made_eligibility, then the masked
     kernels): an ineligible column gives no group its score, represents none and fills no window slot.
     windows: the columns of `music` are windows of tracks (music.duration = the windows' durations, group_id one entry per TRACK):
     each track's best `windows_per_track` windows are localized and their queries merged into up to `moments` moments per track on
-    the track's time axis, a candidate being dropped when its IoU with a better one kept exceeds nms_iou."""
+    the track's time axis, a candidate being dropped when its IoU with a better one kept exceeds nms_iou.
+    shortlist = R (1 .. 256; the score must be cosine + X-Pool): every video's R eligible columns of largest cosine are found first
+    (made_topk_groups on `dual_sims`), only those pairs get the X-Pool score (made_xpool_sims_pairs on the distinct shortlisted
+    columns), and the selection above runs on each row's R exact scores with every other column ineligible (made_topk_candidates).
+    `Grounding.cand_col` / `cand_score` [N_v, R] report what was scored."""
     dev = engine.device
     Nv, Nm = len(videos), len(music)
-    if sims is None:
-        sims = similarity_matrix(engine, videos.vec, music.tokens, music.mask, music.vec)
-    sims = sims.to(dev, torch.float32)
-    if sims.stride(1) != 1:
-        sims = sims.contiguous()
+    shortlist = check_shortlist(engine.cfg, shortlist, sims is not None)
+    if shortlist is None:
+        if sims is None:
+            sims = similarity_matrix(engine, videos.vec, music.tokens, music.mask, music.vec)
+        sims = sims.to(dev, torch.float32)
+        if sims.stride(1) != 1:
+            sims = sims.contiguous()
     bits = None
     if constraints is not None:
         nc = constraints.normalized(Nv)
@@ -307,17 +401,31 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
         up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(col(a), dtype=dt)).to(dev)
         key = np.arange(Nm, dtype=np.int32) if windows is None else windows.track.astype(np.int32)
         bits = _RowConstraints(nc, dev).bits(Nv, Nm, up(t, np.int64), up(l, np.float32), torch.from_numpy(key).to(dev), device=dev)
+    cand = None
+    if shortlist is not None:
+        engine._set_products()
+        R = min(shortlist, Nm)
+        video = videos.vec.to(dev, torch.float32).contiguous()
+        empty = (torch.empty(Nv, 0, 1, device=dev, dtype=torch.int32), torch.empty(Nv, 0, 1, device=dev, dtype=torch.float32))
+        ccol, ccos = _shortlist_fold(engine, video, music.vec.to(dev, torch.float32).contiguous(), bits, R, 0, empty, (None, None))
+        ccol, ccos = ccol.view(Nv, R), ccos.view(Nv, R)
+        tokens = music.tokens.to(dev, engine.tc).contiguous()
+        cand = (ccol, _score_candidates(engine, video, ccol, ccos, _device_fetch(tokens, music.mask.to(dev, torch.float32).contiguous()), 4096))
     if windows is not None:
         return _ground_windows(engine, videos, music, k, sims, group_id, pair_batch, windows, int(windows_per_track), int(moments),
-                               float(nms_iou), bits)
+                               float(nms_iou), bits, cand)
     gid, G = _group_tensor(group_id, Nm, dev)
     kk = max(1, min(int(k), G))
-    track, score = ops.topk_groups(sims, kk, gid, G) if bits is None else ops.topk_groups_masked(sims, bits, kk, gid, G)
+    if cand is not None:
+        track, score = (t.view(Nv, kk) for t in ops.topk_candidates(cand[0], cand[1], kk, 1, gid, G, n_cols=Nm))
+    else:
+        track, score = ops.topk_groups(sims, kk, gid, G) if bits is None else ops.topk_groups_masked(sims, bits, kk, gid, G)
     vi = torch.arange(Nv, device=dev, dtype=torch.int32).repeat_interleave(kk)
     mi = track.reshape(-1)
     mi = torch.where(mi < 0, torch.zeros_like(mi), mi)             # (no track: localized against track 0, reported as -1 / NaN)
     start, end, conf = _pair_moments(engine, videos, music, vi, mi, track.reshape(-1) < 0, pair_batch)
-    return Grounding(track=track, score=score, start=start.view(Nv, kk), end=end.view(Nv, kk), confidence=conf.view(Nv, kk))
+    return Grounding(track=track, score=score, start=start.view(Nv, kk), end=end.view(Nv, kk), confidence=conf.view(Nv, kk),
+                     cand_col=None if cand is None else cand[0], cand_score=None if cand is None else cand[1])
 
 
 def _pad_pairs(vi: Tensor, mi: Tensor, min_pairs: int):
@@ -398,7 +506,7 @@ def _pair_candidates(engine: MadeEngine, videos: Encoded, music: Encoded, vi: Te
 
 
 def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Tensor, group_id, pair_batch: int,
-                    windows: Windows, w: int, n: int, nms_iou: float, bits: Optional[Tensor] = None) -> Grounding:
+                    windows: Windows, w: int, n: int, nms_iou: float, bits: Optional[Tensor] = None, cand=None) -> Grounding:
     dev = engine.device
     Nv, Nm = len(videos), len(music)
     if len(windows) != Nm:
@@ -418,7 +526,10 @@ def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int,
     as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     gid = as_dev(col_group)
     kk = max(1, min(int(k), G))
-    if bits is None:
+    if cand is not None:                                           # ... its best SHORTLISTED window's
+        wcol, wscore = ops.topk_candidates(cand[0], cand[1], kk, w, gid, G)
+        rep, score = wcol[:, :, 0].contiguous(), wscore[:, :, 0].contiguous()
+    elif bits is None:
         rep, score = ops.topk_groups(sims, kk, gid, G)             # a track's score: its best window's similarity
         wcol, wscore = ops.group_topw(sims, rep, gid, as_dev(start), as_dev(cols), w)
     else:                                                          # ... its best ELIGIBLE window's
@@ -432,7 +543,7 @@ def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int,
     track = _window_tracks(rep, as_dev(windows.track))
     shape = (Nv, kk) if n == 1 else (Nv, kk, n)
     return Grounding(track=track, score=score, start=st.view(shape), end=en.view(shape), confidence=cf.view(shape), window=wi.view(shape),
-                     windows=windows)
+                     windows=windows, cand_col=None if cand is None else cand[0], cand_score=None if cand is None else cand[1])
 
 
 def _window_moments(engine: MadeEngine, videos: Encoded, music: Encoded, vi: Tensor, mi: Tensor, wcol: Tensor, wscore: Tensor,
@@ -792,10 +903,75 @@ def _select_constrained(engine: MadeEngine, videos: Encoded, library, kk: int, w
     return run
 
 
+def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, chunk_cols: int, R: int,
+                        constraints: Optional[Constraints], timings: Optional[dict]):
+    """(wcol, wscore [N_v, kk, w], (cand_col, cand_score [N_v, R])): `ground(..., shortlist=R)`'s selection on a stored library.
+    Stage 1 reads `vec` and the attribute arrays only; stage 2 the tokens and masks of the distinct shortlisted columns."""
+    dev = engine.device
+    Nv, N = len(videos), len(library)
+    engine._set_products()
+    cur = torch.cuda.current_stream()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timings is not None else None
+    if ev:
+        ev[0].record(cur)
+    video = videos.vec.to(dev, torch.float32).contiguous()
+    rc = col_tags = col_length = col_key = None
+    if constraints is not None:
+        nc = constraints.normalized(Nv)
+        rc = _RowConstraints(nc, dev)
+        col_tags, col_length, col_key = _library_attributes(library, dev, nc.uses_tags, nc.uses_length)
+    chunks = library._plan(chunk_cols)["chunks"]
+    resident = library.on_device
+    state = [(torch.empty(Nv, R, 1, device=dev, dtype=torch.int32), torch.empty(Nv, R, 1, device=dev, dtype=torch.float32)) for _ in range(2)]
+    run = (torch.empty(Nv, 0, 1, device=dev, dtype=torch.int32), torch.empty(Nv, 0, 1, device=dev, dtype=torch.float32))
+    part = lambda a, c0, c1: None if a is None else a[c0:c1]
+    for i, (c0, c1) in enumerate(chunks):
+        if resident:
+            vec = library.vec[c0:c1]
+        else:
+            v = library.vec[c0:c1]
+            vec = (v if isinstance(v, Tensor) else torch.from_numpy(np.array(v))).to(dev)
+        bits = None if rc is None else rc.bits(Nv, c1 - c0, part(col_tags, c0, c1), part(col_length, c0, c1), part(col_key, c0, c1), device=dev)
+        run = _shortlist_fold(engine, video, vec.to(torch.float32).contiguous(), bits, R, c0, run, state[i % 2])
+    cand_col, cand_cos = run[0].view(Nv, R), run[1].view(Nv, R)
+    if ev:
+        ev[1].record(cur)
+    if resident:
+        fetch = _device_fetch(library.tokens, library.mask)
+    else:
+        def fetch(cols: np.ndarray):                               # the pinned "columns" staging set, as the localization uses it
+            stage = _staging(library, "columns", len(cols), dev, 1)
+            n = stage.fill(0, library, cols)
+            enc = stage.upload(0, n, False)
+            cur.wait_event(stage.uploaded[0])
+            return enc.tokens, enc.mask, (lambda: stage.consumed[0].record(cur))
+    stats = {}
+    cand_score = _score_candidates(engine, video, cand_col, cand_cos, fetch, chunk_cols, stats)
+    if ev:
+        ev[2].record(cur)
+    gid = None
+    if library.grouped:
+        key = ("col_group", str(dev))
+        if key not in library._device_attrs:
+            library._device_attrs[key] = torch.from_numpy(library.col_group).to(dev)
+        gid = library._device_attrs[key]
+    wcol, wscore = ops.topk_candidates(cand_col, cand_score, kk, w, gid, library.n_groups, n_cols=N)
+    if ev:
+        ev[3].record(cur)
+        torch.cuda.synchronize()
+        timings["chunks"] = len(chunks)
+        timings["shortlist_ms"] = ev[0].elapsed_time(ev[1])
+        timings["pair_score_ms"] = ev[1].elapsed_time(ev[2])
+        timings["selection_ms"] = ev[2].elapsed_time(ev[3])
+        timings.update(stats)
+    return wcol, wscore, (cand_col, cand_score)
+
+
 @torch.no_grad()
 def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_batch: int = 64, windows_per_track: int = 1,
                    moments: int = 1, nms_iou: float = 0.5, chunk_cols: int = 4096, video_batch: int = 1024, sims_fn=None,
-                   timings: Optional[dict] = None, constraints: Optional[Constraints] = None, compact: Optional[bool] = None) -> Grounding:
+                   timings: Optional[dict] = None, constraints: Optional[Constraints] = None, compact: Optional[bool] = None,
+                   shortlist: Optional[int] = None) -> Grounding:
     """`ground()` for a stored library (mgsv_amd.library.MusicLibrary: host arrays, a memory-mapped directory, or device tensors):
     the same Grounding, bit for bit, as
         ground(engine, videos, library.as_encoded(dev), k, group_id=library.group_id, windows=library.windows, ...)
@@ -811,9 +987,14 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     column are never uploaded or scored: with compact False the plan's chunks without such a group are skipped; with compact True
     a plan over the kept groups alone is walked, every chunk gathered by its ascending list of library columns (an explicit hook is
     then called as sims_fn(chunk, cols, None), cols the int64 device tensor of those columns).  compact None: False with a hook,
-    else True iff the kept columns are at most half of the library."""
+    else True iff the kept columns are at most half of the library.
+    shortlist = R: `ground(..., shortlist=R)` for the stored library, bit for bit.  Stage 1 walks the chunk plan reading only `vec`
+    (and the attribute arrays under constraints) -- cosines, the best R eligible columns per chunk, made_topk_merge; stage 2 fetches
+    the tokens of the distinct shortlisted columns alone, in chunks of at most chunk_cols, and scores the listed pairs; the selection
+    is made_topk_candidates.  timings then receives shortlist_ms, pairs_scored, columns_projected, pair_score_ms, selection_ms."""
     c = engine.cfg
     dev = engine.device
+    shortlist = check_shortlist(c, shortlist, sims_fn is not None)
     if c.moment_query_type == "xpool":
         raise NotImplementedError("moment_query_type=xpool: the decoder query is the track's pooled vector averaged over the videos of "
                                   "the batch (reference model/model_Uni.py:222-223), a property of the batch with no per-pair meaning")
@@ -832,7 +1013,10 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     kk = max(1, min(int(k), library.n_groups))
     video_batch = max(1, int(video_batch))
     t0 = torch.cuda.Event(enable_timing=True) if timings is not None else None
-    if constraints is None:
+    cand = None
+    if shortlist is not None:
+        wcol, wscore, cand = _select_shortlisted(engine, videos, library, kk, w, int(chunk_cols), min(shortlist, N), constraints, timings)
+    elif constraints is None:
         wcol, wscore = _select_streamed(engine, videos, library, kk, w, int(chunk_cols), sims_fn, timings)
         if timings is not None:
             timings["columns_scored"], timings["chunks_skipped"] = N, 0
@@ -883,10 +1067,11 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
         t1.record()
         torch.cuda.synchronize()
         timings["localization_ms"] = t0.elapsed_time(t1)
+    cc, cs = (None, None) if cand is None else cand
     if windows is None:
-        return Grounding(track=rep, score=score, start=start, end=end, confidence=conf)
+        return Grounding(track=rep, score=score, start=start, end=end, confidence=conf, cand_col=cc, cand_score=cs)
     return Grounding(track=_window_tracks(rep, track_of_col), score=score, start=start, end=end, confidence=conf,
-                     window=torch.cat([p[3] for p in parts]), windows=windows)
+                     window=torch.cat([p[3] for p in parts]), windows=windows, cand_col=cc, cand_score=cs)
 
 
 def moment_iou(start: Tensor, end: Tensor, gt_moment: Tensor, m_duration: Tensor, max_m_duration: float) -> Tensor:

@@ -733,6 +733,36 @@ def xpool_sims(Q: Tensor, K: Tensor, UU: Tensor, key_mask: Optional[Tensor], av:
     return sims
 
 
+def xpool_sims_pairs(Q: Tensor, K: Tensor, UU: Tensor, key_mask: Optional[Tensor], av: Tensor, bv: Tensor, ln3, vn: Tensor, start: Tensor,
+                     video: Tensor, score: Optional[Tensor] = None, *, scale: float, eps: float = 1e-5, max_count: int = 0) -> Tensor:
+    """made_xpool_sims_pairs: `xpool_sims` for the listed pairs of a CSR over the U tracks of K / UU -- pair p in [start[u], start[u + 1])
+    is (video[p], track u); start [U + 1] and video [P] int32 -> score [P] f32 (bf16, D = 256, S <= 96).  A track without a valid segment
+    and a video index outside [0, Nv) give NaN.  max_count: the longest range, if the caller knows it (sizes the grid)."""
+    from ._lib import MadeXpoolPairsArgs
+    Nv, D = Q.shape
+    U, S, _ = K.shape
+    assert Q.dtype == K.dtype == UU.dtype == torch.bfloat16 and Q.stride(1) == 1 and K.stride(2) == 1 and UU.stride(2) == 1
+    assert UU.shape == (U, S, 2 * D) and vn.shape == (Nv, D) and vn.dtype == torch.float32 and vn.stride(1) == 1 and av.shape == (D,) and bv.shape == (D,)
+    assert start.dtype == torch.int32 and start.is_contiguous() and start.numel() == U + 1
+    assert video.dtype == torch.int32 and video.is_contiguous() and video.dim() == 1
+    P = video.numel()
+    if score is None:
+        score = torch.empty(P, device=Q.device, dtype=torch.float32)
+    assert score.dtype == torch.float32 and score.is_contiguous() and score.numel() == P
+    a = MadeXpoolPairsArgs()
+    a.Q, a.ldq = _p(Q), Q.stride(0)
+    a.K, a.UU, a.k_bs, a.ldk, a.u_bs, a.ldu = _p(K), _p(UU), K.stride(0), K.stride(1), UU.stride(0), UU.stride(1)
+    a.key_mask = _p(_f32(key_mask.contiguous(), "key_mask")) if key_mask is not None else None
+    a.av, a.bv = _p(_f32(av, "av")), _p(_f32(bv, "bv"))
+    a.ln3_g, a.ln3_b = _p(_f32(ln3[0], "ln3")), _p(_f32(ln3[1], "ln3"))
+    a.vn, a.ldvn = _p(vn), vn.stride(0)
+    a.start, a.video, a.score = _p(start), _p(video), _p(score)
+    a.Nv, a.U, a.P, a.S, a.D, a.max_count = Nv, U, P, S, D, int(max_count)
+    a.scale, a.eps = scale, eps
+    check(lib().made_xpool_sims_pairs(C.byref(a), _stream()), "made_xpool_sims_pairs")
+    return score
+
+
 def xpool_attention(Q: Tensor, K: Tensor, U: Tensor, key_mask: Optional[Tensor], out: Tensor, scale: float, normalize: bool = True,
                     eps: float = 1e-5, ws: Optional[Tensor] = None) -> Tensor:
     """The X-Pool attention at retrieval scale, head dim = D = 256 or 512, S <= 512 (made_xpool_attention): Q [Nv, D], K / U [Nm, S, D]
@@ -1082,6 +1112,28 @@ def topk_merge(a_col: Tensor, a_score: Tensor, b_col: Tensor, b_score: Tensor, K
                                 _p(b_score) if Kb else None, Kb, int(col_offset), Nv, w, K, _p(out_col), _p(out_score), _stream()),
           "made_topk_merge")
     return out_col, out_score
+
+
+def topk_candidates(cand_col: Tensor, cand_score: Tensor, K: int, w: int = 1, col_group: Optional[Tensor] = None,
+                    n_groups: Optional[int] = None, n_cols: Optional[int] = None):
+    """made_topk_candidates: the selection of rows known only at their candidates -- cand_col [Nv, R] int32 (-1: none) and cand_score
+    [Nv, R] f32, R <= 256 -> (col [Nv, K, w] int32, score [Nv, K, w] f32): what `topk_groups_masked` + `group_topw_masked` give on the
+    dense rows that hold the candidates' scores at their columns and have every other column ineligible.  col_group [N] int32 (None:
+    every column its own group; then n_cols = the number of columns, default: no upper bound)."""
+    assert cand_col.dim() == 2 and cand_col.dtype == torch.int32 and cand_score.dtype == torch.float32 and cand_col.shape == cand_score.shape
+    assert cand_col.is_contiguous() and cand_score.is_contiguous()
+    Nv, R = cand_col.shape
+    G = 0
+    N = (1 << 31) - 1 if n_cols is None else int(n_cols)
+    if col_group is not None:
+        assert col_group.dtype == torch.int32 and col_group.is_contiguous()
+        N = col_group.numel()
+        G = int(col_group.max()) + 1 if n_groups is None else int(n_groups)
+    col = torch.empty(Nv, K, w, device=cand_col.device, dtype=torch.int32)
+    score = torch.empty(Nv, K, w, device=cand_col.device, dtype=torch.float32)
+    check(lib().made_topk_candidates(_p(cand_col), _p(cand_score), Nv, R, _p(col_group), N, G, K, w, _p(col), _p(score), _stream()),
+          "made_topk_candidates")
+    return col, score
 
 
 def merge_moments(cand: Tensor, win_col: Tensor, win_score: Tensor, offset: Tensor, duration: Optional[Tensor], max_m_duration: float,
