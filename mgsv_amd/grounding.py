@@ -16,6 +16,10 @@ w windows of every selected track from the groups' CSR, localization runs on the
 `made_merge_moments` puts every query of those windows on the track's own time axis and keeps the best n after a greedy
 suppression of overlapping ones -- the same passage seen through two overlapping windows is reported once.
 
+`ground_library` is `ground` for a stored library (mgsv_amd/library.py) that is walked chunk by chunk: `walk_plan` names the chunks from
+host data alone (the library's plan; under constraints its chunks that hold a kept column, or a restricted plan of column lists),
+and `_select_walk` is the one loop that uploads, scores, selects and merges them -- constrained or not, contiguous or listed.
+
 A pair's localization depends on that pair's video and track only (every kernel after the towers computes a sample's rows
 independently of the rest of the batch), so the moment found in the ground-truth track is the one the batched evaluation scores.
 """
@@ -30,6 +34,7 @@ import torch
 
 from . import _lib, ops
 from .engine import Encoded, MadeEngine
+from .library import restricted_plan
 from .windows import Windows, group_csr
 
 Tensor = torch.Tensor
@@ -282,6 +287,28 @@ def _group_tensor(group_id, Nm: int, dev):
     return g.to(dev).contiguous(), int(g.max()) + 1
 
 
+def _topk_groups(sims: Tensor, bits: Optional[Tensor], K: int, group_id: Optional[Tensor] = None, n_groups: Optional[int] = None):
+    """made_topk_groups, or under eligibility bits made_topk_groups_masked"""
+    return ops.topk_groups(sims, K, group_id, n_groups) if bits is None else ops.topk_groups_masked(sims, bits, K, group_id, n_groups)
+
+
+def _group_topw(sims: Tensor, bits: Optional[Tensor], sel: Tensor, col_group: Tensor, start: Tensor, cols: Tensor, w: int):
+    """made_group_topw, or under eligibility bits made_group_topw_masked"""
+    if bits is None:
+        return ops.group_topw(sims, sel, col_group, start, cols, w)
+    return ops.group_topw_masked(sims, bits, sel, col_group, start, cols, w)
+
+
+def _window_counts(windows_per_track, moments):
+    """(w, n) as ints, w in [1, 16] and n >= 1"""
+    w, n = int(windows_per_track), int(moments)
+    if not 1 <= w <= 16:
+        raise ValueError(f"windows_per_track = {w}: must lie in [1, 16]")
+    if n < 1:
+        raise ValueError(f"moments = {n}: must be >= 1")
+    return w, n
+
+
 # ---------------------------------------------------------------------------------------------- the cosine shortlist
 SHORTLIST_MAX = 256                     # made_topk_groups' K limit, made_topk_candidates' R limit
 
@@ -327,7 +354,7 @@ def _shortlist_fold(engine: MadeEngine, video: Tensor, vec: Tensor, bits: Option
     Nv, n = video.shape[0], vec.shape[0]
     cos = engine.dual_sims(video, vec, splitk=False)
     kk = min(R, n)
-    idx, sc = ops.topk_groups(cos, kk) if bits is None else ops.topk_groups_masked(cos, bits, kk)
+    idx, sc = _topk_groups(cos, bits, kk)
     return ops.topk_merge(run[0], run[1], idx.view(Nv, kk, 1), sc.view(Nv, kk, 1), R, col_offset=c0, out_col=out[0], out_score=out[1])
 
 
@@ -412,14 +439,14 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
         tokens = music.tokens.to(dev, engine.tc).contiguous()
         cand = (ccol, _score_candidates(engine, video, ccol, ccos, _device_fetch(tokens, music.mask.to(dev, torch.float32).contiguous()), 4096))
     if windows is not None:
-        return _ground_windows(engine, videos, music, k, sims, group_id, pair_batch, windows, int(windows_per_track), int(moments),
-                               float(nms_iou), bits, cand)
+        return _ground_windows(engine, videos, music, k, sims, group_id, pair_batch, windows, windows_per_track, moments, float(nms_iou),
+                               bits, cand)
     gid, G = _group_tensor(group_id, Nm, dev)
     kk = max(1, min(int(k), G))
     if cand is not None:
         track, score = (t.view(Nv, kk) for t in ops.topk_candidates(cand[0], cand[1], kk, 1, gid, G, n_cols=Nm))
     else:
-        track, score = ops.topk_groups(sims, kk, gid, G) if bits is None else ops.topk_groups_masked(sims, bits, kk, gid, G)
+        track, score = _topk_groups(sims, bits, kk, gid, G)
     vi = torch.arange(Nv, device=dev, dtype=torch.int32).repeat_interleave(kk)
     mi = track.reshape(-1)
     mi = torch.where(mi < 0, torch.zeros_like(mi), mi)             # (no track: localized against track 0, reported as -1 / NaN)
@@ -506,15 +533,12 @@ def _pair_candidates(engine: MadeEngine, videos: Encoded, music: Encoded, vi: Te
 
 
 def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Tensor, group_id, pair_batch: int,
-                    windows: Windows, w: int, n: int, nms_iou: float, bits: Optional[Tensor] = None, cand=None) -> Grounding:
+                    windows: Windows, windows_per_track, moments, nms_iou: float, bits: Optional[Tensor] = None, cand=None) -> Grounding:
     dev = engine.device
     Nv, Nm = len(videos), len(music)
     if len(windows) != Nm:
         raise ValueError(f"windows describes {len(windows)} columns, the library has {Nm}")
-    if not 1 <= w <= 16:
-        raise ValueError(f"windows_per_track = {w}: must lie in [1, 16]")
-    if n < 1:
-        raise ValueError(f"moments = {n}: must be >= 1")
+    w, n = _window_counts(windows_per_track, moments)
     if group_id is None:
         col_group, G = windows.track.astype(np.int32), windows.n_tracks
     else:
@@ -526,15 +550,12 @@ def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int,
     as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     gid = as_dev(col_group)
     kk = max(1, min(int(k), G))
-    if cand is not None:                                           # ... its best SHORTLISTED window's
+    if cand is not None:                                           # a track's score: its best SHORTLISTED window's
         wcol, wscore = ops.topk_candidates(cand[0], cand[1], kk, w, gid, G)
         rep, score = wcol[:, :, 0].contiguous(), wscore[:, :, 0].contiguous()
-    elif bits is None:
-        rep, score = ops.topk_groups(sims, kk, gid, G)             # a track's score: its best window's similarity
-        wcol, wscore = ops.group_topw(sims, rep, gid, as_dev(start), as_dev(cols), w)
-    else:                                                          # ... its best ELIGIBLE window's
-        rep, score = ops.topk_groups_masked(sims, bits, kk, gid, G)
-        wcol, wscore = ops.group_topw_masked(sims, bits, rep, gid, as_dev(start), as_dev(cols), w)
+    else:
+        rep, score = _topk_groups(sims, bits, kk, gid, G)          # ... its best window's similarity (under bits: its best ELIGIBLE window's)
+        wcol, wscore = _group_topw(sims, bits, rep, gid, as_dev(start), as_dev(cols), w)
     vi = torch.arange(Nv, device=dev, dtype=torch.int32).repeat_interleave(kk * w)
     mi = wcol.reshape(-1)
     mi = torch.where(mi < 0, torch.zeros_like(mi), mi)             # (no window: localized against column 0, left out by the merge)
@@ -637,102 +658,64 @@ def _staging(library, name: str, rows: int, dev, sets: int) -> _Staging:
 
 
 def _plan_tables(plan: dict, dev):
-    """the plan's group tables on the device, uploaded once per (plan, device): local group ids [N], the chunks' CSR starts, and the
-    CSR's column list 0, 1, 2, ... (groups are contiguous)"""
+    """the plan's group tables on the device, uploaded once per (plan, device): local group ids [N] and the chunks' CSR starts"""
     key = str(dev)
     if key not in plan["device"]:
-        longest = max((b - a for a, b in plan["chunks"]), default=0)
-        plan["device"][key] = (torch.from_numpy(plan["gid"]).to(dev), torch.from_numpy(plan["start"]).to(dev),
-                               torch.arange(longest, device=dev, dtype=torch.int32))
+        plan["device"][key] = (torch.from_numpy(plan["gid"]).to(dev), torch.from_numpy(plan["start"]).to(dev))
     return plan["device"][key]
 
 
-def _select_streamed(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, chunk_cols: int, sims_fn, timings: Optional[dict]):
-    """(wcol int32, wscore f32) [N_v, kk, w]: every video's best kk groups of the library and the best w columns of each, library
-    column numbers -- what made_topk_groups + made_group_topw give on the whole similarity matrix, folded over the chunk plan."""
-    dev = engine.device
-    Nv = len(videos)
+class WalkChunk(NamedTuple):
+    """One chunk of a walk over the library, host data only.  rows: slice(c0, c1), or -- listed -- the chunk's ascending int64
+    library columns; gid int32 [n]: every column's group, dense inside the chunk; start int32 [n_groups + 1]: the groups' CSR starts
+    (the column list is 0, 1, 2, ...); col_offset: c0, what turns a local column into the library's (0 when listed: `rows` maps it);
+    start_at: where `start` begins in the plan's table (None when listed: no table holds it)."""
+    rows: object
+    n: int
+    gid: np.ndarray
+    n_groups: int
+    start: np.ndarray
+    col_offset: int
+    listed: bool
+    start_at: Optional[int]
+
+
+def walk_plan(library, chunk_cols: int, keep: Optional[np.ndarray] = None, compact: bool = False):
+    """(items, skipped): the chunks `ground_library` walks, from host data alone.  No keep: every chunk of the library's plan.  keep
+    (bool [N], the columns some video may be grounded in) with compact False: the plan's chunks that hold a kept column, skipped
+    counting the others; with compact True: the chunks of `restricted_plan`, each a list of columns."""
+    if keep is not None and compact:
+        return [WalkChunk(ch["cols"], len(ch["cols"]), ch["gid"], ch["n_groups"], ch["start"], 0, True, None)
+                for ch in restricted_plan(library, chunk_cols, keep)], 0
     plan = library._plan(chunk_cols)
-    chunks = plan["chunks"]
+    items = []
+    for i, (c0, c1) in enumerate(plan["chunks"]):
+        if keep is not None and not keep[c0:c1].any():
+            continue
+        ng, s0 = plan["n_groups"][i], plan["start_at"][i]
+        items.append(WalkChunk(slice(c0, c1), c1 - c0, plan["gid"][c0:c1], ng, plan["start"][s0:s0 + ng + 1], c0, False, s0))
+    return items, len(plan["chunks"]) - len(items)
+
+
+def _walk_tables(library, items, chunk_cols: int, dev):
+    """[(gid, start, cols), ...]: every item's group tables on the device (None, None for a library without groups) and, for a listed
+    item, its columns as (int32, int64) (else None).  The plan's own chunks are slices of `_plan_tables`, uploaded once per (plan,
+    device); listed chunks exist for one call and are uploaded by it."""
+    up = lambda a: torch.from_numpy(a).to(dev)
     grouped = library.grouped
-    gid_all = start_all = cols_all = None
-    if grouped:
-        gid_all, start_all, cols_all = _plan_tables(plan, dev)
-    longest = max(b - a for a, b in chunks)
-    cur = torch.cuda.current_stream()
-    resident = library.on_device
-    stage = None if resident else _staging(library, "chunks", longest, dev, 2)
-    has_dur = library.duration is not None
-    video = videos.vec.to(dev, torch.float32).contiguous()
-    sims_buf = single_buf = None
-    if sims_fn is None:
-        sims_buf = torch.empty(Nv, longest, device=dev, dtype=torch.float32)
-        single_buf = torch.empty(Nv, longest, device=dev, dtype=torch.float32)
-    state = [(torch.empty(Nv, kk, w, device=dev, dtype=torch.int32), torch.empty(Nv, kk, w, device=dev, dtype=torch.float32))
-             for _ in range(2)]
-    run = (torch.empty(Nv, 0, w, device=dev, dtype=torch.int32), torch.empty(Nv, 0, w, device=dev, dtype=torch.float32))
-    marks = []                                                      # (compute stream reaches the wait, sims start, sims end, merge end) per chunk
-
-    def chunk_encoded(i: int) -> Encoded:
-        c0, c1 = chunks[i]
-        if resident:
-            return Encoded(tokens=library.tokens[c0:c1], mask=library.mask[c0:c1], vec=library.vec[c0:c1],
-                           duration=library.duration[c0:c1] if has_dur else None)
-        if library.pinned:                                          # pinned already: no staging copy
-            return stage.upload(i % 2, c1 - c0, has_dur, src=[None if a is None else a[c0:c1] for a in
-                                                              (library.tokens, library.mask, library.vec, library.duration)])
-        n = stage.fill(i % 2, library, slice(c0, c1))
-        return stage.upload(i % 2, n, has_dur)
-
-    nxt = chunk_encoded(0)
-    for i, (c0, c1) in enumerate(chunks):
-        chunk, n = nxt, c1 - c0
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timings is not None else None
-        if ev:
-            ev[0].record(cur)
-        if not resident:
-            cur.wait_event(stage.uploaded[i % 2])
-        if ev:
-            ev[1].record(cur)
-        if sims_fn is not None:
-            sims = sims_fn(chunk, c0, c1).to(dev, torch.float32)
-            if sims.stride(1) != 1:
-                sims = sims.contiguous()
-            assert tuple(sims.shape) == (Nv, n), "sims_fn must return [N_v, c1 - c0]"
+    gid_all = start_all = None
+    if grouped and any(not it.listed for it in items):
+        gid_all, start_all = _plan_tables(library._plan(chunk_cols), dev)
+    out = []
+    for it in items:
+        if it.listed:
+            c64 = up(it.rows)
+            out.append((up(it.gid) if grouped else None, up(it.start) if grouped else None, (c64.to(torch.int32), c64)))
+        elif grouped:
+            out.append((gid_all[it.rows], start_all[it.start_at:it.start_at + it.n_groups + 1], None))
         else:
-            sims = similarity_matrix(engine, video, chunk.tokens, chunk.mask, chunk.vec, out=sims_buf[:, :n], single_out=single_buf[:, :n])
-        if ev:
-            ev[2].record(cur)
-        if grouped:
-            gid = gid_all[c0:c1]
-            ng = plan["n_groups"][i]
-            rep, score = ops.topk_groups(sims, kk, gid, ng)
-            if w > 1:
-                s0 = plan["start_at"][i]
-                bcol, bscore = ops.group_topw(sims, rep, gid, start_all[s0:s0 + ng + 1], cols_all[:n], w)
-            else:
-                bcol, bscore = rep.view(Nv, kk, 1), score.view(Nv, kk, 1)
-        else:
-            rep, score = ops.topk_groups(sims, kk)
-            bcol, bscore = rep.view(Nv, kk, 1), score.view(Nv, kk, 1)
-        out = state[i % 2]
-        ops.topk_merge(run[0], run[1], bcol, bscore, kk, col_offset=c0, out_col=out[0], out_score=out[1])
-        run = out
-        if not resident:
-            stage.consumed[i % 2].record(cur)
-        if ev:
-            ev[3].record(cur)
-            marks.append(ev)
-        if i + 1 < len(chunks):                                     # the host copies chunk i + 1 under the kernels of chunk i
-            nxt = chunk_encoded(i + 1)
-    if timings is not None:
-        torch.cuda.synchronize()
-        timings["chunks"] = len(chunks)
-        timings["similarities_ms"] = sum(e[1].elapsed_time(e[2]) for e in marks)
-        timings["selection_merge_ms"] = sum(e[2].elapsed_time(e[3]) for e in marks)
-        timings["upload_wait_ms"] = sum(max(0.0, e[0].elapsed_time(e[1])) for e in marks)      # the compute stream's stalls on uploads
-        timings["upload_wait_max_ms"] = max(max(0.0, e[0].elapsed_time(e[1])) for e in marks)
-    return run
+            out.append((None, None, None))
+    return out
 
 
 def _library_attributes(library, dev, want_tags: bool, want_length: bool):
@@ -743,6 +726,19 @@ def _library_attributes(library, dev, want_tags: bool, want_length: bool):
         up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         library._device_attrs[key] = tuple(up(a) for a in library.column_attributes(want_tags, want_length))
     return library._device_attrs[key]
+
+
+def _library_constraints(library, constraints: Constraints, Nv: int, dev):
+    """(the videos' side of made_eligibility, the library's side: `_library_attributes` of what the constraints test)"""
+    nc = constraints.normalized(Nv)
+    return _RowConstraints(nc, dev), _library_attributes(library, dev, nc.uses_tags, nc.uses_length)
+
+
+def _chunk_bits(rc: _RowConstraints, attrs, Nv: int, it: WalkChunk, cols64: Optional[Tensor], out, dev):
+    """made_eligibility on one chunk: the attribute columns at the item's rows (cols64: a listed item's columns on the device);
+    out: `ops.eligibility`'s bits (True allocates, a tensor is written in place)"""
+    part = lambda a: None if a is None else (a.index_select(0, cols64) if it.listed else a[it.rows])
+    return rc.bits(Nv, it.n, *(part(a) for a in attrs), bits=out, device=dev)
 
 
 def _gather_device(t: Tensor, idx32: Tensor, idx64: Tensor) -> Tensor:
@@ -768,82 +764,49 @@ def _kept_columns(library, col_any: Tensor) -> np.ndarray:
     return np.repeat(np.logical_or.reduceat(some, rs[:-1]), np.diff(rs))
 
 
-def _select_constrained(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, chunk_cols: int, sims_fn, timings: Optional[dict],
-                        constraints: Constraints, compact: Optional[bool]):
-    """`_select_streamed` under per-video constraints: what made_topk_groups_masked + made_group_topw_masked give on the whole
-    similarity matrix under made_eligibility's bits.  A union pass over all columns names the kept groups; with compact False the
-    chunk plan is walked and chunks without a kept column are skipped, with compact True a restricted plan holds the kept groups
-    only and every chunk is gathered by its list of library columns (a pinned library then takes the staging copy)."""
-    from .library import restricted_plan
+def _select_walk(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, chunk_cols: int, items: List[WalkChunk], sims_fn,
+                 timings: Optional[dict], rc: Optional[_RowConstraints] = None, attrs=None):
+    """(wcol int32, wscore f32) [N_v, kk, w]: every video's best kk groups among the items' columns and the best w columns of each,
+    library column numbers -- what made_topk_groups + made_group_topw give on the whole similarity matrix, folded over `walk_plan`'s
+    items.  rc / attrs (`_library_constraints`): the same under per-video constraints -- made_eligibility's bits per chunk, then
+    made_topk_groups_masked + made_group_topw_masked.  A listed item is gathered by its columns (a pinned library then takes the
+    staging copy) and its local column numbers are mapped back through them."""
     dev = engine.device
-    Nv, N = len(videos), len(library)
-    nc = constraints.normalized(Nv)
-    rc = _RowConstraints(nc, dev)
-    col_tags, col_length, col_key = _library_attributes(library, dev, nc.uses_tags, nc.uses_length)
+    Nv = len(videos)
+    tables = _walk_tables(library, items, chunk_cols, dev)
+    longest = max((it.n for it in items), default=1)
+    cols_all = torch.arange(longest, device=dev, dtype=torch.int32) if w > 1 else None      # made_group_topw's CSR column list: groups are contiguous
     cur = torch.cuda.current_stream()
-    tu = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timings is not None else None
-    if tu:
-        tu[0].record(cur)
-    col_any = torch.zeros((N + 31) // 32, device=dev, dtype=torch.int32)
-    rc.bits(Nv, N, col_tags, col_length, col_key, bits=None, col_any=col_any, device=dev)
-    keep = _kept_columns(library, col_any)                         # (one host read: the walk is planned from it)
-    if tu:
-        tu[1].record(cur)
-    n_kept = int(keep.sum())
-    if compact is None:                                            # a hook written for (chunk, c0, c1) keeps working
-        compact = False if sims_fn is not None else 2 * n_kept <= N
-    grouped = library.grouped
-    items = []                                                     # (rows: slice or int64 array, n, gid, n_groups, start, col_offset, cols int32 / int64 on the device)
-    if compact:
-        up = lambda a: torch.from_numpy(a).to(dev)
-        for ch in restricted_plan(library, chunk_cols, keep):
-            c64 = up(ch["cols"])
-            items.append((ch["cols"], len(ch["cols"]), up(ch["gid"]) if grouped else None, ch["n_groups"], up(ch["start"]) if grouped else None,
-                          0, (c64.to(torch.int32), c64)))
-        skipped = 0
-    else:
-        plan = library._plan(chunk_cols)
-        gid_all = start_all = None
-        if grouped:
-            gid_all, start_all, _ = _plan_tables(plan, dev)
-        for i, (c0, c1) in enumerate(plan["chunks"]):
-            if not keep[c0:c1].any():
-                continue
-            ng, s0 = plan["n_groups"][i], plan["start_at"][i]
-            items.append((slice(c0, c1), c1 - c0, gid_all[c0:c1] if grouped else None, ng, start_all[s0:s0 + ng + 1] if grouped else None,
-                          c0, None))
-        skipped = len(plan["chunks"]) - len(items)
-    longest = max((it[1] for it in items), default=1)
-    cols_all = torch.arange(longest, device=dev, dtype=torch.int32)
     resident = library.on_device
     stage = None if resident else _staging(library, "chunks", longest, dev, 2)
     has_dur = library.duration is not None
     video = videos.vec.to(dev, torch.float32).contiguous()
-    sims_buf = single_buf = None
+    sims_buf = single_buf = bits_buf = None
     if sims_fn is None:
         sims_buf = torch.empty(Nv, longest, device=dev, dtype=torch.float32)
         single_buf = torch.empty(Nv, longest, device=dev, dtype=torch.float32)
-    bits_buf = torch.empty(Nv, (longest + 31) // 32, device=dev, dtype=torch.int32)
+    if rc is not None:
+        bits_buf = torch.empty(Nv, (longest + 31) // 32, device=dev, dtype=torch.int32)
     state = [(torch.empty(Nv, kk, w, device=dev, dtype=torch.int32), torch.empty(Nv, kk, w, device=dev, dtype=torch.float32))
              for _ in range(2)]
     run = (torch.empty(Nv, 0, w, device=dev, dtype=torch.int32), torch.empty(Nv, 0, w, device=dev, dtype=torch.float32))
-    marks = []                                                      # (reaches the wait, sims start, sims end, eligibility end, merge end) per chunk
+    marks = []                                                      # (reaches the wait, sims start, sims end, eligibility end if any, merge end) per chunk
 
     def chunk_encoded(i: int) -> Encoded:
-        rows, n, cols = items[i][0], items[i][1], items[i][6]
+        rows, n, cols = items[i].rows, items[i].n, tables[i][2]
         arrays = (library.tokens, library.mask, library.vec, library.duration if has_dur else None)
         if resident:
             part = [None if a is None else (a[rows] if cols is None else _gather_device(a, cols[0], cols[1])) for a in arrays]
             return Encoded(tokens=part[0], mask=part[1], vec=part[2], duration=part[3])
         if library.pinned and cols is None:                         # pinned already: no staging copy for a contiguous chunk
-            return stage.upload(i % 2, n, has_dur, src=[None if a is None else a[rows] for a in
-                                                        (library.tokens, library.mask, library.vec, library.duration)])
+            return stage.upload(i % 2, n, has_dur, src=[None if a is None else a[rows] for a in arrays])
         got = stage.fill(i % 2, library, rows)
         return stage.upload(i % 2, got, has_dur)
 
     nxt = chunk_encoded(0) if items else None
-    for i, (rows, n, gid, ng, start, c0, cols) in enumerate(items):
-        chunk = nxt
+    for i, it in enumerate(items):
+        chunk, n, c0 = nxt, it.n, it.col_offset
+        gid, start, cols = tables[i]
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timings is not None else None
         if ev:
             ev[0].record(cur)
@@ -860,18 +823,15 @@ def _select_constrained(engine: MadeEngine, videos: Encoded, library, kk: int, w
             sims = similarity_matrix(engine, video, chunk.tokens, chunk.mask, chunk.vec, out=sims_buf[:, :n], single_out=single_buf[:, :n])
         if ev:
             ev[2].record(cur)
-        part = lambda a: None if a is None else (a[rows] if cols is None else a.index_select(0, cols[1]))
-        bits = rc.bits(Nv, n, part(col_tags), part(col_length), part(col_key), bits=bits_buf[:, :(n + 31) // 32], device=dev)
-        if ev:
-            ev[3].record(cur)
-        if grouped:
-            rep, score = ops.topk_groups_masked(sims, bits, kk, gid, ng)
-            if w > 1:
-                bcol, bscore = ops.group_topw_masked(sims, bits, rep, gid, start, cols_all[:n], w)
-            else:
-                bcol, bscore = rep.view(Nv, kk, 1), score.view(Nv, kk, 1)
+        bits = None
+        if rc is not None:
+            bits = _chunk_bits(rc, attrs, Nv, it, None if cols is None else cols[1], bits_buf[:, :(n + 31) // 32], dev)
+            if ev:
+                ev[3].record(cur)
+        rep, score = _topk_groups(sims, bits, kk, gid, it.n_groups)                  # (gid None, no groups: every column its own)
+        if w > 1:                                                   # (windows: always grouped)
+            bcol, bscore = _group_topw(sims, bits, rep, gid, start, cols_all[:n], w)
         else:
-            rep, score = ops.topk_groups_masked(sims, bits, kk)
             bcol, bscore = rep.view(Nv, kk, 1), score.view(Nv, kk, 1)
         if cols is not None:                                        # local -> library columns (ascending lists keep the tie order)
             bcol = torch.where(bcol < 0, bcol, cols[0][bcol.clamp(min=0).long()]).contiguous()
@@ -883,23 +843,50 @@ def _select_constrained(engine: MadeEngine, videos: Encoded, library, kk: int, w
         if ev:
             ev[4].record(cur)
             marks.append(ev)
-        if i + 1 < len(items):
+        if i + 1 < len(items):                                      # the host copies chunk i + 1 under the kernels of chunk i
             nxt = chunk_encoded(i + 1)
     if not items:                                                   # nothing is eligible for anyone: every slot empty
         run = ops.topk_merge(run[0], run[1], run[0], run[1], kk)
     if timings is not None:
         torch.cuda.synchronize()
-        wait = [max(0.0, e[0].elapsed_time(e[1])) for e in marks]
+        sel = 2 if rc is None else 3                                # the mark the selection starts at
+        wait = [max(0.0, e[0].elapsed_time(e[1])) for e in marks]  # the compute stream's stalls on uploads
         timings["chunks"] = len(items)
-        timings["chunks_skipped"] = skipped
-        timings["columns_scored"] = sum(it[1] for it in items)
-        timings["compact"] = bool(compact)
-        timings["union_ms"] = tu[0].elapsed_time(tu[1])
+        timings["columns_scored"] = sum(it.n for it in items)
         timings["similarities_ms"] = sum(e[1].elapsed_time(e[2]) for e in marks)
-        timings["eligibility_ms"] = sum(e[2].elapsed_time(e[3]) for e in marks)
-        timings["selection_merge_ms"] = sum(e[3].elapsed_time(e[4]) for e in marks)
+        if rc is not None:
+            timings["eligibility_ms"] = sum(e[2].elapsed_time(e[3]) for e in marks)
+        timings["selection_merge_ms"] = sum(e[sel].elapsed_time(e[4]) for e in marks)
         timings["upload_wait_ms"] = sum(wait)
         timings["upload_wait_max_ms"] = max(wait, default=0.0)
+    return run
+
+
+def _select_under_constraints(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, chunk_cols: int, sims_fn,
+                              timings: Optional[dict], constraints: Constraints, compact: Optional[bool]):
+    """`_select_walk` under per-video constraints.  A union pass over all columns names the kept groups; with compact False the chunk
+    plan is walked and chunks without a kept column are skipped, with compact True a restricted plan holds the kept groups only and
+    every chunk is gathered by its list of library columns."""
+    dev = engine.device
+    Nv, N = len(videos), len(library)
+    rc, attrs = _library_constraints(library, constraints, Nv, dev)
+    cur = torch.cuda.current_stream()
+    tu = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timings is not None else None
+    if tu:
+        tu[0].record(cur)
+    col_any = torch.zeros((N + 31) // 32, device=dev, dtype=torch.int32)
+    rc.bits(Nv, N, *attrs, bits=None, col_any=col_any, device=dev)
+    keep = _kept_columns(library, col_any)                         # (one host read: the walk is planned from it)
+    if tu:
+        tu[1].record(cur)
+    if compact is None:                                            # a hook written for (chunk, c0, c1) keeps working
+        compact = False if sims_fn is not None else 2 * int(keep.sum()) <= N
+    items, skipped = walk_plan(library, chunk_cols, keep, compact)
+    run = _select_walk(engine, videos, library, kk, w, chunk_cols, items, sims_fn, timings, rc, attrs)
+    if timings is not None:                                         # (the walk has synchronised)
+        timings["chunks_skipped"] = skipped
+        timings["compact"] = bool(compact)
+        timings["union_ms"] = tu[0].elapsed_time(tu[1])
     return run
 
 
@@ -915,24 +902,19 @@ def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w
     if ev:
         ev[0].record(cur)
     video = videos.vec.to(dev, torch.float32).contiguous()
-    rc = col_tags = col_length = col_key = None
-    if constraints is not None:
-        nc = constraints.normalized(Nv)
-        rc = _RowConstraints(nc, dev)
-        col_tags, col_length, col_key = _library_attributes(library, dev, nc.uses_tags, nc.uses_length)
-    chunks = library._plan(chunk_cols)["chunks"]
+    rc, attrs = _library_constraints(library, constraints, Nv, dev) if constraints is not None else (None, None)
+    items, _ = walk_plan(library, chunk_cols)
     resident = library.on_device
     state = [(torch.empty(Nv, R, 1, device=dev, dtype=torch.int32), torch.empty(Nv, R, 1, device=dev, dtype=torch.float32)) for _ in range(2)]
     run = (torch.empty(Nv, 0, 1, device=dev, dtype=torch.int32), torch.empty(Nv, 0, 1, device=dev, dtype=torch.float32))
-    part = lambda a, c0, c1: None if a is None else a[c0:c1]
-    for i, (c0, c1) in enumerate(chunks):
+    for i, it in enumerate(items):
         if resident:
-            vec = library.vec[c0:c1]
+            vec = library.vec[it.rows]
         else:
-            v = library.vec[c0:c1]
+            v = library.vec[it.rows]
             vec = (v if isinstance(v, Tensor) else torch.from_numpy(np.array(v))).to(dev)
-        bits = None if rc is None else rc.bits(Nv, c1 - c0, part(col_tags, c0, c1), part(col_length, c0, c1), part(col_key, c0, c1), device=dev)
-        run = _shortlist_fold(engine, video, vec.to(torch.float32).contiguous(), bits, R, c0, run, state[i % 2])
+        bits = None if rc is None else _chunk_bits(rc, attrs, Nv, it, None, True, dev)
+        run = _shortlist_fold(engine, video, vec.to(torch.float32).contiguous(), bits, R, it.col_offset, run, state[i % 2])
     cand_col, cand_cos = run[0].view(Nv, R), run[1].view(Nv, R)
     if ev:
         ev[1].record(cur)
@@ -959,7 +941,7 @@ def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w
     if ev:
         ev[3].record(cur)
         torch.cuda.synchronize()
-        timings["chunks"] = len(chunks)
+        timings["chunks"] = len(items)
         timings["shortlist_ms"] = ev[0].elapsed_time(ev[1])
         timings["pair_score_ms"] = ev[1].elapsed_time(ev[2])
         timings["selection_ms"] = ev[2].elapsed_time(ev[3])
@@ -979,7 +961,8 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     Selection walks library.chunk_plan(chunk_cols): per chunk the similarities of its columns (sims_fn(chunk, c0, c1) -> [N_v, c1 - c0]
     if given, else `similarity_matrix` on the chunk), made_topk_groups / made_group_topw over the chunk's groups, and made_topk_merge
     into the running list; a host library's chunks are uploaded through two pinned staging sets on a copy stream, under the kernels
-    of the chunk before.  Localization runs per video_batch videos on the distinct selected columns only.  track: the library
+    of the chunk before (`walk_plan` names the chunks, `_select_walk` is the loop over them, with or without constraints).
+    Localization runs per video_batch videos on the distinct selected columns only.  track: the library
     column without windows, the track's index with windows; `to_records` takes library.ids.  timings: a dict that receives the
     phases' milliseconds, and columns_scored / chunks_skipped (this synchronises the device; for measurements).
     constraints: per-video `Constraints` on the library's tags / length and exclusion lists of tracks -- the same Grounding as
@@ -1003,13 +986,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     if N == 0:
         raise ValueError("the library is empty")
     windows = library.windows
-    w, n = 1, 1
-    if windows is not None:
-        w, n = int(windows_per_track), int(moments)
-        if not 1 <= w <= 16:
-            raise ValueError(f"windows_per_track = {w}: must lie in [1, 16]")
-        if n < 1:
-            raise ValueError(f"moments = {n}: must be >= 1")
+    w, n = _window_counts(windows_per_track, moments) if windows is not None else (1, 1)
     kk = max(1, min(int(k), library.n_groups))
     video_batch = max(1, int(video_batch))
     t0 = torch.cuda.Event(enable_timing=True) if timings is not None else None
@@ -1017,11 +994,12 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     if shortlist is not None:
         wcol, wscore, cand = _select_shortlisted(engine, videos, library, kk, w, int(chunk_cols), min(shortlist, N), constraints, timings)
     elif constraints is None:
-        wcol, wscore = _select_streamed(engine, videos, library, kk, w, int(chunk_cols), sims_fn, timings)
+        items, skipped = walk_plan(library, int(chunk_cols))
+        wcol, wscore = _select_walk(engine, videos, library, kk, w, int(chunk_cols), items, sims_fn, timings)
         if timings is not None:
-            timings["columns_scored"], timings["chunks_skipped"] = N, 0
+            timings["chunks_skipped"] = skipped
     else:
-        wcol, wscore = _select_constrained(engine, videos, library, kk, w, int(chunk_cols), sims_fn, timings, constraints, compact)
+        wcol, wscore = _select_under_constraints(engine, videos, library, kk, w, int(chunk_cols), sims_fn, timings, constraints, compact)
     if t0 is not None:
         t0.record()
     rep, score = wcol[:, :, 0].contiguous(), wscore[:, :, 0].contiguous()

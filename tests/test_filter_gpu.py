@@ -440,7 +440,8 @@ def test_ground_library_is_ground_under_constraints(case, name, dtype, tmp_path)
     lib.save(str(tmp_path / "lib"))
     loaded = MusicLibrary.load(str(tmp_path / "lib"), mmap=True)
     assert isinstance(loaded.tokens, np.memmap) and np.array_equal(loaded.tags, lib.tags)
-    for source in (lib.to("cuda:0"), loaded.pin(), loaded):
+    sources = (lib.to("cuda:0"), loaded.pin(), loaded)
+    for source in sources:
         for compact in (False, True):
             t = {}
             got = ground_library(eng, V, source, k, chunk_cols=chunk_cols, video_batch=5, sims_fn=_hook(full), constraints=c,
@@ -448,6 +449,16 @@ def test_ground_library_is_ground_under_constraints(case, name, dtype, tmp_path)
             TL._assert_same_grounding(got, want)
             assert t["compact"] == compact and t["chunks"] > 1
     assert (want.track >= 0).any()
+    # admit everything: the unconstrained call in every field, on the model's own similarities and on the hook's
+    for source in (sources[0], sources[2]):
+        for fn in (None, _hook(full)):
+            plain = ground_library(eng, V, source, k, chunk_cols=chunk_cols, video_batch=5, sims_fn=fn, **kw)
+            for compact in (False, True):
+                t = {}
+                got = ground_library(eng, V, source, k, chunk_cols=chunk_cols, video_batch=5, sims_fn=fn, constraints=Constraints(),
+                                     compact=compact, timings=t, **kw)
+                TL._assert_same_grounding(got, plain)
+                assert t["compact"] == compact and t["chunks"] > 1 and t["columns_scored"] == len(lib) and t["chunks_skipped"] == 0
 
 
 @pytest.mark.parametrize("name,dtype", [("native", "f32"), ("Q3", "bf16")])

@@ -12,7 +12,8 @@ import torch
 import library_ref as LR
 from mgsv_amd import _lib
 from mgsv_amd.engine import Encoded
-from mgsv_amd.library import MusicLibrary, MusicLibraryWriter, contiguous_order
+from mgsv_amd.grounding import walk_plan
+from mgsv_amd.library import MusicLibrary, MusicLibraryWriter, contiguous_order, restricted_plan
 from mgsv_amd.windows import Windows
 
 
@@ -176,6 +177,64 @@ def test_chunk_plan_properties():
     with pytest.raises(ValueError, match="32768"):                # one LDS slot per group: refused with groups ...
         lib.chunk_plan(32769)
     assert LR.table_library(col_group, grouped=False).chunk_plan(32769) == [(0, N)]  # ... and not without
+
+
+def _same_item(it, rows, gid, n_groups, start, col_offset, listed):
+    if listed:
+        assert it.listed and it.rows.dtype == np.int64 and np.array_equal(it.rows, rows) and it.start_at is None
+    else:
+        assert not it.listed and it.rows == rows
+    assert it.n == len(gid) and it.n_groups == n_groups and it.col_offset == col_offset
+    assert it.gid.dtype == np.int32 and np.array_equal(it.gid, gid) and it.start.dtype == np.int32 and np.array_equal(it.start, start)
+
+
+@pytest.mark.parametrize("grouped", [True, False])
+@pytest.mark.parametrize("chunk_cols", [5, 37, 300])
+def test_walk_plan_is_the_plan_the_kept_chunks_or_the_restricted_plan(chunk_cols, grouped):
+    rng = np.random.default_rng(4)
+    N = 300
+    col_group = LR.contiguous_groups(rng, N)
+    lib = LR.table_library(col_group, grouped=grouped)
+    p = lib._plan(chunk_cols)
+    chunks = p["chunks"]
+
+    def plan_item(it, i):                                           # the plan's chunk i, with its tables
+        c0, c1 = chunks[i]
+        s0, ng = p["start_at"][i], p["n_groups"][i]
+        _same_item(it, slice(c0, c1), p["gid"][c0:c1], ng, p["start"][s0:s0 + ng + 1], c0, False)
+        assert it.start_at == s0
+
+    # no mask: the plan
+    items, skipped = walk_plan(lib, chunk_cols)
+    assert skipped == 0 and len(items) == len(chunks)
+    for i, it in enumerate(items):
+        plan_item(it, i)
+    keep = rng.random(N) < 0.05
+    assert keep.any() and (chunk_cols == N or not all(keep[c0:c1].any() for c0, c1 in chunks))
+    # a mask, not compacted: the chunks that hold a kept column, in order
+    items, skipped = walk_plan(lib, chunk_cols, keep, False)
+    held = [i for i, (c0, c1) in enumerate(chunks) if keep[c0:c1].any()]
+    assert len(items) == len(held) and skipped == len(chunks) - len(held)
+    for it, i in zip(items, held):
+        plan_item(it, i)
+    # compacted: the restricted plan
+    items, skipped = walk_plan(lib, chunk_cols, keep, True)
+    want = restricted_plan(lib, chunk_cols, keep)
+    assert skipped == 0 and len(items) == len(want) > 0
+    for it, ch in zip(items, want):
+        _same_item(it, ch["cols"], ch["gid"], ch["n_groups"], ch["start"], 0, True)
+    # nothing kept: nothing to walk
+    none = np.zeros(N, bool)
+    assert walk_plan(lib, chunk_cols, none, False) == ([], len(chunks)) and walk_plan(lib, chunk_cols, none, True) == ([], 0)
+    # one column of one group: one item, holding that whole group
+    g = int(col_group[N // 2])
+    members = np.flatnonzero(col_group == g)
+    one = np.zeros(N, bool)
+    one[members[-1]] = True
+    (it,), skipped = walk_plan(lib, chunk_cols, one, False)
+    assert skipped == len(chunks) - 1 and it.rows.start <= members[0] and members[-1] < it.rows.stop
+    (it,), _ = walk_plan(lib, chunk_cols, one, True)
+    _same_item(it, members, np.zeros(len(members), np.int32), 1, [0, len(members)], 0, True)
 
 
 # ---------------------------------------------------------------------------------------------- the writer
