@@ -1135,6 +1135,24 @@ int made_topk_merge(const int32_t* a_col, const float* a_score, int64_t Ka, cons
 int made_topk_candidates(const int32_t* cand_col, const float* cand_score, int64_t Nv, int64_t R, const int32_t* col_group, int64_t N,
                          int64_t n_groups, int64_t K, int64_t w, int32_t* out_col, float* out_score, void* stream);
 
+/* made_mmr_select: the greedy re-selection of k results among a pool of P selected groups, for every video independently
+ * (`ground(..., diversity= / max_similarity= / pool=)`).  row [Nv, P] int32: the row of `vec` that holds the vector of slot j
+ * (< 0 or >= n_rows: the slot is absent), score [Nv, P] f32, vec [n_rows, D] f32 with contiguous rows, 16-byte aligned.  Every
+ * present slot keeps m_j, the largest cosine between its vector and the vector of a slot picked so far.  Each of k steps picks,
+ * among the present slots neither picked nor dropped, the one with the largest objective score_j - mu * m_j (score_j before the
+ * first pick; one f32 fused multiply-add), compared in made_topk_groups' order (descending, -inf below every number, NaN lowest,
+ * -0 equals +0), ties to the smaller j; after a pick every m_j is updated and every unpicked slot with m_j > tau is dropped for
+ * good; the steps end when no slot is left.  The cosine is a.b / (|a| |b|) in f32 from norms the kernel computes itself; a norm
+ * that is zero or not finite gives 0.  pos [Nv, k] int32: the picked slots in pick order, -1 past the last pick; redundancy
+ * [Nv, k] f32: m_j of every pick when it was picked, NaN for the first pick and past the last.  With mu = 0 and tau = +inf, and
+ * slots in the selection's order, pos is 0, 1, ... over the present slots.  One workgroup per video; the pool's rows are
+ * gathered into LDS once when P * D * 4 <= 144 KiB and re-read from `vec` in every step otherwise -- every dot product is summed
+ * in one fixed order, so the two forms, any launch and any placement of the rows in `vec` give the same bits.  No atomics, no
+ * workspace.  D in {128, 256, 512} (MADE_ERR_UNSUPPORTED otherwise), 1 <= k <= P <= 256, mu finite and >= 0, tau > -1; the
+ * outputs must not overlap the inputs or each other. */
+int made_mmr_select(const int32_t* row, const float* score, const float* vec, int64_t n_rows, int64_t D, int64_t Nv, int64_t P, int64_t k,
+                    float mu, float tau, int32_t* pos, float* redundancy, void* stream);
+
 /* made_merge_moments: the moments of P (video, track) entries on the track's own time axis from the moments of the track's w
  * windows, one wave per entry, no atomics.  win_col / win_score [P, w] = made_group_topw's columns (-1: no window) and
  * similarities; cand [P, w, Q, 3] f32 = every query's (start, end, foreground probability) in seconds on its window's axis,

@@ -20,6 +20,10 @@ suppression of overlapping ones -- the same passage seen through two overlapping
 host data alone (the library's plan; under constraints its chunks that hold a kept column, or a restricted plan of column lists),
 and `_select_walk` is the one loop that uploads, scores, selects and merges them -- constrained or not, contiguous or listed.
 
+With `diversity` / `max_similarity` the selection returns a pool of P >= k groups per video and `made_mmr_select` re-selects k of them
+greedily -- score minus a penalty for the largest cosine with a group picked before, groups too close to a pick dropped -- so that
+near-duplicate tracks do not fill the top k; only the k kept are localized (`check_diversity`, `_diversify`).
+
 A pair's localization depends on that pair's video and track only (every kernel after the towers computes a sample's rows
 independently of the rest of the batch), so the moment found in the ground-truth track is the one the batched evaluation scores.
 """
@@ -56,6 +60,8 @@ class Grounding:
     windows: Optional[Windows] = None
     cand_col: Optional[Tensor] = None      # grounded with a shortlist: [N_v, R] int32, the library columns that were scored (-1: none) ...
     cand_score: Optional[Tensor] = None    # ... and their exact scores, f32 (NaN where there is no candidate)
+    pool_rank: Optional[Tensor] = None     # grounded with diversity= / max_similarity=: [N_v, k] int32, every result's rank in the pool (-1: none) ...
+    redundancy: Optional[Tensor] = None    # ... and its largest cosine with a result before it, f32 (NaN for the first result and where there is none)
 
     @property
     def k(self) -> int:
@@ -65,10 +71,12 @@ class Grounding:
         """One JSON-ready dict per video: {"video_id", "tracks": [{"music_id", "score", "start", "end", "confidence"}, ...]}
         (music_ids indexed by track column; entries past the number of groups are left out).  Grounded over windows, music_ids is
         indexed by track and every track holds "moments": [{"start", "end", "confidence", "window_offset"}, ...] instead of one
-        start / end / confidence."""
+        start / end / confidence.  Re-selected for diversity (`pool_rank` is set), every track also holds "pool_rank" and "redundancy"
+        (None for a video's first track, which has nothing before it)."""
         if self.windows is not None:
             return self._window_records(video_ids, music_ids)
         tr, sc, st, en, cf = (t.cpu().numpy() for t in (self.track, self.score, self.start, self.end, self.confidence))
+        extra = self._diversity_fields()
         out = []
         for v, vid in enumerate(video_ids):
             ent = []
@@ -78,14 +86,22 @@ class Grounding:
                     continue
                 c = float(cf[v, j])
                 ent.append(dict(music_id=music_ids[m], score=float(sc[v, j]), start=float(st[v, j]), end=float(en[v, j]),
-                                confidence=None if math.isnan(c) else c))
+                                confidence=None if math.isnan(c) else c, **extra(v, j)))
             out.append(dict(video_id=vid, tracks=ent))
         return out
+
+    def _diversity_fields(self):
+        """f(v, j) -> {"pool_rank", "redundancy"} of result j of video v; nothing when the results were not re-selected"""
+        if self.pool_rank is None:
+            return lambda v, j: {}
+        pr, rd = self.pool_rank.cpu().numpy(), self.redundancy.cpu().numpy()
+        return lambda v, j: dict(pool_rank=int(pr[v, j]), redundancy=None if math.isnan(rd[v, j]) else float(rd[v, j]))
 
     def _window_records(self, video_ids: Sequence, music_ids: Sequence) -> List[dict]:
         tr, sc = self.track.cpu().numpy(), self.score.cpu().numpy()
         Nv, k = tr.shape
         st, en, cf, wi = (t.cpu().numpy().reshape(Nv, k, -1) for t in (self.start, self.end, self.confidence, self.window))
+        extra = self._diversity_fields()
         out = []
         for v, vid in enumerate(video_ids):
             ent = []
@@ -100,7 +116,7 @@ class Grounding:
                     c = float(cf[v, j, i])
                     moms.append(dict(start=float(st[v, j, i]), end=float(en[v, j, i]), confidence=None if math.isnan(c) else c,
                                      window_offset=float(self.windows.offset[wi[v, j, i]])))
-                ent.append(dict(music_id=music_ids[m], score=float(sc[v, j]), moments=moms))
+                ent.append(dict(music_id=music_ids[m], score=float(sc[v, j]), moments=moms, **extra(v, j)))
             out.append(dict(video_id=vid, tracks=ent))
         return out
 
@@ -332,6 +348,74 @@ def check_shortlist(cfg, shortlist, explicit_sims: bool) -> Optional[int]:
     return R
 
 
+# ---------------------------------------------------------------------------------------------- diverse results
+POOL_MAX = 256                          # made_mmr_select's P limit (= made_topk_groups' K limit)
+
+
+def check_diversity(k, diversity, max_similarity, pool):
+    """(mu, tau, P) when `diversity` or `max_similarity` is given, None when neither is: mu = diversity (0 when None; finite, >= 0),
+    tau = max_similarity (+inf when None; in (-1, 1]), P = pool (min(256, 4 k) when None; an integer with k <= P <= 256).
+    ValueError for a value outside its range and for a pool without either of the other two."""
+    if diversity is None and max_similarity is None:
+        if pool is not None:
+            raise ValueError("pool is the depth of the diversity re-selection: give diversity= or max_similarity= with it")
+        return None
+    mu, tau = 0.0, float("inf")
+    if diversity is not None:
+        mu = float(diversity)
+        if not (math.isfinite(mu) and mu >= 0.0):
+            raise ValueError(f"diversity = {diversity!r}: must be finite and >= 0")
+    if max_similarity is not None:
+        tau = float(max_similarity)
+        if not -1.0 < tau <= 1.0:
+            raise ValueError(f"max_similarity = {max_similarity!r}: must lie in (-1, 1]")
+    kk = max(1, int(k))
+    if pool is None:
+        P = min(POOL_MAX, 4 * kk)
+    else:
+        P = int(pool)
+        if P != pool:
+            raise ValueError(f"pool = {pool!r}: must be an integer")
+    if not kk <= P <= POOL_MAX:
+        raise ValueError(f"pool = {P}: must be an integer with k <= pool <= {POOL_MAX} (k = {kk})")
+    return mu, tau, P
+
+
+def _pool_size(div, kk: int, G: int) -> int:
+    """how many groups the selection returns: kk, or with a re-selection the pool, clamped to the G groups as kk is"""
+    return kk if div is None else max(kk, min(div[2], G))
+
+
+def _diversify(wcol: Tensor, wscore: Tensor, table: Tensor, row: Tensor, kk: int, mu: float, tau: float):
+    """The pool's selection wcol / wscore [N_v, P, w] re-selected to (wcol, wscore [N_v, kk, w], pos int32 [N_v, kk], redundancy f32
+    [N_v, kk]): made_mmr_select on the slots' scores wscore[:, :, 0] and vectors table[row] (row [N_v, P] int32, < 0: slot absent),
+    then the entries of the picked slots in pick order; -1 / -inf where nothing was picked."""
+    pos, red = ops.mmr_select(row.contiguous(), wscore[:, :, 0].contiguous(), table, kk, mu, tau)
+    none = (pos < 0).unsqueeze(-1)
+    idx = pos.clamp(min=0).long().unsqueeze(-1).expand(-1, -1, wcol.shape[2])
+    col = torch.where(none, torch.full_like(wcol[:, :kk], -1), torch.gather(wcol, 1, idx))
+    score = torch.where(none, torch.full_like(wscore[:, :kk], float("-inf")), torch.gather(wscore, 1, idx))
+    return col.contiguous(), score.contiguous(), pos, red
+
+
+def _diversify_resident(wcol: Tensor, wscore: Tensor, vec: Tensor, kk: int, div):
+    """`_diversify` against a vector table on the device: a slot's row is its representative column"""
+    return _diversify(wcol, wscore, vec.to(wcol.device, torch.float32).contiguous(), wcol[:, :, 0], kk, div[0], div[1])
+
+
+def _diversify_host(wcol: Tensor, wscore: Tensor, library, kk: int, div):
+    """`_diversify` against a host library's `vec`: the distinct representative columns of the call are read and uploaded once, and a
+    slot's row is its column's place among them (the kernel's result does not depend on where a row sits in the table)"""
+    rep = wcol[:, :, 0]
+    uniq, inv = torch.unique(torch.where(rep < 0, torch.zeros_like(rep), rep), return_inverse=True)
+    rows = uniq.cpu().numpy().astype(np.int64)                     # (one host read, as the localization's gather)
+    v = library.vec
+    part = v[torch.from_numpy(rows)] if isinstance(v, Tensor) else torch.from_numpy(np.ascontiguousarray(np.take(v, rows, axis=0)))
+    table = part.to(wcol.device, torch.float32).contiguous()
+    row = torch.where(rep < 0, torch.full_like(rep, -1), inv.to(torch.int32))
+    return _diversify(wcol, wscore, table, row, kk, div[0], div[1])
+
+
 def pair_csr(cand_col: Tensor):
     """The pairs (video i, column cand_col[i, j] >= 0) of a candidate table [N_v, R] (an integer tensor, on any device), sorted by
     column: (cols int64 [U] the distinct columns ascending, start int32 [U + 1], video int32 [P] ascending inside a column, slot
@@ -398,7 +482,8 @@ def _device_fetch(tokens: Tensor, mask: Tensor):
 def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Optional[Tensor] = None, group_id=None,
            pair_batch: int = 64, windows: Optional[Windows] = None, windows_per_track: int = 1, moments: int = 1,
            nms_iou: float = 0.5, constraints: Optional[Constraints] = None, tags=None, length=None,
-           shortlist: Optional[int] = None) -> Grounding:
+           shortlist: Optional[int] = None, diversity: Optional[float] = None, max_similarity: Optional[float] = None,
+           pool: Optional[int] = None) -> Grounding:
     """Each video's best k tracks (groups of columns sharing a music id when group_id [N_m] is given) and the moment in each.
     constraints: per-video `Constraints` on the tracks' `tags` (int64 [tracks]) and `length` (f32 seconds [tracks]; default: the
     durations) -- the selection then runs on every row with its ineligible columns removed (made_eligibility, then the masked
@@ -409,10 +494,16 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     shortlist = R (1 .. 256; the score must be cosine + X-Pool): every video's R eligible columns of largest cosine are found first
     (made_topk_groups on `dual_sims`), only those pairs get the X-Pool score (made_xpool_sims_pairs on the distinct shortlisted
     columns), and the selection above runs on each row's R exact scores with every other column ineligible (made_topk_candidates).
-    `Grounding.cand_col` / `cand_score` [N_v, R] report what was scored."""
+    `Grounding.cand_col` / `cand_score` [N_v, R] report what was scored.
+    diversity = mu (>= 0) / max_similarity = tau (in (-1, 1]) / pool = P (k <= P <= 256, default min(256, 4 k)): the selection returns
+    each video's best P groups, and made_mmr_select picks k of them greedily -- each time the group with the largest score - mu *
+    (largest cosine of its representative column's `vec` with a group picked before), groups whose cosine with a pick exceeds tau
+    dropped.  Only the k kept are localized; `score` stays the similarity, `Grounding.pool_rank` / `redundancy` [N_v, k] report each
+    result's rank in the pool and that largest cosine."""
     dev = engine.device
     Nv, Nm = len(videos), len(music)
     shortlist = check_shortlist(engine.cfg, shortlist, sims is not None)
+    div = check_diversity(k, diversity, max_similarity, pool)
     if shortlist is None:
         if sims is None:
             sims = similarity_matrix(engine, videos.vec, music.tokens, music.mask, music.vec)
@@ -440,19 +531,25 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
         cand = (ccol, _score_candidates(engine, video, ccol, ccos, _device_fetch(tokens, music.mask.to(dev, torch.float32).contiguous()), 4096))
     if windows is not None:
         return _ground_windows(engine, videos, music, k, sims, group_id, pair_batch, windows, windows_per_track, moments, float(nms_iou),
-                               bits, cand)
+                               bits, cand, div)
     gid, G = _group_tensor(group_id, Nm, dev)
     kk = max(1, min(int(k), G))
+    ks = _pool_size(div, kk, G)
     if cand is not None:
-        track, score = (t.view(Nv, kk) for t in ops.topk_candidates(cand[0], cand[1], kk, 1, gid, G, n_cols=Nm))
+        track, score = (t.view(Nv, ks) for t in ops.topk_candidates(cand[0], cand[1], ks, 1, gid, G, n_cols=Nm))
     else:
-        track, score = _topk_groups(sims, bits, kk, gid, G)
+        track, score = _topk_groups(sims, bits, ks, gid, G)
+    pool_rank = redundancy = None
+    if div is not None:
+        track, score, pool_rank, redundancy = _diversify_resident(track.view(Nv, ks, 1), score.view(Nv, ks, 1), music.vec, kk, div)
+        track, score = track.view(Nv, kk), score.view(Nv, kk)
     vi = torch.arange(Nv, device=dev, dtype=torch.int32).repeat_interleave(kk)
     mi = track.reshape(-1)
     mi = torch.where(mi < 0, torch.zeros_like(mi), mi)             # (no track: localized against track 0, reported as -1 / NaN)
     start, end, conf = _pair_moments(engine, videos, music, vi, mi, track.reshape(-1) < 0, pair_batch)
     return Grounding(track=track, score=score, start=start.view(Nv, kk), end=end.view(Nv, kk), confidence=conf.view(Nv, kk),
-                     cand_col=None if cand is None else cand[0], cand_score=None if cand is None else cand[1])
+                     cand_col=None if cand is None else cand[0], cand_score=None if cand is None else cand[1],
+                     pool_rank=pool_rank, redundancy=redundancy)
 
 
 def _pad_pairs(vi: Tensor, mi: Tensor, min_pairs: int):
@@ -533,7 +630,7 @@ def _pair_candidates(engine: MadeEngine, videos: Encoded, music: Encoded, vi: Te
 
 
 def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Tensor, group_id, pair_batch: int,
-                    windows: Windows, windows_per_track, moments, nms_iou: float, bits: Optional[Tensor] = None, cand=None) -> Grounding:
+                    windows: Windows, windows_per_track, moments, nms_iou: float, bits: Optional[Tensor] = None, cand=None, div=None) -> Grounding:
     dev = engine.device
     Nv, Nm = len(videos), len(music)
     if len(windows) != Nm:
@@ -550,12 +647,17 @@ def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int,
     as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     gid = as_dev(col_group)
     kk = max(1, min(int(k), G))
+    ks = _pool_size(div, kk, G)
     if cand is not None:                                           # a track's score: its best SHORTLISTED window's
-        wcol, wscore = ops.topk_candidates(cand[0], cand[1], kk, w, gid, G)
+        wcol, wscore = ops.topk_candidates(cand[0], cand[1], ks, w, gid, G)
         rep, score = wcol[:, :, 0].contiguous(), wscore[:, :, 0].contiguous()
     else:
-        rep, score = _topk_groups(sims, bits, kk, gid, G)          # ... its best window's similarity (under bits: its best ELIGIBLE window's)
+        rep, score = _topk_groups(sims, bits, ks, gid, G)          # ... its best window's similarity (under bits: its best ELIGIBLE window's)
         wcol, wscore = _group_topw(sims, bits, rep, gid, as_dev(start), as_dev(cols), w)
+    pool_rank = redundancy = None
+    if div is not None:                                            # a track's vector: its best window's
+        wcol, wscore, pool_rank, redundancy = _diversify_resident(wcol, wscore, music.vec, kk, div)
+        rep, score = wcol[:, :, 0].contiguous(), wscore[:, :, 0].contiguous()
     vi = torch.arange(Nv, device=dev, dtype=torch.int32).repeat_interleave(kk * w)
     mi = wcol.reshape(-1)
     mi = torch.where(mi < 0, torch.zeros_like(mi), mi)             # (no window: localized against column 0, left out by the merge)
@@ -564,7 +666,8 @@ def _ground_windows(engine: MadeEngine, videos: Encoded, music: Encoded, k: int,
     track = _window_tracks(rep, as_dev(windows.track))
     shape = (Nv, kk) if n == 1 else (Nv, kk, n)
     return Grounding(track=track, score=score, start=st.view(shape), end=en.view(shape), confidence=cf.view(shape), window=wi.view(shape),
-                     windows=windows, cand_col=None if cand is None else cand[0], cand_score=None if cand is None else cand[1])
+                     windows=windows, cand_col=None if cand is None else cand[0], cand_score=None if cand is None else cand[1],
+                     pool_rank=pool_rank, redundancy=redundancy)
 
 
 def _window_moments(engine: MadeEngine, videos: Encoded, music: Encoded, vi: Tensor, mi: Tensor, wcol: Tensor, wscore: Tensor,
@@ -953,7 +1056,8 @@ def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w
 def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_batch: int = 64, windows_per_track: int = 1,
                    moments: int = 1, nms_iou: float = 0.5, chunk_cols: int = 4096, video_batch: int = 1024, sims_fn=None,
                    timings: Optional[dict] = None, constraints: Optional[Constraints] = None, compact: Optional[bool] = None,
-                   shortlist: Optional[int] = None) -> Grounding:
+                   shortlist: Optional[int] = None, diversity: Optional[float] = None, max_similarity: Optional[float] = None,
+                   pool: Optional[int] = None) -> Grounding:
     """`ground()` for a stored library (mgsv_amd.library.MusicLibrary: host arrays, a memory-mapped directory, or device tensors):
     the same Grounding, bit for bit, as
         ground(engine, videos, library.as_encoded(dev), k, group_id=library.group_id, windows=library.windows, ...)
@@ -974,10 +1078,14 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     shortlist = R: `ground(..., shortlist=R)` for the stored library, bit for bit.  Stage 1 walks the chunk plan reading only `vec`
     (and the attribute arrays under constraints) -- cosines, the best R eligible columns per chunk, made_topk_merge; stage 2 fetches
     the tokens of the distinct shortlisted columns alone, in chunks of at most chunk_cols, and scores the listed pairs; the selection
-    is made_topk_candidates.  timings then receives shortlist_ms, pairs_scored, columns_projected, pair_score_ms, selection_ms."""
+    is made_topk_candidates.  timings then receives shortlist_ms, pairs_scored, columns_projected, pair_score_ms, selection_ms.
+    diversity / max_similarity / pool: `ground(..., diversity=, max_similarity=, pool=)` for the stored library, bit for bit: the walk
+    selects the pool, made_mmr_select re-selects k of it against the library's `vec` (a host library: the distinct representative
+    columns of the call, read and uploaded once), and only the k kept are localized.  timings then receives diversify_ms."""
     c = engine.cfg
     dev = engine.device
     shortlist = check_shortlist(c, shortlist, sims_fn is not None)
+    div = check_diversity(k, diversity, max_similarity, pool)
     if c.moment_query_type == "xpool":
         raise NotImplementedError("moment_query_type=xpool: the decoder query is the track's pooled vector averaged over the videos of "
                                   "the batch (reference model/model_Uni.py:222-223), a property of the batch with no per-pair meaning")
@@ -988,18 +1096,32 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     windows = library.windows
     w, n = _window_counts(windows_per_track, moments) if windows is not None else (1, 1)
     kk = max(1, min(int(k), library.n_groups))
+    ks = _pool_size(div, kk, library.n_groups)
     video_batch = max(1, int(video_batch))
     t0 = torch.cuda.Event(enable_timing=True) if timings is not None else None
     cand = None
     if shortlist is not None:
-        wcol, wscore, cand = _select_shortlisted(engine, videos, library, kk, w, int(chunk_cols), min(shortlist, N), constraints, timings)
+        wcol, wscore, cand = _select_shortlisted(engine, videos, library, ks, w, int(chunk_cols), min(shortlist, N), constraints, timings)
     elif constraints is None:
         items, skipped = walk_plan(library, int(chunk_cols))
-        wcol, wscore = _select_walk(engine, videos, library, kk, w, int(chunk_cols), items, sims_fn, timings)
+        wcol, wscore = _select_walk(engine, videos, library, ks, w, int(chunk_cols), items, sims_fn, timings)
         if timings is not None:
             timings["chunks_skipped"] = skipped
     else:
-        wcol, wscore = _select_under_constraints(engine, videos, library, kk, w, int(chunk_cols), sims_fn, timings, constraints, compact)
+        wcol, wscore = _select_under_constraints(engine, videos, library, ks, w, int(chunk_cols), sims_fn, timings, constraints, compact)
+    pool_rank = redundancy = None
+    if div is not None:
+        td = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timings is not None else None
+        if td:
+            td[0].record()
+        if library.on_device:
+            wcol, wscore, pool_rank, redundancy = _diversify_resident(wcol, wscore, library.vec, kk, div)
+        else:
+            wcol, wscore, pool_rank, redundancy = _diversify_host(wcol, wscore, library, kk, div)
+        if td:
+            td[1].record()
+            torch.cuda.synchronize()
+            timings["diversify_ms"] = td[0].elapsed_time(td[1])
     if t0 is not None:
         t0.record()
     rep, score = wcol[:, :, 0].contiguous(), wscore[:, :, 0].contiguous()
@@ -1047,9 +1169,11 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
         timings["localization_ms"] = t0.elapsed_time(t1)
     cc, cs = (None, None) if cand is None else cand
     if windows is None:
-        return Grounding(track=rep, score=score, start=start, end=end, confidence=conf, cand_col=cc, cand_score=cs)
+        return Grounding(track=rep, score=score, start=start, end=end, confidence=conf, cand_col=cc, cand_score=cs,
+                         pool_rank=pool_rank, redundancy=redundancy)
     return Grounding(track=_window_tracks(rep, track_of_col), score=score, start=start, end=end, confidence=conf,
-                     window=torch.cat([p[3] for p in parts]), windows=windows, cand_col=cc, cand_score=cs)
+                     window=torch.cat([p[3] for p in parts]), windows=windows, cand_col=cc, cand_score=cs,
+                     pool_rank=pool_rank, redundancy=redundancy)
 
 
 def moment_iou(start: Tensor, end: Tensor, gt_moment: Tensor, m_duration: Tensor, max_m_duration: float) -> Tensor:

@@ -1156,3 +1156,20 @@ def merge_moments(cand: Tensor, win_col: Tensor, win_score: Tensor, offset: Tens
                                    float(max_m_duration), float(nms_iou), n, _p(start), _p(end), _p(conf), _p(window), _stream()),
           "made_merge_moments")
     return start, end, conf, window
+
+
+def mmr_select(row: Tensor, score: Tensor, vec: Tensor, k: int, mu: float = 0.0, tau: float = float("inf")):
+    """made_mmr_select: the greedy re-selection of k of every video's P pool slots -- row [Nv, P] int32 (the slot's row of vec, < 0:
+    absent), score [Nv, P] f32, vec [n_rows, D] f32 contiguous -> (pos [Nv, k] int32 the picked slots in pick order, -1 past the last;
+    redundancy [Nv, k] f32 each pick's largest cosine with an earlier pick, NaN for the first pick and past the last).  A step picks
+    the largest score - mu * (largest cosine with a pick so far); a slot whose largest cosine exceeds tau is dropped."""
+    assert row.dim() == 2 and row.dtype == torch.int32 and score.dtype == torch.float32 and row.shape == score.shape
+    assert row.is_contiguous() and score.is_contiguous()
+    assert vec.dim() == 2 and vec.dtype == torch.float32 and vec.is_contiguous() and vec.device == row.device == score.device
+    Nv, P = row.shape
+    k = int(k)
+    pos = torch.empty(Nv, k, device=row.device, dtype=torch.int32)
+    red = torch.empty(Nv, k, device=row.device, dtype=torch.float32)
+    check(lib().made_mmr_select(_p(row), _p(score), _p(vec) if vec.shape[0] else None, vec.shape[0], vec.shape[1], Nv, P, k, float(mu),
+                                float(tau), _p(pos), _p(red), _stream()), "made_mmr_select")
+    return pos, red
