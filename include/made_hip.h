@@ -1153,6 +1153,24 @@ int made_topk_candidates(const int32_t* cand_col, const float* cand_score, int64
 int made_mmr_select(const int32_t* row, const float* score, const float* vec, int64_t n_rows, int64_t D, int64_t Nv, int64_t P, int64_t k,
                     float mu, float tau, int32_t* pos, float* redundancy, void* stream);
 
+/* made_cosine_join: the threshold self-join of a vector table, for grouping near-duplicate tracks when a library is built
+ * (mgsv_amd/dedup.py near_duplicate_pairs).  vec [N, D] f32 with contiguous rows, 16-byte aligned, N < 2^31; node [N] int32 or NULL.
+ * Appends every pair (i, j) with r0 <= i < r1, c0 <= j < c1, i < j, node[i] != node[j] (when node is given) and cos(i, j) >= tau.
+ * The cosine is a.b / (|a| |b|) in f32: the table is NOT normalised beforehand, the kernel sums every staged row's squares itself
+ * and divides in the epilogue (one f32 product of the two norms, one f32 division); a row whose norm is zero or not finite, or a
+ * pair whose product of norms is zero or not finite, joins nothing.  Products run on the exact-f32 MFMA (v_mfma_f32_32x32x2_f32):
+ * a dot product is one fmaf chain over the D components in an order that is the same for every tile, range and launch, and a norm
+ * is summed in one fixed order per row, so the bits of a pair's cosine depend on the two rows alone -- not on how the table is cut
+ * into ranges, on a pair's position in a tile, or on the other rows.  128 x 128 tiles of the rectangle; a tile that lies wholly on
+ * or below the diagonal is not computed.  pair_i / pair_j int32 and pair_cos f32 [capacity]; count: one device int64 the call ADDS
+ * to (the caller zeroes it): a workgroup prefix-sums its matches and reserves their slots with one atomic add; a match whose slot
+ * is >= capacity is counted and not written, so count > capacity tells the caller to repeat the range with larger buffers (slots
+ * past min(count, capacity) are left untouched).  The SET of pairs is deterministic; their ORDER in the buffers is not (it is the
+ * order in which workgroups reserve).  D in {128, 256, 512} (MADE_ERR_UNSUPPORTED otherwise, and for a rectangle of 2^31 tiles or
+ * more); tau in (-1, 1]. */
+int made_cosine_join(const float* vec, int64_t N, int64_t D, const int32_t* node, int64_t r0, int64_t r1, int64_t c0, int64_t c1, float tau,
+                     int32_t* pair_i, int32_t* pair_j, float* pair_cos, int64_t capacity, int64_t* count, void* stream);
+
 /* made_merge_moments: the moments of P (video, track) entries on the track's own time axis from the moments of the track's w
  * windows, one wave per entry, no atomics.  win_col / win_score [P, w] = made_group_topw's columns (-1: no window) and
  * similarities; cand [P, w, Q, 3] f32 = every query's (start, end, foreground probability) in seconds on its window's axis,

@@ -320,6 +320,7 @@ SIGNATURES = {
     "made_topk_merge": (C.c_int, [vp, vp, i64, vp, vp, i64, i64, i64, i64, i64, vp, vp, vp]),
     "made_topk_candidates": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i64, i64, vp, vp, vp]),
     "made_mmr_select": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, i64, f32, f32, vp, vp, vp]),
+    "made_cosine_join": (C.c_int, [vp, i64, i64, vp, i64, i64, i64, i64, f32, vp, vp, vp, i64, vp, vp]),
     "made_merge_moments": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, f32, f32, i64, vp, vp, vp, vp, vp]),
     "made_frames_preprocess": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i32, i64, vp, vp]),
     "made_audio_resample": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp]),

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import NamedTuple, Optional, Sequence
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -1173,3 +1173,24 @@ def mmr_select(row: Tensor, score: Tensor, vec: Tensor, k: int, mu: float = 0.0,
     check(lib().made_mmr_select(_p(row), _p(score), _p(vec) if vec.shape[0] else None, vec.shape[0], vec.shape[1], Nv, P, k, float(mu),
                                 float(tau), _p(pos), _p(red), _stream()), "made_mmr_select")
     return pos, red
+
+
+def cosine_join(vec: Tensor, tau: float, pair_i: Tensor, pair_j: Tensor, pair_cos: Tensor, count: Tensor, node: Optional[Tensor] = None,
+                rows: Optional[Tuple[int, int]] = None, cols: Optional[Tuple[int, int]] = None) -> None:
+    """made_cosine_join: appends to (pair_i, pair_j int32, pair_cos f32, each [capacity]) every pair i < j of rows [r0, r1) x columns
+    [c0, c1) of vec [N, D] f32 (D 128 / 256 / 512; default: the whole table) with cosine >= tau and, with node [N] int32, node[i] !=
+    node[j].  count: one int64 on the device that the call ADDS the number of matches to; matches whose slot is >= capacity are
+    counted, not written.  The set of pairs is deterministic, their order in the buffers is not."""
+    assert vec.dim() == 2 and vec.dtype == torch.float32 and vec.is_contiguous()
+    N, D = vec.shape
+    cap = pair_i.numel()
+    assert pair_i.dtype == torch.int32 and pair_j.dtype == torch.int32 and pair_cos.dtype == torch.float32
+    assert pair_j.numel() == cap and pair_cos.numel() == cap and pair_i.is_contiguous() and pair_j.is_contiguous() and pair_cos.is_contiguous()
+    assert count.dtype == torch.int64 and count.numel() == 1
+    assert pair_i.device == pair_j.device == pair_cos.device == count.device == vec.device
+    if node is not None:
+        assert node.dtype == torch.int32 and node.is_contiguous() and node.numel() == N and node.device == vec.device
+    r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+    c0, c1 = (0, N) if cols is None else (int(cols[0]), int(cols[1]))
+    check(lib().made_cosine_join(_p(vec) if N else None, N, D, _p(node), r0, r1, c0, c1, float(tau), _p(pair_i) if cap else None,
+                                 _p(pair_j) if cap else None, _p(pair_cos) if cap else None, cap, _p(count), _stream()), "made_cosine_join")
