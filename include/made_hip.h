@@ -457,7 +457,10 @@ int made_tape_replay_range(uint64_t handle, int64_t first, int64_t count);   /* 
                                                                                one phase of a step on its own (measurements) */
 int made_tape_op(uint64_t handle, int64_t index, int32_t* kind, uint64_t* function, uint64_t* stream, uint32_t* grid3);
                                                               /* what operation `index` is: kind 0 = kernel launch (function = its host-side
-                                                                 address, grid3 = workgroups per axis), other kinds: events, fills, copies */
+                                                                 address, grid3 = workgroups per axis), other kinds: events, fills, copies.
+                                                                 Event operations (kind 1 = record on `stream` + wait, 4 = record on `stream`,
+                                                                 5 = `stream` waits) return the event's handle in `function`: a wait refers to
+                                                                 the latest record of the same handle in front of it */
 int made_stream_wait(void* src_stream, void* dst_stream);            /* dst waits for all work queued on src so far */
 /* recording only, executes nothing: a HOST callback at this point of the issue order; a replay calls fn(user) there (non-zero return:
  * the replay stops with an error).  For work the library does not launch itself but that must sit between the step's launches: the
@@ -808,7 +811,9 @@ typedef struct MadeGemmTNGroup {
                                             1.2 TB/s the atomic units sustain: 83 of the launch's 146 us).  At least
                                             made_gemm_tn_grouped_workspace(group) bytes, 16-byte aligned, contents arbitrary; calls that share a
                                             workspace, or update the same C, must be ordered on one stream.  The result is then bitwise
-                                            reproducible.  NULL: the atomics */
+                                            reproducible.  NULL: the atomics.  A group whose need reaches 2^32 bytes (the first launch addresses its
+                                            slots with 32-bit offsets; eight problems of 4096 x 4096 at M = 36864 need 4.36e9) is MADE_ERR_UNSUPPORTED
+                                            with a workspace: pass NULL for it */
 } MadeGemmTNGroup;
 int made_gemm_tn_grouped(const MadeGemmTNGroup* group, void* stream);
 /* bytes of workspace the group's launch can use (0: none -- not the 256 x 256-tile form); reads n_problems, tile_size, M and the problems' N, K */

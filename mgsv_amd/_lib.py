@@ -360,6 +360,24 @@ def check(status: int, what: str = "") -> None:
         raise MadeError(f"{what or 'libmade_hip'} failed (status {status}): {msg}")
 
 
+def scoped_f32_products(fn):
+    """Decorator of an entry point whose first argument is an engine / encoder: the library's process-wide f32 product mode
+    (made_set_f32_products) is that object's `_f32_products` (0 when it has none) for the duration of the call and what it was before
+    afterwards -- an "f32x3" engine's split-bf16 mode never outlives the engine's own launches."""
+    import functools
+
+    @functools.wraps(fn)
+    def run(owner, *args, **kw):
+        l = lib()
+        before = int(l.made_get_f32_products())
+        check(l.made_set_f32_products(int(getattr(owner, "_f32_products", 0))), "made_set_f32_products")
+        try:
+            return fn(owner, *args, **kw)
+        finally:
+            check(l.made_set_f32_products(before), "made_set_f32_products")
+    return run
+
+
 def device_info():
     l = lib()
     name = C.create_string_buffer(64)

@@ -104,20 +104,34 @@ extern "C" int made_tape_begin(void) {
 // Dropped here, once, at the end of the recording:
 //   * a record on a stream that has been given nothing since its previous record marks the same point: its event becomes an alias of the earlier one;
 //   * a wait of a stream for an event it has already waited for (same record) adds nothing.
+// An alias holds until either of its events is recorded again: the event then marks a new point, and what was said about its old one no longer
+// applies to waits that follow.
 static void tape_dedup(Tape* t) {
     const size_t n = t->ops.size();
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> alias;                 // event -> the earlier event that marks the same point
-    auto canon = [&](hipEvent_t e) { for (auto& a : alias) if (a.first == e) return a.second; return e; };
+    struct Alias { hipEvent_t ev, to; size_t rec; };                      // event -> the earlier event that marks the same point; rec: the dropped record
+    std::vector<Alias> alias;
+    auto canon = [&](hipEvent_t e) { for (auto& a : alias) if (a.ev == e) return a.to; return e; };
     std::vector<std::pair<hipStream_t, hipEvent_t>> last_rec;             // stream -> event of its latest record with nothing issued to the stream since
     std::vector<std::pair<hipStream_t, std::vector<hipEvent_t>>> waited;  // stream -> events it has waited for
     auto forget = [&](hipStream_t st) { for (auto& lr : last_rec) if (lr.first == st) lr.second = nullptr; };
     std::vector<char> drop(n, 0);
+    // `ev` is recorded again (operation i).  Its own alias ends: later waits for it mean this record.  Events that were aliased TO it marked its
+    // old point, which it stops marking on replay once this record is kept: their dropped records come back and they stand for themselves again.
+    auto rerecorded = [&](hipEvent_t ev, bool kept) {
+        for (size_t k = 0; k < alias.size();) {
+            if (alias[k].ev == ev) { alias.erase(alias.begin() + (long)k); continue; }
+            if (kept && alias[k].to == ev) { drop[alias[k].rec] = 0; alias.erase(alias.begin() + (long)k); continue; }
+            ++k;
+        }
+    };
     for (size_t i = 0; i < n; ++i) {
         TapeOp& op = t->ops[i];
         if (op.kind == TAPE_EV_RECORD) {
             hipEvent_t prev = nullptr;
             for (auto& lr : last_rec) if (lr.first == op.st) prev = lr.second;
-            if (prev != nullptr) { alias.push_back({op.ev, prev}); drop[i] = 1; continue; }
+            if (prev == op.ev) { drop[i] = 1; continue; }     // (the same event twice with nothing in between: the first record stands)
+            if (prev != nullptr) { rerecorded(op.ev, false); alias.push_back({op.ev, prev, i}); drop[i] = 1; continue; }
+            rerecorded(op.ev, true);
             bool found = false;
             for (auto& lr : last_rec) if (lr.first == op.st) { lr.second = op.ev; found = true; }
             if (!found) last_rec.push_back({op.st, op.ev});
@@ -363,7 +377,7 @@ extern "C" int made_tape_op(uint64_t handle, int64_t index, int32_t* kind, uint6
     MADE_REQUIRE(t != nullptr && index >= 0 && (size_t)index < t->ops.size(), "made_tape_op: bad tape or index");
     const TapeOp& op = t->ops[(size_t)index];
     if (kind) *kind = (int32_t)op.kind;
-    if (function) *function = (uint64_t)(uintptr_t)op.fn;
+    if (function) *function = (op.kind == TAPE_EV_RECORD || op.kind == TAPE_EV_WAIT || op.kind == TAPE_WAIT) ? (uint64_t)(uintptr_t)op.ev : (uint64_t)(uintptr_t)op.fn;
     if (stream) *stream = (uint64_t)(uintptr_t)op.st;
     if (grid3) { grid3[0] = op.grid.x; grid3[1] = op.grid.y; grid3[2] = op.grid.z; }
     return MADE_OK;

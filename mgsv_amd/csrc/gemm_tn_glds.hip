@@ -606,6 +606,7 @@ __global__ __launch_bounds__(T2_NT, 1) void gemm_tn_256_reduce_kernel(const Made
 
 // workspace of the 256 x 256-tile form: gridDim * F partial slots of 256 KB
 static int t2_flushes(int tiles, int grid) { const int nwg = grid / 8 > 0 ? grid / 8 : 1; return (tiles + nwg - 1) / nwg + 1; }
+static const int64_t T2_WS_LIMIT = (int64_t)1 << 32;        // workspaces of this size or more are refused (made_gemm_tn_grouped)
 static int64_t t2_workspace_bytes(int tiles, int grid) { return (int64_t)grid * t2_flushes(tiles, grid) * 262144; }
 static bool t2_shape(const MadeGemmTNGroup& g, int* tiles_out, int* grid_out) {
     int tiles2 = 0;
@@ -653,17 +654,21 @@ extern "C" int made_gemm_tn_grouped(const MadeGemmTNGroup* group, void* stream) 
         int tiles_chk = 0, grid_n = 0;
         t2_shape(g, &tiles_chk, &grid_n);                       // one workgroup per CU; fewer when there is less than a slab for each (small M)
         dim3 grid2((unsigned)grid_n, 1, 1);
-        static const bool once2 = hipFuncSetAttribute((const void*)gemm_tn_256_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS) == hipSuccess;
-        (void)once2;
+        // the workspace, checked before anything reaches the runtime
         T2Ws w; w.part = nullptr; w.F = 0;
         if (g.workspace != nullptr && made_variant_env("MADE_TN256_ATOMIC_FLUSH") == nullptr) {
             const int64_t need = t2_workspace_bytes(tiles2, (int)grid2.x);
+            // the first launch addresses its partial slots with 32-bit byte offsets (flush_ws): from 4 GiB on they would wrap onto each other
+            MADE_UNSUPPORTED(need < T2_WS_LIMIT, "made_gemm_tn_grouped(256): the group needs a workspace of %lld bytes, the limit is 2^32 - 1 "
+                             "(32-bit slot offsets): pass no workspace (atomic flush) or split the group", (long long)need);
             MADE_REQUIRE(g.workspace_bytes >= need && ((uintptr_t)g.workspace % 16) == 0,
                          "made_gemm_tn_grouped(256): workspace of %lld bytes, %lld needed (made_gemm_tn_grouped_workspace), 16-byte aligned",
                          (long long)g.workspace_bytes, (long long)need);
             w.part = (float*)g.workspace;
             w.F = t2_flushes(tiles2, (int)grid2.x);
         }
+        static const bool once2 = hipFuncSetAttribute((const void*)gemm_tn_256_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS) == hipSuccess;
+        (void)once2;
         hipLaunchKernelGGL(gemm_tn_256_grouped_kernel, grid2, dim3(T2_NT), T2_LDS, (hipStream_t)stream, g, w);
         if (w.part != nullptr && made_variant_env("MADE_TN256_NO_REDUCE") == nullptr) {      // (measurement knob: the first launch alone -- wrong results)
             const int rc1 = made_check_launch("made_gemm_tn_grouped(256)");

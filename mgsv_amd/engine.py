@@ -619,11 +619,12 @@ class MadeEngine:
         return ops.linear(vn, mn, None, R=add, out=out, out_dtype=torch.float32)
 
     def _set_products(self) -> None:
-        """the library's process-wide f32 product mode <- this engine's (read by the f32 kernels' launchers)"""
-        if self.tc == torch.float32:
-            from . import _lib
-            _lib.check(_lib.lib().made_set_f32_products(self._f32_products), "made_set_f32_products")
+        """the library's process-wide f32 product mode <- this engine's (read by the f32 kernels' launchers; a bf16 engine issues f32
+        launches too and sets the exact mode).  The entry points are scoped (_lib.scoped_f32_products): the mode they leave behind is the one
+        they found."""
+        _lib.check(_lib.lib().made_set_f32_products(self._f32_products), "made_set_f32_products")
 
+    @_lib.scoped_f32_products
     def retrieval_sim_matrix(self, video_embeds: Tensor, segment_embeds: Tensor, segment_masks: Tensor,
                              music_embeds: Tensor, chunk_m: Optional[int] = None, out: Optional[Tensor] = None,
                              single_out: Optional[Tensor] = None) -> Tensor:
@@ -636,6 +637,7 @@ class MadeEngine:
 
     # ------------------------------------------------------------------ full forward
     @torch.no_grad()
+    @_lib.scoped_f32_products
     def forward(self, frame_feats: Tensor, segment_feats: Tensor, frame_masks: Tensor, segment_masks: Tensor,
                 spans_target: Tensor, with_losses: bool = True, want_pooled: bool = False,
                 v_duration: Optional[Tensor] = None) -> Dict[str, Tensor]:
@@ -933,6 +935,7 @@ class MadeEngine:
         """The music temporal tower only over [N, T_a, ast_dim] features."""
         return self._encode_items(segment_feats, segment_masks, m_duration, "audio", batch)
 
+    @_lib.scoped_f32_products
     def _encode_items(self, feats: Tensor, masks: Tensor, duration: Optional[Tensor], which: str, batch: int) -> "Encoded":
         self._set_products()
         dev, D = self.device, self.cfg.D
@@ -1003,6 +1006,7 @@ class MadeEngine:
             yield p0, min(B, P - p0), out
 
     @torch.no_grad()
+    @_lib.scoped_f32_products
     def localize_pairs(self, videos: "Encoded", music: "Encoded", vi, mi, pair_batch: int = 64) -> Dict[str, Optional[Tensor]]:
         """Moment localization of arbitrary (video vi[p], track mi[p]) pairs from per-item tower outputs (encode_videos /
         encode_music): per batch of pairs one made_gather_pairs, then the eval path after the towers (fusion, DETR, heads) -- no

@@ -277,6 +277,7 @@ class _RowConstraints:
                                self.start, self.keys, bits=bits, col_any=col_any, device=device)
 
 
+@_lib.scoped_f32_products
 def similarity_matrix(engine: MadeEngine, video: Tensor, seg: Tensor, seg_mask: Tensor, music: Tensor, out: Optional[Tensor] = None,
                       single_out: Optional[Tensor] = None) -> Tensor:
     """[N_v, N_m] f32 similarities by the configuration's vmr loss, the branch the evaluation ranks with (reference
@@ -479,6 +480,7 @@ def _device_fetch(tokens: Tensor, mask: Tensor):
 
 
 @torch.no_grad()
+@_lib.scoped_f32_products
 def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Optional[Tensor] = None, group_id=None,
            pair_batch: int = 64, windows: Optional[Windows] = None, windows_per_track: int = 1, moments: int = 1,
            nms_iou: float = 0.5, constraints: Optional[Constraints] = None, tags=None, length=None,
@@ -1053,6 +1055,7 @@ def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w
 
 
 @torch.no_grad()
+@_lib.scoped_f32_products
 def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_batch: int = 64, windows_per_track: int = 1,
                    moments: int = 1, nms_iou: float = 0.5, chunk_cols: int = 4096, video_batch: int = 1024, sims_fn=None,
                    timings: Optional[dict] = None, constraints: Optional[Constraints] = None, compact: Optional[bool] = None,

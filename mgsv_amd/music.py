@@ -341,9 +341,10 @@ class MusicEncoder:
                         "feat": torch.empty(B, WIDTH, device=dev)}
         return self._ws
 
+    _f32_products = 0                                        # exact f32 products (made_set_f32_products), scoped to the entry points
+
     def _set_products(self) -> None:
-        if self.tc == torch.float32:
-            _lib.check(_lib.lib().made_set_f32_products(0), "made_set_f32_products")
+        _lib.check(_lib.lib().made_set_f32_products(self._f32_products), "made_set_f32_products")
 
     def tower(self, patches: Tensor, out: Tensor) -> Tensor:
         """The tower over one chunk of patch rows [chunk * 1212, 256] -> out [chunk, 768] f32."""
@@ -424,6 +425,7 @@ class MusicEncoder:
 
     # -------------------------------------------------------------------------------------------- spectrograms -> features
     @torch.no_grad()
+    @_lib.scoped_f32_products
     def encode_spectrograms(self, spec: Tensor) -> Tensor:
         """[S', 768] f32 features of normalised spectrograms spec [S', 1024, 128] f32 (the reference's `audio` rows)."""
         if spec.dim() != 3 or tuple(spec.shape[1:]) != (ROWS, MELS):
@@ -441,6 +443,7 @@ class MusicEncoder:
         return out
 
     @torch.no_grad()
+    @_lib.scoped_f32_products
     def encode_tracks(self, tracks: Sequence, stride: float = 2.5, filter: float = 4.0, max_m_duration: float = 240
                       ) -> Tuple[Tensor, Tensor, Tensor]:
         """(feats [N, S, 768] f32, mask [N, S] f32, m_duration [N] f64) of N tracks, each (waveform, sr) with a float32 [C, n] or [n]
@@ -470,6 +473,7 @@ class MusicEncoder:
 
     # -------------------------------------------------------------------------------------------- whole tracks -> windows
     @torch.no_grad()
+    @_lib.scoped_f32_products
     def encode_windows(self, tracks: Sequence, stride: float = 2.5, filter: float = 4.0, window: float = 240, hop: float = 120,
                        group_samples: int = 1 << 26):
         """(feats [Nw, S, 768] f32, mask [Nw, S] f32, Windows) of N whole tracks cut into overlapping windows of `window` seconds every

@@ -18,6 +18,7 @@ Tensor = torch.Tensor
 Pair = Tuple[int, int]
 
 
+_TN_WS_LIMIT = 1 << 32  # made_gemm_tn_grouped refuses a workspace of this size or more (32-bit slot offsets: include/made_hip.h)
 _TN_SLAB_US = 1.3       # (0.7 / 2.5 / 4.0 alternated in the step: 4.70 / 4.72 / 4.73 against 4.69 ms; profiles/r06_ab_tn_splits.txt)
 
 
@@ -134,7 +135,7 @@ def gemm_tn_grouped(problems, rows=None, alpha: float = 1.0, split_m: Optional[i
         # the tile partials meet in a workspace instead of being added to the gradients with atomics (MADE_TN256_ATOMIC_FLUSH=1, measurement knob: the atomics)
         if workspace is not None and _lib.variant_env("MADE_TN256_ATOMIC_FLUSH", "") in ("", "0"):
             need = int(lib().made_gemm_tn_grouped_workspace(C.byref(g)))
-            if need > 0:
+            if 0 < need < _TN_WS_LIMIT:                          # (at the limit or past it: no workspace, the atomic flush)
                 ws = workspace(need)
                 assert ws.dtype == torch.uint8 and ws.numel() >= need and ws.is_contiguous()
                 from . import tape as _tape

@@ -98,6 +98,11 @@ class MadeTrainer(MadeEngine):
         c = self.cfg
         return (("video_mlp", "Video_encoder_projection", c.max_v_frames), ("audio_mlp", "Music_encoder_projection", c.max_snippet_num))
 
+    def _towers_share(self) -> bool:
+        """Both temporal towers run the same block (transformer_is_share): their gradient keys alias."""
+        c = self.cfg
+        return bool(c.transformer_is_share) and c.video_transformer_depth == c.audio_transformer_depth and c.video_transformer_depth > 0
+
     def _table(self) -> Tuple[List[Tuple[str, object]], List[Tuple[str, object]]]:
         """(kernel key, reference name(s)) for matrices and for vectors, mirroring MadeEngine.load_state_dict."""
         c = self.cfg
@@ -114,9 +119,10 @@ class MadeTrainer(MadeEngine):
         if c.with_cls_token and c.agg_module != "mlp":        # reference model/model_Base.py:314-321: [1, 1, D] learned tokens
             vecs.append(("cls_video", "video_cls_token")); vecs.append(("cls_audio", "audio_cls_token"))
         # one block for both towers when transformer_is_share (reference model/model_Base.py:300-302,322-331): both towers' keys view the
-        # same masters and the same gradient ranges; every gradient kernel accumulates atomically, so the two towers' backward passes
-        # (on two streams) simply add up there
-        share = bool(c.transformer_is_share) and c.video_transformer_depth == c.audio_transformer_depth and c.video_transformer_depth > 0
+        # same masters and the same gradient ranges.  The two towers' backward passes run on two streams and add up there, which holds only
+        # for kernels that accumulate atomically: the workspace form of the grouped weight gradients does not (its second launch adds the
+        # tile partials with a plain load and store), so a shared block's launches never take it (_encode_bwd -> _flush_dw(atomic=True))
+        share = self._towers_share()
         if c.agg_module == "mlp":                              # EmbeddingNet aggregators (reference model/model_Base.py:216-249,357-377)
             for key, mod, _ in self._mlp_towers():
                 lin(key + ".0", mod + ".net.0"); lin(key + ".3", mod + ".net.3"); lin(key + ".6", mod + ".net.6")
@@ -1147,8 +1153,10 @@ class MadeTrainer(MadeEngine):
         return (self.tc == torch.bfloat16 and dz.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and gw.shape[0] % 128 == 0
                 and gw.shape[1] % 128 == 0 and dz.stride(0) % 8 == 0 and x.stride(0) % 8 == 0 and dz.shape[0] >= 256)
 
-    def _flush_dw(self, pending: list, row_mask: Optional[Tensor]) -> None:
-        """The weight gradients a layer's backward has queued (they reduce over the same rows) in one launch (made_gemm_tn_grouped)."""
+    def _flush_dw(self, pending: list, row_mask: Optional[Tensor], atomic: bool = False) -> None:
+        """The weight gradients a layer's backward has queued (they reduce over the same rows) in one launch (made_gemm_tn_grouped).
+        atomic: another stream may add to the same gradients at the same time -- no workspace, so every form of the launch adds with atomics
+        (include/made_hip.h: launches that update the same C through the workspace form must be ordered on one stream)."""
         rows = self._rw(row_mask)
         # the launch's workspace (tile partials: ops_train.gemm_tn_grouped): one for the trainer's second stream, one for whatever stream the step
         # runs on -- the launches of a stream are ordered, so they can share one
@@ -1162,7 +1170,7 @@ class MadeTrainer(MadeEngine):
                 wsd[lane] = tr.gemm_tn_grouped_workspace(self.device, nbytes)
             return wsd[lane]
         for i in range(0, len(pending), 8):
-            tr.gemm_tn_grouped(pending[i:i + 8], rows=rows, workspace=workspace)
+            tr.gemm_tn_grouped(pending[i:i + 8], rows=rows, workspace=None if atomic else workspace)
         pending.clear()
 
     def _lin_bwd(self, dz: Tensor, x: Tensor, key: str, *, dx_out: Optional[Tensor] = None, row_mask: Optional[Tensor] = None,
@@ -1979,7 +1987,7 @@ class MadeTrainer(MadeEngine):
                 # instead of a launch of its own (round 6: 63 us at the very end of the main stream for the audio tower)
                 pend.append((dx, tw[tag + ".xin"], G[proj + ".w"], G[proj + ".b"]))
                 proj_grouped = True
-            self._flush_dw(pend, mflat)
+            self._flush_dw(pend, mflat, atomic=self._towers_share())      # (a shared block: the other tower adds to the same dW on the other stream)
         if proj_grouped:
             return
         xin = tw[tag + ".xin"] if self.tc == torch.bfloat16 else feats.view(rows, Kin)

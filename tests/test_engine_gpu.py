@@ -486,3 +486,34 @@ def test_two_batches_in_flight_match_one_at_a_time():
         for l in range(2):
             for k in keys:
                 assert torch.equal(outs[l][k], alone[l][k]), f"replay {it}, lane {l}: {k} differs when two batches are in flight"
+
+
+def test_f32x3_engine_leaves_the_exact_product_mode_behind():
+    """made_set_f32_products is process-wide: an "f32x3" engine switches every f32 product to three bf16 products on split operands for its own
+    launches only.  A bare f32 ops.linear gives the same bits before and after such an engine's forward, and the mode reads 0 (exact) after the
+    call and after a bf16 engine's forward that follows."""
+    from mgsv_amd import _lib, ops
+    l = _lib.lib()
+    _lib.check(l.made_set_f32_products(0), "made_set_f32_products")              # the library's default, whatever ran before this test
+    try:
+        g = torch.Generator(device="cuda").manual_seed(7)
+        x = torch.randn(300, 256, device="cuda", generator=g)
+        w = torch.randn(128, 256, device="cuda", generator=g) / 16
+        bias = torch.randn(128, device="cuda", generator=g)
+        before = ops.linear(x, w, bias).clone()
+        cfg = cfg_native()
+        sd = synth.make_state_dict(cfg, seed=0)
+        inp = synth.make_inputs(cfg, 2, 20, 40, seed=1)
+        MadeEngine(cfg, sd, dtype="f32x3").forward_numpy(inp)
+        assert l.made_get_f32_products() == 0
+        after = ops.linear(x, w, bias).clone()
+        torch.cuda.synchronize()
+        assert torch.equal(before, after), float((before - after).abs().max())
+        MadeEngine(cfg, sd, dtype="bf16").forward_numpy(inp)
+        assert l.made_get_f32_products() == 0
+        _lib.check(l.made_set_f32_products(1), "made_set_f32_products")          # (the two modes do differ on this product: the check above can fail)
+        split = ops.linear(x, w, bias).clone()
+        torch.cuda.synchronize()
+        assert not torch.equal(before, split)
+    finally:
+        _lib.check(l.made_set_f32_products(0), "made_set_f32_products")

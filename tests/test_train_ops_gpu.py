@@ -697,6 +697,29 @@ def test_gemm_tn_grouped_workspace_flush(T, M, shapes):
         assert "ws" in holder
 
 
+def test_gemm_tn_grouped_past_the_workspace_limit_flushes_with_atomics(T):
+    """Eight problems with N = K = 4096 at M = 36864 would need a workspace of 4.36e9 bytes, past what the first launch's 32-bit slot offsets
+    address (made_gemm_tn_grouped refuses it: tests/test_gemm_tn_limits_cpu.py).  ops_train.gemm_tn_grouped then asks the caller for no
+    workspace and the launch adds its partials with atomics: every problem's gradient is the f32 product (one shared pair of operands, the
+    reference computed once)."""
+    ops, tr = T
+    M, N = 36864, 4096
+    g = torch.Generator(device="cuda").manual_seed(1)                             # (drawn on the device: 2 x 151 M values)
+    A, B = (torch.randn(M, N, device="cuda", generator=g).to(torch.bfloat16) for _ in range(2))
+    ref = A.float().t() @ B.float()
+    sc = float(ref.abs().max())
+    probs = [(A, B, torch.ones(N, N, device="cuda"), None) for _ in range(8)]
+    asked = []
+
+    def workspace(n):
+        asked.append(n)
+        return tr.gemm_tn_grouped_workspace(torch.device("cuda"), n)
+    tr.gemm_tn_grouped(probs, alpha=0.5, workspace=workspace)
+    assert not asked, asked
+    for i, (_, _, Cw, _) in enumerate(probs):
+        assert float((Cw - (1.0 + 0.5 * ref)).abs().max()) <= 2e-3 * sc, i
+
+
 def test_clip_loss_same_music_exclusion_forward_and_backward(T):
     """row_exclude of made_clip_loss / made_clip_loss_bwd = the same-music-aware InfoNCE of reference modules/loss.py:90-114
     (oracle restatement info_nce_same_music): loss and d(loss)/d(sims), d/d(logit_scale) against its autograd."""
@@ -1062,4 +1085,44 @@ def test_launch_tape_drops_duplicate_cross_stream_dependencies(T):
     y.zero_(); z.zero_(); torch.cuda.synchronize()
     tp.replay(); torch.cuda.synchronize()
     assert torch.equal(z, 3 * x) and torch.equal(y, 4 * x)
+    tp.close()
+
+
+def test_launch_tape_event_recorded_again_keeps_no_old_alias(T):
+    """An event whose record was dropped as a duplicate (it marked the same point of its stream as an earlier event) and that is recorded AGAIN
+    behind a kernel marks a new point: the other stream's wait for it must refer to that record, not to the earlier event it was once an alias of
+    -- the wait would otherwise sit in front of the kernel and the dependency be lost on replay.  Checked on the recorded operations (made_tape_op
+    returns an event operation's handle) and by replaying."""
+    ops, tr = T
+    from mgsv_amd import tape as _tape
+    n = 1 << 24
+    x = (torch.arange(n, device="cuda", dtype=torch.float32) % 1021) + 1
+    y, z = torch.zeros_like(x), torch.zeros_like(x)
+    a, b = torch.cuda.current_stream(), torch.cuda.Stream()
+    e1, e2 = torch.cuda.Event(), torch.cuda.Event()
+
+    def program():
+        e1.record(a); e2.record(a)                                                 # the same point of a: e2's record is dropped, e2 an alias of e1
+        tr.add3(y, x, x)                                                           # K: y = 2 x
+        e2.record(a)                                                               # a NEW point, behind K
+        b.wait_event(e2)
+        with torch.cuda.stream(b):
+            tr.add3(z, y, x)                                                       # z = 3 x, needs K
+        a.wait_stream(b)
+    program(); torch.cuda.synchronize()
+    with _tape.LaunchTape.record() as tp:
+        program()
+    torch.cuda.synchronize()
+    KERNEL, EV_RECORD, EV_WAIT = 0, 4, 5
+    rec = tp.ops()
+    kinds = [(k, st) for k, _, st, _ in rec]
+    sa, sb = a.cuda_stream, b.cuda_stream
+    assert kinds == [(EV_RECORD, sa), (KERNEL, sa), (EV_RECORD, sa), (EV_WAIT, sb), (KERNEL, sb), (EV_RECORD, sb), (EV_WAIT, sa)], kinds
+    first, again, wait = rec[0][1], rec[2][1], rec[3][1]
+    assert first != 0 and again != 0 and first != again
+    assert wait == again, "the wait refers to the event recorded in front of the kernel"
+    assert rec[6][1] == rec[5][1] != 0
+    y.zero_(); z.zero_(); torch.cuda.synchronize()
+    tp.replay(); torch.cuda.synchronize()
+    assert torch.equal(y, 2 * x) and torch.equal(z, 3 * x)
     tp.close()
