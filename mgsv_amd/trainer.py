@@ -584,148 +584,44 @@ class MadeTrainer(MadeEngine):
     def forward_train(self, frame_feats: Tensor, segment_feats: Tensor, frame_masks: Tensor, segment_masks: Tensor,
                       spans_target: Tensor, seed: int = 0, music_ids=None, v_duration: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """reference model/model_Uni.py:177-322 under model.train(): same outputs as MadeEngine.forward plus everything
-        the backward needs, kept in the training workspace."""
-        c, P = self.cfg, self.P
+        the backward needs, kept in the training workspace.
+        This function is the schedule only -- which stage runs on which stream and who waits for whom; the launches are the stages'."""
+        c = self.cfg
         self._set_products()
         if c.predict_center == 1 and v_duration is None:
             raise ValueError("predict_center=1 needs v_duration (reference model/model_Uni.py:280-282)")
         self.seed = int(seed)
         B, Tv, _ = frame_feats.shape
         Ta = segment_feats.shape[1]
-        concat = "concat" in c.mml_fusion
-        D, L, Q, nd, H = c.D, (Tv + Ta if concat else Ta), c.num_moment_queries, c.detr_dec_layers, c.detr_nheads
         ws, tw = self._buffers(B, Tv, Ta), self._train_buffers(B, Tv, Ta)
         fm, sm = frame_masks.contiguous(), segment_masks.contiguous()
-        pd = float(c.detr_dropout)
         self._shape = (B, Tv, Ta)
         self._inputs = (frame_feats.contiguous(), segment_feats.contiguous(), fm, sm, spans_target.contiguous())
+        self._groups, self._rows, self._order = {}, {}, {}
+        regression = "regression" in c.mml_localization
+        xq = c.moment_query_type == "xpool"
 
-        fus, fus_mask = ws["fus"], ws["fus_mask"]
-        # valid-token lists: every large GEMM (forward, dX and dW) gathers the valid rows only, so padding costs nothing; issue order of
-        # the attention workgroups: longest sample first (a padded batch otherwise waits on whichever long sample happens to start
-        # last).  These are single-workgroup scans of ~10 us each at the very head of the step: only the audio branch's two stay on the
-        # main stream, the other five (+ the position embedding) go to the second stream with the video branch.
         # The video branch (B*T_v rows: launches far smaller than the chip) runs on a second HIP stream beside the audio branch;
-        # so does the X-Pool / similarity / retrieval-loss branch beside the DETR stack (joined at the end of the step)
-        self._groups = {}
+        # so does the X-Pool / similarity / retrieval-loss branch beside the DETR stack (joined at the end of the step).
+        # Of the index lists (single-workgroup scans of ~10 us each at the very head of the step) only the audio branch's two stay on
+        # the main stream, the other five (+ the position embedding) go to the second stream with the video branch.
         cur, side = torch.cuda.current_stream(), self._side_stream()
         side.wait_stream(cur)
-        self._rows = {sm.data_ptr(): ops.row_index(sm, out=tw["rows_a"])}
-        self._order = {sm.data_ptr(): ops.batch_order(sm, out=tw["order_a"])}
+        self._index_lists(sm, tw["rows_a"], tw["order_a"])
         with torch.cuda.stream(side):
-            ops.concat_cols(fm if concat else None, sm, fus_mask)
-            self._rows[fm.data_ptr()] = ops.row_index(fm, out=tw["rows_v"])
-            self._order[fm.data_ptr()] = ops.batch_order(fm, out=tw["order_v"])
-            self._rows[fus_mask.data_ptr()] = ops.row_index(fus_mask, out=tw["rows_f"])
-            self._order[fus_mask.data_ptr()] = ops.batch_order(fus_mask, out=tw["order_f"])
-            # the decoder's cross-attention (6 layers, forward and backward) deals its key tiles over the chip by the samples' lengths
-            self._wide_plan = (ops.wide_slice_plan(fus_mask, n_slots=self._wide_slots(), max_slices=WIDE_SLICES,
-                                                   order=self._order[fus_mask.data_ptr()], out=tw["wide_plan"])
-                               if "regression" not in c.mml_localization and self._wide_planned_ok(B, H * Q, D) else None)
-            pos = ops.sine_pe(fus_mask, P["dim_t"], out=ws["pos"])
+            self._fused_lists_fwd(ws, tw)
             self._encode_train(self._inputs[0], fm, "video", ws, tw, 0)
         self._encode_train(self._inputs[1], sm, "audio", ws, tw, Tv)
         cur.wait_stream(side)
-        rows_f = self._rows[fus_mask.data_ptr()]
-        if concat:
-            frame, seg = fus[:, :Tv], fus[:, Tv:]
+        if "concat" in c.mml_fusion:
+            frame, seg = ws["fus"][:, :Tv], ws["fus"][:, Tv:]
         else:
             frame, seg = ws["frame_buf"], ws["seg_buf"]
             self._ca_fusion_train(ws, tw, frame, seg, fm, sm, B, Tv, Ta)
         self._views = (frame, seg)
-        video, music = ws["video"], ws["music"]
-        out: Dict[str, Tensor] = dict(video_feats=video, music_feats=music, frame_feats=frame, segment_feats=seg)
-
-        # ---- the decoder's query side (defined here: layer 0's runs on the second stream beside the DETR encoder, see below)
-        qp = P["query_embed"]
-        hd = D // H
-        ca_scale = 1.0 / math.sqrt(hd)
-        GQ = tw.get("GQ")                                    # [B, 2, nd, H*Q, D]: part 1 holds the q' rows of every layer
-        regression = "regression" in c.mml_localization
-
-        def dec_fill_tgt() -> None:
-            tgt = tw["d.0.tgt"]
-            if c.moment_query_type in ("video", "music", "xpool"):
-                if c.moment_query_type == "xpool":
-                    cur.wait_stream(side)                    # the X-Pool branch (second stream) produces the query
-                src_vec = video if c.moment_query_type == "video" else (music if c.moment_query_type == "music" else tw["xpool_q"])
-                if Q == 1:
-                    tr.add3(tgt, src_vec)                     # (f32 clip vector -> compute dtype; no framework kernel inside the step)
-                else:
-                    tgt.view(B, Q, D).copy_(src_vec[:, None, :].expand(B, Q, D))
-            else:                                            # "zero" / "random": reference music_detr/transformer.py:73-74
-                _tape.zero_(tgt)
-            if Q > 1 and not c.detr_pre_norm:                # (a single query's q / k projections are never formed: see the loop)
-                tr.add3(tw["d.0.tq"], tgt, qp, b_mod=Q * D)
-
-        # bf16, one moment query: the chain's LayerNorms run in the prologue of the Linear that consumes them (made_dec_stage, as on
-        # the eval path; dropout and the saved GEMM input in its epilogue / prologue), the value bias of the
-        # memory-space attention is the per-head Linear's epilogue: 10 launches per layer instead of 14
-        stage = self._dec_stage_chain()
-
-        def dec_query_side(l: int) -> None:
-            """the part of decoder layer l in front of its cross-attention: self-attention block, LayerNorm, cross-attention query and
-            its per-head fold -- it reads the layer's input and the weights, nothing the DETR encoder produces"""
-            p, d = f"detr_transformer.decoder.layers.{l}", f"d.{l}"
-            tgt, tq = tw[d + ".tgt"], tw[d + ".tq"]
-            qkv = tw[d + ".qkv"]
-            Win, bin_ = P[p + ".ca.in.w"], P[p + ".ca.in.b"]
-            Wt = P[p + ".ca.in.wt"]                           # [D, 3D] = in_proj^T
-            if c.detr_pre_norm:
-                # reference music_detr/transformer.py:246-257 (forward_pre): tgt is the un-normalised stream; the self-attention reads
-                # n1 = LN1(tgt) (q = k = n1 + query_pos, v = n1) and always runs; the cross-attention's query is LN2(stream) + query_pos.
-                # Buffers keep their roles: .t_a = stream after the self-attention, .t1 / .t1q = the cross-attention query's input.
-                n1 = tw[d + ".n1"]
-                qp_rows = qp.expand(B * Q, D) if Q == 1 else qp.repeat(B, 1)
-                if Q == 1:                                    # one query, one key: the value path only (see the post-norm branch below)
-                    Wsa, bsa = P[p + ".sa.in.w"], P[p + ".sa.in.b"]
-                    ops.layernorm(tgt, P[p + ".ln1.g"], P[p + ".ln1.b"], out=n1)
-                    ops.linear(n1, Wsa[2 * D:], bsa[2 * D:], out=tw[d + ".att"], drop=self._drop(f"dec.{l}" + ".sa_attn", pd), drop_ld=H, drop_col_div=hd)
-                else:
-                    ops.layernorm_add(tgt, P[p + ".ln1.g"], P[p + ".ln1.b"], qp_rows, n1, tq)
-                    ops.linear(n1, P[p + ".sa.in.w"], P[p + ".sa.in.b"], A2=tq, a2_replace=True,
-                               segs=[Seg(out=qkv, col_begin=0, use_a2=True), Seg(out=qkv[:, 2 * D:], col_begin=2 * D, ldo=qkv.stride(0))])
-                    q3 = qkv.view(B, Q, 3 * D)
-                    ops.attention(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], tw[d + ".att"].view(B, Q, D), H, lse=tw[d + ".lse"],
-                                  drop=self._drop(f"dec.{l}" + ".sa_attn", pd))
-                ta = ops.linear(tw[d + ".att"], P[p + ".sa.out.w"], P[p + ".sa.out.b"], R=tgt, out=tw[d + ".t_a"], drop=self._drop(f"dec.{l}" + ".drop1", pd))
-                ops.layernorm_add(ta, P[p + ".ln2.g"], P[p + ".ln2.b"], qp_rows, tw[d + ".t1"], tw[d + ".t1q"])
-                qc = ops.linear(tw[d + ".t1q"], Win[:D], bin_[:D], out=tw[d + ".qc"])
-            elif stage:
-                Wsa, bsa = P[p + ".sa.in.w"], P[p + ".sa.in.b"]
-                sa_drop = dict(drop=self._drop(f"dec.{l}" + ".sa_attn", pd), drop_ld=H, drop_col_div=hd)
-                if l == 0:
-                    ops.dec_stage(tgt, Wsa[2 * D:], bsa[2 * D:], tw[d + ".att"], **sa_drop)
-                else:                                         # the previous layer's norm 3 in the prologue: t3 = this layer's input
-                    q_ = f"detr_transformer.decoder.layers.{l - 1}"
-                    ops.dec_stage(tw[f"d.{l - 1}.t_c"], Wsa[2 * D:], bsa[2 * D:], tw[d + ".att"], ln=(P[q_ + ".ln3.g"], P[q_ + ".ln3.b"]),
-                                  x_out=tgt, **sa_drop)
-                ta = ops.linear(tw[d + ".att"], P[p + ".sa.out.w"], P[p + ".sa.out.b"], R=tgt, out=tw[d + ".t_a"], drop=self._drop(f"dec.{l}" + ".drop1", pd))
-                qc = ops.dec_stage(ta, Win[:D], bin_[:D], tw[d + ".qc"], ln=(P[p + ".ln1.g"], P[p + ".ln1.b"]), add=qp,
-                                   x_out=tw[d + ".t1"], a_out=tw[d + ".t1q"])
-            else:
-                if Q == 1:
-                    # one query, one key: the softmax weight is 1, so the block is the value path; its attention-weight dropout is one
-                    # draw per (sample, head) (element index (b*H + h)*1*1), and q / k get no gradient
-                    # (the draw is the value Linear's epilogue: the undropped value itself is needed by nobody)
-                    Wsa, bsa = P[p + ".sa.in.w"], P[p + ".sa.in.b"]
-                    ops.linear(tgt, Wsa[2 * D:], bsa[2 * D:], out=tw[d + ".att"], drop=self._drop(f"dec.{l}" + ".sa_attn", pd), drop_ld=H, drop_col_div=hd)
-                else:
-                    ops.linear(tgt, P[p + ".sa.in.w"], P[p + ".sa.in.b"], A2=tq, a2_replace=True,
-                               segs=[Seg(out=qkv, col_begin=0, use_a2=True), Seg(out=qkv[:, 2 * D:], col_begin=2 * D, ldo=qkv.stride(0))])
-                    q3 = qkv.view(B, Q, 3 * D)
-                    ops.attention(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], tw[d + ".att"].view(B, Q, D), H, lse=tw[d + ".lse"],
-                                  drop=self._drop(f"dec.{l}" + ".sa_attn", pd))
-                ta = ops.linear(tw[d + ".att"], P[p + ".sa.out.w"], P[p + ".sa.out.b"], R=tgt, out=tw[d + ".t_a"], drop=self._drop(f"dec.{l}" + ".drop1", pd))
-                t1 = tw[d + ".t1"]
-                ops.layernorm_add(ta, P[p + ".ln1.g"], P[p + ".ln1.b"], qp.expand(B * Q, D) if Q == 1 else qp.repeat(B, 1), t1, tw[d + ".t1q"])
-                qc = ops.linear(tw[d + ".t1q"], Win[:D], bin_[:D], out=tw[d + ".qc"])
-            qprime = GQ[:, 1, l]                              # [B, H*Q, D] view; q'_h = W_k,h^T qc_h  (b_k shifts all keys alike)
-            ops.linear(qc[:, :hd], Wt[:, D:D + hd], None, M=B * Q, N=D, K=hd, batch=H, a_z_stride=hd, w_z_stride=hd,
-                       segs=[Seg(out=qprime, ldo=D, rows_per_batch=Q, out_batch_stride=qprime.stride(0), out_z_stride=Q * D)])
+        out: Dict[str, Tensor] = dict(video_feats=ws["video"], music_feats=ws["music"], frame_feats=frame, segment_feats=seg)
 
         dec_early = None
-        # ---- X-Pool (in-batch) + similarities + retrieval loss
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             if getattr(self, "_zero_grad_in_forward", False):
@@ -734,58 +630,109 @@ class MadeTrainer(MadeEngine):
                 # streams join at the end of the forward)
                 _tape.zero_(self.flat_grad)
                 self._grads_zeroed = True
-            if Q == 1 and not regression and c.moment_query_type != "xpool" and c.detr_enc_layers > 0:
+            if c.num_moment_queries == 1 and not regression and not xq and c.detr_enc_layers > 0:
                 # the query side of decoder layer 0 depends on the clip-level vector and the weights only: here, beside the DETR encoder,
                 # instead of at the head of the decoder's chain of dependent launches (as MadeEngine does for the eval path).
                 # (While the raw barriers of the LDS-DMA GEMM kernels lacked their lgkmcnt(0) -- csrc/linear.hip, linear_ring_kernel --
                 # this placement made one stage of the chain come out a few ulps off in a fifth of the steps; 0 of 80 since:
                 # tools/race_probe3.py)
-                dec_fill_tgt()
-                dec_query_side(0)
+                self._dec_fill_tgt(ws, tw)
+                self._dec_query_side(tw, 0)
                 dec_early = torch.cuda.Event()
                 dec_early.record(side)
-            xmask = sm if c.fusion_mask == 1 else None
-            if "music" in c.vmr_fusion:
-                self._xpool_train(video, seg, xmask, ws, tw, B, Ta)
-            if "video" in c.vmr_fusion and c.vmr_loss == "single":
-                # music-guided video pooling gives sims[m, v]; the reference adds its transpose to the music-pooling similarities in
-                # the `single` loss and uses it nowhere else (model_Uni.py:203,247-251)
-                self._xpool_train(music, frame, fm if c.fusion_mask == 1 else None, ws, tw, B, Tv, key="xav", pre="y", sims_out=tw["sims_vp_t"])
-                if "music" in c.vmr_fusion:
-                    ws["sims_single"].add_(tw["sims_vp_t"].t())
-                else:
-                    ws["sims_single"].copy_(tw["sims_vp_t"].t())
-                out["sims_video_pooling"] = tw["sims_vp_t"].t()
-            ops.l2norm_rows(video, out_f32=tw["vn"]); ops.l2norm_rows(music, out_f32=tw["mn"])
-            if B % 4 == 0 and B <= 256:                      # one output tile: split K over workgroups (exact-f32 MFMA either way)
-                split = max(2, min(16, D // 32))
-                ops.linear_splitk(tw["vn"], tw["mn"], None, tw["sd_ws"][:split * B * B], split, out=ws["sims_dual"])
-            else:
-                ops.linear(tw["vn"], tw["mn"], None, out=ws["sims_dual"])
-            static_ex = getattr(self, "_static_exclusion", None)  # TrainStepGraph: a fixed buffer the host refills before each replay
-            self._row_exclude = static_ex if static_ex is not None else self.same_music_exclusion(music_ids)
-            self._retrieval_loss(ws, video, music, row_exclude=self._row_exclude,
-                                 pooled=tw["xpooled"] if c.vmr_loss == "dual_single_feature_fuse" else None)
-        out.update(sims_single=ws["sims_single"], sims_dual=ws["sims_dual"], retrieval_loss=ws["ret_loss"])
-
-        # ---- DETR encoder
-        rows = B * L
-        fskip = fus_mask.view(-1)
-        qskip = fus_mask
-        regression = "regression" in c.mml_localization
+            out.update(self._retrieval_fwd(ws, tw, music_ids))
+        out["memory"] = self._detr_encoder_fwd(ws, tw)
         if regression:
+            out.update(self._regression_train(ws, tw, v_duration))
+        else:
+            if dec_early is not None:
+                cur.wait_event(dec_early)                    # layer 0's query side ran beside the DETR encoder (second stream)
+            else:
+                if xq:
+                    cur.wait_stream(side)                    # the X-Pool branch (second stream) produces the query
+                self._dec_fill_tgt(ws, tw)
+                self._dec_query_side(tw, 0)
+            out.update(self._decoder_fwd(ws, tw))
+            out.update(self._heads_fwd(ws, tw, v_duration))
+        cur.wait_stream(side)
+        return out
+
+    def _index_lists(self, mask: Tensor, rows_out, order_out: Tensor) -> None:
+        """Row index and batch order of a token mask into self._rows / self._order.  Every large GEMM (forward, dX and dW) gathers the
+        valid rows only, so padding costs nothing; the attention workgroups are issued longest sample first (a padded batch otherwise
+        waits on whichever long sample happens to start last)."""
+        self._rows[mask.data_ptr()] = ops.row_index(mask, out=rows_out)
+        self._order[mask.data_ptr()] = ops.batch_order(mask, out=order_out)
+
+    def _fused_lists_fwd(self, ws, tw) -> None:
+        """What the second stream does first: the DETR token mask, the index lists of the video and the fused sequence, the slice plan
+        of the decoder's cross-attention and the position embedding (ws["pos"])."""
+        c = self.cfg
+        fm, sm = self._inputs[2:4]
+        fus_mask = ws["fus_mask"]
+        ops.concat_cols(fm if "concat" in c.mml_fusion else None, sm, fus_mask)
+        self._index_lists(fm, tw["rows_v"], tw["order_v"])
+        self._index_lists(fus_mask, tw["rows_f"], tw["order_f"])
+        # the decoder's cross-attention (6 layers, forward and backward) deals its key tiles over the chip by the samples' lengths
+        self._wide_plan = (ops.wide_slice_plan(fus_mask, n_slots=self._wide_slots(), max_slices=WIDE_SLICES,
+                                               order=self._order[fus_mask.data_ptr()], out=tw["wide_plan"])
+                           if "regression" not in c.mml_localization
+                           and self._wide_planned_ok(self._shape[0], c.detr_nheads * c.num_moment_queries, c.D) else None)
+        ops.sine_pe(fus_mask, self.P["dim_t"], out=ws["pos"])
+
+    def _retrieval_fwd(self, ws, tw, music_ids) -> Dict[str, Tensor]:
+        """Retrieval branch: X-Pool (in-batch) tower(s), the dual cosine similarities, the retrieval loss.  Returns its outputs."""
+        c = self.cfg
+        B, Tv, Ta = self._shape
+        fm, sm = self._inputs[2:4]
+        frame, seg = self._views
+        video, music = ws["video"], ws["music"]
+        out: Dict[str, Tensor] = {}
+        if "music" in c.vmr_fusion:
+            self._xpool_train(video, seg, sm if c.fusion_mask == 1 else None, ws, tw, B, Ta)
+        if "video" in c.vmr_fusion and c.vmr_loss == "single":
+            # music-guided video pooling gives sims[m, v]; the reference adds its transpose to the music-pooling similarities in
+            # the `single` loss and uses it nowhere else (model_Uni.py:203,247-251)
+            self._xpool_train(music, frame, fm if c.fusion_mask == 1 else None, ws, tw, B, Tv, key="xav", pre="y", sims_out=tw["sims_vp_t"])
+            if "music" in c.vmr_fusion:
+                ws["sims_single"].add_(tw["sims_vp_t"].t())
+            else:
+                ws["sims_single"].copy_(tw["sims_vp_t"].t())
+            out["sims_video_pooling"] = tw["sims_vp_t"].t()
+        ops.l2norm_rows(video, out_f32=tw["vn"]); ops.l2norm_rows(music, out_f32=tw["mn"])
+        if B % 4 == 0 and B <= 256:                          # one output tile: split K over workgroups (exact-f32 MFMA either way)
+            split = max(2, min(16, c.D // 32))
+            ops.linear_splitk(tw["vn"], tw["mn"], None, tw["sd_ws"][:split * B * B], split, out=ws["sims_dual"])
+        else:
+            ops.linear(tw["vn"], tw["mn"], None, out=ws["sims_dual"])
+        static_ex = getattr(self, "_static_exclusion", None)  # TrainStepGraph: a fixed buffer the host refills before each replay
+        self._row_exclude = static_ex if static_ex is not None else self.same_music_exclusion(music_ids)
+        self._retrieval_loss(ws, video, music, row_exclude=self._row_exclude,
+                             pooled=tw["xpooled"] if c.vmr_loss == "dual_single_feature_fuse" else None)
+        out.update(sims_single=ws["sims_single"], sims_dual=ws["sims_dual"], retrieval_loss=ws["ret_loss"])
+        return out
+
+    def _detr_encoder_fwd(self, ws, tw) -> Tensor:
+        """DETR encoder over the fused sequence + position embedding -> tw["mem"] / tw["mempos"] (memory, memory + pos).  Returns the
+        memory as [B, L, D]."""
+        c, P = self.cfg, self.P
+        B, L, D, H = self._shape[0], self._fused_len(), c.D, c.detr_nheads
+        pd = float(c.detr_dropout)
+        fus_mask = ws["fus_mask"]
+        rows = B * L
+        rows_f, fskip, qskip = self._rows[fus_mask.data_ptr()], fus_mask.view(-1), fus_mask
+        if "regression" in c.mml_localization:
             # the regression head sums the memory over ALL positions, padded ones included (reference model_Uni.py:229): the encoder
             # computes them too (keys stay masked)
             fskip = qskip = rows_f = None
-        pos2 = pos.view(rows, D)
-        src = fus.view(rows, D)
+        pos2 = ws["pos"].view(rows, D)
+        src = ws["fus"].view(rows, D)
+        pre = bool(c.detr_pre_norm)
         if c.detr_enc_layers == 0:                            # no encoder: memory = the fused sequence itself
             ops.layernorm_add(src, None, None, pos2, tw["mem"], tw["mempos"], row_skip=fskip)
-        else:
+        elif not pre:
             srcpos = tw["e.0.srcpos"]
-            if not c.detr_pre_norm:
-                ops.layernorm_add(src, None, None, pos2, None, srcpos, row_skip=fskip)
-        pre = bool(c.detr_pre_norm)
+            ops.layernorm_add(src, None, None, pos2, None, srcpos, row_skip=fskip)
         xin = src                                             # pre-norm: the un-normalised residual stream entering the layer
         for l in range(c.detr_enc_layers):
             p, e = f"detr_transformer.encoder.layers.{l}", f"e.{l}"
@@ -820,30 +767,115 @@ class MadeTrainer(MadeEngine):
                 continue
             nsrc, nsp = (tw["mem"], tw["mempos"]) if last else (tw[f"e.{l + 1}.src"], tw[f"e.{l + 1}.srcpos"])
             ops.layernorm_add(x2, P[p + ".ln2.g"], P[p + ".ln2.b"], pos2, nsrc, nsp, row_skip=fskip)
-        memory, mempos = tw["mem"], tw["mempos"]
-        out["memory"] = memory.view(B, L, D)
+        return tw["mem"].view(B, L, D)
 
-        if regression:
-            return self._regression_train(out, ws, tw, memory.view(B, L, D), fus_mask, v_duration, cur, side)
+    def _query_pos_rows(self) -> Tensor:
+        """the decoder's query embedding as [B*Q, D] rows"""
+        B, Q, qp = self._shape[0], self.cfg.num_moment_queries, self.P["query_embed"]
+        return qp.expand(B * Q, self.cfg.D) if Q == 1 else qp.repeat(B, 1)
 
-        # ---- DETR decoder (memory-space cross-attention, per-head products written out)
-        mem3, mempos3 = memory.view(B, L, D), mempos.view(B, L, D)
-        if dec_early is None:
-            dec_fill_tgt()
-        hs = ws["hs"]
-        GQ = tw["GQ"]                                        # [B, 2, nd, H*Q, D]: part 1 holds the q' rows of every layer
+    def _dec_fill_tgt(self, ws, tw) -> None:
+        """the decoder's content query (layer 0's input) and, where layer 0's self-attention forms q / k, its sum with the query embedding"""
+        c = self.cfg
+        B, Q, D = self._shape[0], c.num_moment_queries, c.D
+        tgt = tw["d.0.tgt"]
+        if c.moment_query_type in ("video", "music", "xpool"):
+            src_vec = {"video": ws["video"], "music": ws["music"], "xpool": tw["xpool_q"]}[c.moment_query_type]
+            if Q == 1:
+                tr.add3(tgt, src_vec)                         # (f32 clip vector -> compute dtype; no framework kernel inside the step)
+            else:
+                tgt.view(B, Q, D).copy_(src_vec[:, None, :].expand(B, Q, D))
+        else:                                                # "zero" / "random": reference music_detr/transformer.py:73-74
+            _tape.zero_(tgt)
+        if Q > 1 and not c.detr_pre_norm:                    # (a single query's q / k projections are never formed: _dec_self_attn_fwd)
+            tr.add3(tw["d.0.tq"], tgt, self.P["query_embed"], b_mod=Q * D)
+
+    def _dec_self_attn_fwd(self, tw, l: int, x: Tensor) -> None:
+        """A decoder layer's self-attention in front of its out-projection -> tw[d.l.att].  x: the block's input (the layer's input, or
+        LN1 of it with pre-norm layers); q and k read tw[d.l.tq] = x + query embedding."""
+        c, P = self.cfg, self.P
+        B, D, Q, H = self._shape[0], c.D, c.num_moment_queries, c.detr_nheads
+        p, d = f"detr_transformer.decoder.layers.{l}", f"d.{l}"
+        Wsa, bsa = P[p + ".sa.in.w"], P[p + ".sa.in.b"]
+        drop = self._drop(f"dec.{l}" + ".sa_attn", float(c.detr_dropout))
+        if Q == 1:
+            # one query, one key: the softmax weight is 1, so the block is the value path; its attention-weight dropout is one
+            # draw per (sample, head) (element index (b*H + h)*1*1), and q / k get no gradient
+            # (the draw is the value Linear's epilogue: the undropped value itself is needed by nobody)
+            ops.linear(x, Wsa[2 * D:], bsa[2 * D:], out=tw[d + ".att"], drop=drop, drop_ld=H, drop_col_div=D // H)
+            return
+        qkv = tw[d + ".qkv"]
+        ops.linear(x, Wsa, bsa, A2=tw[d + ".tq"], a2_replace=True,
+                   segs=[Seg(out=qkv, col_begin=0, use_a2=True), Seg(out=qkv[:, 2 * D:], col_begin=2 * D, ldo=qkv.stride(0))])
+        q3 = qkv.view(B, Q, 3 * D)
+        ops.attention(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], tw[d + ".att"].view(B, Q, D), H, lse=tw[d + ".lse"], drop=drop)
+
+    def _dec_query_side(self, tw, l: int) -> None:
+        """the part of decoder layer l in front of its cross-attention: self-attention block, LayerNorm, cross-attention query and
+        its per-head fold -- it reads the layer's input and the weights, nothing the DETR encoder produces"""
+        c, P = self.cfg, self.P
+        B, D, Q, H = self._shape[0], c.D, c.num_moment_queries, c.detr_nheads
+        hd, pd = D // H, float(c.detr_dropout)
+        p, d = f"detr_transformer.decoder.layers.{l}", f"d.{l}"
+        tgt, qp = tw[d + ".tgt"], P["query_embed"]
+        Win, bin_ = P[p + ".ca.in.w"], P[p + ".ca.in.b"]
+        Wt = P[p + ".ca.in.wt"]                               # [D, 3D] = in_proj^T
+        stage, pre = self._dec_stage_chain(), bool(c.detr_pre_norm)
+        if stage:
+            # bf16, one moment query: the chain's LayerNorms run in the prologue of the Linear that consumes them (made_dec_stage, as on
+            # the eval path; dropout and the saved GEMM input in its epilogue / prologue), the value bias of the
+            # memory-space attention is the per-head Linear's epilogue: 10 launches per layer instead of 14
+            Wsa, bsa = P[p + ".sa.in.w"], P[p + ".sa.in.b"]
+            sa_drop = dict(drop=self._drop(f"dec.{l}" + ".sa_attn", pd), drop_ld=H, drop_col_div=hd)
+            if l == 0:
+                ops.dec_stage(tgt, Wsa[2 * D:], bsa[2 * D:], tw[d + ".att"], **sa_drop)
+            else:                                             # the previous layer's norm 3 in the prologue: t3 = this layer's input
+                q_ = f"detr_transformer.decoder.layers.{l - 1}"
+                ops.dec_stage(tw[f"d.{l - 1}.t_c"], Wsa[2 * D:], bsa[2 * D:], tw[d + ".att"], ln=(P[q_ + ".ln3.g"], P[q_ + ".ln3.b"]),
+                              x_out=tgt, **sa_drop)
+        elif pre:
+            # reference music_detr/transformer.py:246-257 (forward_pre): tgt is the un-normalised stream; the self-attention reads
+            # n1 = LN1(tgt) (q = k = n1 + query_pos, v = n1) and always runs; the cross-attention's query is LN2(stream) + query_pos.
+            # Buffers keep their roles: .t_a = stream after the self-attention, .t1 / .t1q = the cross-attention query's input.
+            n1 = tw[d + ".n1"]
+            qp_rows = self._query_pos_rows()
+            if Q == 1:
+                ops.layernorm(tgt, P[p + ".ln1.g"], P[p + ".ln1.b"], out=n1)
+            else:
+                ops.layernorm_add(tgt, P[p + ".ln1.g"], P[p + ".ln1.b"], qp_rows, n1, tw[d + ".tq"])
+            self._dec_self_attn_fwd(tw, l, n1)
+        else:
+            self._dec_self_attn_fwd(tw, l, tgt)
+        ta = ops.linear(tw[d + ".att"], P[p + ".sa.out.w"], P[p + ".sa.out.b"], R=tgt, out=tw[d + ".t_a"], drop=self._drop(f"dec.{l}" + ".drop1", pd))
+        if stage:
+            qc = ops.dec_stage(ta, Win[:D], bin_[:D], tw[d + ".qc"], ln=(P[p + ".ln1.g"], P[p + ".ln1.b"]), add=qp,
+                               x_out=tw[d + ".t1"], a_out=tw[d + ".t1q"])
+        else:
+            ln = ".ln2" if pre else ".ln1"
+            ops.layernorm_add(ta, P[p + ln + ".g"], P[p + ln + ".b"], qp_rows if pre else self._query_pos_rows(), tw[d + ".t1"], tw[d + ".t1q"])
+            qc = ops.linear(tw[d + ".t1q"], Win[:D], bin_[:D], out=tw[d + ".qc"])
+        qprime = tw["GQ"][:, 1, l]                            # [B, H*Q, D] view of GQ [B, 2, nd, H*Q, D]; q'_h = W_k,h^T qc_h  (b_k shifts all keys alike)
+        ops.linear(qc[:, :hd], Wt[:, D:D + hd], None, M=B * Q, N=D, K=hd, batch=H, a_z_stride=hd, w_z_stride=hd,
+                   segs=[Seg(out=qprime, ldo=D, rows_per_batch=Q, out_batch_stride=qprime.stride(0), out_z_stride=Q * D)])
+
+    def _decoder_fwd(self, ws, tw) -> Dict[str, Tensor]:
+        """DETR decoder behind layer 0's query side (memory-space cross-attention, per-head products written out) and the output norm
+        over the stack of layer outputs -> ws["hs"].  Returns its output."""
+        c, P = self.cfg, self.P
+        B, L = self._shape[0], self._fused_len()
+        D, Q, nd, H = c.D, c.num_moment_queries, c.detr_dec_layers, c.detr_nheads
+        hd, pd = D // H, float(c.detr_dropout)
+        ca_scale = 1.0 / math.sqrt(hd)
+        fus_mask, hs = ws["fus_mask"], ws["hs"]
+        mem3, mempos3 = tw["mem"].view(B, L, D), tw["mempos"].view(B, L, D)
+        stage = self._dec_stage_chain()                       # fused chain: see _dec_query_side
         n_split, wplan = self._wide_split(B)
-        t3_stack = tw["dstack"]["tgt"][1:]                   # [nd, B*Q, D]: slot l + 1 = layer l's output (t3)
         for l in range(nd):
             p, d = f"detr_transformer.decoder.layers.{l}", f"d.{l}"
-            tgt, tq = tw[d + ".tgt"], tw[d + ".tq"]
-            qkv = tw[d + ".qkv"]
-            if l == 0 and dec_early is not None:
-                cur.wait_event(dec_early)                      # layer 0's query side ran beside the DETR encoder (second stream)
-            else:
-                dec_query_side(l)
+            if l > 0:                                         # (layer 0's is the schedule's: forward_train)
+                self._dec_query_side(tw, l)
             Win, bin_ = P[p + ".ca.in.w"], P[p + ".ca.in.b"]
-            qprime, t1 = GQ[:, 1, l], tw[d + ".t1"]
+            qprime, t1 = tw["GQ"][:, 1, l], tw[d + ".t1"]
             pooled = tw[d + ".pooled"]                        # [B*Q, H*D]: row (b, q), head-major columns
             s_out = tw[d + ".s"] if Q == 1 else tw["s_raw"]   # the kernel numbers its rows (b, h, q); the Linears below (b, q, h)
             ops.attention_wide(qprime.view(B, H, Q, D), mempos3, mem3, pooled.view(B, Q, H, D).permute(0, 2, 1, 3), scale=ca_scale,
@@ -882,15 +914,22 @@ class MadeTrainer(MadeEngine):
                 if l + 1 == nd:                               # (inside the chain norm 3 is the next layer's prologue; the last one has no consumer)
                     ops.layernorm(tcx, P[p + ".ln3.g"], P[p + ".ln3.b"], out=t3)
             elif l + 1 < nd:
-                ops.layernorm_add(tcx, P[p + ".ln3.g"], P[p + ".ln3.b"], qp.expand(B * Q, D) if Q == 1 else qp.repeat(B, 1), t3, tw[f"d.{l + 1}.tq"])
+                ops.layernorm_add(tcx, P[p + ".ln3.g"], P[p + ".ln3.b"], self._query_pos_rows(), t3, tw[f"d.{l + 1}.tq"])
             else:
                 ops.layernorm(tcx, P[p + ".ln3.g"], P[p + ".ln3.b"], out=t3)
         # the shared output norm of every layer feeds the heads only, not the next layer: one launch over the [nd, B*Q] stack
-        # of layer outputs after the chain instead of one inside every layer
-        ops.layernorm(t3_stack.reshape(nd * B * Q, D), P["dec.norm.g"], P["dec.norm.b"], out=hs.view(nd * B * Q, D))
-        out["hs"] = hs.view(nd, B, Q, D)
+        # of layer outputs (slot l + 1 of the tgt stack = layer l's output) after the chain instead of one inside every layer
+        ops.layernorm(tw["dstack"]["tgt"][1:].reshape(nd * B * Q, D), P["dec.norm.g"], P["dec.norm.b"], out=hs.view(nd * B * Q, D))
+        return dict(hs=hs.view(nd, B, Q, D))
 
-        # ---- heads
+    def _heads_fwd(self, ws, tw, v_duration: Optional[Tensor]) -> Dict[str, Tensor]:
+        """Heads over every decoder layer's output (class, span, moment embedding, contrastive projections), matcher and criterion.
+        Returns their outputs; the match is kept for the backward (self._match)."""
+        c, P = self.cfg, self.P
+        B, Tv, _ = self._shape
+        D, Q, nd = c.D, c.num_moment_queries, c.detr_dec_layers
+        hs, music, frame = ws["hs"], ws["music"], self._views[0]
+        out: Dict[str, Tensor] = {}
         hs2 = hs.view(nd * B * Q, D)
         logits, spans = ws["logits"], ws["spans"]
         ops.linear(hs2, P["class_embed.w"], P["class_embed.b"], out=logits.view(-1, 2))
@@ -944,7 +983,6 @@ class MadeTrainer(MadeEngine):
         self._match = (pi, ti, cnt)
         out.update(matcher_pred_idx=pi.view(nd, B, -1), matcher_tgt_idx=ti.view(nd, B, -1), matcher_count=cnt.view(nd, B),
                    matcher_status=status, criterion_losses=losses, localization_loss=total)
-        cur.wait_stream(side)
         return out
 
     def _opt_stream(self):
@@ -1007,8 +1045,7 @@ class MadeTrainer(MadeEngine):
             # reference model_Base.py:527-530: the learned token goes first with mask entry 1; the block then runs on T + 1 positions
             mask1 = tw[tag + ".mask1"]
             mask1[:, 0] = 1.0; mask1[:, 1:] = mask
-            self._rows[mask1.data_ptr()] = ops.row_index(mask1, out=tw[tag + ".rows1"])
-            self._order[mask1.data_ptr()] = ops.batch_order(mask1, out=tw[tag + ".order1"])
+            self._index_lists(mask1, tw[tag + ".rows1"], tw[tag + ".order1"])
             x3 = x.view(B, T1, D)
             x3[:, 0] = (P["cls_" + name].float() + P[pe][0].float()).to(self.tc)
             lin_out = dict(segs=[Seg(out=x3[:, 1:], ldo=D, rows_per_batch=T, out_batch_stride=T1 * D)])
@@ -1065,9 +1102,6 @@ class MadeTrainer(MadeEngine):
         s1 = ops.layernorm(seg, P[key + ".ln1.g"], P[key + ".ln1.b"], out=tw[pre + "s1"], row_skip=skip)
         ops.linear(s1, P[key + ".kv.w"], P[key + ".kv.b"], rows=self._rw(skip), tile_skip_mask=skip if self._rw(skip) is None else None,
                    segs=[Seg(out=tw[pre + "k"], col_begin=0), Seg(out=tw[pre + "u"], col_begin=D)])
-        # 64 videos x 64 tracks: one workgroup per track would leave three quarters of the chip idle on a kernel that streams 1 MB of
-        # K / U per track at one CU's rate -- the keys are split over workgroups (up to 256 of them), a second launch merges the slices
-        # (tools/xpool_qk_bench.py, profiles/r03_xpool_qk_microbench.txt: 56.8 us unsplit, 34.9 us split four ways)
         inbatch = (self.tc == torch.bfloat16 and B <= 64 and S <= 512 and S * D >= 65536 and D in (256, 512) and _lib.variant_env("MADE_XPOOL_INBATCH", "1") != "0")   # (shorter / narrower tracks: one launch of made_attention_wide is faster -- 10.9 vs 12.3 us at S = 96, D = 256)
         if inbatch:
             # round 4: scores per (track, 128 segments), then P.V per (track, 128 value columns) -- two launches of one workgroup per CU, only the
@@ -1076,15 +1110,16 @@ class MadeTrainer(MadeEngine):
                 tw[pre + "xib_ws"] = torch.zeros(ops.xpool_inbatch_ws_bytes(B, S), device=self.device, dtype=torch.uint8)
             ops.xpool_inbatch(q, tw[pre + "k"].view(B, S, D), tw[pre + "u"].view(B, S, D), seg_mask, tw[pre + "o"].view(B, B, D),
                               scale=1.0 / math.sqrt(D), ws=tw[pre + "xib_ws"])
-        xsplit = max(1, min(4, 256 // max(B, 1), S // 64)) if (B <= 64 and self.tc == torch.bfloat16) else 1
-        if inbatch:
-            pass
-        elif xsplit > 1:
-            need = B * xsplit * B
-            if tw.get("xpart_o") is None or tw["xpart_o"].numel() < need * D:
-                tw["xpart_o"] = torch.empty(need * D, device=self.device, dtype=torch.float32)
-                tw["xpart_ml"] = torch.empty(need * 4, device=self.device, dtype=torch.float32)
-        if not inbatch:
+        else:
+            # 64 videos x 64 tracks: one workgroup per track would leave three quarters of the chip idle on a kernel that streams 1 MB of
+            # K / U per track at one CU's rate -- the keys are split over workgroups (up to 256 of them), a second launch merges the slices
+            # (tools/xpool_qk_bench.py, profiles/r03_xpool_qk_microbench.txt: 56.8 us unsplit, 34.9 us split four ways)
+            xsplit = max(1, min(4, 256 // max(B, 1), S // 64)) if (B <= 64 and self.tc == torch.bfloat16) else 1
+            if xsplit > 1:
+                need = B * xsplit * B
+                if tw.get("xpart_o") is None or tw["xpart_o"].numel() < need * D:
+                    tw["xpart_o"] = torch.empty(need * D, device=self.device, dtype=torch.float32)
+                    tw["xpart_ml"] = torch.empty(need * 4, device=self.device, dtype=torch.float32)
             ops.attention_wide(q.view(1, B, 1, D), tw[pre + "k"].view(B, S, D), tw[pre + "u"].view(B, S, D), tw[pre + "o"].view(B, B, 1, D),
                                scale=1.0 / math.sqrt(D), key_mask=seg_mask, shared_q=True, n_split=xsplit,
                                part_o=tw.get("xpart_o") if xsplit > 1 else None, part_ml=tw.get("xpart_ml") if xsplit > 1 else None)
@@ -1391,7 +1426,7 @@ class MadeTrainer(MadeEngine):
         ca_scale = 1.0 / math.sqrt(hd)
         st = tw["dstack"]
         dtgt = None
-        stage = self._dec_stage_chain()                    # fused chain: see forward_train
+        stage = self._dec_stage_chain()                    # fused chain: see _dec_query_side
         pre = bool(c.detr_pre_norm)                        # pre-norm layers (reference music_detr/transformer.py:246-271): separate launches
         if stage:
             n_split, wplan = self._wide_split(B, backward=True)
@@ -1623,7 +1658,7 @@ class MadeTrainer(MadeEngine):
         pd = float(c.detr_dropout)
         inv_keep = 1.0 / (1.0 - pd) if (self.training_dropout and pd > 0) else 1.0
         fus, fus_mask = ws["fus"], ws["fus_mask"]
-        # the regression head sums the memory over ALL positions: the encoder computed the padded ones too (forward_train)
+        # the regression head sums the memory over ALL positions: the encoder computed the padded ones too (_detr_encoder_fwd)
         fskip = None if "regression" in c.mml_localization else fus_mask.view(-1)
         dsrc = dmem
         for l in range(ne - 1, -1, -1):
@@ -1711,12 +1746,13 @@ class MadeTrainer(MadeEngine):
             dxv = tw["ydseg"] if dxv is None else tr.add3(tw["dframe_sum"], dxv, tw["ydseg"])
         self._encode_bwd("video", ws, tw, d_local, dxv.view(B, Tv, D) if dxv is not None else None, tw["dvideo"], fm, feats_v)
 
-    def _regression_train(self, out, ws, tw, mem3: Tensor, fus_mask: Tensor, v_duration, cur, side) -> Dict[str, Tensor]:
+    def _regression_train(self, ws, tw, v_duration: Optional[Tensor]) -> Dict[str, Tensor]:
         """reference model/model_Uni.py:228-232,290-300 in train mode: memory summed over all L positions / number of valid ones ->
         3-layer ReLU MLP -> sigmoid; loss = 20 * L1 (mean over every element of the [B, 1, 2] spans).  No decoder on this path."""
         c, P = self.cfg, self.P
-        B = mem3.shape[0]
-        cnt = fus_mask.sum(dim=1, keepdim=True)
+        B = self._shape[0]
+        mem3 = tw["mem"].view(B, self._fused_len(), c.D)
+        cnt = ws["fus_mask"].sum(dim=1, keepdim=True)
         fx = (ops.masked_mean(mem3, None) / cnt).to(self.tc)
         h1 = ops.linear(fx, P["reg_mlp.0.w"], P["reg_mlp.0.b"], act=ops.ACT_RELU)
         h2 = ops.linear(h1, P["reg_mlp.1.w"], P["reg_mlp.1.b"], act=ops.ACT_RELU)
@@ -1730,9 +1766,7 @@ class MadeTrainer(MadeEngine):
         assert tg.shape == (B, 1, 2), f"spans_target.shape {tuple(tg.shape)} must equal to src_spans.shape {(B, 1, 2)}"
         l1 = (spans.view(B, 1, 2) - tg).abs().mean()
         self._reg = (fx, h1, h2, spans, cnt, tg)
-        out.update(pred_spans=spans.view(B, 1, 2), regression_loss_span=l1, localization_loss=(l1 * 20).view(1))
-        cur.wait_stream(side)
-        return out
+        return dict(pred_spans=spans.view(B, 1, 2), regression_loss_span=l1, localization_loss=(l1 * 20).view(1))
 
     def _regression_bwd(self, ws, tw, g_loc: Optional[Tensor], B: int, L: int) -> Tensor:
         """Gradient of g_loc * 20 * mean|spans - target| back through the regression MLP to the encoder memory: every one of the L
