@@ -1194,6 +1194,36 @@ int made_merge_moments(const float* cand, const int32_t* win_col, const float* w
                        float* start_out, float* end_out, float* conf_out, int32_t* window_out, void* stream);
 
 /* ==========================================================================================
+ * FP8 token storage of a music library (mgsv_amd/library.py dtype "fp8"; csrc/fp8.hip, csrc/fp8_format.h).  A token row is the D
+ * bf16 values of one (column, segment).  It is stored as one int8 exponent e and D bytes:
+ *   e       0 for a row of zeros; else the smallest integer with amax * 2^-e <= 448 (amax = max |x| over the row), clamped to
+ *           [-120, 120]: with amax = m * 2^ex, m in [0.5, 1), e = ex - 9 if m <= 0.875 and ex - 8 otherwise;
+ *   byte    the OCP e4m3fn encoding (not the MI300X fnuz one) of x * 2^-e, round to nearest, ties to even, with subnormals; the
+ *           product is exact and at most 448, so neither saturation nor a NaN code arises; -0 keeps its sign;
+ *   value   bf16(byte) * 2^e, which is exact in bf16 (a 4-bit significand into 8; 2^-9 * 2^-120 is still a bf16 subnormal).
+ * Non-finite tokens have no encoding, and neither have the seven bf16 magnitudes from 248 * 2^120 on (they scale past 248, round
+ * to the payload 256 and would widen to 2^128): the callers refuse both before quantising (mgsv_amd/library.py FP8_MAX_TOKEN); a
+ * NaN or infinity here would set amax's pattern above every number and give meaningless bytes.  Re-quantising the dequantised row
+ * gives the same values, and the same bytes unless the row's scaled maximum rounded down to 224: the smallest exponent is then
+ * one less and every byte the code of twice its value.  The reference stores f32 features only.
+ * ========================================================================================== */
+
+/* made_fp8_quantize_rows: q [R, D] uint8 and exp [R] int8 of the rows of src [R, D] bf16 (contiguous).  A 16-lane group per row,
+ * 16-byte loads, amax by a DPP reduction over the group, the exponent from amax's bits, integer arithmetic on the patterns.  No
+ * LDS, no atomics, no workspace.  D in {128, 256, 512} (MADE_ERR_UNSUPPORTED otherwise); src and q 16-byte aligned; the outputs
+ * must not overlap the input or each other. */
+int made_fp8_quantize_rows(const void* src, int64_t R, int64_t D, uint8_t* q, int8_t* exp, void* stream);
+
+/* made_fp8_dequantize_rows: dst [R * rows_per_index, D] bf16 from q [U, rows_per_index, D] uint8 and exp [U, rows_per_index] int8.
+ * index [R] device int32: dst block r = the dequantised block index[r] (rows_per_index = S gathers whole columns of [N, S, D]
+ * tokens, every row with its own exponent); an index < 0 or >= U writes a zero block and reads nothing, as made_gather_rows does.
+ * index == NULL: blocks 0 .. R - 1 of the given base (R <= U), so a contiguous slice needs no index.  One lane per 16 values: 16
+ * payload bytes in, two 16-byte stores out.  No LDS, no atomics, no workspace.  D in {128, 256, 512} (MADE_ERR_UNSUPPORTED
+ * otherwise); q and dst 16-byte aligned; dst must not overlap q, exp or index. */
+int made_fp8_dequantize_rows(const uint8_t* q, const int8_t* exp, int64_t U, const int32_t* index, int64_t R, int64_t rows_per_index,
+                             int64_t D, void* dst, void* stream);
+
+/* ==========================================================================================
  * Frames: decoded video frames -> the input of the CLIP ViT-B/32 visual tower (mgsv_amd/frames.py).  The reference extracts its
  * frame features with OpenAI's clip package (model/model_Base.py:286-289,406-450) after torchvision preprocessing
  * (dataloaders/dataloader_MGSV_EC_rawdata.py:16-25); the tower itself runs on made_linear / made_layernorm / made_attention.

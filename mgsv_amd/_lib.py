@@ -322,6 +322,8 @@ SIGNATURES = {
     "made_mmr_select": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, i64, f32, f32, vp, vp, vp]),
     "made_cosine_join": (C.c_int, [vp, i64, i64, vp, i64, i64, i64, i64, f32, vp, vp, vp, i64, vp, vp]),
     "made_merge_moments": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, f32, f32, i64, vp, vp, vp, vp, vp]),
+    "made_fp8_quantize_rows": (C.c_int, [vp, i64, i64, vp, vp, vp]),
+    "made_fp8_dequantize_rows": (C.c_int, [vp, vp, i64, vp, i64, i64, i64, vp, vp]),
     "made_frames_preprocess": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i32, i64, vp, vp]),
     "made_audio_resample": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp]),
     "made_audio_fbank": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, i32, vp, vp]),

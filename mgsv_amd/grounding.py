@@ -479,6 +479,16 @@ def _device_fetch(tokens: Tensor, mask: Tensor):
     return fetch
 
 
+def _device_fetch_fp8(library, deq: "_Dequantize"):
+    """`_score_candidates`' fetch from a device FP8 library: the listed columns gathered and dequantised in one launch"""
+    dev = library.tokens.device
+    def fetch(cols: np.ndarray):
+        i64 = torch.from_numpy(cols).to(dev)
+        i32 = i64.to(torch.int32)
+        return deq(library.tokens, library.tokens_exp, i32), _gather_device(library.mask, i32, i64), (lambda: None)
+    return fetch
+
+
 @torch.no_grad()
 @_lib.scoped_f32_products
 def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Optional[Tensor] = None, group_id=None,
@@ -705,14 +715,42 @@ def _host_view(t: Tensor) -> np.ndarray:
     return t.view(torch.int16).numpy().view(np.uint16) if t.dtype == torch.bfloat16 else t.numpy()
 
 
+class _Dequantize:
+    """The made_fp8_dequantize_rows launches of one `ground_library` call on an FP8 library (every place that turns library rows into
+    an `Encoded` goes through here), with an event pair around each when the call is timed."""
+
+    def __init__(self, timed: bool):
+        self.marks = [] if timed else None
+
+    def __call__(self, q: Tensor, exp: Tensor, index: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+        if self.marks is None:
+            return ops.fp8_dequantize_rows(q, exp, index, out)
+        e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        e[0].record()
+        out = ops.fp8_dequantize_rows(q, exp, index, out)
+        e[1].record()
+        self.marks.append(e)
+        return out
+
+    def total_ms(self) -> float:
+        """(after a synchronisation)"""
+        return sum(a.elapsed_time(b) for a, b in self.marks or [])
+
+
 class _Staging:
     """`sets` pinned host sets and as many device sets of (tokens, mask, vec, duration) for `rows` columns, a copy stream and the
-    events that order them.  Kept on the library, so that later calls reuse the pinned memory."""
+    events that order them.  Kept on the library, so that later calls reuse the pinned memory.  An FP8 library's sets hold the
+    uint8 payload and, as a fifth array, the int8 exponents; `wide` is the ONE bf16 device buffer `widen` dequantises a set into on
+    the compute stream -- one suffices, since its readers run in order on that stream."""
 
     def __init__(self, library, rows: int, dev, sets: int):
         S, D = library.S, library.D
-        tc = torch.bfloat16 if library.dtype == "bf16" else torch.float32
+        fp8 = library.dtype == "fp8"
+        tc = torch.uint8 if fp8 else (torch.bfloat16 if library.dtype == "bf16" else torch.float32)
         shapes = (((rows, S, D), tc), ((rows, S), torch.float32), ((rows, D), torch.float32), ((rows,), torch.float32))
+        if fp8:
+            shapes += (((rows, S), torch.int8),)
+        self.wide = torch.empty((rows, S, D), dtype=torch.bfloat16, device=dev) if fp8 else None
         self.rows = rows
         self.host = [[torch.empty(s, dtype=t, pin_memory=True) for s, t in shapes] for _ in range(sets)]
         self.dev = [[torch.empty(s, dtype=t, device=dev) for s, t in shapes] for _ in range(sets)]
@@ -725,7 +763,7 @@ class _Staging:
         """Host: the library's rows (a slice, or an index array) into pinned set j, once the upload that last read it has finished."""
         self.uploaded[j].synchronize()
         n = 0
-        for dst, src in zip(self.host[j], (library.tokens, library.mask, library.vec, library.duration)):
+        for dst, src in zip(self.host[j], (library.tokens, library.mask, library.vec, library.duration, library.tokens_exp)):
             if src is None:
                 continue
             if isinstance(src, Tensor):
@@ -747,11 +785,20 @@ class _Staging:
         self.copy.wait_event(self.consumed[j])
         with torch.cuda.stream(self.copy):
             for k, (dst, s) in enumerate(zip(self.dev[j], self.host[j] if src is None else src)):
-                if k < 3 or has_duration:
+                if k != 3 or has_duration:
                     dst[:n].copy_(s[:n], non_blocking=True)
             self.uploaded[j].record(self.copy)
-        tok, mask, vec, dur = (t[:n] for t in self.dev[j])
+        tok, mask, vec, dur = (t[:n] for t in self.dev[j][:4])
         return Encoded(tokens=tok, mask=mask, vec=vec, duration=dur if has_duration else None)
+
+    def widen(self, j: int, enc: Encoded, deq: Optional[_Dequantize]) -> Encoded:
+        """Compute stream, after `uploaded[j]` was waited on: the Encoded of device set j with bf16 tokens -- an FP8 library's payload
+        dequantised into `wide`; any other library's set as it is."""
+        if self.wide is None:
+            return enc
+        n = enc.tokens.shape[0]
+        tokens = deq(self.dev[j][0][:n], self.dev[j][4][:n], out=self.wide[:n])
+        return Encoded(tokens=tokens, mask=enc.mask, vec=enc.vec, duration=enc.duration)
 
 
 def _staging(library, name: str, rows: int, dev, sets: int) -> _Staging:
@@ -870,20 +917,24 @@ def _kept_columns(library, col_any: Tensor) -> np.ndarray:
 
 
 def _select_walk(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, chunk_cols: int, items: List[WalkChunk], sims_fn,
-                 timings: Optional[dict], rc: Optional[_RowConstraints] = None, attrs=None):
+                 timings: Optional[dict], rc: Optional[_RowConstraints] = None, attrs=None, deq: Optional[_Dequantize] = None):
     """(wcol int32, wscore f32) [N_v, kk, w]: every video's best kk groups among the items' columns and the best w columns of each,
     library column numbers -- what made_topk_groups + made_group_topw give on the whole similarity matrix, folded over `walk_plan`'s
     items.  rc / attrs (`_library_constraints`): the same under per-video constraints -- made_eligibility's bits per chunk, then
     made_topk_groups_masked + made_group_topw_masked.  A listed item is gathered by its columns (a pinned library then takes the
-    staging copy) and its local column numbers are mapped back through them."""
+    staging copy) and its local column numbers are mapped back through them.  deq (an FP8 library): every chunk's payload is
+    dequantised into one bf16 buffer in front of its similarities -- a host library's after its upload, a device library's slice or
+    listed columns directly -- and that is the chunk a hook receives."""
     dev = engine.device
     Nv = len(videos)
+    fp8 = library.dtype == "fp8"
     tables = _walk_tables(library, items, chunk_cols, dev)
     longest = max((it.n for it in items), default=1)
     cols_all = torch.arange(longest, device=dev, dtype=torch.int32) if w > 1 else None      # made_group_topw's CSR column list: groups are contiguous
     cur = torch.cuda.current_stream()
     resident = library.on_device
     stage = None if resident else _staging(library, "chunks", longest, dev, 2)
+    wide = torch.empty(longest, library.S, library.D, device=dev, dtype=torch.bfloat16) if resident and fp8 and items else None
     has_dur = library.duration is not None
     video = videos.vec.to(dev, torch.float32).contiguous()
     sims_buf = single_buf = bits_buf = None
@@ -901,10 +952,15 @@ def _select_walk(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, 
         rows, n, cols = items[i].rows, items[i].n, tables[i][2]
         arrays = (library.tokens, library.mask, library.vec, library.duration if has_dur else None)
         if resident:
-            part = [None if a is None else (a[rows] if cols is None else _gather_device(a, cols[0], cols[1])) for a in arrays]
+            part = [None if a is None or (fp8 and a is library.tokens) else (a[rows] if cols is None else _gather_device(a, cols[0], cols[1]))
+                    for a in arrays]
+            if fp8 and cols is None:                                # the slice needs no index ...
+                part[0] = deq(library.tokens[rows], library.tokens_exp[rows], out=wide[:n])
+            elif fp8:                                               # ... the listed columns are gathered by the same launch
+                part[0] = deq(library.tokens, library.tokens_exp, cols[0], out=wide[:n])
             return Encoded(tokens=part[0], mask=part[1], vec=part[2], duration=part[3])
         if library.pinned and cols is None:                         # pinned already: no staging copy for a contiguous chunk
-            return stage.upload(i % 2, n, has_dur, src=[None if a is None else a[rows] for a in arrays])
+            return stage.upload(i % 2, n, has_dur, src=[None if a is None else a[rows] for a in arrays + (library.tokens_exp,)])
         got = stage.fill(i % 2, library, rows)
         return stage.upload(i % 2, got, has_dur)
 
@@ -912,13 +968,17 @@ def _select_walk(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, 
     for i, it in enumerate(items):
         chunk, n, c0 = nxt, it.n, it.col_offset
         gid, start, cols = tables[i]
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timings is not None else None
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)] if timings is not None else None
         if ev:
             ev[0].record(cur)
         if not resident:
             cur.wait_event(stage.uploaded[i % 2])
         if ev:
             ev[1].record(cur)
+        if not resident and fp8:                                    # (its own phase: dequantize_ms)
+            chunk = stage.widen(i % 2, chunk, deq)
+        if ev:
+            ev[5].record(cur)
         if sims_fn is not None:
             sims = (sims_fn(chunk, c0, c0 + n) if cols is None else sims_fn(chunk, cols[1], None)).to(dev, torch.float32)
             if sims.stride(1) != 1:
@@ -958,7 +1018,7 @@ def _select_walk(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, 
         wait = [max(0.0, e[0].elapsed_time(e[1])) for e in marks]  # the compute stream's stalls on uploads
         timings["chunks"] = len(items)
         timings["columns_scored"] = sum(it.n for it in items)
-        timings["similarities_ms"] = sum(e[1].elapsed_time(e[2]) for e in marks)
+        timings["similarities_ms"] = sum(e[5].elapsed_time(e[2]) for e in marks)
         if rc is not None:
             timings["eligibility_ms"] = sum(e[2].elapsed_time(e[3]) for e in marks)
         timings["selection_merge_ms"] = sum(e[sel].elapsed_time(e[4]) for e in marks)
@@ -968,7 +1028,7 @@ def _select_walk(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, 
 
 
 def _select_under_constraints(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, chunk_cols: int, sims_fn,
-                              timings: Optional[dict], constraints: Constraints, compact: Optional[bool]):
+                              timings: Optional[dict], constraints: Constraints, compact: Optional[bool], deq: Optional[_Dequantize] = None):
     """`_select_walk` under per-video constraints.  A union pass over all columns names the kept groups; with compact False the chunk
     plan is walked and chunks without a kept column are skipped, with compact True a restricted plan holds the kept groups only and
     every chunk is gathered by its list of library columns."""
@@ -987,7 +1047,7 @@ def _select_under_constraints(engine: MadeEngine, videos: Encoded, library, kk: 
     if compact is None:                                            # a hook written for (chunk, c0, c1) keeps working
         compact = False if sims_fn is not None else 2 * int(keep.sum()) <= N
     items, skipped = walk_plan(library, chunk_cols, keep, compact)
-    run = _select_walk(engine, videos, library, kk, w, chunk_cols, items, sims_fn, timings, rc, attrs)
+    run = _select_walk(engine, videos, library, kk, w, chunk_cols, items, sims_fn, timings, rc, attrs, deq)
     if timings is not None:                                         # (the walk has synchronised)
         timings["chunks_skipped"] = skipped
         timings["compact"] = bool(compact)
@@ -996,7 +1056,7 @@ def _select_under_constraints(engine: MadeEngine, videos: Encoded, library, kk: 
 
 
 def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, chunk_cols: int, R: int,
-                        constraints: Optional[Constraints], timings: Optional[dict]):
+                        constraints: Optional[Constraints], timings: Optional[dict], deq: Optional[_Dequantize] = None):
     """(wcol, wscore [N_v, kk, w], (cand_col, cand_score [N_v, R])): `ground(..., shortlist=R)`'s selection on a stored library.
     Stage 1 reads `vec` and the attribute arrays only; stage 2 the tokens and masks of the distinct shortlisted columns."""
     dev = engine.device
@@ -1024,13 +1084,14 @@ def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w
     if ev:
         ev[1].record(cur)
     if resident:
-        fetch = _device_fetch(library.tokens, library.mask)
+        fetch = _device_fetch_fp8(library, deq) if library.dtype == "fp8" else _device_fetch(library.tokens, library.mask)
     else:
         def fetch(cols: np.ndarray):                               # the pinned "columns" staging set, as the localization uses it
             stage = _staging(library, "columns", len(cols), dev, 1)
             n = stage.fill(0, library, cols)
             enc = stage.upload(0, n, False)
             cur.wait_event(stage.uploaded[0])
+            enc = stage.widen(0, enc, deq)
             return enc.tokens, enc.mask, (lambda: stage.consumed[0].record(cur))
     stats = {}
     cand_score = _score_candidates(engine, video, cand_col, cand_cos, fetch, chunk_cols, stats)
@@ -1084,7 +1145,12 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     is made_topk_candidates.  timings then receives shortlist_ms, pairs_scored, columns_projected, pair_score_ms, selection_ms.
     diversity / max_similarity / pool: `ground(..., diversity=, max_similarity=, pool=)` for the stored library, bit for bit: the walk
     selects the pool, made_mmr_select re-selects k of it against the library's `vec` (a host library: the distinct representative
-    columns of the call, read and uploaded once), and only the k kept are localized.  timings then receives diversify_ms."""
+    columns of the call, read and uploaded once), and only the k kept are localized.  timings then receives diversify_ms.
+    An FP8 library (`MusicLibrary.quantize`; a bf16 engine only): the same Grounding, bit for bit, as for `library.dequantized()`.
+    Host chunks and column sets are staged and uploaded as bytes and exponents -- half the traffic -- and one
+    made_fp8_dequantize_rows launch widens each to bf16 on the compute stream in front of the kernels that read it; a device
+    library's slices and listed columns are widened into a scratch buffer; localization and the shortlist's second stage gather
+    and widen the distinct selected columns (the whole library is never widened).  timings then receives dequantize_ms."""
     c = engine.cfg
     dev = engine.device
     shortlist = check_shortlist(c, shortlist, sims_fn is not None)
@@ -1102,16 +1168,18 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     ks = _pool_size(div, kk, library.n_groups)
     video_batch = max(1, int(video_batch))
     t0 = torch.cuda.Event(enable_timing=True) if timings is not None else None
+    fp8 = library.dtype == "fp8"
+    deq = _Dequantize(timings is not None) if fp8 else None
     cand = None
     if shortlist is not None:
-        wcol, wscore, cand = _select_shortlisted(engine, videos, library, ks, w, int(chunk_cols), min(shortlist, N), constraints, timings)
+        wcol, wscore, cand = _select_shortlisted(engine, videos, library, ks, w, int(chunk_cols), min(shortlist, N), constraints, timings, deq)
     elif constraints is None:
         items, skipped = walk_plan(library, int(chunk_cols))
-        wcol, wscore = _select_walk(engine, videos, library, ks, w, int(chunk_cols), items, sims_fn, timings)
+        wcol, wscore = _select_walk(engine, videos, library, ks, w, int(chunk_cols), items, sims_fn, timings, deq=deq)
         if timings is not None:
             timings["chunks_skipped"] = skipped
     else:
-        wcol, wscore = _select_under_constraints(engine, videos, library, ks, w, int(chunk_cols), sims_fn, timings, constraints, compact)
+        wcol, wscore = _select_under_constraints(engine, videos, library, ks, w, int(chunk_cols), sims_fn, timings, constraints, compact, deq)
     pool_rank = redundancy = None
     if div is not None:
         td = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timings is not None else None
@@ -1129,7 +1197,8 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
         t0.record()
     rep, score = wcol[:, :, 0].contiguous(), wscore[:, :, 0].contiguous()
     resident = library.on_device
-    if resident:
+    whole = resident and not fp8                                    # (an FP8 library is never widened whole: its distinct selected columns are)
+    if whole:
         music_all = library.as_encoded(dev)
     offset = track_of_col = duration = None
     if windows is not None:
@@ -1144,8 +1213,15 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
         cols = wcol[v0:v1].reshape(-1)
         mi = torch.where(cols < 0, torch.zeros_like(cols), cols)   # (nothing there: localized against column 0, as in `ground`)
         vi = torch.arange(v0, v1, device=dev, dtype=torch.int32).repeat_interleave(kk * w)
-        if resident:
+        if whole:
             music = music_all
+        elif resident:                                              # a device FP8 library: the distinct columns gathered and widened
+            uniq, inv = torch.unique(mi, return_inverse=True)
+            u32, u64 = uniq.to(torch.int32).contiguous(), uniq.to(torch.int64)
+            music = Encoded(tokens=deq(library.tokens, library.tokens_exp, u32), mask=_gather_device(library.mask, u32, u64),
+                            vec=_gather_device(library.vec, u32, u64),
+                            duration=None if library.duration is None else library.duration.index_select(0, u64))
+            mi = inv.to(torch.int32).contiguous()
         else:                                                       # the distinct columns of this batch, uploaded as a compact Encoded
             uniq, inv = torch.unique(mi, return_inverse=True)
             rows = uniq.cpu().numpy().astype(np.int64)
@@ -1153,6 +1229,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
             nrows = stage.fill(0, library, rows)
             music = stage.upload(0, nrows, library.duration is not None)
             torch.cuda.current_stream().wait_event(stage.uploaded[0])
+            music = stage.widen(0, music, deq)
             mi = inv.to(torch.int32).contiguous()
         if windows is None:
             st, en, cf = _pair_moments(engine, videos, music, vi, mi, cols < 0, pair_batch, min_pairs=min_pairs)
@@ -1170,6 +1247,8 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
         t1.record()
         torch.cuda.synchronize()
         timings["localization_ms"] = t0.elapsed_time(t1)
+        if fp8:
+            timings["dequantize_ms"] = deq.total_ms()
     cc, cs = (None, None) if cand is None else cand
     if windows is None:
         return Grounding(track=rep, score=score, start=start, end=end, confidence=conf, cand_col=cc, cand_score=cs,

@@ -11,6 +11,11 @@ arrays tokens [N, S, D] (float32, or uint16 holding bf16 bit patterns), mask [N,
 source [N] int64, optionally duration [N] f32, win_track int32 / win_offset f32 / win_duration f32 [N], track_group [n_tracks]
 int32, and ids.json.  Optional track attributes for `ground_library(..., constraints=...)`: tags.npy int64 and length.npy f32, one
 entry per track, named by the manifest's "attributes" {tags, length, tag_names}; a manifest without that entry has none.
+
+FP8 token storage (dtype "fp8"): tokens.npy is uint8 [N, S, D], one OCP e4m3fn byte per value, and tokens_exp.npy int8 [N, S] holds
+one power-of-two exponent per token row (the format: include/made_hip.h, csrc/fp8_format.h); the manifest says "dtype": "fp8" and
+"compute": "bf16", the dtype the tokens are widened to on the device and the only engine dtype such a library serves.  The widening
+is exact, so an FP8 library is the bf16 library of its dequantised tokens (`dequantized()`); every other array is unchanged.
 """
 from __future__ import annotations
 
@@ -31,6 +36,93 @@ VERSION = 1
 MAX_GROUPED_CHUNK = 32768               # made_topk_groups: one LDS slot per group, and a chunk has at most as many groups as columns
 MAX_CHUNK = 1 << 24                     # made_topk_groups: columns of one call
 _NPY_HEADER = 128                       # the writer's fixed-size .npy header, rewritten with the final shape on close()
+
+
+FP8_WIDTHS = (128, 256, 512)              # made_fp8_quantize_rows / made_fp8_dequantize_rows: the row widths they take
+FP8_MAX_TOKEN = 247 * 2.0 ** 120         # the largest magnitude the format holds: from 248 * 2^120 on a value rounds to the payload 256 * 2^120 = 2^128
+_FP8_STEP = 1 << 22                      # token values the host formulation and the conversions handle at a time
+_TOP_BIT = np.array([0] + [int(np.log2(i)) for i in range(1, 256)], np.int32)       # floor(log2 i) for i < 256 (entry 0 unused)
+
+
+def _check_fp8_width(D: int) -> None:
+    if int(D) not in FP8_WIDTHS:
+        raise ValueError(f"D = {int(D)}: FP8 token storage takes rows of {FP8_WIDTHS} values")
+
+
+def fp8_quantize_host(bits: np.ndarray):
+    """The FP8 token format on the host, in numpy integer arithmetic on the bf16 patterns (csrc/fp8_format.h restated): bits uint16
+    [..., D] -> (payload uint8 [..., D], exponent int8 [...]), bit for bit what made_fp8_quantize_rows writes.  Finite values only."""
+    bits = np.asarray(bits)
+    assert bits.dtype == np.uint16
+    x = bits.astype(np.int32)
+    mag = x & 0x7FFF
+    amax = mag.max(axis=-1) if mag.shape[-1] else np.zeros(mag.shape[:-1], np.int32)
+    aE, aM = amax >> 7, amax & 0x7F
+    e = np.clip(aE - 126 - np.where(aM <= 96, 9, 8), -120, 120)
+    e = np.where(aE == 0, -120, e)
+    e = np.where(amax == 0, 0, e).astype(np.int32)
+    E, M = mag >> 7, mag & 0x7F
+    sig = np.where(E > 0, 128 | M, M)
+    t = np.maximum(E, 1) - 134 - e[..., None]                      # x * 2^-e = sig * 2^t
+    k = _TOP_BIT[sig] + t
+    qe = np.maximum(k, -6) - 3                                     # the quantum of the scaled value is 2^qe
+    sh = qe - t
+    up = sig << np.clip(-sh, 0, 8)                                 # sh <= 0: exact
+    dn = np.clip(sh, 1, 10)
+    down = (sig + (1 << (dn - 1)) - 1 + ((sig >> dn) & 1)) >> dn   # sh > 0: round to nearest, ties to even
+    n = np.where(sh <= 0, up, down)
+    code = np.minimum((qe + 10) * 8 + n - 8, 0x7E)
+    code = np.where(sig == 0, 0, code) | ((x >> 8) & 0x80)
+    return code.astype(np.uint8), e.astype(np.int8)
+
+
+def fp8_dequantize_host(q: np.ndarray, e: np.ndarray) -> np.ndarray:
+    """bf16 patterns uint16 [..., D] of payload q uint8 [..., D] and exponents e int8 [...]: a table of the 256 e4m3fn values times
+    2^e in f32 -- exact, so the bf16 pattern is the upper half of the f32 one."""
+    code = np.arange(256)
+    E, M = (code >> 3) & 15, code & 7
+    val = np.where(E > 0, np.ldexp(1.0 + M / 8.0, E - 7), np.ldexp(M.astype(np.float64), -9))
+    val[(code & 0x7F) == 0x7F] = np.nan
+    table = np.where(code & 0x80, -val, val).astype(np.float32)
+    scale = np.ldexp(np.float32(1), np.asarray(e).astype(np.int32)).astype(np.float32)
+    out = table[np.asarray(q)] * scale[..., None]
+    return (out.view(np.uint32) >> 16).astype(np.uint16)
+
+
+def _bf16_view(a: np.ndarray) -> Tensor:
+    """a bf16 tensor over (a copy of, if it is not writable) uint16 patterns"""
+    a = np.ascontiguousarray(a)
+    if not a.flags.writeable:
+        a = a.copy()
+    return torch.from_numpy(a.view(np.int16)).view(torch.bfloat16)
+
+
+def _quantize_tokens(tokens: Tensor, device=None):
+    """(payload uint8, exponents int8) host arrays of bf16 tokens [n, S, D] (a host or device tensor): on `device` through
+    made_fp8_quantize_rows -- the tokens' own device when they are on one -- else by `fp8_quantize_host`.  ValueError for a
+    non-finite token, and for one of the seven bf16 magnitudes past FP8_MAX_TOKEN."""
+    assert tokens.dtype == torch.bfloat16 and tokens.dim() == 3
+    _check_fp8_width(tokens.shape[2])
+    dev = tokens.device if tokens.is_cuda else (None if device is None else torch.device(device))
+    if dev is not None and dev.type != "cuda":
+        dev = None
+    n, S, D = tokens.shape
+    q, e = np.empty((n, S, D), np.uint8), np.empty((n, S), np.int8)
+    step = max(1, _FP8_STEP // (S * D))
+    for a in range(0, n, step):
+        part = tokens[a:a + step]
+        if dev is not None:
+            part = part.to(dev).contiguous()
+        if not bool((part.float().abs() <= FP8_MAX_TOKEN).all()):   # (false for a NaN, too)
+            raise ValueError(f"a non-finite token, or one past {FP8_MAX_TOKEN:.4g} (which would widen to infinity): the FP8 token "
+                             "format has no encoding for it")
+        if dev is not None:
+            from . import ops
+            pq, pe = ops.fp8_quantize_rows(part)
+            q[a:a + step], e[a:a + step] = pq.cpu().numpy(), pe.cpu().numpy()
+        else:
+            q[a:a + step], e[a:a + step] = fp8_quantize_host(_tokens_to_host(part))
+    return q, e
 
 
 def _dtype_name(t: torch.dtype) -> str:
@@ -70,7 +162,7 @@ def _tokens_tensor(a: np.ndarray, dtype: str) -> Tensor:
         a = a.copy()
     if dtype == "bf16":
         return torch.from_numpy(a.view(np.int16)).view(torch.bfloat16)
-    return torch.from_numpy(a)
+    return torch.from_numpy(a)                                     # (f32; an FP8 library's payload stays uint8)
 
 
 def _runs(col_group: np.ndarray) -> np.ndarray:
@@ -91,18 +183,35 @@ def contiguous_order(col_group: np.ndarray) -> np.ndarray:
 
 
 class MusicLibrary:
-    """The music side of `ground()` in library order.  Host libraries hold numpy arrays (possibly memory-mapped, tokens as float32
-    or as uint16 bf16 patterns); `to(device)` gives a library whose tokens / mask / vec / duration are device tensors, which
+    """The music side of `ground()` in library order.  Host libraries hold numpy arrays (possibly memory-mapped, tokens as float32,
+    as uint16 bf16 patterns, or -- dtype "fp8" -- as uint8 e4m3fn bytes with tokens_exp int8 [N, S], widened to `compute` = bf16 on the
+    device); `to(device)` gives a library whose tokens / mask / vec / duration are device tensors, which
     `ground_library` slices in place.  group_id / windows: the arguments that make
     `ground(engine, videos, lib.as_encoded(dev), k, group_id=lib.group_id, windows=lib.windows, ...)` the resident counterpart of
     `ground_library(engine, videos, lib, k, ...)`."""
 
     def __init__(self, tokens, mask, vec, col_group, source, dtype: str, duration=None, windows: Optional[Windows] = None,
-                 ids: Optional[Sequence] = None, group_id=None, tags=None, length=None, tag_names: Optional[Sequence[str]] = None):
-        if dtype not in ("f32", "bf16"):
-            raise ValueError(f"dtype = {dtype!r}: a library holds f32 or bf16 tokens")
+                 ids: Optional[Sequence] = None, group_id=None, tags=None, length=None, tag_names: Optional[Sequence[str]] = None,
+                 tokens_exp=None, compute: Optional[str] = None):
+        if dtype not in ("f32", "bf16", "fp8"):
+            raise ValueError(f"dtype = {dtype!r}: a library holds f32, bf16 or fp8 tokens")
         self.tokens, self.mask, self.vec, self.duration = tokens, mask, vec, duration
         self.dtype = dtype
+        self.tokens_exp = tokens_exp
+        self.compute = dtype if dtype != "fp8" else ("bf16" if compute is None else compute)      # the dtype the kernels read
+        if dtype == "fp8":
+            if self.compute != "bf16":
+                raise ValueError(f"compute = {compute!r}: FP8 tokens are widened to bf16 only")
+            if tokens_exp is None:
+                raise ValueError("an FP8 library needs tokens_exp, the token rows' exponents")
+            u8, i8 = (torch.uint8, torch.int8) if isinstance(tokens, Tensor) else (np.uint8, np.int8)
+            if tokens.dtype != u8 or tokens_exp.dtype != i8 or tuple(tokens_exp.shape) != tuple(tokens.shape[:2]):
+                raise ValueError(f"FP8 tokens are uint8 [N, S, D] with int8 [N, S] exponents, not {tokens.dtype} {tuple(tokens.shape)} "
+                                 f"with {tokens_exp.dtype} {tuple(tokens_exp.shape)}")
+            if len(tokens.shape) == 3:
+                _check_fp8_width(tokens.shape[2])
+        elif tokens_exp is not None or compute not in (None, dtype):
+            raise ValueError(f"tokens_exp / compute belong to an FP8 library, not to a {dtype} one")
         self.col_group = np.ascontiguousarray(col_group, dtype=np.int32).reshape(-1)
         self.source = np.ascontiguousarray(source, dtype=np.int64).reshape(-1)
         self.windows = windows
@@ -257,7 +366,8 @@ class MusicLibrary:
         tok = self.tokens.to(dev) if isinstance(self.tokens, Tensor) else _tokens_tensor(self.tokens, self.dtype).to(dev)
         return MusicLibrary(tok, up(self.mask), up(self.vec), self.col_group, self.source, self.dtype,
                             duration=None if self.duration is None else up(self.duration), windows=self.windows, ids=self.ids,
-                            group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names)
+                            group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
+                            tokens_exp=None if self.tokens_exp is None else up(self.tokens_exp), compute=self._compute_arg)
 
     def pin(self) -> "MusicLibrary":
         """The same library with tokens / mask / vec / duration copied into pinned host tensors: `ground_library` uploads its
@@ -266,22 +376,81 @@ class MusicLibrary:
         tok = self.tokens.cpu() if isinstance(self.tokens, Tensor) else _tokens_tensor(self.tokens, self.dtype)
         return MusicLibrary(tok.pin_memory(), pin(self.mask), pin(self.vec), self.col_group, self.source, self.dtype,
                             duration=None if self.duration is None else pin(self.duration), windows=self.windows, ids=self.ids,
-                            group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names)
+                            group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
+                            tokens_exp=None if self.tokens_exp is None else pin(self.tokens_exp), compute=self._compute_arg)
 
     @property
     def pinned(self) -> bool:
         return isinstance(self.tokens, Tensor) and not self.tokens.is_cuda and self.tokens.is_pinned()
 
+    @property
+    def _compute_arg(self) -> Optional[str]:
+        return self.compute if self.dtype == "fp8" else None
+
     def as_encoded(self, device) -> Encoded:
-        """The whole library as a resident `Encoded`, in library order."""
+        """The whole library as a resident `Encoded`, in library order.  An FP8 library's tokens are dequantised on the device, all
+        of them, into a new bf16 tensor (one made_fp8_dequantize_rows launch): for tests and for libraries that fit --
+        `ground_library` never does this, it widens one chunk at a time."""
         lib = self if self.on_device and self.tokens.device == torch.device(device) else self.to(device)
-        return Encoded(tokens=lib.tokens, mask=lib.mask, vec=lib.vec, duration=lib.duration)
+        tokens = lib.tokens
+        if self.dtype == "fp8":
+            from . import ops
+            tokens = ops.fp8_dequantize_rows(lib.tokens.contiguous(), lib.tokens_exp.contiguous())
+        return Encoded(tokens=tokens, mask=lib.mask, vec=lib.vec, duration=lib.duration)
+
+    # ------------------------------------------------------------------ FP8 token storage
+    def _like(self, tokens, dtype: str, tokens_exp=None) -> "MusicLibrary":
+        """this library with other tokens"""
+        return MusicLibrary(tokens, self.mask, self.vec, self.col_group, self.source, dtype, duration=self.duration, windows=self.windows,
+                            ids=self.ids, group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
+                            tokens_exp=tokens_exp)
+
+    def quantize(self, device=None) -> "MusicLibrary":
+        """The FP8 library of a bf16 library: the same arrays with the tokens as e4m3fn bytes and one power-of-two exponent per
+        token row.  device: where to quantise -- a CUDA device runs made_fp8_quantize_rows there; "cpu", or None without a GPU, the
+        numpy formulation of the same contract, with the same bits (None with a GPU: the library's own device, else the current
+        one).  The result lives where this library does.  ValueError for an f32 library (nothing is cast), for a non-finite
+        token and for a D the format does not take."""
+        if self.dtype != "bf16":
+            raise ValueError(f"quantize() takes a bf16 library, this one holds {self.dtype} tokens (nothing is cast)")
+        _check_fp8_width(self.D)
+        if device is None and not self.on_device and torch.cuda.is_available():
+            device = torch.device("cuda", torch.cuda.current_device())
+        tok = self.tokens if isinstance(self.tokens, Tensor) else None
+        N, step = len(self), max(1, _FP8_STEP // max(1, self.S * self.D))
+        q, e = np.empty((N, self.S, self.D), np.uint8), np.empty((N, self.S), np.int8)
+        for a in range(0, N, step):                                # (a memory-mapped library is read a step at a time)
+            part = tok[a:a + step] if tok is not None else _bf16_view(self.tokens[a:a + step])
+            q[a:a + step], e[a:a + step] = _quantize_tokens(part, device)
+        if tok is not None:
+            put = (lambda a: torch.from_numpy(a).to(tok.device)) if tok.is_cuda else (
+                (lambda a: torch.from_numpy(a).pin_memory()) if tok.is_pinned() else torch.from_numpy)
+            q, e = put(q), put(e)
+        return self._like(q, "fp8", e)
+
+    def dequantized(self) -> "MusicLibrary":
+        """The bf16 host library of an FP8 library (numpy formulation): its tokens are the values every kernel reads after the
+        device widens the FP8 ones, so grounding in it and in the FP8 library is the same computation."""
+        if self.dtype != "fp8":
+            raise ValueError(f"dequantized() takes an FP8 library, this one holds {self.dtype} tokens")
+        host = lambda a: a.cpu().numpy() if isinstance(a, Tensor) else a
+        q, e = host(self.tokens), host(self.tokens_exp)
+        N, step = len(self), max(1, _FP8_STEP // max(1, self.S * self.D))
+        out = np.empty((N, self.S, self.D), np.uint16)
+        for a in range(0, N, step):
+            out[a:a + step] = fp8_dequantize_host(q[a:a + step], e[a:a + step])
+        lib = self._like(out, "bf16")
+        for name in ("mask", "vec", "duration"):
+            a = getattr(lib, name)
+            setattr(lib, name, None if a is None else np.ascontiguousarray(host(a)))
+        return lib
 
     def check_engine(self, engine) -> None:
         """ValueError unless the stored tower outputs are this engine's: compute dtype and width (nothing is cast)."""
         want = _dtype_name(engine.tc)
-        if self.dtype != want:
-            raise ValueError(f"the library holds {self.dtype} tokens, the engine computes in {want}")
+        if self.compute != want:
+            held = self.dtype if self.dtype != "fp8" else f"fp8 (widened to {self.compute} on the device)"
+            raise ValueError(f"the library holds {held} tokens, the engine computes in {want}")
         if self.D != int(engine.cfg.D):
             raise ValueError(f"the library's D = {self.D}, the engine's {int(engine.cfg.D)}")
         if self.S < 1:
@@ -294,6 +463,8 @@ class MusicLibrary:
         os.makedirs(path, exist_ok=True)
         sv = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
         sv("tokens", self.tokens)
+        if self.dtype == "fp8":
+            sv("tokens_exp", self.tokens_exp)
         sv("mask", self.mask)
         sv("vec", self.vec)
         sv("col_group", self.col_group)
@@ -302,7 +473,7 @@ class MusicLibrary:
             sv("duration", self.duration)
         _write_tables(path, self.windows, self.group_id, self.ids)
         _write_manifest(path, self.dtype, len(self), self.S, self.D, self.duration is not None, self.windows, self.ids is not None,
-                        self.group_id is not None, _write_attributes(path, self.tags, self.length, self.tag_names))
+                        self.group_id is not None, _write_attributes(path, self.tags, self.length, self.tag_names), self._compute_arg)
 
     @classmethod
     def load(cls, path: str, mmap: bool = True) -> "MusicLibrary":
@@ -313,10 +484,17 @@ class MusicLibrary:
         ld = lambda name: np.load(os.path.join(path, name + ".npy"), mmap_mode="r" if mmap else None)
         tokens, mask, vec = ld("tokens"), ld("mask"), ld("vec")
         N, S, D = int(man["N"]), int(man["S"]), int(man["D"])
-        want = np.dtype(np.uint16) if man["dtype"] == "bf16" else np.dtype(np.float32)
-        if man["dtype"] not in ("f32", "bf16") or tokens.dtype != want or tuple(tokens.shape) != (N, S, D):
+        want = {"bf16": np.dtype(np.uint16), "fp8": np.dtype(np.uint8)}.get(man["dtype"], np.dtype(np.float32))
+        if man["dtype"] not in ("f32", "bf16", "fp8") or tokens.dtype != want or tuple(tokens.shape) != (N, S, D):
             raise ValueError(f"{path}: the manifest says {man['dtype']} tokens [{N}, {S}, {D}], tokens.npy holds {tokens.dtype} "
                              f"{tuple(tokens.shape)}")
+        tokens_exp = None
+        if man["dtype"] == "fp8":
+            if not os.path.isfile(os.path.join(path, "tokens_exp.npy")):
+                raise ValueError(f"{path}: the manifest says fp8 tokens, but there is no tokens_exp.npy")
+            tokens_exp = ld("tokens_exp")
+            if tokens_exp.dtype != np.int8 or tuple(tokens_exp.shape) != (N, S):
+                raise ValueError(f"{path}: tokens_exp.npy must hold int8 [{N}, {S}], not {tokens_exp.dtype} {tuple(tokens_exp.shape)}")
         windows = None
         if man["windows"]:
             windows = Windows(track=np.load(os.path.join(path, "win_track.npy")), offset=np.load(os.path.join(path, "win_offset.npy")),
@@ -333,7 +511,8 @@ class MusicLibrary:
         return cls(tokens, mask, vec, col_group, np.load(os.path.join(path, "source.npy")), man["dtype"],
                    duration=ld("duration") if man["duration"] else None, windows=windows, ids=ids, group_id=group_id,
                    tags=np.load(os.path.join(path, "tags.npy")) if attr.get("tags") else None,
-                   length=np.load(os.path.join(path, "length.npy")) if attr.get("length") else None, tag_names=attr.get("tag_names"))
+                   length=np.load(os.path.join(path, "length.npy")) if attr.get("length") else None, tag_names=attr.get("tag_names"),
+                   tokens_exp=tokens_exp, compute=man.get("compute") if man["dtype"] == "fp8" else None)
 
     # ------------------------------------------------------------------ the chunk plan
     def chunk_plan(self, chunk_cols: int) -> List[Tuple[int, int]]:
@@ -442,12 +621,14 @@ def _write_attributes(path: str, tags, length, tag_names) -> Optional[dict]:
 
 
 def _write_manifest(path: str, dtype: str, N: int, S: int, D: int, duration: bool, windows: Optional[Windows], ids: bool,
-                    grouped: bool, attributes: Optional[dict] = None) -> None:
+                    grouped: bool, attributes: Optional[dict] = None, compute: Optional[str] = None) -> None:
     man = dict(format=FORMAT, version=VERSION, dtype=dtype, N=int(N), S=int(S), D=int(D), duration=bool(duration),
                windows=windows is not None, ids=bool(ids), grouped=bool(grouped),
                n_tracks=int(windows.n_tracks) if windows is not None else None)
     if attributes is not None:
         man["attributes"] = attributes
+    if compute is not None:                                        # an FP8 library: the dtype its tokens are widened to
+        man["compute"] = compute
     with open(os.path.join(path, "manifest.json"), "w") as f:
         json.dump(man, f, indent=1)
         f.write("\n")
@@ -468,16 +649,24 @@ class MusicLibraryWriter:
     col_group [n]: the group of every added column, contiguous inside the batch, none seen in an earlier add.  windows_rows: a
     `Windows` (or a (track, offset, duration) triple) for the added columns with the LIBRARY's track numbers -- then ids holds one
     entry per new track, else one per column; tags (int64) / length (f32 seconds) go like ids, one entry per new track, and every
-    add carries them or none does.  duration defaults to music.duration.  tag_names: the library's names of the tag bits."""
+    add carries them or none does.  duration defaults to music.duration.  tag_names: the library's names of the tag bits.
+    dtype "fp8": `add` takes bf16 tokens as a bf16 writer does and appends their FP8 payload and exponents -- quantised on the device
+    when the tokens are there, so only the bytes cross to the host -- and `close()` returns what `build(...).quantize()` of the
+    concatenation gives, byte for byte."""
 
     def __init__(self, path: str, S: int, D: int, dtype: str, tag_names: Optional[Sequence[str]] = None):
-        if dtype not in ("f32", "bf16"):
-            raise ValueError(f"dtype = {dtype!r}: a library holds f32 or bf16 tokens")
+        if dtype not in ("f32", "bf16", "fp8"):
+            raise ValueError(f"dtype = {dtype!r}: a library holds f32, bf16 or fp8 tokens")
+        if dtype == "fp8":
+            _check_fp8_width(D)
         self.path, self.S, self.D, self.dtype = path, int(S), int(D), dtype
         os.makedirs(path, exist_ok=True)
-        self._tok_dtype = np.dtype(np.uint16) if dtype == "bf16" else np.dtype(np.float32)
+        self._tok_dtype = {"bf16": np.dtype(np.uint16), "fp8": np.dtype(np.uint8)}.get(dtype, np.dtype(np.float32))
         self._files = {}
-        for name, dt, tail in (("tokens", self._tok_dtype, (self.S, self.D)), ("mask", np.float32, (self.S,)), ("vec", np.float32, (self.D,))):
+        arrays = [("tokens", self._tok_dtype, (self.S, self.D)), ("mask", np.float32, (self.S,)), ("vec", np.float32, (self.D,))]
+        if dtype == "fp8":
+            arrays.append(("tokens_exp", np.int8, (self.S,)))
+        for name, dt, tail in arrays:
             f = open(os.path.join(path, name + ".npy"), "wb")
             f.write(_npy_header(dt, (0,) + tail))
             self._files[name] = (f, np.dtype(dt), tail)
@@ -500,8 +689,9 @@ class MusicLibraryWriter:
             raise ValueError("the writer is closed")
         n = len(music)
         g = _host(col_group, np.int32).reshape(-1)
-        if _dtype_name(music.tokens.dtype) != self.dtype or tuple(music.tokens.shape[1:]) != (self.S, self.D):
-            raise ValueError(f"the writer takes {self.dtype} tokens [n, {self.S}, {self.D}], not {music.tokens.dtype} {tuple(music.tokens.shape)}")
+        takes = "bf16" if self.dtype == "fp8" else self.dtype
+        if _dtype_name(music.tokens.dtype) != takes or tuple(music.tokens.shape[1:]) != (self.S, self.D):
+            raise ValueError(f"the writer takes {takes} tokens [n, {self.S}, {self.D}], not {music.tokens.dtype} {tuple(music.tokens.shape)}")
         if g.size != n:
             raise ValueError("col_group needs one entry per added column")
         if n == 0:
@@ -541,7 +731,12 @@ class MusicLibraryWriter:
             self._win.append((tr, off, dur))
         elif ids is not None and len(ids) != n:
             raise ValueError("ids needs one entry per added column")
-        for name, a in (("tokens", _tokens_to_host(music.tokens)), ("mask", _host(music.mask, np.float32)), ("vec", _host(music.vec, np.float32))):
+        if self.dtype == "fp8":                                    # (refuses a non-finite token before anything is written)
+            payload, exps = _quantize_tokens(music.tokens.detach())
+            arrays = [("tokens", payload), ("tokens_exp", exps)]
+        else:
+            arrays = [("tokens", _tokens_to_host(music.tokens))]
+        for name, a in arrays + [("mask", _host(music.mask, np.float32)), ("vec", _host(music.vec, np.float32))]:
             f, dt, tail = self._files[name]
             assert a.dtype == dt and tuple(a.shape) == (n,) + tail, (name, a.dtype, a.shape)
             f.write(a.tobytes())
@@ -590,5 +785,5 @@ class MusicLibraryWriter:
                 raise ValueError(f"{name} needs one entry per track ({n_tracks}), got {len(a)}")
         _write_tables(self.path, windows, track_group, self._ids)
         _write_manifest(self.path, self.dtype, self.N, self.S, self.D, bool(self._duration), windows, self._ids is not None, True,
-                        _write_attributes(self.path, tags, length, self._tag_names))
+                        _write_attributes(self.path, tags, length, self._tag_names), "bf16" if self.dtype == "fp8" else None)
         return MusicLibrary.load(self.path, mmap=True)

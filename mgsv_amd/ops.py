@@ -1057,6 +1057,43 @@ def gather_rows(src: Tensor, index: Tensor, dst: Tensor) -> Tensor:
     return dst
 
 
+def fp8_quantize_rows(src: Tensor, q: Optional[Tensor] = None, exp: Optional[Tensor] = None):
+    """made_fp8_quantize_rows: (q uint8 of src's shape, exp int8 of src's shape without the last dimension) of the bf16 rows
+    src [..., D] (contiguous), the FP8 token format of include/made_hip.h.  D in {128, 256, 512}.  Non-finite values are the
+    caller's to refuse."""
+    assert src.dtype == torch.bfloat16 and src.is_contiguous() and src.dim() >= 1
+    D = src.shape[-1]
+    R = src.numel() // max(D, 1)
+    q = torch.empty(src.shape, device=src.device, dtype=torch.uint8) if q is None else q
+    exp = torch.empty(src.shape[:-1], device=src.device, dtype=torch.int8) if exp is None else exp
+    assert q.dtype == torch.uint8 and q.is_contiguous() and q.numel() == src.numel()
+    assert exp.dtype == torch.int8 and exp.is_contiguous() and exp.numel() == R
+    check(lib().made_fp8_quantize_rows(_p(src), R, D, _p(q), _p(exp), _stream()), "made_fp8_quantize_rows")
+    return q, exp
+
+
+def fp8_dequantize_rows(q: Tensor, exp: Tensor, index: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """made_fp8_dequantize_rows: the bf16 rows of q [U, ..., D] uint8 with exponents exp [U, ...] int8 (both contiguous).  index
+    [R] int32: out [R, ..., D] holds the blocks q[index[r]] (zeros where the index is < 0 or >= U); None: all U blocks.  out: a
+    contiguous bf16 tensor of that shape to write into."""
+    assert q.dtype == torch.uint8 and exp.dtype == torch.int8 and q.is_contiguous() and exp.is_contiguous() and q.dim() >= 2
+    assert tuple(exp.shape) == tuple(q.shape[:-1])
+    U, D = q.shape[0], q.shape[-1]
+    rpi = 1
+    for s in q.shape[1:-1]:
+        rpi *= int(s)
+    R = U if index is None else index.numel()
+    if index is not None:
+        assert index.dtype == torch.int32 and index.is_contiguous() and index.dim() == 1
+    shape = (R,) + tuple(q.shape[1:])
+    if out is None:
+        out = torch.empty(shape, device=q.device, dtype=torch.bfloat16)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == shape
+    check(lib().made_fp8_dequantize_rows(_p(q) if U else None, _p(exp) if U else None, U, None if index is None else _p(index), R, rpi, D,
+                                         _p(out), _stream()), "made_fp8_dequantize_rows")
+    return out
+
+
 def group_topw(sims: Tensor, sel: Tensor, col_group: Tensor, start: Tensor, cols: Tensor, w: int):
     """made_group_topw: the best w columns of the group of every selected column sel [Nv, K] (topk_groups' idx) in its row of sims
     [Nv, Nm] f32 -> (idx [Nv, K, w] int32, score [Nv, K, w] f32), score descending then column ascending, -1 / -inf past the group's
