@@ -1176,6 +1176,31 @@ int made_mmr_select(const int32_t* row, const float* score, const float* vec, in
 int made_cosine_join(const float* vec, int64_t N, int64_t D, const int32_t* node, int64_t r0, int64_t r1, int64_t c0, int64_t c1, float tau,
                      int32_t* pair_i, int32_t* pair_j, float* pair_cos, int64_t capacity, int64_t* count, void* stream);
 
+/* made_cosine_topk: the k nearest nodes by cosine of every query row over a vector table ("which tracks are like this track":
+ * mgsv_amd/similar.py nearest_columns).  query [Q, D] and vec [N, D] f32 with contiguous rows, 16-byte aligned, read only, NOT
+ * normalised beforehand; query may point into vec.  The node of column j is node[j] (int32 [N]), or j itself when node is NULL; a
+ * column with node[j] < 0 is ignored (made_topk_groups' convention).  Query i excludes the node query_node[i] (int32 [Q]); a
+ * negative value, or a NULL array, excludes nothing -- a row of the table looks itself up with query_node[i] = its own node.  Column
+ * j is admissible for query i iff its node is >= 0 and differs from query_node[i], both norms are finite and > 0, the f32 product of
+ * the two norms is finite and > 0, and the cosine is not NaN; a query whose norm is zero or not finite has no neighbours.  A node's
+ * score is the largest cosine over its admissible columns, its representative the lowest column that attains it.  out_col int32 /
+ * out_cos f32 [Q, k]: the best k nodes' representatives and scores in the selection's total order -- score descending through the
+ * order-preserving key (so -0 equals +0), then representative column ascending; slots past the nodes present hold -1 / -inf.
+ * The cosine is a.b / (|a| |b|) exactly as made_cosine_join forms it (the same fmaf chain over D on v_mfma_f32_32x32x2_f32, the
+ * same four-chain sum of squares per row, one f32 product of the norms, one f32 division): a (query row, table row) pair has the
+ * bits made_cosine_join gives the same two rows, and they do not depend on Q, N, n_splits, the pair's position in a tile or any
+ * other row.  A workgroup takes 128 query rows and walks the 128-column tiles of its column split, keeping every row's sorted list
+ * of k entries in LDS; each split writes its lists to ws ([splits, Q, k] of (f32 cos, int32 col)), and a second launch on the same
+ * stream merges them by the same order and node rule, so the result is bit-identical for every n_splits.  n_splits = 0: the
+ * launcher chooses (enough splits to fill the chip when Q is small); n_splits >= 1 is honoured, clamped to the number of column
+ * tiles.  No atomics.  made_cosine_topk_ws_bytes: the bytes ws must hold for a call with these arguments (-1 for arguments the
+ * call refuses).  D in {128, 256, 512}, 1 <= k <= 64, N < 2^31, Q < 2^31, ws_bytes >= made_cosine_topk_ws_bytes(...):
+ * MADE_ERR_UNSUPPORTED otherwise.  Q = 0 returns MADE_OK and writes nothing; N = 0 fills -1 / -inf.  ws 8-byte aligned; the outputs
+ * must not overlap the inputs, the workspace or each other. */
+int64_t made_cosine_topk_ws_bytes(int64_t Q, int64_t N, int64_t k, int32_t n_splits);
+int made_cosine_topk(const float* query, int64_t Q, const int32_t* query_node, const float* vec, int64_t N, int64_t D, const int32_t* node,
+                     int64_t k, int32_t n_splits, int32_t* out_col, float* out_cos, void* ws, int64_t ws_bytes, void* stream);
+
 /* made_merge_moments: the moments of P (video, track) entries on the track's own time axis from the moments of the track's w
  * windows, one wave per entry, no atomics.  win_col / win_score [P, w] = made_group_topw's columns (-1: no window) and
  * similarities; cand [P, w, Q, 3] f32 = every query's (start, end, foreground probability) in seconds on its window's axis,

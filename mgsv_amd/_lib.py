@@ -321,6 +321,8 @@ SIGNATURES = {
     "made_topk_candidates": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i64, i64, vp, vp, vp]),
     "made_mmr_select": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, i64, f32, f32, vp, vp, vp]),
     "made_cosine_join": (C.c_int, [vp, i64, i64, vp, i64, i64, i64, i64, f32, vp, vp, vp, i64, vp, vp]),
+    "made_cosine_topk_ws_bytes": (C.c_int64, [i64, i64, i64, i32]),
+    "made_cosine_topk": (C.c_int, [vp, i64, vp, vp, i64, i64, vp, i64, i32, vp, vp, vp, i64, vp]),
     "made_merge_moments": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, f32, f32, i64, vp, vp, vp, vp, vp]),
     "made_fp8_quantize_rows": (C.c_int, [vp, i64, i64, vp, vp, vp]),
     "made_fp8_dequantize_rows": (C.c_int, [vp, vp, i64, vp, i64, i64, i64, vp, vp]),

@@ -217,6 +217,40 @@ def link_groups(pairs, node, node_cols=None, max_group_cols: int = 64) -> Links:
     return Links(node_group=dense.astype(np.int32).reshape(-1), n_links=n_links, n_refused=n_refused, largest=largest)
 
 
+def column_nodes(music_or_library, group_id=None, windows=None):
+    """(node [N] int64 per column, n_nodes, unit_node [n_units] int64, track [N] int64, trivial) of an `Encoded` or a `MusicLibrary`
+    (its own group_id / windows unless given).  The node of a column is its labelled group (group_id: per column, or per TRACK with
+    windows), numbered densely in label order; with windows and no labels its track; otherwise the column itself.  A unit is what
+    group_id has one entry for: the track with windows, the column without; track is every column's unit.  trivial: every column is
+    its own node."""
+    vec = music_or_library.vec
+    if windows is None:
+        windows = getattr(music_or_library, "windows", None)
+    if group_id is None:
+        group_id = getattr(music_or_library, "group_id", None)
+    N = int(vec.shape[0])
+    if group_id is not None:
+        group_id = np.ascontiguousarray(group_id.cpu().numpy() if hasattr(group_id, "cpu") else group_id).astype(np.int64).reshape(-1)
+    if windows is not None:
+        track = np.asarray(windows.track).astype(np.int64).reshape(-1)
+        n_units = int(windows.n_tracks)
+        if track.size != N:
+            raise ValueError(f"windows describes {track.size} columns, the table has {N}")
+    else:
+        track = np.arange(N, dtype=np.int64)
+        n_units = N
+    if group_id is not None and group_id.size != n_units:
+        raise ValueError("group_id needs one entry per track")
+    if group_id is None:
+        unit_node, n_nodes = np.arange(n_units, dtype=np.int64), n_units
+    else:
+        labels, unit_node = np.unique(group_id, return_inverse=True)
+        unit_node, n_nodes = unit_node.reshape(-1).astype(np.int64), labels.size
+    node = unit_node[track]                                      # per column
+    trivial = windows is None and group_id is None
+    return node, n_nodes, unit_node, track, trivial
+
+
 @dataclass
 class NearDuplicates:
     """near_duplicate_groups' result.  group_id: one entry per track (per column without windows), for `MusicLibrary.build(group_id=)` /
@@ -246,30 +280,7 @@ def near_duplicate_groups(music_or_library, threshold: float, group_id=None, win
         raise ValueError(f"max_group_cols must be in [1, {MAX_GROUP_COLS}] (a group must fit in a chunk), got {max_group_cols}")
     _check_threshold(threshold)
     vec = music_or_library.vec
-    if windows is None:
-        windows = getattr(music_or_library, "windows", None)
-    if group_id is None:
-        group_id = getattr(music_or_library, "group_id", None)
-    N = int(vec.shape[0])
-    if group_id is not None:
-        group_id = np.ascontiguousarray(group_id.cpu().numpy() if hasattr(group_id, "cpu") else group_id).astype(np.int64).reshape(-1)
-    if windows is not None:
-        track = np.asarray(windows.track).astype(np.int64).reshape(-1)
-        n_units = int(windows.n_tracks)
-        if track.size != N:
-            raise ValueError(f"windows describes {track.size} columns, the table has {N}")
-    else:
-        track = np.arange(N, dtype=np.int64)
-        n_units = N
-    if group_id is not None and group_id.size != n_units:
-        raise ValueError("group_id needs one entry per track")
-    if group_id is None:
-        unit_node, n_nodes = np.arange(n_units, dtype=np.int64), n_units
-    else:
-        labels, unit_node = np.unique(group_id, return_inverse=True)
-        unit_node, n_nodes = unit_node.reshape(-1).astype(np.int64), labels.size
-    node = unit_node[track]                                      # per column
-    trivial = windows is None and group_id is None
+    node, n_nodes, unit_node, _, trivial = column_nodes(music_or_library, group_id, windows)
     pairs = near_duplicate_pairs(vec, threshold, node=None if trivial else node, **pairs_kw)
     links = link_groups(pairs, node, np.bincount(node, minlength=n_nodes), int(max_group_cols))
     # group ids per unit, renumbered by first appearance over the units (nodes without columns included)

@@ -1231,3 +1231,27 @@ def cosine_join(vec: Tensor, tau: float, pair_i: Tensor, pair_j: Tensor, pair_co
     c0, c1 = (0, N) if cols is None else (int(cols[0]), int(cols[1]))
     check(lib().made_cosine_join(_p(vec) if N else None, N, D, _p(node), r0, r1, c0, c1, float(tau), _p(pair_i) if cap else None,
                                  _p(pair_j) if cap else None, _p(pair_cos) if cap else None, cap, _p(count), _stream()), "made_cosine_join")
+
+
+def cosine_topk(query: Tensor, vec: Tensor, k: int, node: Optional[Tensor] = None, query_node: Optional[Tensor] = None, n_splits: int = 0):
+    """made_cosine_topk: the k nearest nodes by cosine of every row of query [Q, D] over vec [N, D] (both f32 contiguous, D 128 / 256 /
+    512; query may be a slice of vec) -> (col [Q, k] int32, cos [Q, k] f32): every node's best column, score descending then column
+    ascending, -1 / -inf past the nodes present.  node [N] int32: every column's node (None: the column itself; < 0: ignored);
+    query_node [Q] int32: the node a query excludes (None or < 0: nothing).  n_splits = 0 lets the launcher choose the column splits;
+    the result does not depend on them."""
+    assert query.dim() == 2 and vec.dim() == 2 and query.dtype == torch.float32 and vec.dtype == torch.float32
+    assert query.is_contiguous() and vec.is_contiguous() and query.device == vec.device and query.shape[1] == vec.shape[1]
+    Q, D = query.shape
+    N = vec.shape[0]
+    if node is not None:
+        assert node.dtype == torch.int32 and node.is_contiguous() and node.numel() == N and node.device == vec.device
+    if query_node is not None:
+        assert query_node.dtype == torch.int32 and query_node.is_contiguous() and query_node.numel() == Q and query_node.device == vec.device
+    k, n_splits = int(k), int(n_splits)
+    col = torch.empty(Q, max(k, 0), device=vec.device, dtype=torch.int32)
+    cos = torch.empty(Q, max(k, 0), device=vec.device, dtype=torch.float32)
+    need = max(0, int(lib().made_cosine_topk_ws_bytes(Q, N, k, n_splits)))
+    ws = torch.empty(max(need, 8) // 8, device=vec.device, dtype=torch.int64)
+    check(lib().made_cosine_topk(_p(query), Q, _p(query_node), _p(vec) if N else None, N, D, _p(node), k, n_splits, _p(col), _p(cos), _p(ws),
+                                 need, _stream()), "made_cosine_topk")
+    return col, cos
