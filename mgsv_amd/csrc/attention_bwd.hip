@@ -1,7 +1,6 @@
 // made_attention_bwd: flash-style backward of made_attention on MFMA, gfx950.
 //
-// Three kernels, none of which writes anything of size Lq x Lk:
-//   delta   : delta[b,h,i] = dO_i . O_i                                  (one wave per query row)
+// Two kernels, neither of which writes anything of size Lq x Lk:
 //   dq      : one workgroup = 128 queries of one (batch, head), loop over key tiles of 64.  Same SWAPPED layout as the
 //             forward (S^T = K Q^T: the query sits on the lane), so lse / delta are per-lane scalars and dS^T is directly
 //             the B operand of dQ^T += K^T dS^T (K^T fragments through the transposing LDS read).
@@ -26,39 +25,6 @@ template <> struct Frag<bf16_t> { typedef bf16x8 type; };
 
 __device__ __forceinline__ bool drop_keep(uint64_t seed, uint32_t site, uint32_t thr, uint64_t idx) {
     return (made_rng_mix(seed, site, idx) >> 8) >= thr;
-}
-
-// ---------------------------------------------------------------------------------------------- delta
-// delta[b,h,i] = dO_i,h . O_i,h : one wave per token row (all heads at once, 16-byte loads), head sums by lane-group shuffles;
-// rows whose q_skip_mask is 0 are skipped (their delta is never read)
-__global__ __launch_bounds__(NTH) void attn_delta_kernel(const MadeAttnBwdArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);      // (b, i)
-    if (row >= a.B * a.Lq) return;
-    const int64_t i = row % a.Lq, b = row / a.Lq;
-    if (a.q_skip_mask && a.q_skip_mask[row] == 0.f) return;
-    const int D = (int)(a.H * a.hd);
-    const int per = a.dtype == MADE_F32 ? 4 : 8;                           // elements per 16-byte chunk
-    const int lanes_per_head = a.hd / per;                                 // 4, 8, 16 (bf16) / 8, 16, 32 (f32): powers of two
-    for (int c0 = 0; c0 < D; c0 += 64 * per) {
-        const int c = c0 + lane * per;
-        float acc = 0.f;
-        if (c < D) {
-            if (a.dtype == MADE_F32) {
-                const f32x4 o = *(const f32x4*)((const float*)a.O + b * a.o_bs + i * a.ldo + c);
-                const f32x4 g = *(const f32x4*)((const float*)a.dO + b * a.do_bs + i * a.lddo + c);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc += o[j] * g[j];
-            } else {
-                const bf16x8 o = *(const bf16x8*)((const bf16_t*)a.O + b * a.o_bs + i * a.ldo + c);
-                const bf16x8 g = *(const bf16x8*)((const bf16_t*)a.dO + b * a.do_bs + i * a.lddo + c);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc += (float)o[j] * (float)g[j];
-            }
-        }
-        for (int o2 = lanes_per_head >> 1; o2 > 0; o2 >>= 1) acc += __shfl_xor(acc, o2);
-        if (c < D && (lane % lanes_per_head) == 0) a.delta[(b * a.H + c / a.hd) * a.Lq + i] = acc;
-    }
 }
 
 // transposing fragment: A operand X^T (row index on the lane, reduction rows kb.. of an LDS tile stored [row][col], pitch P)
@@ -133,7 +99,7 @@ __global__ __launch_bounds__(NTH, (sizeof(TC) == 2 && HD <= 64) ? 2 : 1) void at
     const float lse_q = my_valid ? a.lse[(b * a.H + h) * a.Lq + qc] : INFINITY;     // +inf: every probability is 0
     // delta_q = dO_q . O_q: the bf16 path makes it here, from the dO fragments this lane holds anyway (its partner lane has the other
     // half of the head's columns), and writes it for the dK / dV kernel behind it -- the separate delta launch (13 us per attention
-    // layer on the step's main stream) is gone.  The f32 parity path keeps that launch and its summation order.
+    // layer on the step's main stream) is gone.
     float delta_q;
     if constexpr (IS_BF16) {
         const TC* op_ = (const TC*)a.O + b * a.o_bs + qc * a.ldo + h * HD;
@@ -148,7 +114,30 @@ __global__ __launch_bounds__(NTH, (sizeof(TC) == 2 && HD <= 64) ? 2 : 1) void at
         delta_q = my_valid ? dacc : 0.f;
         if (my_valid && hh == 0) a.delta[(b * a.H + h) * a.Lq + qc] = dacc;
     } else {
-        delta_q = my_valid ? a.delta[(b * a.H + h) * a.Lq + qc] : 0.f;
+        // f32: delta through the SAME product chain as dP below (O in the place of V: the diagonal of O dO^T), so that the rounding of
+        // dP - delta cancels where O is a row of V -- a query with one valid key has P = 1, dS = 0 exactly, and with delta summed in
+        // another order (the separate launch this replaces) dQ / dK there were six ulps of |dO . V| instead (docs/EXPERIMENTS.md 3k).
+        // Under dropout O carries the factor c = 1 / (1 - p) that dP gets only after its sum: the chain runs on O (1 - p) and the sum is
+        // scaled by c, as dP is below (there O (1 - p) is the row of V again, up to an ulp on some elements).
+        const TC* op_ = (const TC*)a.O + b * a.o_bs + qc * a.ldo + h * HD;
+        const float keep_p = a.drop.p > 0.f ? 1.f - a.drop.p : 1.f, dsc_o = a.drop.p > 0.f ? 1.f / (1.f - a.drop.p) : 1.f;
+        f32x16 dd;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) dd[e] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < NQF; ++ks) {
+            const frag_t of = *(const frag_t*)(op_ + ks * 2 * PER16 + hh * PER16);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dd = __builtin_amdgcn_mfma_f32_32x32x2f32(of[e] * keep_p, dof[ks][e], dd, 0, 0, 0);
+        }
+        // column r of the product sits on lanes (r, 0) and (r, 1); row r of it in the half hh = (r >> 2) & 1, register (r & 3) + 4 (r >> 3)
+        float mine = 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) mine = acc_row(e, hh) == r ? dd[e] : mine;
+        const float other = __shfl_xor(mine, 32);
+        const float dacc = (hh == ((r >> 2) & 1) ? mine : other) * dsc_o;
+        delta_q = my_valid ? dacc : 0.f;
+        if (my_valid && hh == 0) a.delta[(b * a.H + h) * a.Lq + qc] = dacc;
     }
 
     // load_tile only ISSUES the next tile's loads (a use right behind them would make the wave wait before multiplying the current
@@ -738,9 +727,7 @@ int launch_bwd_hd(const MadeAttnBwdArgs& a, dim3 gq, dim3 gk, size_t lds_q, size
 
 template <typename TC>
 int launch_bwd(const MadeAttnBwdArgs& a, hipStream_t st) {
-    const int64_t rows = a.B * a.Lq;
-    if (a.dtype != MADE_BF16)                               // (bf16: the dQ kernel makes delta itself and hands it to the dK / dV kernel)
-        hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(NTH), 0, st, a);
+    // (delta = dO . O per query and head: the dQ kernel makes it and hands it to the dK / dV kernel behind it)
     const int64_t pairs8 = 8 * ((a.H * a.B + 7) / 8);
     dim3 gq((unsigned)(((a.Lq + 127) / 128) * pairs8)), gk((unsigned)(((a.Lk + 127) / 128) * pairs8));
     const size_t lds_q = (size_t)((a.Lk + BKEY - 1) / BKEY) * BKEY * 4, lds_k = (size_t)((a.Lq + BQT - 1) / BQT) * BQT * 12;
