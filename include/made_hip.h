@@ -1335,6 +1335,48 @@ int made_audio_fbank(const float* pcm, int64_t pcm_len, const MadeAudioSegDesc* 
  * for fi < 12, ti < 101, k, l < 16.  spec [n_segs, 1024, 128] f32; patch_dtype MADE_F32 or MADE_BF16 (rounded). */
 int made_ast_patches(const float* spec, int64_t n_segs, void* patches, int32_t patch_dtype, int64_t ld_patch, void* stream);
 
+/* ==========================================================================================
+ * Batches from a device-resident feature store (mgsv_amd/feature_store.py DeviceFeatureStore): a split's features stay on the
+ * device in their storage format and every batch of the training / evaluation loop is assembled by one launch.  The reference
+ * loads four files per sample in worker processes (dataloaders/dataloader_MGSV_EC_feature.py:57-67).
+ * ========================================================================================== */
+
+#define MADE_GATHER_MAX_ARRAYS 8
+enum MadeGatherKind { MADE_GATHER_F32 = 0, MADE_GATHER_BF16 = 1, MADE_GATHER_U8 = 2 };
+
+/* One array of made_gather_batch.  src [rows, row_elems] contiguous rows of `kind`; row [n_samples] device int32 (sample s reads
+ * row row[s]) or NULL (sample s reads row s); dst [B, row_elems] contiguous f32. */
+typedef struct MadeGatherArray {
+    const void*    src;
+    const int32_t* row;
+    float*         dst;
+    int64_t        rows;
+    int64_t        row_elems;
+    int32_t        kind;       /* MadeGatherKind */
+    int32_t        _pad;
+} MadeGatherArray;
+
+typedef struct MadeGatherBatchArgs {
+    MadeGatherArray a[MADE_GATHER_MAX_ARRAYS];
+    const int32_t*  index;     /* [B] device int32: the batch's sample numbers */
+    int64_t         n_samples;
+    int64_t         B;
+    int32_t         n_arrays;  /* 1 .. MADE_GATHER_MAX_ARRAYS */
+    int32_t         _pad;
+} MadeGatherBatchArgs;
+
+/* made_gather_batch: for every b < B and array a, with s = index[b] and r = row_a ? row_a[s] : s:
+ *     dst_a[b, :] = widen(src_a[r, :])   if 0 <= s < n_samples and 0 <= r < rows_a,   a zero row (nothing is read) otherwise
+ * -- made_gather_rows' rule.  widen is exact: f32 the same 32 bits (copied as integers: NaN payloads and -0 survive), bf16 the
+ * pattern << 16, u8 (float)v.  One launch; the descriptors travel in the kernel's arguments (no upload, no host sync).  Grid:
+ * y = the array, x = (sample, piece of the row), so one long row is spread over the chip.  Per array the launcher takes the
+ * 16-byte path (one 16-byte load per lane; one, two or four 16-byte stores for f32, bf16, u8) when the row's source bytes are a
+ * multiple of 16 and src and dst are 16-byte aligned, and the element path (one element per lane) otherwise; both give the same
+ * bits.  No LDS, no atomics, no workspace.  B == 0 is a no-op; an array with row_elems == 0 is skipped.  Refused: null args /
+ * index / src (with rows > 0) / dst, n_arrays outside [1, 8], negative sizes, rows, n_samples or B past 2^31, B * row_elems of
+ * one array past 2^31, pointers not aligned to their element, a dst that overlaps its src. */
+int made_gather_batch(const MadeGatherBatchArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,6 +218,18 @@ class MadeAudioSegDesc(C.Structure):
     _fields_ = [("first", i64), ("count", i64)]
 
 
+GATHER_MAX_ARRAYS = 8
+GATHER_F32, GATHER_BF16, GATHER_U8 = 0, 1, 2
+
+
+class MadeGatherArray(C.Structure):
+    _fields_ = [("src", vp), ("row", vp), ("dst", vp), ("rows", i64), ("row_elems", i64), ("kind", i32), ("_pad", i32)]
+
+
+class MadeGatherBatchArgs(C.Structure):
+    _fields_ = [("a", MadeGatherArray * GATHER_MAX_ARRAYS), ("index", vp), ("n_samples", i64), ("B", i64), ("n_arrays", i32), ("_pad", i32)]
+
+
 # name -> (restype, argtypes); every symbol include/made_hip.h declares
 SIGNATURES = {
     "made_abi_version": (C.c_int, []),
@@ -330,6 +342,7 @@ SIGNATURES = {
     "made_audio_resample": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp]),
     "made_audio_fbank": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, i32, vp, vp]),
     "made_ast_patches": (C.c_int, [vp, i64, vp, i32, i64, vp]),
+    "made_gather_batch": (C.c_int, [C.POINTER(MadeGatherBatchArgs), vp]),
 }
 
 _lib = None

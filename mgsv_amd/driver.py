@@ -9,7 +9,9 @@ What is different on purpose:
   * launched with `python -m torch.distributed.run` (or plain `python` for one GPU): one process per GPU, RCCL;
   * `--synthetic_features 1` replaces the `.pt` feature files (absent from this repository) by seeded random features of the
     same shapes, so the drivers run end to end from the CSV metadata alone; `--max_samples N` truncates a split;
-  * `--fused_step 1` (default) uses MadeTrainer.train_step (fused clip + Adam); `0` runs the reference's torch optimizer path.
+  * `--fused_step 1` (default) uses MadeTrainer.train_step (fused clip + Adam); `0` runs the reference's torch optimizer path;
+  * `--device_features 1` replaces the DataLoaders by a DeviceLoader over a device-resident DeviceFeatureStore (mgsv_amd/feature_store.py):
+    the same batches in the same order, gathered on the GPU by one launch each.
 """
 from __future__ import annotations
 
@@ -69,7 +71,8 @@ TEST_DROPS = {"matching_lr", "detection_lr"}                  # the test parser 
 EXTRA = [("synthetic_features", int, 0, None), ("max_samples", int, 0, None), ("compute_dtype", str, "bf16", ["bf16", "f32"]),
          ("fused_step", int, 1, None),
          ("eval_in_flight", int, 2, None),                    # evaluation: independent batches in flight (engine workspace + stream each)
-         ("ground_topk", int, 0, None)]                       # evaluation: > 0 also grounds every video in the split's tracks (top k + moment)
+         ("ground_topk", int, 0, None),                       # evaluation: > 0 also grounds every video in the split's tracks (top k + moment)
+         ("device_features", int, 0, None)]                   # 1: the splits' features stay on the GPU, batches are gathered there (feature_store.py)
 
 
 def build_parser(for_test: bool = False) -> argparse.ArgumentParser:
@@ -147,7 +150,8 @@ class MGSV_EC_Dataset(torch.utils.data.Dataset):
             raise FileNotFoundError(f"{fp} (pass --synthetic_features 1 to run without extracted features)")
         return feats.masked_fill(mask.unsqueeze(-1) == 0, 0).float(), mask.float()
 
-    def __getitem__(self, idx):
+    def sample_meta(self, idx):
+        """The part of an item that needs no feature: (meta_map, spans_target, v_duration, m_duration as Python floats) of row `idx`."""
         a, r = self.args, self.csv.iloc[idx]
         video_id, music_id = str(r["video_id"]), str(r["music_id"])
         m_duration = float(r["music_total_duration"])
@@ -160,13 +164,32 @@ class MGSV_EC_Dataset(torch.utils.data.Dataset):
         g = gt
         g[:, 1] = torch.clamp(g[:, 1], max=a.max_m_duration)
         spans_target = torch.stack([(g[:, 0] + g[:, 1]) / 2.0 / a.max_m_duration, (g[:, 1] - g[:, 0]) / a.max_m_duration], dim=-1)
-        ff, fm = self._features(a.frame_frozen_feature_path, "vit", video_id, a.max_v_frames, 512, v_dur)
-        sf, sm = self._features(a.music_frozen_feature_path, "ast", music_id, a.max_snippet_num, 768, m_duration / a.stride)
+        return meta, spans_target, v_dur, m_duration
+
+    def video_features(self, video_id: str, v_dur: float):
+        a = self.args
+        return self._features(a.frame_frozen_feature_path, "vit", video_id, a.max_v_frames, 512, v_dur)
+
+    def music_features(self, music_id: str, m_duration: float):
+        a = self.args
+        return self._features(a.music_frozen_feature_path, "ast", music_id, a.max_snippet_num, 768, m_duration / a.stride)
+
+    def __getitem__(self, idx):
+        meta, spans_target, v_dur, m_duration = self.sample_meta(idx)
+        ff, fm = self.video_features(meta["video_id"], v_dur)
+        sf, sm = self.music_features(meta["music_id"], m_duration)
         return {"frame_feats": ff, "frame_mask": fm, "segment_feats": sf, "segment_mask": sm}, meta, spans_target
 
 
-def make_loader(csv_path: str, args, batch_size: int, train: bool, world: int, rank: int):
+def make_loader(csv_path: str, args, batch_size: int, train: bool, world: int, rank: int, device=None):
+    """The split's loader, its length and its sampler.  --device_features 1: a DeviceLoader over a DeviceFeatureStore on `device`
+    (default: this rank's GPU) -- the same batches in the same order, assembled on the device (mgsv_amd/feature_store.py)."""
     ds = MGSV_EC_Dataset(csv_path, args)
+    if getattr(args, "device_features", 0):
+        from .feature_store import DeviceFeatureStore, DeviceLoader
+        store = DeviceFeatureStore.from_dataset(ds, device if device is not None else torch.device("cuda", args.local_rank))
+        dl = DeviceLoader(store, max(1, batch_size // max(world, 1)), train, world, rank)
+        return dl, len(ds), dl.sampler
     sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=train) if world > 1 else None
     dl = torch.utils.data.DataLoader(ds, batch_size=max(1, batch_size // max(world, 1)), num_workers=args.num_workers,
                                      shuffle=(train and sampler is None), sampler=sampler, drop_last=train, pin_memory=True)
@@ -296,9 +319,21 @@ def train_one_epoch(epoch, args, model, loader, optimizer, device, dist, logger,
     """reference train-MaDe.py:300-425."""
     from .utils.util_test import IoU_metrics, detr_iou_device
     model.train()
-    ious: List[float] = []
     t0 = time.time()
     meter = {"loss": 0.0, "ret": 0.0, "loc": 0.0, "n": 0}
+    # Nothing is read back inside a step (a read empties the launch queue, whichever loader feeds the loop): the per-step device
+    # scalars and IoU tensors wait in these lists and are converted at the display points and at the end of the epoch, by the
+    # arithmetic a per-step read would have done, in the same order -- every logged and returned number is the same.
+    pending: List[tuple] = []                                   # (loss, ret, loc device scalars, batch size) of the steps not yet metered
+    iou_steps: List[torch.Tensor] = []
+
+    def settle():
+        if pending:
+            vals = torch.stack([x.detach().to(torch.float64) for tot, ret, loc, _ in pending for x in (tot, ret, loc)]).tolist()
+            for k, (_, _, _, b) in enumerate(pending):              # f32 -> f64 is exact: float(x) of every scalar
+                meter["loss"] += vals[3 * k] * b; meter["ret"] += vals[3 * k + 1] * b; meter["loc"] += vals[3 * k + 2] * b; meter["n"] += b
+            pending.clear()
+
     for step, (data_map, meta_map, spans_target) in enumerate(loader):
         ff, sf, fm, sm, tg, vdur = _to_device(data_map, meta_map, spans_target, device)
         fac = lr_factor(args, args.total_step, warmup_steps, total_step)
@@ -326,14 +361,16 @@ def train_one_epoch(epoch, args, model, loader, optimizer, device, dist, logger,
             torch.nn.utils.clip_grad_norm_(model.get_detection_parameter(), args.max_grad_norm)
             optimizer.step(); optimizer.zero_grad()
         iou = _batch_iou(args, model, om, meta_map, device)
-        ious.extend(iou.cpu().tolist())
+        iou_steps.append(iou.detach())
         args.total_step += 1
-        b = ff.shape[0]
-        meter["loss"] += float(ret + loc) * b; meter["ret"] += float(ret) * b; meter["loc"] += float(loc) * b; meter["n"] += b
+        pending.append(((ret.detach() + loc.detach()).reshape(()), ret.detach().reshape(()), loc.detach().reshape(()), ff.shape[0]))
         if args.rank == 0 and (step + 1) % max(1, len(loader) // max(args.num_display, 1)) == 0:
+            settle()
             logger.info(f"Train [{epoch}/{args.epochs}, {step + 1}/{len(loader)}] loss {meter['loss'] / meter['n']:.4f} "
                         f"ret {meter['ret'] / meter['n']:.4f} loc {meter['loc'] / meter['n']:.4f} lr x{fac:.3f} "
                         f"{(time.time() - t0) / (step + 1) * 1e3:.1f} ms/step")
+    settle()
+    ious: List[float] = torch.cat([t.reshape(-1) for t in iou_steps]).cpu().tolist() if iou_steps else []
     return meter["loss"] / max(meter["n"], 1), IoU_metrics(ious) if ious else {"mIoU": 0.0}
 
 
@@ -362,6 +399,12 @@ def eval_epoch(epoch, args, model, loader, device, dist, logger, split: str = "v
         if streams[lane] is not None:
             streams[lane].wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(streams[lane]) if streams[lane] is not None else contextlib.nullcontext():
+            if streams[lane] is not None:
+                # a device loader's tensors were allocated on the main stream; this lane reads them (and keeps some of them until the
+                # end): tell the allocator, or a block dropped below could be handed to the next batch while the lane still reads it
+                for t in (*data_map.values(), *meta_map.values(), spans_target):
+                    if isinstance(t, torch.Tensor) and t.is_cuda:
+                        t.record_stream(streams[lane])
             ff, sf, fm, sm, tg, vdur = _to_device(data_map, meta_map, spans_target, device)
             om, lm, feat, mask, ids = model(ff, sf, fm, sm, tg, v_duration=vdur, video_ids=meta_map["video_id"], music_ids=meta_map["music_id"],
                                             is_train=False, lane=lane)

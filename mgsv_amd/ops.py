@@ -1094,6 +1094,36 @@ def fp8_dequantize_rows(q: Tensor, exp: Tensor, index: Optional[Tensor] = None, 
     return out
 
 
+def gather_batch_args(arrays: Sequence[Tuple[Tensor, Optional[Tensor], Optional[Tensor]]], index: Tensor, n_samples: int):
+    """The MadeGatherBatchArgs of `gather_batch` (raw pointers: the caller keeps the tensors alive)."""
+    kinds = {torch.float32: _lib.GATHER_F32, torch.bfloat16: _lib.GATHER_BF16, torch.uint8: _lib.GATHER_U8}
+    assert index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous()
+    B = index.numel()
+    a = _lib.MadeGatherBatchArgs()
+    a.index, a.n_samples, a.B, a.n_arrays = (_p(index) if B else None), int(n_samples), B, len(arrays)
+    for d, (src, row, dst) in zip(a.a, arrays):                  # (a ninth array is the library's refusal: n_arrays says so)
+        if src.dtype not in kinds:
+            raise TypeError(f"gather_batch: unsupported source dtype {src.dtype}")
+        assert src.dim() >= 1 and src.is_contiguous()
+        elems = src[0].numel() if src.shape[0] else int(math.prod(src.shape[1:]))
+        if dst is not None:
+            assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.numel() == B * elems, "gather_batch: dst must be [B, row] f32"
+        if row is not None:
+            assert row.dtype == torch.int32 and row.is_contiguous() and row.numel() == n_samples
+        d.src, d.row, d.dst = (_p(src) if src.numel() else None), _p(row), (_p(dst) if dst is not None and dst.numel() else None)
+        d.rows, d.row_elems, d.kind = src.shape[0], elems, kinds[src.dtype]
+    return a
+
+
+def gather_batch(arrays: Sequence[Tuple[Tensor, Optional[Tensor], Optional[Tensor]]], index: Tensor, n_samples: int) -> None:
+    """made_gather_batch: every array of a batch in one launch.  arrays: up to 8 (src, row, dst) with src [rows, ...] contiguous
+    f32 / bf16 / u8, row [n_samples] int32 (sample -> row of src) or None (sample s reads row s), dst [B, ...] contiguous f32 with
+    src's trailing sizes.  index [B] int32: dst[b] = widen(src[row[index[b]]]), a zero row where the sample or its row is out of
+    range.  Exact: f32 copied as bits, bf16 << 16, u8 -> float.  Sizes and pointers are validated by the library."""
+    a = gather_batch_args(arrays, index, n_samples)
+    check(lib().made_gather_batch(C.byref(a), _stream()), "made_gather_batch")
+
+
 def group_topw(sims: Tensor, sel: Tensor, col_group: Tensor, start: Tensor, cols: Tensor, w: int):
     """made_group_topw: the best w columns of the group of every selected column sel [Nv, K] (topk_groups' idx) in its row of sims
     [Nv, Nm] f32 -> (idx [Nv, K, w] int32, score [Nv, K, w] f32), score descending then column ascending, -1 / -inf past the group's
