@@ -58,6 +58,7 @@ class MadeEngine:
         self._f32_products = 1 if dtype == "f32x3" else 0
         self._check_supported()
         self._ws: Dict[tuple, Dict[str, Tensor]] = {}
+        self._side: Optional[torch.cuda.Stream] = None       # the second stream, created on first use (_side_stream)
         self.load_state_dict(state_dict)
 
     # ------------------------------------------------------------------ config support
@@ -237,7 +238,11 @@ class MadeEngine:
     def _side_stream(self):
         if _lib.variant_env("MADE_ONE_STREAM", "0") == "1":     # debugging: every branch on the caller's stream, in issue order
             return torch.cuda.current_stream()
-        if getattr(self, "_side", None) is None:
+        # never the caller's own stream: the framework deals streams out of a pool of 32 in turn, so a stream made earlier (a hipGraph's
+        # capture stream, a warm-up's) can be the one this engine was given as its second -- both branches would share it, and the
+        # trainer's per-stream weight-gradient workspaces (MadeTrainer._flush_dw) would be looked up under the wrong lane
+        cur = torch.cuda.current_stream()
+        while self._side is None or self._side == cur:
             self._side = torch.cuda.Stream(device=self.device)
         return self._side
 

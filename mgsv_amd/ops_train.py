@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, tape as _tape
 from ._lib import BF16, F32, MadeAttnBwdArgs, MadeDropout, MadeGemmTNArgs, MadeGemmTNGroup, check, lib
 from .ops import _f32, _p, _stream, _timed, dt_of, set_drop
 
@@ -124,7 +124,6 @@ def gemm_tn_grouped(problems, rows=None, alpha: float = 1.0, split_m: Optional[i
         nbytes += float(M * (N + K) * 2 + N * K * 4)
     if rows is not None:
         g.row_index, g.n_rows = _p(rows[0]), _p(rows[1])
-    import os
     big = (all(pr[0].shape[1] % 256 == 0 and pr[1].shape[1] % 256 == 0 for pr in problems) and 4096 <= M <= 36864
            and _lib.variant_env("MADE_TN_TILE", "256") == "256")
     if big:
@@ -138,8 +137,7 @@ def gemm_tn_grouped(problems, rows=None, alpha: float = 1.0, split_m: Optional[i
             if 0 < need < _TN_WS_LIMIT:                          # (at the limit or past it: no workspace, the atomic flush)
                 ws = workspace(need)
                 assert ws.dtype == torch.uint8 and ws.numel() >= need and ws.is_contiguous()
-                from . import tape as _tape
-                _tape.keep(ws)
+                _tape.keep(ws)                                # (a tape recorded outside TrainStepGraph has no other owner for it)
                 g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel()
     if split_m is None:
         split_m = _tn_splits(tiles, (M + 63) // 64, rows is not None, 64)

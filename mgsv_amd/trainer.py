@@ -20,8 +20,12 @@ so the gradients of in_proj / out_proj come out of ordinary Linear backward step
 """
 from __future__ import annotations
 
+import contextlib
+import ctypes as C
+import functools
 import math
 import os
+import struct
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -43,12 +47,22 @@ XA = "video_guided_to_music_pooling_cross_transformer"
 HEAD_PAD = 64
 
 
+def bucket_cut(group_ranges) -> int:
+    """Where the flat parameter / gradient buffers split into the two buckets of a step: [0, cut) is the temporal group, whose gradients are
+    final only when the backward pass ends; [cut, end) the matching + detection groups (~85 % of the bytes), final at backward's grad_sync point."""
+    return group_ranges[0][1]
+
+
 class MadeTrainer(MadeEngine):
     def __init__(self, cfg: MadeConfig, state_dict: Dict[str, object], device="cuda:0", dtype: str = "f32"):
         if dtype == "f32x3":
             raise ValueError('dtype "f32x3" (split-bf16 products) is an inference mode: it meets the forward\'s 1e-4 gate, its gradients do not meet '
                              'the f32 training path\'s (measured up to 3e-2 relative per tensor); train in "f32" or "bf16"')
         super().__init__(cfg, state_dict, device, dtype)
+        self._seed_dev: Optional[Tensor] = None              # while a TrainStepGraph is recorded: the device word the kernels read the seed from
+        self._static_exclusion: Optional[Tensor] = None      # ... and its fixed same-music exclusion buffer (TrainStepGraph._device_inputs)
+        self._grads_zeroed = False                           # forward_train(zero_grad=True) has made the gradient fill: backward() skips its own
+        self._tn_ws: Dict[str, Tensor] = {}                  # weight-gradient workspaces, one per lane (_tn_workspace has the ownership rule)
         self._check_train_supported()
         self._init_master(state_dict)
         self.repack()
@@ -269,7 +283,6 @@ class MadeTrainer(MadeEngine):
         (made_repack) into buffers allocated once, so the pointers the kernels (and a captured hipGraph) see never change.
         Vectors (biases, LayerNorm parameters) and, in f32 mode, the matrices themselves alias the masters.
         part: None = every matrix; "early" / "rest" = the matching + detection groups' / the temporal group's (optimizer_step)."""
-        import ctypes as C
         if getattr(self, "_pack_desc", None) is None:
             P, tc, dev = self.P, self.tc, self.device
             mats, vecs = self._table()
@@ -281,7 +294,7 @@ class MadeTrainer(MadeEngine):
                 self.G[key] = g.view(-1) if g.dim() != 1 else g
             descs = []
             tiles = 0
-            cut = self.group_ranges[0][1]                     # masters below: the temporal group (final last in the backward pass)
+            cut = bucket_cut(self.group_ranges)               # masters below: the temporal group (final last in the backward pass)
             part_of = []
             for key, ref in mats:
                 m = self._view(self.master, ref)
@@ -346,7 +359,6 @@ class MadeTrainer(MadeEngine):
         "early": the matching + detection groups (~85 % of the parameters), whose gradients are final before the temporal encoders'
         backward starts (backward(early_opt=...) runs this on a third stream under it); then "rest": the temporal group.
         None: everything at once."""
-        import ctypes as C
         assert part in (None, "early", "rest")
         if part != "rest":
             self.opt_step += 1
@@ -377,34 +389,53 @@ class MadeTrainer(MadeEngine):
                    music_ids=None, v_duration: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """One iteration of the reference's loop body (train-MaDe.py:337-381): forward, backward, (data-parallel gradient
         average: one RCCL all-reduce of the flat buffer), clip + Adam, repack."""
-        self._zero_grad_in_forward = True
-        try:
-            out = self.forward_train(frame_feats, segment_feats, frame_masks, segment_masks, spans_target, seed=seed, music_ids=music_ids,
-                                     v_duration=v_duration)
-        finally:
-            self._zero_grad_in_forward = False
-        scale = 1.0
-        if dist is not None and dist.get_world_size() > 1:
-            # two buckets of the flat f32 gradient buffer (RCCL all-reduce, sum; the 1/W goes into the optimizer's grad_scale): the
-            # matching + detection ranges (~85 % of the bytes) are final before the temporal encoders' backward starts and travel
-            # under it; the temporal range follows at the end
-            cut = self.group_ranges[0][1]
-            works = []
-            self.backward(w_ret, w_loc, grad_sync=lambda: works.append(dist.all_reduce(self.flat_grad[cut:], async_op=True)))
-            works.append(dist.all_reduce(self.flat_grad[:cut], async_op=True))
+        batch = (frame_feats, segment_feats, frame_masks, segment_masks, spans_target)
+        kw = dict(w_ret=w_ret, w_loc=w_loc, music_ids=music_ids, v_duration=v_duration)
+        if dist is not None and dist.get_world_size() > 1:    # (the sums' 1/W goes into the optimizer's grad_scale)
+            return self._step_body(batch, seed, lrs, dict(max_grad_norm=max_grad_norm, grad_scale=1.0 / dist.get_world_size()),
+                                   **self._dp_hooks(dist), **kw)
+        return self._step_body(batch, seed, lrs, dict(max_grad_norm=max_grad_norm), early=self._early_opt_ok(), **kw)
+
+    def _step_body(self, batch, seed: int, lrs, opt_kw: dict, *, grad_sync=None, after_backward=None, early: bool = False,
+                   fill_in_forward: bool = True, w_ret: Optional[Tensor] = None, w_loc: Optional[Tensor] = None, music_ids=None,
+                   v_duration: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        """The order of an iteration, for the eager step and every recorder of TrainStepGraph: forward with the gradient fill inside,
+        backward, optimizer (clip + Adam + repack).  The callers differ in three points:
+          grad_sync(cut): inside backward, where the large bucket [cut, end) is final (bucket_cut) -- its all-reduce starts, a capture is cut;
+          after_backward(cut): behind backward, the temporal bucket [0, cut) final too -- its all-reduce and the wait for both;
+          opt_kw / early: how optimizer_step(*lrs, ...) is invoked -- host scalars or device_state, grad_scale; early (opt-in,
+            _early_opt_ok): in two parts, "early" at backward's grad_sync point on a third stream and "rest" here.
+        fill_in_forward=False leaves the gradient fill to backward, at the head of the main stream: only the three-graph capture asks for
+        it -- it has always recorded the fill there, and moving it would change the launch sequence of its first graph.
+        Needs of self only forward_train, backward, optimizer_step and group_ranges (tests/test_step_body_cpu.py)."""
+        cut = bucket_cut(self.group_ranges)
+        out = self.forward_train(*batch, seed=seed, music_ids=music_ids, v_duration=v_duration, zero_grad=fill_in_forward)
+        hooks = {}
+        if grad_sync is not None:
+            hooks["grad_sync"] = lambda: grad_sync(cut)
+        if early:
+            hooks["early_opt"] = lambda: self.optimizer_step(*lrs, part="early", **opt_kw)
+        self.backward(w_ret, w_loc, **hooks)
+        if after_backward is not None:
+            after_backward(cut)
+        self.optimizer_step(*lrs, part="rest" if early else None, **opt_kw)
+        return out
+
+    def _dp_hooks(self, dist, defer=lambda fn: fn()) -> dict:
+        """_step_body's two hooks of a data-parallel step: two buckets of the flat f32 gradient buffer (RCCL all-reduce, sum).  The
+        matching + detection ranges are final before the temporal encoders' backward starts and travel under it (reference
+        train-MaDe.py:238-241,371); the temporal range follows behind backward, then the wait that orders the optimizer's launches
+        behind both.  defer: how a collective is issued -- at once, or tape.callback (now and again in every replay)."""
+        works = []
+
+        def reduce(lo, hi):
+            defer(lambda: works.append(dist.all_reduce(self.flat_grad[lo:hi], async_op=True)))
+
+        def wait_all():
             for w in works:
                 w.wait()
-            scale = 1.0 / dist.get_world_size()
-        elif self._early_opt_ok():
-            # (opt-in) the matching + detection groups' gradients (~85 % of the parameters) are final before the temporal encoders'
-            # backward starts -- their clip + Adam + repack run on a third stream under it, the temporal group's at the end
-            self.backward(w_ret, w_loc, early_opt=lambda: self.optimizer_step(*lrs, max_grad_norm=max_grad_norm, part="early"))
-            self.optimizer_step(*lrs, max_grad_norm=max_grad_norm, part="rest")
-            return out
-        else:
-            self.backward(w_ret, w_loc)
-        self.optimizer_step(*lrs, max_grad_norm=max_grad_norm, grad_scale=scale)
-        return out
+            works.clear()
+        return dict(grad_sync=lambda cut: reduce(cut, None), after_backward=lambda cut: (reduce(0, cut), defer(wait_all)))
 
     def _early_opt_ok(self) -> bool:
         """the step applied in two parts (see optimizer_step): MADE_EARLY_OPT=1.  Off by default -- measured on MI355X (B = 64 headline
@@ -420,6 +451,25 @@ class MadeTrainer(MadeEngine):
         return TrainStepGraph(self, frame_feats, segment_feats, frame_masks, segment_masks, spans_target, max_grad_norm=max_grad_norm,
                               music_ids=music_ids, v_duration=v_duration, dist=dist, mode=mode)
 
+    @contextlib.contextmanager
+    def _state_kept(self, device_state: Tensor):
+        """Whatever steps run inside, real ones included, leave no trace: parameters, both Adam moments, every buffer, `opt_step` and
+        `generation` are copied on entry and put back on exit, normal or exceptional; then the kernel-facing copies are repacked and
+        device_state's step word (MadeAdamDeviceState, see TrainStepGraph) is set to the count again."""
+        tensors = [self.flat_param, self.exp_avg, self.exp_avg_sq, *self.buffers.values()]
+        saved = [x.clone() for x in tensors]
+        step, gen = self.opt_step, self.generation
+        try:
+            yield
+        finally:
+            torch.cuda.synchronize()
+            for dst, src in zip(tensors, saved):
+                dst.copy_(src)
+            self.opt_step, self.generation = step, gen
+            self.repack()
+            device_state[0] = step
+            torch.cuda.synchronize()
+
     def state_dict_numpy(self) -> Dict[str, np.ndarray]:
         sd = {k: v.detach().cpu().numpy().copy() for k, v in self.master.items()}
         sd.update({k: v.detach().cpu().numpy().copy() for k, v in self.buffers.items()})
@@ -433,8 +483,8 @@ class MadeTrainer(MadeEngine):
     def _drop(self, site: str, p: float):
         if not self.training_dropout or p <= 0.0:
             return None
-        seed_dev = getattr(self, "_seed_dev", None)           # set while a TrainStepGraph is captured: the kernels read the seed there
-        return (seed_dev if seed_dev is not None else self.seed, dr.site_id(site), float(p))
+        # (_seed_dev: set while a TrainStepGraph is captured, the kernels read the seed there)
+        return (self._seed_dev if self._seed_dev is not None else self.seed, dr.site_id(site), float(p))
 
     # ------------------------------------------------------------------ training workspace
     def _train_buffers(self, B: int, Tv: int, Ta: int) -> Dict[str, Tensor]:
@@ -582,9 +632,11 @@ class MadeTrainer(MadeEngine):
         return ex.to(self.device)
 
     def forward_train(self, frame_feats: Tensor, segment_feats: Tensor, frame_masks: Tensor, segment_masks: Tensor,
-                      spans_target: Tensor, seed: int = 0, music_ids=None, v_duration: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                      spans_target: Tensor, seed: int = 0, music_ids=None, v_duration: Optional[Tensor] = None,
+                      zero_grad: bool = False) -> Dict[str, Tensor]:
         """reference model/model_Uni.py:177-322 under model.train(): same outputs as MadeEngine.forward plus everything
         the backward needs, kept in the training workspace.
+        zero_grad: also clear `flat_grad` for the backward pass that follows, on the second stream (backward() then skips its own fill).
         This function is the schedule only -- which stage runs on which stream and who waits for whom; the launches are the stages'."""
         c = self.cfg
         self._set_products()
@@ -624,8 +676,8 @@ class MadeTrainer(MadeEngine):
         dec_early = None
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            if getattr(self, "_zero_grad_in_forward", False):
-                # train_step: the 120 MB fill of the gradient buffer that opens the backward pass runs here, on the second stream beside
+            if zero_grad:
+                # a whole step (_step_body): the 120 MB fill of the gradient buffer that opens the backward pass runs here, on the second stream beside
                 # the DETR encoder (the previous step's optimizer is behind us on the main stream; nothing writes a gradient before the
                 # streams join at the end of the forward)
                 _tape.zero_(self.flat_grad)
@@ -705,7 +757,7 @@ class MadeTrainer(MadeEngine):
             ops.linear_splitk(tw["vn"], tw["mn"], None, tw["sd_ws"][:split * B * B], split, out=ws["sims_dual"])
         else:
             ops.linear(tw["vn"], tw["mn"], None, out=ws["sims_dual"])
-        static_ex = getattr(self, "_static_exclusion", None)  # TrainStepGraph: a fixed buffer the host refills before each replay
+        static_ex = self._static_exclusion                    # TrainStepGraph: a fixed buffer the host refills before each replay
         self._row_exclude = static_ex if static_ex is not None else self.same_music_exclusion(music_ids)
         self._retrieval_loss(ws, video, music, row_exclude=self._row_exclude,
                              pooled=tw["xpooled"] if c.vmr_loss == "dual_single_feature_fuse" else None)
@@ -1195,18 +1247,21 @@ class MadeTrainer(MadeEngine):
         rows = self._rw(row_mask)
         # the launch's workspace (tile partials: ops_train.gemm_tn_grouped): one for the trainer's second stream, one for whatever stream the step
         # runs on -- the launches of a stream are ordered, so they can share one
-        lane = "side" if torch.cuda.current_stream() == getattr(self, "_side", None) else "main"
-
-        def workspace(nbytes: int) -> Tensor:
-            wsd = self.__dict__.setdefault("_tn_ws", {})
-            if lane not in wsd or wsd[lane].numel() < nbytes:
-                if _tape.recording() or torch.cuda.is_current_stream_capturing():
-                    raise _lib.MadeError("the weight-gradient workspace has to exist before the step is recorded (the warm-up run allocates it)")
-                wsd[lane] = tr.gemm_tn_grouped_workspace(self.device, nbytes)
-            return wsd[lane]
+        lane = "side" if torch.cuda.current_stream() == self._side else "main"
         for i in range(0, len(pending), 8):
-            tr.gemm_tn_grouped(pending[i:i + 8], rows=rows, workspace=None if atomic else workspace)
+            tr.gemm_tn_grouped(pending[i:i + 8], rows=rows, workspace=None if atomic else functools.partial(self._tn_workspace, lane))
         pending.clear()
+
+    def _tn_workspace(self, lane: str, nbytes: int) -> Tensor:
+        """The lane's weight-gradient workspace, at least nbytes long: one buffer per lane, replaced by a larger one when a step needs it --
+        never while a step is recorded or captured, whose launches keep the address they were given.  The replaced buffer is freed when its
+        last owner lets go: at once, or when the captured steps that point at it are closed (TrainStepGraph._workspaces)."""
+        ws = self._tn_ws.get(lane)
+        if ws is None or ws.numel() < nbytes:
+            if _tape.recording() or torch.cuda.is_current_stream_capturing():
+                raise _lib.MadeError("the weight-gradient workspace has to exist before the step is recorded (the warm-up run allocates it)")
+            ws = self._tn_ws[lane] = tr.gemm_tn_grouped_workspace(self.device, nbytes)
+        return ws
 
     def _lin_bwd(self, dz: Tensor, x: Tensor, key: str, *, dx_out: Optional[Tensor] = None, row_mask: Optional[Tensor] = None,
                  skip: Optional[Tensor] = None, gw: Optional[Tensor] = None, gb: Optional[Tensor] = None, wt: Optional[Tensor] = None,
@@ -1253,7 +1308,7 @@ class MadeTrainer(MadeEngine):
         ws, tw = self._buffers(B, Tv, Ta), self._train_buffers(B, Tv, Ta)
         regression = "regression" in c.mml_localization
         xq = c.moment_query_type == "xpool" and not regression
-        if zero_grad and not getattr(self, "_grads_zeroed", False):
+        if zero_grad and not self._grads_zeroed:
             _tape.zero_(self.flat_grad)
         self._grads_zeroed = False
         _tape.zero_(tw["dclip"])                              # dvideo, dmusic and the contrastive head's dvid_sum in one fill
@@ -2074,7 +2129,6 @@ class TrainStepGraph:
         self.seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
         # MadeAdamDeviceState {int64 step; float lr[4]; float bc1, bc2_sqrt} in device memory, laid out by the ctypes mirror (which
         # tests/test_abi_cpu.py holds to the header): the step count is word 0, the learning rates start at the `lr` field
-        import ctypes as C
         S = _lib.MadeAdamDeviceState
         assert C.sizeof(S) % 8 == 0 and S.step.offset == 0 and S.lr.offset % 4 == 0
         self.adam_state = torch.zeros(C.sizeof(S) // 8, device=dev, dtype=torch.int64)
@@ -2084,145 +2138,107 @@ class TrainStepGraph:
         ex = t.same_music_exclusion(music_ids)
         self.exclusion = ex.clone() if ex is not None else None
         scale = 1.0 / self.dist.get_world_size() if self.dist is not None else 1.0
-        i = self.inputs
+        self._opt_kw = dict(max_grad_norm=max_grad_norm, grad_scale=scale, device_state=self.adam_state)
+        self._early = self.dist is None and t._early_opt_ok()  # (opt-in: the step applied in two parts, see MadeTrainer._step_body)
+        self.graphs: list = []
+        self.tape: Optional[_tape.LaunchTape] = None
+        self._workspaces: Dict[str, Tensor] = {}             # this capture's share of the trainer's weight-gradient workspaces (_warm_up)
+        record = {("tape", False): self._record_tape, ("tape", True): self._record_tape_dp,
+                  ("graph", False): self._capture_graph, ("graph", True): self._capture_three_graphs}[mode, self.dist is not None]
+        step0, gen0 = t.opt_step, t.generation
+        with self._device_inputs():
+            self._warm_up()
+            self.out = record()
+        t.opt_step, t.generation = step0, gen0                # capturing runs the Python side of optimizer_step, not the kernels
+        self._dev_step = step0
 
-        early = self.dist is None and t._early_opt_ok()       # (opt-in: the step applied in two parts, see MadeTrainer.train_step)
-
-        def fwd_bwd():
-            t._zero_grad_in_forward = True
-            try:
-                out = t.forward_train(i["frame_feats"], i["segment_feats"], i["frame_masks"], i["segment_masks"], i["spans_target"], seed=0,
-                                      v_duration=self.v_duration)
-            finally:
-                t._zero_grad_in_forward = False
-            if early:
-                t.backward(None, None, early_opt=lambda: t.optimizer_step(0.0, 0.0, 0.0, max_grad_norm=max_grad_norm, grad_scale=scale,
-                                                                           device_state=self.adam_state, part="early"))
-            else:
-                t.backward(None, None)
-            return out
-
-        def opt():
-            t.optimizer_step(0.0, 0.0, 0.0, max_grad_norm=max_grad_norm, grad_scale=scale, device_state=self.adam_state,
-                             part="rest" if early else None)
-
-        # warm-up run (loads the kernels, allocates the workspaces, creates the side streams) on a copy of the state
-        keep = [x.clone() for x in (t.flat_param, t.exp_avg, t.exp_avg_sq)]
-        keep_buf = {k: v.clone() for k, v in t.buffers.items()}
-        keep_step, keep_gen = t.opt_step, t.generation
+    @contextlib.contextmanager
+    def _device_inputs(self):
+        """While the step is warmed up and recorded, the trainer's launches read the dropout seed and the same-music exclusion from
+        this capture's device buffers instead of host values."""
+        t = self.trainer
         t._seed_dev, t._static_exclusion = self.seed_dev, self.exclusion
         try:
-            cur = torch.cuda.current_stream()
-            side = torch.cuda.Stream()
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                fwd_bwd(); opt()
-            cur.wait_stream(side)
-            torch.cuda.synchronize()
-            for dst, src in zip((t.flat_param, t.exp_avg, t.exp_avg_sq), keep):
-                dst.copy_(src)
-            for k, v in keep_buf.items():
-                t.buffers[k].copy_(v)
-            t.opt_step, t.generation = keep_step, keep_gen
-            t.repack()
-            self.adam_state[0] = keep_step
-            torch.cuda.synchronize()
-            self.graphs = []
-            if mode == "tape":
-                keep2 = [x.clone() for x in (t.flat_param, t.exp_avg, t.exp_avg_sq)]
-                if self.dist is not None:
-                    # data parallel: the two bucketed all-reduces of the flat gradient buffer (RCCL calls of the framework) ride the tape
-                    # as host callbacks at the points where the eager step makes them -- the large bucket inside backward's grad_sync
-                    # hook (both streams joined, the temporal encoders' backward still to come), the temporal range behind backward,
-                    # then the wait that orders the optimizer's launches behind both (reference train-MaDe.py:238-241,371)
-                    dist_, works = self.dist, []
-                    cut = t.group_ranges[0][1]
-
-                    def fwd_bwd():                              # noqa: F811 (the data-parallel form of the step's first part)
-                        t._zero_grad_in_forward = True
-                        try:
-                            out = t.forward_train(i["frame_feats"], i["segment_feats"], i["frame_masks"], i["segment_masks"], i["spans_target"], seed=0,
-                                                  v_duration=self.v_duration)
-                        finally:
-                            t._zero_grad_in_forward = False
-                        t.backward(None, None, grad_sync=lambda: _tape.callback(lambda: works.append(dist_.all_reduce(t.flat_grad[cut:], async_op=True))))
-                        _tape.callback(lambda: works.append(dist_.all_reduce(t.flat_grad[:cut], async_op=True)))
-
-                        def wait_all():
-                            for w in works:
-                                w.wait()
-                            works.clear()
-                        _tape.callback(wait_all)
-                        return out
-                # the tape replays only the library's launches: a step that still runs a framework kernel (some non-headline
-                # configurations do: the BatchNorm affine of agg_module='mlp', Q > 1 copies, the regression head ...) is refused here
-                # (ForeignKernelError names the operators) instead of silently skipping that work on every replay
-                # The recording runs the step for real (in data-parallel mode: with its all-reduces), so the state is put back afterwards
-                # -- also when the recording is refused (ForeignKernelError on leaving the `with`) or fails: the caller's fallback
-                # (mode='graph' / the eager step) must start from the parameters, Adam moments and step count it had before.
-                try:
-                    with _tape.LaunchTape.record(check=os.environ.get("MADE_TAPE_CHECK", "1") != "0") as tp:
-                        self.out = fwd_bwd(); opt()
-                    torch.cuda.synchronize()
-                    self.tape = tp
-                    tw_ = int(_lib.variant_env("MADE_TAPE_INTERLEAVE", "2"))   # 0: replay in program order (knob for A/B measurements)
-                    if tw_ > 0:
-                        tp.interleave(tw_)
-                finally:
-                    torch.cuda.synchronize()
-                    for dst, src in zip((t.flat_param, t.exp_avg, t.exp_avg_sq), keep2):
-                        dst.copy_(src)
-                    for k, v in keep_buf.items():
-                        t.buffers[k].copy_(v)
-                    t.opt_step, t.generation = keep_step, keep_gen
-                    t.repack()
-                    self.adam_state[0] = keep_step
-                    torch.cuda.synchronize()
-            elif self.dist is None:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self.out = fwd_bwd(); opt()
-                self.graphs.append(g)
-            else:
-                # three graphs cut where the eager path starts its collectives: [forward .. backward of everything but the temporal
-                # encoders] | all-reduce of the matching + detection ranges starts | [encoders' backward] | all-reduce of the
-                # temporal range | [optimizer].  The capture is switched from the first graph to the second inside backward's
-                # grad_sync hook (both streams are joined there).
-                ga, gb, gc_ = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                ctx = [torch.cuda.graph(ga)]
-                ctx[0].__enter__()
-
-                def cut():
-                    ctx[0].__exit__(None, None, None)
-                    ctx[0] = torch.cuda.graph(gb, pool=ga.pool())
-                    ctx[0].__enter__()
-                try:
-                    self.out = t.forward_train(i["frame_feats"], i["segment_feats"], i["frame_masks"], i["segment_masks"], i["spans_target"],
-                                               seed=0, v_duration=self.v_duration)
-                    t.backward(None, None, grad_sync=cut)
-                finally:
-                    ctx[0].__exit__(None, None, None)
-                with torch.cuda.graph(gc_, pool=ga.pool()):
-                    opt()
-                self.graphs += [ga, gb, gc_]
-            t.opt_step, t.generation = keep_step, keep_gen        # capturing runs the Python side of optimizer_step, not the kernels
-            self._dev_step = keep_step
+            yield
         finally:
             t._seed_dev, t._static_exclusion = None, None
+
+    def _run(self, **policy) -> Dict[str, Tensor]:
+        """MadeTrainer._step_body on the fixed buffers, with every per-step scalar read from device memory"""
+        batch = tuple(self.inputs.values())                   # (built in the order of forward_train's arguments)
+        return self.trainer._step_body(batch, 0, (0.0, 0.0, 0.0), self._opt_kw, early=self._early, v_duration=self.v_duration, **policy)
+
+    def _warm_up(self) -> None:
+        """One real step on a stream of its own (loads the kernels, allocates the workspaces, creates the side streams), undone afterwards.
+        A captured step shares ownership of every workspace it points at: the references taken here keep a buffer the trainer later
+        replaces by a larger one (_tn_workspace) alive under the recorded launches, in both modes, until close()."""
+        t = self.trainer
+        with t._state_kept(self.adam_state):
+            cur, side = torch.cuda.current_stream(), torch.cuda.Stream()
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                self._run()
+            cur.wait_stream(side)
+        self._workspaces = dict(t._tn_ws)
+
+    def _record_tape(self, **policy) -> Dict[str, Tensor]:
+        """The tape replays only the library's launches: a step that still runs a framework kernel (some non-headline configurations do:
+        the BatchNorm affine of agg_module='mlp', Q > 1 copies, the regression head ...) is refused here (ForeignKernelError names the
+        operators) instead of silently skipping that work on every replay.
+        The recording runs the step for real (in data-parallel mode: with its all-reduces), so the state is put back afterwards -- also
+        when the recording is refused (ForeignKernelError on leaving the recorder) or fails: the caller's fallback (mode='graph' / the
+        eager step) must start from the parameters, Adam moments and step count it had before."""
+        with self.trainer._state_kept(self.adam_state):
+            with _tape.LaunchTape.record(check=os.environ.get("MADE_TAPE_CHECK", "1") != "0") as tp:
+                out = self._run(**policy)
+            torch.cuda.synchronize()
+            self.tape = tp
+            weight = int(_lib.variant_env("MADE_TAPE_INTERLEAVE", "2"))   # 0: replay in program order (knob for A/B measurements)
+            if weight > 0:
+                tp.interleave(weight)
+        return out
+
+    def _record_tape_dp(self) -> Dict[str, Tensor]:
+        """Data parallel: the two bucketed all-reduces of the flat gradient buffer (RCCL calls of the framework) and the wait for them
+        ride the tape as host callbacks at the points where the eager step makes them (MadeTrainer._dp_hooks)."""
+        return self._record_tape(**self.trainer._dp_hooks(self.dist, defer=_tape.callback))
+
+    def _capture_graph(self) -> Dict[str, Tensor]:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            out = self._run()
+        self.graphs = [g]
+        return out
+
+    def _capture_three_graphs(self) -> Dict[str, Tensor]:
+        """Data parallel: three graphs cut where the eager path starts its collectives: [forward .. backward of everything but the
+        temporal encoders] | all-reduce of the matching + detection ranges starts | [encoders' backward] | all-reduce of the temporal
+        range | [optimizer]; step() makes the collectives between the replays.  The capture moves on to the next graph inside
+        backward's grad_sync hook (both streams are joined there) and behind backward."""
+        ga, gb, gc_ = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with contextlib.ExitStack() as capture:
+            capture.enter_context(torch.cuda.graph(ga))
+
+            def move_on_to(g):
+                capture.close()
+                capture.enter_context(torch.cuda.graph(g, pool=ga.pool()))
+            out = self._run(fill_in_forward=False, grad_sync=lambda cut: move_on_to(gb), after_backward=lambda cut: move_on_to(gc_))
+        self.graphs = [ga, gb, gc_]
+        return out
 
     def close(self) -> None:
         """Waits for the last replay, then releases the tape / graphs and every buffer they reference.  Dropping a TrainStepGraph without
         this is safe too (LaunchTape.close synchronises before it frees), this just makes the point in time explicit."""
         torch.cuda.synchronize()
-        if getattr(self, "tape", None) is not None:
+        if self.tape is not None:
             self.tape.close()
             self.tape = None
         self.graphs = []
+        self._workspaces = {}
 
     @staticmethod
     def _store_words(dst: Tensor, words) -> None:
         """dst's first len(words) 32-bit words = words, stream-ordered (the values travel as kernel arguments: made_store_words)"""
-        import ctypes as C
         arr = (C.c_uint32 * len(words))(*[int(w) & 0xFFFFFFFF for w in words])
         _lib.check(_lib.lib().made_store_words(dst.data_ptr(), arr, len(words), torch.cuda.current_stream().cuda_stream), "made_store_words")
 
@@ -2252,7 +2268,6 @@ class TrainStepGraph:
         self._store_words(self.seed_dev, (sd & 0xFFFFFFFF, sd >> 32))
         lrs = tuple(float(x) for x in lrs)
         if lrs != self._lrs:
-            import struct
             self._store_words(self._lr_view, tuple(struct.unpack("<I", struct.pack("<f", x))[0] for x in lrs))
             self._lrs = lrs
         if t.opt_step != self._dev_step:                      # eager optimizer steps in between: realign the device-side count
@@ -2264,7 +2279,7 @@ class TrainStepGraph:
         else:
             self.graphs[0].replay()
         if self.dist is not None and self.mode != "tape":         # (the tape makes the all-reduces itself: host callbacks)
-            cut = t.group_ranges[0][1]
+            cut = bucket_cut(t.group_ranges)
             w1 = self.dist.all_reduce(t.flat_grad[cut:], async_op=True)      # travels under the encoders' backward
             self.graphs[1].replay()
             w2 = self.dist.all_reduce(t.flat_grad[:cut], async_op=True)

@@ -404,6 +404,104 @@ def test_refused_tape_recording_leaves_the_trainer_state_untouched(monkeypatch):
     assert moved <= 0.05 * float((ref.flat_param - keep[0]).double().norm()), moved
 
 
+def test_failed_warm_up_leaves_the_trainer_state_untouched(monkeypatch):
+    """The other position of the snapshot (the one above covers the tape recording): capture_train_step's warm-up runs a real step, and a
+    failure inside it -- here the optimizer's first call raises -- must leave parameters, Adam moments, buffers and both counters as
+    they were, and the trainer reading its seed and exclusion from the host again."""
+    from mgsv_amd.trainer import MadeTrainer
+    cfg, sd, _ = _setup(4, 20, 40)
+    ref, trn = MadeTrainer(cfg, sd, dtype="bf16"), MadeTrainer(cfg, sd, dtype="bf16")
+    b = _batch(cfg, 4, 20, 40, seed=12)
+    trn.train_step(*b, seed=3, lrs=(1e-3, 1e-3, 1e-3)); ref.train_step(*b, seed=3, lrs=(1e-3, 1e-3, 1e-3))   # moments and step count are non-trivial
+    torch.cuda.synchronize()
+    keep = [x.clone() for x in (trn.flat_param, trn.exp_avg, trn.exp_avg_sq)]
+    keep_buf = {k: v.clone() for k, v in trn.buffers.items()}
+    orig, calls = trn.optimizer_step, []
+
+    def failing_once(*a, **kw):
+        calls.append(kw.get("part"))
+        if len(calls) == 1:
+            raise RuntimeError("the optimizer failed in the warm-up")
+        return orig(*a, **kw)
+    monkeypatch.setattr(trn, "optimizer_step", failing_once)
+    with pytest.raises(RuntimeError, match="the optimizer failed in the warm-up"):
+        trn.capture_train_step(*b, mode="graph")
+    torch.cuda.synchronize()
+    assert len(calls) == 1, "the failure was not in the warm-up"
+    assert trn.opt_step == 1 and trn.generation == ref.generation
+    assert trn._seed_dev is None and trn._static_exclusion is None
+    for a, c in zip((trn.flat_param, trn.exp_avg, trn.exp_avg_sq), keep):
+        assert torch.equal(a, c)
+    for k, v in keep_buf.items():
+        assert torch.equal(trn.buffers[k], v), k
+    g = trn.capture_train_step(*b, mode="graph")                                 # a second attempt, from the untouched state
+    og = g.step(*b, seed=4, lrs=(1e-3, 1e-3, 1e-3))
+    oe = ref.train_step(*b, seed=4, lrs=(1e-3, 1e-3, 1e-3))
+    torch.cuda.synchronize()
+    assert torch.equal(og["hs"], oe["hs"]) and trn.opt_step == ref.opt_step == 2
+
+
+def test_second_stream_is_never_the_callers_own():
+    """The framework deals streams out of a pool in turn, so the stream a step is later run or captured on can be the very one the trainer
+    made as its second stream; the two branches of a step would then share a stream and the weight-gradient workspaces be looked up under the
+    wrong lane (a capture at the workspace form's sizes was refused for it).  _side_stream() replaces such a second stream."""
+    from mgsv_amd.trainer import MadeTrainer
+    cfg, sd, _ = _setup(4, 20, 40)
+    trn = MadeTrainer(cfg, sd, dtype="bf16")
+    first = trn._side_stream()
+    assert first != torch.cuda.current_stream() and trn._side_stream() == first
+    with torch.cuda.stream(first):
+        second = trn._side_stream()
+        assert second != first and trn._side_stream() == second
+    assert trn._side_stream() == second
+
+
+@pytest.mark.parametrize("mode", ["graph", "tape"])
+def test_captured_step_keeps_its_weight_gradient_workspaces_alive(mode):
+    """A captured step shares ownership of every weight-gradient workspace its launches point at (TrainStepGraph._workspaces, dropped in
+    close()): when the trainer replaces a lane's buffer by a larger one, the old one stays allocated under the recorded launches.  At the
+    smallest step that takes the workspace form: after the growth the capture still holds the old addresses and its replay lands where the
+    replay of a trainer that never grew lands.  The first step runs with zero learning rates, so that both trainers enter the second with the
+    same weights bit for bit and its forward can be compared bit for bit; the parameters after it within the bound of
+    test_captured_train_step_follows_the_eager_steps for bf16 (the f32 atomic gradient sums of the video tower come in a free order)."""
+    from mgsv_amd.trainer import MadeTrainer
+    from test_bench_shapes_gpu import _workspace_step
+    cfg, sd, inp, _ = _workspace_step(0)
+    b = tuple(torch.from_numpy(np.asarray(inp[k])).cuda() for k in ("frame_feats", "segment_feats", "frame_masks", "segment_masks", "spans_target"))
+
+    def two_steps(trn, g, between=lambda: None):
+        hs1 = g.step(*b, seed=5, lrs=(0.0, 0.0, 0.0))["hs"].clone()
+        torch.cuda.synchronize()
+        p1 = trn.flat_param.clone()
+        between()
+        hs2 = g.step(*b, seed=6, lrs=(1e-3, 1e-3, 1e-3))["hs"].clone()
+        torch.cuda.synchronize()
+        return hs1, p1, hs2
+
+    grown = MadeTrainer(cfg, sd, dtype="bf16")
+    g = grown.capture_train_step(*b, mode=mode)
+    old = {lane: ws.data_ptr() for lane, ws in grown._tn_ws.items()}
+    assert old, "no lane has a workspace: the path under test went unused"
+    assert {lane: ws.data_ptr() for lane, ws in g._workspaces.items()} == old
+
+    def grow():
+        for lane, ws in list(grown._tn_ws.items()):
+            assert grown._tn_workspace(lane, 2 * ws.numel()).numel() == 2 * ws.numel()
+        assert all(grown._tn_ws[lane].data_ptr() != ptr for lane, ptr in old.items()), "the trainer's buffers did not change"
+        assert {lane: ws.data_ptr() for lane, ws in g._workspaces.items()} == old, "the capture lost a buffer its launches write"
+    hs1, p1, hs2 = two_steps(grown, g, grow)
+
+    plain = MadeTrainer(cfg, sd, dtype="bf16")
+    g2 = plain.capture_train_step(*b, mode=mode)
+    ref_hs1, ref_p1, ref_hs2 = two_steps(plain, g2)
+    assert torch.equal(p1, ref_p1) and torch.equal(hs1, ref_hs1) and torch.equal(hs2, ref_hs2)
+    num = float((grown.flat_param - plain.flat_param).double().pow(2).sum())
+    den = float((plain.flat_param - ref_p1).double().pow(2).sum())
+    assert den > 0 and num <= 0.3 * den, (num, den)
+    g.close(); g2.close()
+    assert g._workspaces == {} and g2._workspaces == {}
+
+
 def test_captured_train_step_reads_seed_and_learning_rates_from_the_device():
     from mgsv_amd.trainer import MadeTrainer
     cfg, sd, _ = _setup(4, 20, 40)
