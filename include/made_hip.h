@@ -1201,6 +1201,24 @@ int64_t made_cosine_topk_ws_bytes(int64_t Q, int64_t N, int64_t k, int32_t n_spl
 int made_cosine_topk(const float* query, int64_t Q, const int32_t* query_node, const float* vec, int64_t N, int64_t D, const int32_t* node,
                      int64_t k, int32_t n_splits, int32_t* out_col, float* out_cos, void* ws, int64_t ws_bytes, void* stream);
 
+/* made_cosine_topk_ex: made_cosine_topk under an eligibility mask and with a choice of first-stage kernel.  Everything not named
+ * here -- arguments, order, node rule, fill, the bits of a cosine, the workspace layout, the merge launch -- is made_cosine_topk's.
+ * bits [Q, bits_ld] uint32 is made_eligibility's matrix with one row per QUERY (bits_ld >= ceil(N / 32), column c = bit c & 31 of
+ * word c >> 5; the bits past N of the last word and the words past ceil(N / 32) are not read as columns); NULL: every column is
+ * eligible.  "Admissible" gains one clause: the column's bit in the query's row is set.  An ineligible column gives no node its
+ * score and represents none; a node without an eligible admissible column is absent; slots past the nodes present hold -1 / -inf.
+ * The mask is tested in the first stage only (a template parameter; the unmasked instantiation is made_cosine_topk's code).
+ * form: 1 = a workgroup takes 128 query rows (made_cosine_topk's kernel); 2 = a workgroup takes 32 query rows, staged once for its
+ * whole walk, and Q > 32 takes several row blocks -- for few queries, where a 128-row tile pays for rows that do not exist; 0 = the
+ * launcher chooses.  Both forms run the dot product as the same chain on v_mfma_f32_32x32x2_f32 with the same operand layout, so a
+ * (query row, table row) pair has the same bits in both, and the result is bit-identical across forms and splits.
+ * made_cosine_topk_ex_ws_bytes: the bytes ws must hold (the forms choose different splits for n_splits = 0); -1 for arguments the
+ * call refuses.  form outside 0..2 and ws_bytes below that: MADE_ERR_UNSUPPORTED; bits_ld < ceil(N / 32): MADE_ERR_INVALID_ARG. */
+int64_t made_cosine_topk_ex_ws_bytes(int64_t Q, int64_t N, int64_t k, int32_t n_splits, int32_t form);
+int made_cosine_topk_ex(const float* query, int64_t Q, const int32_t* query_node, const float* vec, int64_t N, int64_t D,
+                        const int32_t* node, const uint32_t* bits, int64_t bits_ld, int64_t k, int32_t n_splits, int32_t form,
+                        int32_t* out_col, float* out_cos, void* ws, int64_t ws_bytes, void* stream);
+
 /* made_merge_moments: the moments of P (video, track) entries on the track's own time axis from the moments of the track's w
  * windows, one wave per entry, no atomics.  win_col / win_score [P, w] = made_group_topw's columns (-1: no window) and
  * similarities; cand [P, w, Q, 3] f32 = every query's (start, end, foreground probability) in seconds on its window's axis,

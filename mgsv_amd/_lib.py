@@ -335,6 +335,8 @@ SIGNATURES = {
     "made_cosine_join": (C.c_int, [vp, i64, i64, vp, i64, i64, i64, i64, f32, vp, vp, vp, i64, vp, vp]),
     "made_cosine_topk_ws_bytes": (C.c_int64, [i64, i64, i64, i32]),
     "made_cosine_topk": (C.c_int, [vp, i64, vp, vp, i64, i64, vp, i64, i32, vp, vp, vp, i64, vp]),
+    "made_cosine_topk_ex_ws_bytes": (C.c_int64, [i64, i64, i64, i32, i32]),
+    "made_cosine_topk_ex": (C.c_int, [vp, i64, vp, vp, i64, i64, vp, vp, i64, i64, i32, i32, vp, vp, vp, i64, vp]),
     "made_merge_moments": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i32, f32, f32, i64, vp, vp, vp, vp, vp]),
     "made_fp8_quantize_rows": (C.c_int, [vp, i64, i64, vp, vp, vp]),
     "made_fp8_dequantize_rows": (C.c_int, [vp, vp, i64, vp, i64, i64, i64, vp, vp]),

@@ -349,6 +349,82 @@ def check_shortlist(cfg, shortlist, explicit_sims: bool) -> Optional[int]:
     return R
 
 
+def check_candidates(cfg, candidates, Nv: int, shortlist, explicit_sims: bool) -> Optional[Tensor]:
+    """`candidates` as an integer tensor [N_v, R], 1 <= R <= 256, where it was given (None stays None).  ValueError for candidates
+    together with shortlist= or similarities of the caller's, a dtype that is not an integer's, a first dimension that is not N_v, R
+    outside [1, 256], and the configurations `check_shortlist` refuses."""
+    if candidates is None:
+        return None
+    if shortlist is not None or explicit_sims:
+        raise ValueError("candidates replaces the shortlist's first stage and is scored with the model's own cosine and X-Pool: it cannot "
+                         "be combined with shortlist=, sims= / sims_fn=")
+    c = candidates
+    if not isinstance(c, Tensor):
+        a = np.asarray(c)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"candidates must hold integers (library columns, -1: none), got dtype {a.dtype}")
+        c = torch.from_numpy(np.ascontiguousarray(a.astype(np.int64)))
+    elif c.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise ValueError(f"candidates must hold integers (library columns, -1: none), got dtype {c.dtype}")
+    if c.dim() != 2 or c.shape[0] != Nv:
+        raise ValueError(f"candidates must be [N_v, R] = [{Nv}, R], got {tuple(c.shape)}")
+    R = int(c.shape[1])
+    if not 1 <= R <= SHORTLIST_MAX:
+        raise ValueError(f"candidates lists {R} columns per video: must lie in [1, {SHORTLIST_MAX}]")
+    check_shortlist(cfg, R, False)
+    return c
+
+
+def _normalize_candidates(c: Tensor, N: int, dev) -> Tensor:
+    """int32 [N_v, R] on the device: negative entries as -1, a later duplicate of a column within a row as -1; an entry >= N is a
+    ValueError (torch ops; one host read for the range check)"""
+    c = c.to(dev).to(torch.int64)
+    if c.numel() and int(c.max()) >= N:
+        raise ValueError(f"candidates names column {int(c.max())}: the library has {N}")
+    none = torch.full_like(c, -1)
+    c = torch.where(c < 0, none, c)
+    vals, idx = torch.sort(c, dim=1, stable=True)                  # (stable: the first of equal columns stays first)
+    dup = torch.zeros_like(vals, dtype=torch.bool)
+    dup[:, 1:] = (vals[:, 1:] == vals[:, :-1]) & (vals[:, 1:] >= 0)
+    later = torch.zeros_like(dup).scatter(1, idx, dup)
+    return torch.where(later, none, c).to(torch.int32).contiguous()
+
+
+def _eligible_candidates(c: Tensor, rc: "_RowConstraints", attrs, Nv: int, dev) -> Tensor:
+    """c with every entry its video may not be grounded in set to -1: made_eligibility over the compact table of the call's distinct
+    candidate columns (attrs: the columns' tags / length / key on the device, None where nothing tests one), gathered at the slots"""
+    uniq = torch.unique(c[c >= 0])                                 # ascending
+    U = int(uniq.numel())
+    if U == 0:
+        return c
+    u64 = uniq.to(torch.int64)
+    bits = rc.bits(Nv, U, *(None if a is None else a.index_select(0, u64).contiguous() for a in attrs), device=dev)
+    pos = torch.searchsorted(uniq, c.clamp(min=0).contiguous())    # every slot's place in the compact table
+    word = bits.gather(1, pos >> 5)
+    ok = ((word >> (pos & 31).to(torch.int32)) & 1) != 0
+    return torch.where((c >= 0) & ok, c, torch.full_like(c, -1))
+
+
+def _candidate_cos(engine: MadeEngine, video: Tensor, cand_col: Tensor, csr, fetch_vec, chunk_cols: int) -> Tensor:
+    """cand_cos [N_v, R] f32 (NaN where there is no candidate): `dual_sims(video, vec[distinct columns], splitk=False)` gathered at the
+    slots -- the bits the shortlist's first stage gives the same pair -- along `pair_csr`'s walk, in chunks of at most chunk_cols
+    distinct columns; fetch_vec(cols int64 numpy, cols int64 device) -> their `vec` rows on the device."""
+    Nv, R = cand_col.shape
+    cols_d, start_d, vidx_d, slot_d = csr
+    cols, start = cols_d.cpu().numpy(), start_d.cpu().numpy().astype(np.int64)
+    cos = torch.full((Nv * R,), float("nan"), device=video.device, dtype=torch.float32)
+    chunk_cols = max(1, int(chunk_cols))
+    for u0 in range(0, len(cols), chunk_cols):
+        u1 = min(len(cols), u0 + chunk_cols)
+        p0, p1 = int(start[u0]), int(start[u1])
+        vec = fetch_vec(cols[u0:u1], cols_d[u0:u1]).to(torch.float32).contiguous()
+        sims = engine.dual_sims(video, vec, splitk=False)
+        counts = (start_d[u0 + 1:u1 + 1] - start_d[u0:u1]).to(torch.int64)
+        local = torch.repeat_interleave(torch.arange(u1 - u0, device=video.device), counts, output_size=p1 - p0)
+        cos[slot_d[p0:p1]] = sims[vidx_d[p0:p1].to(torch.int64), local]
+    return cos.view(Nv, R)
+
+
 # ---------------------------------------------------------------------------------------------- diverse results
 POOL_MAX = 256                          # made_mmr_select's P limit (= made_topk_groups' K limit)
 
@@ -443,13 +519,14 @@ def _shortlist_fold(engine: MadeEngine, video: Tensor, vec: Tensor, bits: Option
     return ops.topk_merge(run[0], run[1], idx.view(Nv, kk, 1), sc.view(Nv, kk, 1), R, col_offset=c0, out_col=out[0], out_score=out[1])
 
 
-def _score_candidates(engine: MadeEngine, video: Tensor, cand_col: Tensor, cand_cos: Tensor, fetch, chunk_cols: int, stats: Optional[dict] = None):
+def _score_candidates(engine: MadeEngine, video: Tensor, cand_col: Tensor, cand_cos: Tensor, fetch, chunk_cols: int, stats: Optional[dict] = None,
+                      csr=None):
     """Stage 2: cand_score [N_v, R] f32 = cosine + X-Pool of every candidate (NaN where there is none).  The pairs are sorted by
     column; the distinct columns are walked in chunks of at most chunk_cols, each fetched by fetch(cols int64 numpy) -> (tokens
     [n, S, D], mask [n, S], done()) and scored by `MadeEngine.xpool_pair_sims`."""
     dev = engine.device
     Nv, R = cand_col.shape
-    cols_d, start_d, vidx_d, slot_d = pair_csr(cand_col)
+    cols_d, start_d, vidx_d, slot_d = pair_csr(cand_col) if csr is None else csr
     cols, start = cols_d.cpu().numpy(), start_d.cpu().numpy().astype(np.int64)      # (one host read: the walk is planned from it)
     xp = torch.full((Nv * R,), float("nan"), device=dev, dtype=torch.float32)
     cache = {}
@@ -495,7 +572,7 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
            pair_batch: int = 64, windows: Optional[Windows] = None, windows_per_track: int = 1, moments: int = 1,
            nms_iou: float = 0.5, constraints: Optional[Constraints] = None, tags=None, length=None,
            shortlist: Optional[int] = None, diversity: Optional[float] = None, max_similarity: Optional[float] = None,
-           pool: Optional[int] = None) -> Grounding:
+           pool: Optional[int] = None, candidates=None) -> Grounding:
     """Each video's best k tracks (groups of columns sharing a music id when group_id [N_m] is given) and the moment in each.
     constraints: per-video `Constraints` on the tracks' `tags` (int64 [tracks]) and `length` (f32 seconds [tracks]; default: the
     durations) -- the selection then runs on every row with its ineligible columns removed (made_eligibility, then the masked
@@ -507,6 +584,13 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     (made_topk_groups on `dual_sims`), only those pairs get the X-Pool score (made_xpool_sims_pairs on the distinct shortlisted
     columns), and the selection above runs on each row's R exact scores with every other column ineligible (made_topk_candidates).
     `Grounding.cand_col` / `cand_score` [N_v, R] report what was scored.
+    candidates = C (an integer tensor or array [N_v, R] of library COLUMNS, -1: none, 1 <= R <= 256): the caller's list in place of
+    the shortlist's first stage -- neighbours of tracks the user liked (`similar.neighbour_candidates`), a playlist, a search's hits.
+    An entry >= N_m is a ValueError, a later duplicate within a row and, under constraints, an ineligible entry (made_eligibility
+    over the call's distinct candidate columns) become -1; the cosines are `dual_sims` on the distinct columns, gathered -- the first
+    stage's bits for the same pair -- and the X-Pool scoring, the selection, the windows (a track is scored by its best LISTED
+    window) and the diversity are the shortlist's.  `Grounding.cand_col` is the normalised table, `cand_score` its exact scores.
+    Not with shortlist=, sims=, or a configuration a shortlist refuses.
     diversity = mu (>= 0) / max_similarity = tau (in (-1, 1]) / pool = P (k <= P <= 256, default min(256, 4 k)): the selection returns
     each video's best P groups, and made_mmr_select picks k of them greedily -- each time the group with the largest score - mu *
     (largest cosine of its representative column's `vec` with a group picked before), groups whose cosine with a pick exceeds tau
@@ -514,9 +598,10 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     result's rank in the pool and that largest cosine."""
     dev = engine.device
     Nv, Nm = len(videos), len(music)
+    candidates = check_candidates(engine.cfg, candidates, Nv, shortlist, sims is not None)
     shortlist = check_shortlist(engine.cfg, shortlist, sims is not None)
     div = check_diversity(k, diversity, max_similarity, pool)
-    if shortlist is None:
+    if shortlist is None and candidates is None:
         if sims is None:
             sims = similarity_matrix(engine, videos.vec, music.tokens, music.mask, music.vec)
         sims = sims.to(dev, torch.float32)
@@ -530,8 +615,22 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
         col = (lambda a: a) if windows is None else (lambda a: a[windows.track])      # track attributes -> columns
         up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(col(a), dtype=dt)).to(dev)
         key = np.arange(Nm, dtype=np.int32) if windows is None else windows.track.astype(np.int32)
-        bits = _RowConstraints(nc, dev).bits(Nv, Nm, up(t, np.int64), up(l, np.float32), torch.from_numpy(key).to(dev), device=dev)
+        rc, attrs = _RowConstraints(nc, dev), (up(t, np.int64), up(l, np.float32), torch.from_numpy(key).to(dev))
+        if candidates is None:
+            bits = rc.bits(Nv, Nm, *attrs, device=dev)
     cand = None
+    if candidates is not None:
+        engine._set_products()
+        video = videos.vec.to(dev, torch.float32).contiguous()
+        ccol = _normalize_candidates(candidates, Nm, dev)
+        if constraints is not None:
+            ccol = _eligible_candidates(ccol, rc, attrs, Nv, dev)
+        csr = pair_csr(ccol)
+        vec = music.vec.to(dev, torch.float32).contiguous()
+        ccos = _candidate_cos(engine, video, ccol, csr, lambda rows, rows_d: vec.index_select(0, rows_d), 4096)
+        tokens = music.tokens.to(dev, engine.tc).contiguous()
+        fetch = _device_fetch(tokens, music.mask.to(dev, torch.float32).contiguous())
+        cand = (ccol, _score_candidates(engine, video, ccol, ccos, fetch, 4096, csr=csr))
     if shortlist is not None:
         engine._set_products()
         R = min(shortlist, Nm)
@@ -1056,9 +1155,12 @@ def _select_under_constraints(engine: MadeEngine, videos: Encoded, library, kk: 
 
 
 def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w: int, chunk_cols: int, R: int,
-                        constraints: Optional[Constraints], timings: Optional[dict], deq: Optional[_Dequantize] = None):
+                        constraints: Optional[Constraints], timings: Optional[dict], deq: Optional[_Dequantize] = None,
+                        candidates: Optional[Tensor] = None):
     """(wcol, wscore [N_v, kk, w], (cand_col, cand_score [N_v, R])): `ground(..., shortlist=R)`'s selection on a stored library.
-    Stage 1 reads `vec` and the attribute arrays only; stage 2 the tokens and masks of the distinct shortlisted columns."""
+    Stage 1 reads `vec` and the attribute arrays only; stage 2 the tokens and masks of the distinct shortlisted columns.
+    candidates [N_v, R]: `ground(..., candidates=)`'s -- stage 1 is the caller's table, normalised, and the cosines of its distinct
+    columns alone (a host library reads `vec` at those columns only)."""
     dev = engine.device
     Nv, N = len(videos), len(library)
     engine._set_products()
@@ -1068,8 +1170,22 @@ def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w
         ev[0].record(cur)
     video = videos.vec.to(dev, torch.float32).contiguous()
     rc, attrs = _library_constraints(library, constraints, Nv, dev) if constraints is not None else (None, None)
-    items, _ = walk_plan(library, chunk_cols)
     resident = library.on_device
+    items = [] if candidates is not None else walk_plan(library, chunk_cols)[0]
+    csr = None
+    if candidates is not None:
+        cand_col = _normalize_candidates(candidates, N, dev)
+        if rc is not None:
+            cand_col = _eligible_candidates(cand_col, rc, attrs, Nv, dev)
+        csr = pair_csr(cand_col)
+
+        def fetch_vec(rows: np.ndarray, rows_d: Tensor):
+            v = library.vec
+            if resident:
+                return v.index_select(0, rows_d)
+            part = v[torch.from_numpy(rows)] if isinstance(v, Tensor) else torch.from_numpy(np.ascontiguousarray(np.take(v, rows, axis=0)))
+            return part.to(dev)
+        cand_cos = _candidate_cos(engine, video, cand_col, csr, fetch_vec, chunk_cols)
     state = [(torch.empty(Nv, R, 1, device=dev, dtype=torch.int32), torch.empty(Nv, R, 1, device=dev, dtype=torch.float32)) for _ in range(2)]
     run = (torch.empty(Nv, 0, 1, device=dev, dtype=torch.int32), torch.empty(Nv, 0, 1, device=dev, dtype=torch.float32))
     for i, it in enumerate(items):
@@ -1080,7 +1196,8 @@ def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w
             vec = (v if isinstance(v, Tensor) else torch.from_numpy(np.array(v))).to(dev)
         bits = None if rc is None else _chunk_bits(rc, attrs, Nv, it, None, True, dev)
         run = _shortlist_fold(engine, video, vec.to(torch.float32).contiguous(), bits, R, it.col_offset, run, state[i % 2])
-    cand_col, cand_cos = run[0].view(Nv, R), run[1].view(Nv, R)
+    if candidates is None:
+        cand_col, cand_cos = run[0].view(Nv, R), run[1].view(Nv, R)
     if ev:
         ev[1].record(cur)
     if resident:
@@ -1094,7 +1211,7 @@ def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w
             enc = stage.widen(0, enc, deq)
             return enc.tokens, enc.mask, (lambda: stage.consumed[0].record(cur))
     stats = {}
-    cand_score = _score_candidates(engine, video, cand_col, cand_cos, fetch, chunk_cols, stats)
+    cand_score = _score_candidates(engine, video, cand_col, cand_cos, fetch, chunk_cols, stats, csr=csr)
     if ev:
         ev[2].record(cur)
     gid = None
@@ -1121,7 +1238,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
                    moments: int = 1, nms_iou: float = 0.5, chunk_cols: int = 4096, video_batch: int = 1024, sims_fn=None,
                    timings: Optional[dict] = None, constraints: Optional[Constraints] = None, compact: Optional[bool] = None,
                    shortlist: Optional[int] = None, diversity: Optional[float] = None, max_similarity: Optional[float] = None,
-                   pool: Optional[int] = None) -> Grounding:
+                   pool: Optional[int] = None, candidates=None) -> Grounding:
     """`ground()` for a stored library (mgsv_amd.library.MusicLibrary: host arrays, a memory-mapped directory, or device tensors):
     the same Grounding, bit for bit, as
         ground(engine, videos, library.as_encoded(dev), k, group_id=library.group_id, windows=library.windows, ...)
@@ -1143,6 +1260,9 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     (and the attribute arrays under constraints) -- cosines, the best R eligible columns per chunk, made_topk_merge; stage 2 fetches
     the tokens of the distinct shortlisted columns alone, in chunks of at most chunk_cols, and scores the listed pairs; the selection
     is made_topk_candidates.  timings then receives shortlist_ms, pairs_scored, columns_projected, pair_score_ms, selection_ms.
+    candidates = C: `ground(..., candidates=C)` for the stored library, bit for bit: no walk over the library at all -- `vec`, the
+    attribute arrays and the tokens are read at the distinct candidate columns only.  timings as for a shortlist (shortlist_ms is the
+    normalisation and the cosines).
     diversity / max_similarity / pool: `ground(..., diversity=, max_similarity=, pool=)` for the stored library, bit for bit: the walk
     selects the pool, made_mmr_select re-selects k of it against the library's `vec` (a host library: the distinct representative
     columns of the call, read and uploaded once), and only the k kept are localized.  timings then receives diversify_ms.
@@ -1153,6 +1273,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     and widen the distinct selected columns (the whole library is never widened).  timings then receives dequantize_ms."""
     c = engine.cfg
     dev = engine.device
+    candidates = check_candidates(c, candidates, len(videos), shortlist, sims_fn is not None)
     shortlist = check_shortlist(c, shortlist, sims_fn is not None)
     div = check_diversity(k, diversity, max_similarity, pool)
     if c.moment_query_type == "xpool":
@@ -1171,7 +1292,10 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     fp8 = library.dtype == "fp8"
     deq = _Dequantize(timings is not None) if fp8 else None
     cand = None
-    if shortlist is not None:
+    if candidates is not None:
+        wcol, wscore, cand = _select_shortlisted(engine, videos, library, ks, w, int(chunk_cols), int(candidates.shape[1]), constraints, timings,
+                                                 deq, candidates)
+    elif shortlist is not None:
         wcol, wscore, cand = _select_shortlisted(engine, videos, library, ks, w, int(chunk_cols), min(shortlist, N), constraints, timings, deq)
     elif constraints is None:
         items, skipped = walk_plan(library, int(chunk_cols))

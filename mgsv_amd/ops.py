@@ -1263,12 +1263,21 @@ def cosine_join(vec: Tensor, tau: float, pair_i: Tensor, pair_j: Tensor, pair_co
                                  _p(pair_j) if cap else None, _p(pair_cos) if cap else None, cap, _p(count), _stream()), "made_cosine_join")
 
 
-def cosine_topk(query: Tensor, vec: Tensor, k: int, node: Optional[Tensor] = None, query_node: Optional[Tensor] = None, n_splits: int = 0):
+_COSINE_TOPK_FORMS = {"auto": 0, "wide": 1, "narrow": 2, 0: 0, 1: 1, 2: 2}
+
+
+def cosine_topk(query: Tensor, vec: Tensor, k: int, node: Optional[Tensor] = None, query_node: Optional[Tensor] = None, n_splits: int = 0,
+                bits: Optional[Tensor] = None, form="auto"):
     """made_cosine_topk: the k nearest nodes by cosine of every row of query [Q, D] over vec [N, D] (both f32 contiguous, D 128 / 256 /
     512; query may be a slice of vec) -> (col [Q, k] int32, cos [Q, k] f32): every node's best column, score descending then column
     ascending, -1 / -inf past the nodes present.  node [N] int32: every column's node (None: the column itself; < 0: ignored);
     query_node [Q] int32: the node a query excludes (None or < 0: nothing).  n_splits = 0 lets the launcher choose the column splits;
-    the result does not depend on them."""
+    the result does not depend on them.
+
+    bits [Q, >= ceil(N / 32)] int32 (`eligibility`'s matrix, one row per query): a column whose bit is clear is no candidate for that
+    query.  form: "auto" (0), "wide" (1: 128 query rows per workgroup) or "narrow" (2: 32 query rows per workgroup, for few queries);
+    the result does not depend on it.  The call is made_cosine_topk_ex; with bits None, form "wide" (and "auto" wherever the launcher
+    keeps the 128-row form) is made_cosine_topk's kernel and launch."""
     assert query.dim() == 2 and vec.dim() == 2 and query.dtype == torch.float32 and vec.dtype == torch.float32
     assert query.is_contiguous() and vec.is_contiguous() and query.device == vec.device and query.shape[1] == vec.shape[1]
     Q, D = query.shape
@@ -1277,11 +1286,18 @@ def cosine_topk(query: Tensor, vec: Tensor, k: int, node: Optional[Tensor] = Non
         assert node.dtype == torch.int32 and node.is_contiguous() and node.numel() == N and node.device == vec.device
     if query_node is not None:
         assert query_node.dtype == torch.int32 and query_node.is_contiguous() and query_node.numel() == Q and query_node.device == vec.device
+    if form not in _COSINE_TOPK_FORMS:
+        raise ValueError(f"form must be 'auto', 'wide' or 'narrow' (0, 1, 2), got {form!r}")
+    form = _COSINE_TOPK_FORMS[form]
+    bits_ld = 0
+    if bits is not None:
+        assert bits.device == vec.device
+        bits_ld = _mask_ld(bits, Q, N) if Q else 0
     k, n_splits = int(k), int(n_splits)
     col = torch.empty(Q, max(k, 0), device=vec.device, dtype=torch.int32)
     cos = torch.empty(Q, max(k, 0), device=vec.device, dtype=torch.float32)
-    need = max(0, int(lib().made_cosine_topk_ws_bytes(Q, N, k, n_splits)))
+    need = max(0, int(lib().made_cosine_topk_ex_ws_bytes(Q, N, k, n_splits, form)))
     ws = torch.empty(max(need, 8) // 8, device=vec.device, dtype=torch.int64)
-    check(lib().made_cosine_topk(_p(query), Q, _p(query_node), _p(vec) if N else None, N, D, _p(node), k, n_splits, _p(col), _p(cos), _p(ws),
-                                 need, _stream()), "made_cosine_topk")
+    check(lib().made_cosine_topk_ex(_p(query), Q, _p(query_node), _p(vec) if N else None, N, D, _p(node), _p(bits) if Q else None, bits_ld, k,
+                                    n_splits, form, _p(col), _p(cos), _p(ws), need, _stream()), "made_cosine_topk")
     return col, cos
