@@ -21,12 +21,12 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, ops_train
 from .config import MadeConfig
 from .ops import Seg, round_up
 
@@ -44,6 +44,23 @@ class Encoded:
 
     def __len__(self) -> int:
         return self.tokens.shape[0]
+
+
+class _Call(NamedTuple):
+    """What the stages of one forward, or of one batch of `localize_pairs`, share.  One record per call, never engine state: an engine
+    serves two batches in flight."""
+    ws: Dict[str, Tensor]                 # MadeEngine._buffers(B, Tv, Ta)
+    B: int
+    fm: Tensor                            # frame / segment masks [B, Tv] / [B, Ta] f32
+    sm: Tensor
+    frame: Tensor                         # the towers' token outputs [B, Tv, D] / [B, Ta, D] (views into the workspace)
+    seg: Tensor
+    video: Tensor                         # clip / track vectors [B, D] f32
+    music: Tensor
+    pos: Tensor                           # MadeEngine._fused_lists: position embedding and index lists of the fused sequence
+    rows_f: tuple
+    order_f: Tensor
+    v_duration: Optional[Tensor]
 
 
 class MadeEngine:
@@ -419,8 +436,7 @@ class MadeEngine:
         if P[pe].shape[0] < T1:
             raise ValueError(f"{which} position table holds {P[pe].shape[0]} positions < T+1={T1} (reference model/model_Base.py:533)")
         mask1 = torch.cat([torch.ones_like(mask[:, :1]), mask], dim=1).contiguous()
-        rows1 = ops.row_index(mask1)
-        order1 = ops.batch_order(mask1)
+        rows1, order1 = self._row_lists(mask1)
         act = ops.ACT_QUICKGELU if c.with_act_after_proj else ops.ACT_NONE
         x = ws["x0"][:B * T1]
         x3d = x.view(B, T1, D)
@@ -439,6 +455,51 @@ class MadeEngine:
         local.copy_(y3[:, 1:])
 
     # ------------------------------------------------------------------ X-Pool scoring
+    def _xpool_path(self, Nv: int, S: int, D: int, pooled_out: Optional[Tensor]) -> str:
+        """Which kernel chain scores Nv videos against tracks of S segments (xpool_sims has the chains)."""
+        bf16, knob = self.tc == torch.bfloat16, _lib.variant_env
+        if bf16 and D == 256 and pooled_out is None and Nv >= 256:
+            return "sims" if S <= 96 and knob("MADE_XPOOL_SIMS", "1") != "0" else "fused"
+        if bf16 and D in (256, 512) and S <= 512 and pooled_out is None and Nv >= 256 and knob("MADE_XPOOL_ATTN", "1") != "0":
+            return "attention"
+        if bf16 and Nv <= 64 and S <= 512 and S * D >= 65536 and D in (256, 512) and knob("MADE_XPOOL_INBATCH", "1") != "0":
+            return "inbatch"
+        return "wide"
+
+    def _xpool_track_bufs(self, cm: int, S: int, D: int, hoist: bool, fold: bool = False) -> tuple:
+        """What `_xpool_tracks` needs for chunks of at most cm tracks: (cm, hoist, fold) and its buffers -- LN1 rows, K, U and (hoist) U after
+        the out-projection, [cm*S, D] each, [cm*S, 2D] for the last one under `fold`."""
+        E = lambda cols: torch.empty(cm * S, cols, device=self.device, dtype=self.tc)
+        return cm, hoist, fold, E(D), E(D), E(D), (E(2 * D if fold else D) if hoist else None)
+
+    def _xpool_tracks(self, tower: str, seg: Tensor, mask: Optional[Tensor], bufs: tuple):
+        """The per-track operands of one chunk of tracks, seg [n, S, D] (a view is fine) -> K, U [n, S, D]: LayerNorm 1, then the k | v
+        Linear.  hoist: out_proj applied to U here, once per segment (it commutes with the softmax-weighted sum, whose rows sum to 1).
+        fold: U is [n, S, 2D], out_proj(u) | W'' out_proj(u) with W'' the folded LayerNorm-2 Linear (load_state_dict, `linf`)."""
+        P = self.P
+        n, S, D = seg.shape
+        _, hoist, fold, s1, kbuf, ubuf, u2 = bufs
+        rows = n * S
+        skip = mask.reshape(-1) if mask is not None else None           # masked segments are never attended to
+        ops.layernorm(seg, P[tower + ".ln1.g"], P[tower + ".ln1.b"], out=s1[:rows], row_skip=skip)   # [n,S,D] view -> compact rows
+        ops.linear(s1[:rows], P[tower + ".kv.w"], P[tower + ".kv.b"], tile_skip_mask=skip,
+                   segs=[Seg(out=kbuf, col_begin=0), Seg(out=ubuf, col_begin=D)])
+        if not hoist:
+            return kbuf[:rows].view(n, S, D), ubuf[:rows].view(n, S, D)
+        ops.linear(ubuf[:rows], P[tower + ".out.w"], P[tower + ".out.b"], out=u2[:rows, :D], tile_skip_mask=skip)
+        if fold:
+            ops.linear(u2[:rows, :D], P[tower + ".linf.w"], None, out=u2[:rows, D:], tile_skip_mask=skip)
+        return kbuf[:rows].view(n, S, D), u2[:rows].view(n, S, -1)
+
+    def _xpool_chunks(self, tower: str, seg: Tensor, seg_mask: Optional[Tensor], bufs: tuple, pairs) -> None:
+        """The walk over the tracks, bufs' cm at a time: their operands, then the path's per-pair stage pairs(m0, n, K, U, mask)."""
+        Nm, cm = seg.shape[0], bufs[0]
+        for m0 in range(0, Nm, cm):
+            n = min(cm, Nm - m0)
+            mask = seg_mask[m0:m0 + n] if seg_mask is not None else None
+            K, U = self._xpool_tracks(tower, seg[m0:m0 + n], mask, bufs)
+            pairs(m0, n, K, U, mask)
+
     def xpool_sims(self, video: Tensor, seg: Tensor, seg_mask: Tensor, sims_out: Optional[Tensor] = None,
                    pooled_out: Optional[Tensor] = None, chunk_m: Optional[int] = None, tower: str = "xa") -> Tensor:
         """sims[n, m] = <v_n/|v_n|, XA(v, seg, mask)[m, n]/|.|>: reference modules/transformer.py:156-180 +
@@ -451,128 +512,77 @@ class MadeEngine:
         Nm, S, _ = seg.shape
         if sims_out is None:
             sims_out = torch.empty(Nv, Nm, device=dev, dtype=torch.float32)
-        chunk_m_given = chunk_m is not None
-        if chunk_m is None:
-            budget = 6 << 30                                             # bytes of per-pair intermediates per chunk
-            per_m = Nv * 3 * D * tc.itemsize + 4 * S * D * tc.itemsize
-            chunk_m = max(1, min(Nm, budget // max(per_m, 1)))
+        path = self._xpool_path(Nv, S, D, pooled_out)
         v1 = ops.layernorm(video, P[tower + ".ln1.g"], P[tower + ".ln1.b"], out_dtype=tc)
         q = ops.linear(v1, P[tower + ".q.w"], P[tower + ".q.b"])
-        hoist = Nv > S          # out_proj commutes with the softmax-weighted sum (rows sum to 1): apply it to U instead
-        if tc == torch.bfloat16 and D == 256 and pooled_out is None and Nv >= 256:
+        scale = 1.0 / math.sqrt(D)
+        ln2, ln3 = [(P[tower + f".ln{i}.g"], P[tower + f".ln{i}.b"]) for i in (2, 3)]
+        E = lambda *shape, dtype=tc: torch.empty(shape, device=dev, dtype=dtype)
+        track_bufs = lambda cm, hoist=True, fold=False: self._xpool_track_bufs(cm, S, D, hoist, fold)
+        if path in ("sims", "fused"):
             # retrieval scale: the per-pair chain (attention -> LayerNorm2 -> Linear + residual -> LayerNorm3 -> cosine) in one
             # kernel, nothing per pair ever written to HBM (made_xpool_fused); the per-track K / U projections stay GEMMs
             vn = ops.l2norm_rows(video)
             cm = min(Nm, max(1, (2 << 30) // (3 * S * D * tc.itemsize)), 65535)
-            if S <= 96 and _lib.variant_env("MADE_XPOOL_SIMS", "1") != "0":
+            bufs = track_bufs(cm, fold=path == "sims")
+            if path == "sims":
                 # round 4: the per-pair Linear moved onto the values.  W'' o = sum_s p_s (W'' u_s), so u''_s = W'' u_s is made once per
                 # segment (one more GEMM over the tracks) and the pair costs a second P.V product (2 S D flops) instead of the Linear (2 D^2):
                 # 2.2x fewer flops per pair at S = 96.  The default for tracks of at most 96 segments (made_xpool_sims: 52.5 ms against
                 # made_xpool_fused's 60.7-61.3 on the 53 k x 4 k set); MADE_XPOOL_SIMS=0: the fused kernel
-                s1 = torch.empty(cm * S, D, device=dev, dtype=tc)
-                kbuf = torch.empty(cm * S, D, device=dev, dtype=tc)
-                ubuf = torch.empty(cm * S, D, device=dev, dtype=tc)
-                uu = torch.empty(cm * S, 2 * D, device=dev, dtype=tc)
-                xws = torch.empty(ops.xpool_sims_ws_bytes(Nv, cm, D), device=dev, dtype=torch.uint8)
-                for m0 in range(0, Nm, cm):
-                    n = min(cm, Nm - m0)
-                    skip = seg_mask[m0:m0 + n].reshape(-1) if seg_mask is not None else None
-                    ops.layernorm(seg[m0:m0 + n], P[tower + ".ln1.g"], P[tower + ".ln1.b"], out=s1[:n * S], row_skip=skip)
-                    ops.linear(s1[:n * S], P[tower + ".kv.w"], P[tower + ".kv.b"], tile_skip_mask=skip,
-                               segs=[Seg(out=kbuf, col_begin=0), Seg(out=ubuf, col_begin=D)])
-                    ops.linear(ubuf[:n * S], P[tower + ".out.w"], P[tower + ".out.b"], out=uu[:n * S, :D], tile_skip_mask=skip)
-                    ops.linear(uu[:n * S, :D], P[tower + ".linf.w"], None, out=uu[:n * S, D:], tile_skip_mask=skip)
-                    ops.xpool_sims(q, kbuf[:n * S].view(n, S, D), uu[:n * S].view(n, S, 2 * D),
-                                   seg_mask[m0:m0 + n] if seg_mask is not None else None, P[tower + ".linf.b"], P[tower + ".linf.rs"],
-                                   (P[tower + ".ln3.g"], P[tower + ".ln3.b"]), vn, sims_out[:, m0:m0 + n], scale=1.0 / math.sqrt(D),
+                xws = E(ops.xpool_sims_ws_bytes(Nv, cm, D), dtype=torch.uint8)
+
+                def pairs(m0, n, K, UU, mask):
+                    ops.xpool_sims(q, K, UU, mask, P[tower + ".linf.b"], P[tower + ".linf.rs"], ln3, vn, sims_out[:, m0:m0 + n], scale=scale,
                                    ws=xws, prepare_ws=(m0 == 0))
-                return sims_out
-            s1 = torch.empty(cm * S, D, device=dev, dtype=tc)
-            kbuf = torch.empty(cm * S, D, device=dev, dtype=tc)
-            ubuf = torch.empty(cm * S, D, device=dev, dtype=tc)
-            ubuf2 = torch.empty(cm * S, D, device=dev, dtype=tc)
-            xws = torch.empty(ops.xpool_fused_ws_floats(Nv, cm, D), device=dev, dtype=torch.float32)
-            for m0 in range(0, Nm, cm):
-                n = min(cm, Nm - m0)
-                skip = seg_mask[m0:m0 + n].reshape(-1) if seg_mask is not None else None
-                ops.layernorm(seg[m0:m0 + n], P[tower + ".ln1.g"], P[tower + ".ln1.b"], out=s1[:n * S], row_skip=skip)
-                ops.linear(s1[:n * S], P[tower + ".kv.w"], P[tower + ".kv.b"], tile_skip_mask=skip,
-                           segs=[Seg(out=kbuf, col_begin=0), Seg(out=ubuf, col_begin=D)])
-                ops.linear(ubuf[:n * S], P[tower + ".out.w"], P[tower + ".out.b"], out=ubuf2[:n * S], tile_skip_mask=skip)
-                ops.xpool_fused(q, kbuf[:n * S].view(n, S, D), ubuf2[:n * S].view(n, S, D),
-                                seg_mask[m0:m0 + n] if seg_mask is not None else None,
-                                (P[tower + ".ln2.g"], P[tower + ".ln2.b"]), P[tower + ".lin.w"], P[tower + ".lin.b"],
-                                (P[tower + ".ln3.g"], P[tower + ".ln3.b"]), vn, sims_out[:, m0:m0 + n], scale=1.0 / math.sqrt(D),
-                                ws=xws, prepare_ws=(m0 == 0))
-            return sims_out
-        if tc == torch.bfloat16 and D in (256, 512) and S <= 512 and pooled_out is None and Nv >= 256 and _lib.variant_env("MADE_XPOOL_ATTN", "1") != "0":
+            else:
+                xws = E(ops.xpool_fused_ws_floats(Nv, cm, D), dtype=torch.float32)
+
+                def pairs(m0, n, K, U, mask):
+                    ops.xpool_fused(q, K, U, mask, ln2, P[tower + ".lin.w"], P[tower + ".lin.b"], ln3, vn, sims_out[:, m0:m0 + n], scale=scale,
+                                    ws=xws, prepare_ws=(m0 == 0))
+        elif path == "attention":
             # retrieval scale at the widths / lengths made_xpool_fused does not serve (D = 512, or more than its segments): the attention
             # as ONE two-pass kernel per chunk of tracks (made_xpool_attention: scores of a whole track in LDS, the normalisation of
             # LayerNorm2 in its tail), then the folded Linear and LayerNorm3 + cosine.  Chunks of about 1 GB of per-pair rows per tensor:
             # measured (tools/retr512_breakdown.py, 8192 x 512 x S 512), chunks small enough to stay in the Infinity Cache lose more to
             # short launches (13.8 ms per pass at 12 tracks per chunk) than they gain (11.45 ms at 96).
-            cm = chunk_m if chunk_m is not None and chunk_m_given else max(1, min(Nm, (1 << 30) // max(Nv * D * tc.itemsize, 1)))
-            s1 = torch.empty(cm * S, D, device=dev, dtype=tc)
-            kbuf = torch.empty(cm * S, D, device=dev, dtype=tc)
-            ubuf = torch.empty(cm * S, D, device=dev, dtype=tc)
-            ubuf2 = torch.empty(cm * S, D, device=dev, dtype=tc)
-            xh = torch.empty(cm * Nv, D, device=dev, dtype=tc)
-            y = torch.empty(cm * Nv, D, device=dev, dtype=tc)
-            iws = torch.empty(cm * 32, device=dev, dtype=torch.int32)
-            for m0 in range(0, Nm, cm):
-                n = min(cm, Nm - m0)
-                skip = seg_mask[m0:m0 + n].reshape(-1) if seg_mask is not None else None
-                ops.layernorm(seg[m0:m0 + n], P[tower + ".ln1.g"], P[tower + ".ln1.b"], out=s1[:n * S], row_skip=skip)
-                ops.linear(s1[:n * S], P[tower + ".kv.w"], P[tower + ".kv.b"], tile_skip_mask=skip,
-                           segs=[Seg(out=kbuf, col_begin=0), Seg(out=ubuf, col_begin=D)])
-                ops.linear(ubuf[:n * S], P[tower + ".out.w"], P[tower + ".out.b"], out=ubuf2[:n * S], tile_skip_mask=skip)
-                ops.xpool_attention(q, kbuf[:n * S].view(n, S, D), ubuf2[:n * S].view(n, S, D),
-                                    seg_mask[m0:m0 + n] if seg_mask is not None else None, xh[:n * Nv].view(n, Nv, D),
-                                    scale=1.0 / math.sqrt(D), ws=iws)
+            cm = chunk_m if chunk_m is not None else max(1, min(Nm, (1 << 30) // max(Nv * D * tc.itemsize, 1)))
+            bufs = track_bufs(cm)
+            xh, y, iws = E(cm * Nv, D), E(cm * Nv, D), E(cm * 32, dtype=torch.int32)
+
+            def pairs(m0, n, K, U, mask):
+                ops.xpool_attention(q, K, U, mask, xh[:n * Nv].view(n, Nv, D), scale=scale, ws=iws)
                 ops.linear(xh[:n * Nv], P[tower + ".linf.w"], P[tower + ".linf.b"], out=y[:n * Nv])
-                ops.xpool_tail(y[:n * Nv], P[tower + ".ln3.g"], P[tower + ".ln3.b"], video, sims_out[:, m0:m0 + n], n, Nv)
-            return sims_out
-        cm = min(chunk_m, Nm)
-        s1 = torch.empty(cm * S, D, device=dev, dtype=tc)
-        kbuf = torch.empty(cm * S, D, device=dev, dtype=tc)
-        ubuf = torch.empty(cm * S, D, device=dev, dtype=tc)
-        ubuf2 = torch.empty(cm * S, D, device=dev, dtype=tc) if hoist else None
-        o = torch.empty(cm * Nv, D, device=dev, dtype=tc)
-        o2 = torch.empty(cm * Nv, D, device=dev, dtype=tc)
-        o3 = torch.empty(cm * Nv, D, device=dev, dtype=tc)
-        scale = 1.0 / math.sqrt(D)
-        xib_ws = None
-        for m0 in range(0, Nm, cm):
-            n = min(cm, Nm - m0)
-            skip = seg_mask[m0:m0 + n].reshape(-1) if seg_mask is not None else None    # masked segments are never attended to
-            ops.layernorm(seg[m0:m0 + n], P[tower + ".ln1.g"], P[tower + ".ln1.b"], out=s1[:n * S], row_skip=skip)   # [n,S,D] view -> compact rows
-            ops.linear(s1[:n * S], P[tower + ".kv.w"], P[tower + ".kv.b"], tile_skip_mask=skip,
-                       segs=[Seg(out=kbuf, col_begin=0), Seg(out=ubuf, col_begin=D)])
-            u = ubuf
-            if hoist:
-                u = ops.linear(ubuf[:n * S], P[tower + ".out.w"], P[tower + ".out.b"], out=ubuf2[:n * S], tile_skip_mask=skip)
-            # all videos attend to each track's segments: softmax over segments, scores never leave the chip
-            if tc == torch.bfloat16 and Nv <= 64 and S <= 512 and S * D >= 65536 and D in (256, 512) and _lib.variant_env("MADE_XPOOL_INBATCH", "1") != "0":
-                # the in-batch shape (round 4): scores per (track, 128 segments), P.V per (track, 128 columns), bf16 probabilities between them
-                if xib_ws is None:
-                    xib_ws = torch.empty(ops.xpool_inbatch_ws_bytes(cm, S), device=dev, dtype=torch.uint8)      # (no counters in it since the one-launch form went: nothing to clear)
-                ops.xpool_inbatch(q, kbuf[:n * S].view(n, S, D), u[:n * S].view(n, S, D), seg_mask[m0:m0 + n] if seg_mask is not None else None,
-                                  o[:n * Nv].view(n, Nv, D), scale=scale, ws=xib_ws)
-            else:
-                ops.attention_wide(q.view(1, Nv, 1, D), kbuf[:n * S].view(n, S, D), u[:n * S].view(n, S, D),
-                                   o[:n * Nv].view(n, Nv, 1, D), scale=scale,
-                                   key_mask=seg_mask[m0:m0 + n] if seg_mask is not None else None, shared_q=True,
-                                   n_split=1)   # (splitting the keys over workgroups + a merge launch is no faster here and costs the other stream CUs:
-                                   # 1.2 % of the eval throughput with two batches in flight)
-            rows = n * Nv
-            if hoist:
-                a2 = o[:rows]
-            else:
-                a2 = ops.linear(o[:rows], P[tower + ".out.w"], P[tower + ".out.b"], out=o2[:rows])
-            a3 = ops.layernorm(a2, P[tower + ".ln2.g"], P[tower + ".ln2.b"], out=o3[:rows])
-            y = ops.linear(a3, P[tower + ".lin.w"], P[tower + ".lin.b"], R=a3, out=o2[:rows] if hoist else o[:rows])
-            ops.xpool_tail(y, P[tower + ".ln3.g"], P[tower + ".ln3.b"], video, sims_out[:, m0:m0 + n], n, Nv,
-                           pooled_out=pooled_out[m0 * Nv:(m0 + n) * Nv] if pooled_out is not None else None)
+                ops.xpool_tail(y[:n * Nv], ln3[0], ln3[1], video, sims_out[:, m0:m0 + n], n, Nv)
+        else:
+            if chunk_m is None:
+                budget = 6 << 30                                         # bytes of per-pair intermediates per chunk
+                per_m = Nv * 3 * D * tc.itemsize + 4 * S * D * tc.itemsize
+                chunk_m = max(1, min(Nm, budget // max(per_m, 1)))
+            cm = min(chunk_m, Nm)
+            hoist = Nv > S
+            bufs = track_bufs(cm, hoist)
+            o, o2, o3 = E(cm * Nv, D), E(cm * Nv, D), E(cm * Nv, D)
+            # (no counters in the in-batch workspace since the one-launch form went: nothing to clear)
+            xib_ws = E(ops.xpool_inbatch_ws_bytes(cm, S), dtype=torch.uint8) if path == "inbatch" else None
+
+            def pairs(m0, n, K, U, mask):
+                # all videos attend to each track's segments: softmax over segments, scores never leave the chip
+                rows = n * Nv
+                if path == "inbatch":
+                    # the in-batch shape (round 4): scores per (track, 128 segments), P.V per (track, 128 columns), bf16 probabilities between them
+                    ops.xpool_inbatch(q, K, U, mask, o[:rows].view(n, Nv, D), scale=scale, ws=xib_ws)
+                else:
+                    # n_split=1: splitting the keys over workgroups + a merge launch is no faster here and costs the other stream CUs
+                    # (1.2 % of the eval throughput with two batches in flight)
+                    ops.attention_wide(q.view(1, Nv, 1, D), K, U, o[:rows].view(n, Nv, 1, D), scale=scale, key_mask=mask, shared_q=True, n_split=1)
+                a2 = o[:rows] if hoist else ops.linear(o[:rows], P[tower + ".out.w"], P[tower + ".out.b"], out=o2[:rows])
+                a3 = ops.layernorm(a2, ln2[0], ln2[1], out=o3[:rows])
+                y = ops.linear(a3, P[tower + ".lin.w"], P[tower + ".lin.b"], R=a3, out=o2[:rows] if hoist else o[:rows])
+                ops.xpool_tail(y, ln3[0], ln3[1], video, sims_out[:, m0:m0 + n], n, Nv,
+                               pooled_out=pooled_out[m0 * Nv:(m0 + n) * Nv] if pooled_out is not None else None)
+        self._xpool_chunks(tower, seg, seg_mask, bufs, pairs)
         return sims_out
 
     def xpool_pair_sims(self, video: Tensor, seg: Tensor, seg_mask: Optional[Tensor], start: Tensor, vidx: Tensor, max_count: int = 0,
@@ -595,16 +605,8 @@ class MadeEngine:
             v1 = ops.layernorm(video, P[tower + ".ln1.g"], P[tower + ".ln1.b"], out_dtype=tc)
             cache["q"] = ops.linear(v1, P[tower + ".q.w"], P[tower + ".q.b"])
             cache["vn"] = ops.l2norm_rows(video)
-        skip = seg_mask.reshape(-1) if seg_mask is not None else None
-        s1 = torch.empty(U * S, D, device=dev, dtype=tc)
-        kbuf = torch.empty(U * S, D, device=dev, dtype=tc)
-        ubuf = torch.empty(U * S, D, device=dev, dtype=tc)
-        uu = torch.empty(U * S, 2 * D, device=dev, dtype=tc)
-        ops.layernorm(seg, P[tower + ".ln1.g"], P[tower + ".ln1.b"], out=s1, row_skip=skip)
-        ops.linear(s1, P[tower + ".kv.w"], P[tower + ".kv.b"], tile_skip_mask=skip, segs=[Seg(out=kbuf, col_begin=0), Seg(out=ubuf, col_begin=D)])
-        ops.linear(ubuf, P[tower + ".out.w"], P[tower + ".out.b"], out=uu[:, :D], tile_skip_mask=skip)
-        ops.linear(uu[:, :D], P[tower + ".linf.w"], None, out=uu[:, D:], tile_skip_mask=skip)
-        return ops.xpool_sims_pairs(cache["q"], kbuf.view(U, S, D), uu.view(U, S, 2 * D), seg_mask, P[tower + ".linf.b"], P[tower + ".linf.rs"],
+        K, UU = self._xpool_tracks(tower, seg, seg_mask, self._xpool_track_bufs(U, S, D, hoist=True, fold=True))
+        return ops.xpool_sims_pairs(cache["q"], K, UU, seg_mask, P[tower + ".linf.b"], P[tower + ".linf.rs"],
                                     (P[tower + ".ln3.g"], P[tower + ".ln3.b"]), cache["vn"], start, vidx, scale=1.0 / math.sqrt(D),
                                     max_count=max_count)
 
@@ -646,245 +648,294 @@ class MadeEngine:
     def forward(self, frame_feats: Tensor, segment_feats: Tensor, frame_masks: Tensor, segment_masks: Tensor,
                 spans_target: Tensor, with_losses: bool = True, want_pooled: bool = False,
                 v_duration: Optional[Tensor] = None) -> Dict[str, Tensor]:
-        c, P = self.cfg, self.P
+        """reference model/model_Uni.py:177-322 in eval mode.  This function is the schedule only -- which stage runs on which stream and
+        who waits for whom (its tail, shared with `localize_pairs`, is `_after_fusion`); the launches are the stages'."""
+        c = self.cfg
         self._set_products()
-        regression = "regression" in c.mml_localization
         if c.predict_center == 1 and v_duration is None:
             raise ValueError("predict_center=1 needs v_duration (reference model/model_Uni.py:280-282)")
         B, Tv, _ = frame_feats.shape
         Ta = segment_feats.shape[1]
-        concat = "concat" in c.mml_fusion
-        D, L, Q, nd = c.D, (Tv + Ta if concat else Ta), c.num_moment_queries, c.detr_dec_layers
-        H = c.detr_nheads
         ws = self._buffers(B, Tv, Ta)
         fm, sm = frame_masks.contiguous(), segment_masks.contiguous()
+        concat = "concat" in c.mml_fusion
+        # the temporal encoders (K1-K4) write straight into the fused DETR input
+        frame, seg = (ws["fus"][:, :Tv], ws["fus"][:, Tv:]) if concat else (ws["frame_buf"], ws["seg_buf"])
 
-        # ---- temporal encoders (K1-K4) write straight into the fused DETR input.  The video branch (B*T_v rows: every
-        # launch far smaller than the chip) runs on a second HIP stream beside the audio branch and joins before X-Pool.
-        cur = torch.cuda.current_stream()
-        side = self._side_stream()
-        fus, fus_mask = ws["fus"], ws["fus_mask"]
+        # The video branch (B*T_v rows: every launch far smaller than the chip) runs on a second HIP stream beside the audio branch and
+        # joins before X-Pool.  The audio branch (the launches that fill the chip) is enqueued first, the video branch (17 launches of
+        # at most a few hundred workgroups) second: eager launching is 1-3 % faster this way, graph replay unchanged.
+        cur, side = torch.cuda.current_stream(), self._side_stream()
         side.wait_stream(cur)
-        # The audio branch (the launches that fill the chip) is enqueued first, the video branch (17 launches of at most a few
-        # hundred workgroups) second on the side stream: eager launching is 1-3 % faster this way, graph replay unchanged.
-        self._encode(segment_feats.contiguous(), sm, "audio", ws, Tv, rows=ops.row_index(sm, out=ws["rows_a"]),
-                     order=ops.batch_order(sm, out=ws["order_a"]))
+        self._encode(segment_feats.contiguous(), sm, "audio", ws, Tv, *self._row_lists(sm, ws, "a"))
         with torch.cuda.stream(side):
-            # the DETR mask and its sine position embedding depend on the masks only: off the critical path
-            ops.concat_cols(fm if concat else None, sm, fus_mask)
-            pos = ops.sine_pe(fus_mask, P["dim_t"], out=ws["pos"])
-            rows_f = ops.row_index(fus_mask, out=ws["rows_f"])
-            order_f = ops.batch_order(fus_mask, out=ws["order_f"])       # attention workgroups: longest sample first
-            self._encode(frame_feats.contiguous(), fm, "video", ws, 0, rows=ops.row_index(fm, out=ws["rows_v"]),
-                         order=ops.batch_order(fm, out=ws["order_v"]))
+            lists = self._fused_lists(ws, fm, sm)                # (they depend on the masks only: off the critical path)
+            self._encode(frame_feats.contiguous(), fm, "video", ws, 0, *self._row_lists(fm, ws, "v"))
         cur.wait_stream(side)
-        if concat:
-            frame, seg = fus[:, :Tv], fus[:, Tv:]
-        else:
-            frame, seg = ws["frame_buf"], ws["seg_buf"]
+        k = _Call(ws, B, fm, sm, frame, seg, ws["video"], ws["music"], *lists, v_duration)
+        if not concat:
             self._ca_fusion(ws, frame, seg, fm, sm, B, Tv, Ta)
-        video, music = ws["video"], ws["music"]
-        out: Dict[str, Tensor] = dict(video_feats=video, music_feats=music, frame_feats=frame, segment_feats=seg)
+        out: Dict[str, Tensor] = dict(video_feats=k.video, music_feats=k.music, frame_feats=frame, segment_feats=seg)
 
-        # ---- X-Pool similarities + retrieval loss (K5-K7): independent of the DETR branch, so they run on the side stream
-        # beside the (latency-bound) decoder and join at the end of the step
+        # X-Pool similarities + retrieval loss (K5-K7): independent of the DETR branch, so they run on the side stream beside the
+        # (latency-bound) decoder and join at the end of the step
         side.wait_stream(cur)
         dec_early = None
         with torch.cuda.stream(side):
-            if not regression and c.moment_query_type != "xpool" and not c.detr_pre_norm:
+            if "regression" not in c.mml_localization and c.moment_query_type != "xpool" and not c.detr_pre_norm:
                 # The query side of decoder layer 0 (initial queries -> self-attention block -> the folded cross-attention
                 # query) reads nothing the DETR encoder produces: it runs here, beside the encoder, instead of at the head of
                 # the decoder's chain of dependent launches.
-                if self._fused_decoder():
-                    self._dec_fused_query_side(ws, 0, self._dec_first_rows(ws, video, music))
-                else:
-                    self._decoder_queries(ws, video, music, None, B)
-                    self._decoder_query_side(ws, 0, B)
+                self._dec_open(k, None)
                 dec_early = torch.cuda.Event()
                 dec_early.record(side)
             need_pooled = want_pooled or c.moment_query_type == "xpool" or c.vmr_loss == "dual_single_feature_fuse"
-            pooled = torch.empty(B * B, D, device=self.device, dtype=torch.float32) if (need_pooled and "music" in c.vmr_fusion) else None
-            if "music" in c.vmr_fusion:
-                self.xpool_sims(video, seg, sm if c.fusion_mask == 1 else None, sims_out=ws["sims_single"], pooled_out=pooled)
-            if "video" in c.vmr_fusion:
-                # music-guided video pooling (reference model_Uni.py:203, metrics.py:26-41): the same block with the roles
-                # swapped gives sims[m, v]; the reference adds its transpose to the music-pooling similarities (:247-251)
-                vp = self.xpool_sims(music, frame, fm if c.fusion_mask == 1 else None, sims_out=ws["sims_vp_t"], tower="xav")
-                out["sims_video_pooling"] = vp.t()
-                if "music" in c.vmr_fusion:
-                    ws["sims_single"].add_(vp.t())
-                else:
-                    ws["sims_single"].copy_(vp.t())
-            self.dual_sims(video, music, out=ws["sims_dual"])
-            if with_losses:
-                self._retrieval_loss(ws, video, music, pooled=pooled)
-        out.update(sims_single=ws["sims_single"], sims_dual=ws["sims_dual"])
+            pooled = torch.empty(B * B, c.D, device=self.device, dtype=torch.float32) if (need_pooled and "music" in c.vmr_fusion) else None
+            out.update(self._retrieval(k, pooled, with_losses))
         if pooled is not None:
-            out["music_feats_pooled"] = pooled.view(B, B, D)
-        if with_losses:
-            out["retrieval_loss"] = ws["ret_loss"]
+            out["music_feats_pooled"] = pooled.view(B, B, c.D)
+        return self._after_fusion(k, out, cur, side, dec_early=dec_early, pooled=pooled, spans_target=spans_target, with_losses=with_losses)
 
-        return self._localize(ws, out, B, Tv, Ta, fm, sm, video, music, frame, pos, rows_f, order_f, dec_early, pooled, spans_target,
-                              v_duration, with_losses, cur, side)
-
-    def _localize(self, ws, out: Dict[str, Tensor], B: int, Tv: int, Ta: int, fm: Tensor, sm: Tensor, video: Tensor, music: Tensor,
-                  frame: Tensor, pos: Tensor, rows_f, order_f: Tensor, dec_early, pooled: Optional[Tensor], spans_target: Optional[Tensor],
-                  v_duration: Optional[Tensor], with_losses: bool, cur, side) -> Dict[str, Tensor]:
-        """Everything after the towers and the fusion (K8-K14): DETR encoder, decoder, heads and (with_losses) matcher + criterion,
-        on the fused input ws["fus"] / ws["fus_mask"].  Shared by `forward` and `localize_pairs`.  dec_early: the event of decoder
-        layer 0's query side when it already ran beside the encoder (forward's side stream), else None."""
-        c, P = self.cfg, self.P
+    def _after_fusion(self, k: "_Call", out: Dict[str, Tensor], cur, side, *, dec_early=None, pooled: Optional[Tensor] = None,
+                      spans_target: Optional[Tensor] = None, with_losses: bool = False) -> Dict[str, Tensor]:
+        """The schedule after the towers and the fusion (K8-K14), on the fused input ws["fus"] / ws["fus_mask"]: `forward`'s tail, and a
+        batch of `localize_pairs` (no second stream there: side is cur).  dec_early: the event of decoder layer 0's query side when it
+        already ran beside the encoder (forward's side stream), else None."""
+        c = self.cfg
         regression = "regression" in c.mml_localization
-        concat = "concat" in c.mml_fusion
-        D, L, Q, nd = c.D, (Tv + Ta if concat else Ta), c.num_moment_queries, c.detr_dec_layers
-        H = c.detr_nheads
-        fus, fus_mask = ws["fus"], ws["fus_mask"]
-
-        # ---- DETR encoder (K8, K9)
-        rows = B * L
-        src = fus.view(rows, D)
-        pos2 = pos.view(rows, D)
-        srcpos = ws["srcpos"]
-        fskip = fus_mask.view(-1)             # padded tokens of the fused sequence: skipped everywhere below
-        enc_rows, order_e = rows_f, order_f
+        out["memory"] = memory = self._detr_encoder(k, all_rows=regression)
         if regression:
-            # the regression head sums the memory over ALL positions, padded ones included (reference model_Uni.py:229), so
-            # here the encoder computes them too
-            fskip = enc_rows = None
-        if c.detr_pre_norm:
-            # reference music_detr/transformer.py:170-189 (forward_pre): the residual stream x is never normalised inside a layer; norm 1 feeds
-            # the attention (q = k = LN1(x) + pos, v = LN1(x)), norm 2 the FFN, and one more norm follows the last layer (:33-35,107-108)
-            x = src
-            for l in range(c.detr_enc_layers):
-                p = f"detr_transformer.encoder.layers.{l}"
-                n1 = ws["x2"][:rows]
-                ops.layernorm_add(x, P[p + ".ln1.g"], P[p + ".ln1.b"], pos2, n1, srcpos, row_skip=fskip)
-                att = self._mha_block(n1, B, L, P[p + ".in.w"], P[p + ".in.b"], fus_mask, ws, H, pos=srcpos, skip=fskip, rows=enc_rows, order=order_e)
-                xa = ops.linear(att, P[p + ".out.w"], P[p + ".out.b"], R=x, out=ws["x1"][:rows], rows=enc_rows)
-                n2 = ops.layernorm(xa, P[p + ".ln2.g"], P[p + ".ln2.b"], out=ws["x2"][:rows], row_skip=fskip)
-                h = ops.linear(n2, P[p + ".ff1.w"], P[p + ".ff1.b"], act=ops.ACT_RELU, out=ws["ffn"][:rows, :c.detr_dim_feedforward], rows=enc_rows)
-                x = ops.linear(h, P[p + ".ff2.w"], P[p + ".ff2.b"], R=xa, out=ws["x0"][:rows], rows=enc_rows)
-            if c.detr_enc_layers > 0:
-                src = ws["x3"][:rows]
-                ops.layernorm_add(x, P["enc.norm.g"], P["enc.norm.b"], pos2, src, srcpos, row_skip=fskip)
+            out.update(self._regression_head(k, memory, spans_target, with_losses))
+        else:
+            if dec_early is not None:
+                cur.wait_event(dec_early)                    # layer 0's query side was computed beside the encoder
             else:
-                ops.layernorm_add(src, None, None, pos2, None, srcpos, row_skip=fskip)
-        else:
-            ops.layernorm_add(src, None, None, pos2, None, srcpos, row_skip=fskip)      # layer 0: src + pos (no norm)
-        for l in range(0 if c.detr_pre_norm else c.detr_enc_layers):
-            p = f"detr_transformer.encoder.layers.{l}"
-            att = self._mha_block(src, B, L, P[p + ".in.w"], P[p + ".in.b"], fus_mask, ws, H, pos=srcpos, skip=fskip, rows=enc_rows, order=order_e)
-            x = ops.linear(att, P[p + ".out.w"], P[p + ".out.b"], R=src, out=ws["x1"][:rows], rows=enc_rows)
-            s1 = ops.layernorm(x, P[p + ".ln1.g"], P[p + ".ln1.b"], out=ws["x2"][:rows], row_skip=fskip)
-            h = ops.linear(s1, P[p + ".ff1.w"], P[p + ".ff1.b"], act=ops.ACT_RELU, out=ws["ffn"][:rows, :c.detr_dim_feedforward], rows=enc_rows)
-            x = ops.linear(h, P[p + ".ff2.w"], P[p + ".ff2.b"], R=s1, out=ws["x1"][:rows], rows=enc_rows)
-            # the norm that produces the next src also emits src + pos (next layer's q/k input, decoder's keys)
-            src = ws["x3" if l % 2 == 0 else "x0"][:rows]
-            ops.layernorm_add(x, P[p + ".ln2.g"], P[p + ".ln2.b"], pos2, src, srcpos, row_skip=fskip)
-        memory = src
-        out["memory"] = memory.view(B, L, D)
-        if regression:
-            return self._regression_head(out, ws, memory.view(B, L, D), fus_mask, spans_target, v_duration, with_losses, cur, side)
+                if c.moment_query_type == "xpool":           # reference model_Uni.py:222-223: the track's pooled vectors, averaged
+                    cur.wait_stream(side)                    # over the videos of the batch (X-Pool branch first)
+                self._dec_open(k, pooled)
+            out.update(self._decoder(k, memory))
+            out.update(self._heads(k))
+            if with_losses:
+                out.update(self._criterion(k, spans_target))
+        cur.wait_stream(side)
+        return out
 
-        # ---- DETR decoder (K10).  Cross-attention runs in memory space (made_attention_wide): no projection of
-        # the L memory rows at all; self-attention collapses to one folded Linear when there is a single query.
-        mem3, mempos3 = memory.view(B, L, D), srcpos.view(B, L, D)
-        tgt = ws["tgt"]
-        if dec_early is not None:
-            cur.wait_event(dec_early)                                    # layer 0's query side was computed beside the encoder
-        else:
-            if c.moment_query_type == "xpool":                           # reference model_Uni.py:222-223: the track's pooled vectors,
-                cur.wait_stream(side)                                    # averaged over the videos of the batch (X-Pool branch first)
-            if not self._fused_decoder():
-                self._decoder_queries(ws, video, music, pooled, B)
-        qp = P["query_embed"]
-        hs = ws["hs"]
-        ca_scale = 1.0 / math.sqrt(D // H)
-        dq_all, dpool = ws["dq_all"], ws["dpool"]
-        dq4 = dq_all.view(B, Q, H, D).permute(0, 2, 1, 3)               # [B, H, Q, D] view: row (b,q), head-major columns
-        dp4 = dpool.view(B, Q, H, D).permute(0, 2, 1, 3)
+    # ------------------------------------------------------------------ stages (they touch no stream)
+    def _row_lists(self, mask: Tensor, ws=None, tag: str = "") -> tuple:
+        """(rows, order) of a token mask [B, T]: the valid-row list the GEMMs gather by, and the samples by descending length (attention
+        workgroups: longest sample first).  Into ws["rows_" + tag] / ws["order_" + tag] when a workspace is given."""
+        out_r, out_o = (ws["rows_" + tag], ws["order_" + tag]) if ws is not None else (None, None)
+        return ops.row_index(mask, out=out_r), ops.batch_order(mask, out=out_o)
+
+    def _fused_lists(self, ws, fm: Tensor, sm: Tensor) -> tuple:
+        """The DETR token mask ws["fus_mask"], then (pos, rows_f, order_f): its sine position embedding and its index lists."""
+        fus_mask = ops.concat_cols(fm if "concat" in self.cfg.mml_fusion else None, sm, ws["fus_mask"])
+        pos = ops.sine_pe(fus_mask, self.P["dim_t"], out=ws["pos"])
+        return (pos, *self._row_lists(fus_mask, ws, "f"))
+
+    def _retrieval(self, k: "_Call", pooled: Optional[Tensor], with_losses: bool) -> Dict[str, Tensor]:
+        """Retrieval branch: the X-Pool tower(s), the dual cosine similarities, (with_losses) the retrieval loss.  Returns its outputs."""
+        c, ws = self.cfg, k.ws
+        out: Dict[str, Tensor] = {}
+        if "music" in c.vmr_fusion:
+            self.xpool_sims(k.video, k.seg, k.sm if c.fusion_mask == 1 else None, sims_out=ws["sims_single"], pooled_out=pooled)
+        if "video" in c.vmr_fusion:
+            # music-guided video pooling (reference model_Uni.py:203, metrics.py:26-41): the same block with the roles
+            # swapped gives sims[m, v]; the reference adds its transpose to the music-pooling similarities (:247-251)
+            vp = self.xpool_sims(k.music, k.frame, k.fm if c.fusion_mask == 1 else None, sims_out=ws["sims_vp_t"], tower="xav")
+            out["sims_video_pooling"] = vp.t()
+            if "music" in c.vmr_fusion:
+                ws["sims_single"].add_(vp.t())
+            else:
+                ws["sims_single"].copy_(vp.t())
+        self.dual_sims(k.video, k.music, out=ws["sims_dual"])
+        out.update(sims_single=ws["sims_single"], sims_dual=ws["sims_dual"])
+        if with_losses:
+            self._retrieval_loss(ws, k.video, k.music, pooled=pooled)
+            out["retrieval_loss"] = ws["ret_loss"]
+        return out
+
+    def _detr_encoder(self, k: "_Call", all_rows: bool) -> Tensor:
+        """DETR encoder (K8, K9) over ws["fus"] + position embedding -> the memory [B, L, D]; ws["srcpos"] holds memory + pos, the
+        decoder's keys.  all_rows: padded positions are computed too -- the regression head sums the memory over ALL of them (reference
+        model_Uni.py:229); otherwise padded tokens of the fused sequence are skipped everywhere."""
+        c, P, ws = self.cfg, self.P, k.ws
+        B, L, D = ws["fus"].shape
+        rows, n_layers = B * L, c.detr_enc_layers
+        x, pos2, srcpos = ws["fus"].view(rows, D), k.pos.view(rows, D), ws["srcpos"]
+        fskip, enc_rows = (None, None) if all_rows else (ws["fus_mask"].view(-1), k.rows_f)
+        final_norm = c.detr_pre_norm and n_layers > 0     # (the reference has it with normalize_before only, transformer.py:33-35,107-108)
+        if not final_norm:
+            ops.layernorm_add(x, None, None, pos2, None, srcpos, row_skip=fskip)      # src + pos (no norm): layer 0's q / k input
+        layer = self._enc_layer_pre_norm if c.detr_pre_norm else self._enc_layer_post_norm
+        for l in range(n_layers):
+            x = layer(k, l, x, fskip, enc_rows)
+        if final_norm:
+            x, last = ws["x3"][:rows], x
+            ops.layernorm_add(last, P["enc.norm.g"], P["enc.norm.b"], pos2, x, srcpos, row_skip=fskip)
+        return x.view(B, L, D)
+
+    def _enc_layer_post_norm(self, k: "_Call", l: int, src: Tensor, fskip, enc_rows) -> Tensor:
+        """reference music_detr/transformer.py:153-168 (forward_post); reads ws["srcpos"] = src + pos and leaves the next one there."""
+        c, P, ws = self.cfg, self.P, k.ws
+        B, L, D = ws["fus"].shape
+        rows = B * L
+        p = f"detr_transformer.encoder.layers.{l}"
+        att = self._mha_block(src, B, L, P[p + ".in.w"], P[p + ".in.b"], ws["fus_mask"], ws, c.detr_nheads, pos=ws["srcpos"], skip=fskip,
+                              rows=enc_rows, order=k.order_f)
+        x = ops.linear(att, P[p + ".out.w"], P[p + ".out.b"], R=src, out=ws["x1"][:rows], rows=enc_rows)
+        s1 = ops.layernorm(x, P[p + ".ln1.g"], P[p + ".ln1.b"], out=ws["x2"][:rows], row_skip=fskip)
+        h = ops.linear(s1, P[p + ".ff1.w"], P[p + ".ff1.b"], act=ops.ACT_RELU, out=ws["ffn"][:rows, :c.detr_dim_feedforward], rows=enc_rows)
+        x = ops.linear(h, P[p + ".ff2.w"], P[p + ".ff2.b"], R=s1, out=ws["x1"][:rows], rows=enc_rows)
+        # the norm that produces the next src also emits src + pos (next layer's q/k input, decoder's keys)
+        src = ws["x3" if l % 2 == 0 else "x0"][:rows]
+        ops.layernorm_add(x, P[p + ".ln2.g"], P[p + ".ln2.b"], k.pos.view(rows, D), src, ws["srcpos"], row_skip=fskip)
+        return src
+
+    def _enc_layer_pre_norm(self, k: "_Call", l: int, x: Tensor, fskip, enc_rows) -> Tensor:
+        """reference music_detr/transformer.py:170-189 (forward_pre): the residual stream x is never normalised inside a layer; norm 1 feeds
+        the attention (q = k = LN1(x) + pos, v = LN1(x)), norm 2 the FFN."""
+        c, P, ws = self.cfg, self.P, k.ws
+        B, L, D = ws["fus"].shape
+        rows = B * L
+        p = f"detr_transformer.encoder.layers.{l}"
+        n1, srcpos = ws["x2"][:rows], ws["srcpos"]
+        ops.layernorm_add(x, P[p + ".ln1.g"], P[p + ".ln1.b"], k.pos.view(rows, D), n1, srcpos, row_skip=fskip)
+        att = self._mha_block(n1, B, L, P[p + ".in.w"], P[p + ".in.b"], ws["fus_mask"], ws, c.detr_nheads, pos=srcpos, skip=fskip,
+                              rows=enc_rows, order=k.order_f)
+        xa = ops.linear(att, P[p + ".out.w"], P[p + ".out.b"], R=x, out=ws["x1"][:rows], rows=enc_rows)
+        n2 = ops.layernorm(xa, P[p + ".ln2.g"], P[p + ".ln2.b"], out=ws["x2"][:rows], row_skip=fskip)
+        h = ops.linear(n2, P[p + ".ff1.w"], P[p + ".ff1.b"], act=ops.ACT_RELU, out=ws["ffn"][:rows, :c.detr_dim_feedforward], rows=enc_rows)
+        return ops.linear(h, P[p + ".ff2.w"], P[p + ".ff2.b"], R=xa, out=ws["x0"][:rows], rows=enc_rows)
+
+    def _dec_open(self, k: "_Call", pooled: Optional[Tensor]) -> None:
+        """The initial decoder queries and layer 0 up to its cross-attention: what the decoder reads of the towers only.  (The pre-norm
+        layer has its self-attention block inside: there the queries alone.)"""
+        ws = k.ws
+        if self._fused_decoder():
+            self._dec_fused_query_side(ws, 0, self._dec_first_rows(ws, k.video, k.music))
+            return
+        self._decoder_queries(ws, k.video, k.music, pooled, k.B)
+        if not self.cfg.detr_pre_norm:
+            self._decoder_query_side(ws, 0, k.B)
+
+    def _decoder(self, k: "_Call", memory: Tensor) -> Dict[str, Tensor]:
+        """DETR decoder (K10) behind `_dec_open` -> hs.  Cross-attention runs in memory space (made_attention_wide): no projection of
+        the L memory rows at all; self-attention collapses to one folded Linear when there is a single query."""
+        c = self.cfg
+        layer = self._dec_layer_pre_norm if c.detr_pre_norm else (self._dec_layer_fused if self._fused_decoder() else self._dec_layer_splitk)
+        for l in range(c.detr_dec_layers):
+            layer(k, l, memory)
+        return dict(hs=k.ws["hs"].view(c.detr_dec_layers, k.B, c.num_moment_queries, c.D))
+
+    def _dec_self_attn(self, ws, l: int, x: Tensor, B: int, **to) -> None:
+        """Self-attention block of decoder layer l over the queries x [B*Q, D]: one folded Linear when Q = 1, else qkv (q, k from
+        x + query_pos) -> attention -> out_proj.  to: the last Linear's residual and outputs (R=, out= or ln1=, ln1_out=)."""
+        c, P = self.cfg, self.P
+        Q, D = c.num_moment_queries, c.D
+        p = f"detr_transformer.decoder.layers.{l}"
+        if Q == 1:
+            return self._skinny(ws, x, p + ".sa.fold", **to)
+        dqkv = ws["dqkv"]
+        ops.linear(x, P[p + ".sa.in.w"], P[p + ".sa.in.b"], A2=P["query_embed"], a2_row_mod=Q,
+                   segs=[Seg(out=dqkv, col_begin=0, use_a2=True), Seg(out=dqkv[:, 2 * D:], col_begin=2 * D, ldo=dqkv.stride(0))])
+        d3 = dqkv.view(B, Q, 3 * D)
+        ops.attention(d3[:, :, :D], d3[:, :, D:2 * D], d3[:, :, 2 * D:], ws["datt"].view(B, Q, D), c.detr_nheads)
+        self._skinny(ws, ws["datt"], p + ".sa.out", **to)
+
+    def _dec_cross_attn(self, k: "_Call", memory: Tensor) -> None:
+        """ws["dq_all"] (the queries folded with W_k per head) against memory + pos, values = memory -> ws["dpool"], both [B*Q, H*D]."""
+        c, ws = self.cfg, k.ws
+        B, Q, H, D = k.B, c.num_moment_queries, c.detr_nheads, c.D
+        heads = lambda t: t.view(B, Q, H, D).permute(0, 2, 1, 3)         # [B, H, Q, D] view: row (b,q), head-major columns
+        ops.attention_wide(heads(ws["dq_all"]), ws["srcpos"].view(memory.shape), memory, heads(ws["dpool"]), scale=1.0 / math.sqrt(D // H),
+                           key_mask=ws["fus_mask"], n_split=max(1, min(8, 256 // max(B, 1))), part_o=ws["part_o"], part_ml=ws["part_ml"])
+
+    def _dec_layer_pre_norm(self, k: "_Call", l: int, memory: Tensor) -> None:
+        """reference music_detr/transformer.py:246-271 (forward_pre): tgt is the un-normalised residual stream; every branch reads a
+        norm of it.  The self-attention always runs here.  hs[l] = decoder.norm(tgt after the layer) (:135-136)."""
+        P, ws = self.P, k.ws
+        p = f"detr_transformer.decoder.layers.{l}"
         skinny = lambda A, wkey, **kw: self._skinny(ws, A, wkey, **kw)
+        t1, t2 = ws["t1"], ws["t2"]
+        ta, tb = ws["dz"][0], ws["dz"][1]                     # (f32 rows: the stream is rounded to the compute dtype nowhere)
+        tcur = ws["tgt"] if l == 0 else ws["dz"][2]
+        ops.layernorm(tcur, P[p + ".ln1.g"], P[p + ".ln1.b"], out=t1)
+        self._dec_self_attn(ws, l, t1, k.B, R=tcur, out=ta)
+        ops.layernorm(ta, P[p + ".ln2.g"], P[p + ".ln2.b"], out=t2)
+        skinny(t2, p + ".ca.qk", A2=P["query_embed"], a2_row_mod=self.cfg.num_moment_queries, out=ws["dq_all"])
+        self._dec_cross_attn(k, memory)
+        skinny(ws["dpool"], p + ".ca.vo", R=ta, out=tb)
+        ops.layernorm(tb, P[p + ".ln3.g"], P[p + ".ln3.b"], out=t1)
+        skinny(t1, p + ".ff1", act=ops.ACT_RELU, out=ws["dffn"])
+        skinny(ws["dffn"], p + ".ff2", R=tb, out=ws["dz"][2], ln1=(P["dec.norm.g"], P["dec.norm.b"]), ln1_out=ws["hs"][l])
 
-        n_split = max(1, min(8, 256 // max(B, 1)))
-        fused = self._fused_decoder()
-        for l in range(nd):
-            p = f"detr_transformer.decoder.layers.{l}"
-            ln2, ln3 = [(P[p + f".ln{i}.g"], P[p + f".ln{i}.b"]) for i in (2, 3)]
-            t1, t2 = ws["t1"], ws["t2"]
-            if c.detr_pre_norm:
-                # reference music_detr/transformer.py:246-271 (forward_pre): tgt is the un-normalised residual stream; every branch reads a
-                # norm of it.  The self-attention always runs here.  hs[l] = decoder.norm(tgt after the layer) (:135-136).
-                ta, tb = ws["dz"][0], ws["dz"][1]                 # (f32 rows: the stream is rounded to the compute dtype nowhere)
-                tcur = tgt if l == 0 else ws["dz"][2]
-                ops.layernorm(tcur, P[p + ".ln1.g"], P[p + ".ln1.b"], out=t1)
-                if Q == 1:
-                    skinny(t1, p + ".sa.fold", R=tcur, out=ta)
-                else:
-                    dqkv = ws["dqkv"]
-                    ops.linear(t1, P[p + ".sa.in.w"], P[p + ".sa.in.b"], A2=qp, a2_row_mod=Q,
-                               segs=[Seg(out=dqkv, col_begin=0, use_a2=True), Seg(out=dqkv[:, 2 * D:], col_begin=2 * D, ldo=dqkv.stride(0))])
-                    d3 = dqkv.view(B, Q, 3 * D)
-                    ops.attention(d3[:, :, :D], d3[:, :, D:2 * D], d3[:, :, 2 * D:], ws["datt"].view(B, Q, D), H)
-                    skinny(ws["datt"], p + ".sa.out", R=tcur, out=ta)
-                ops.layernorm(ta, ln2[0], ln2[1], out=t2)
-                skinny(t2, p + ".ca.qk", A2=qp, a2_row_mod=Q, out=ws["dq_all"])
-                ops.attention_wide(dq4, mempos3, mem3, dp4, scale=ca_scale, key_mask=fus_mask,
-                                   n_split=n_split, part_o=ws["part_o"], part_ml=ws["part_ml"])
-                skinny(dpool, p + ".ca.vo", R=ta, out=tb)
-                ops.layernorm(tb, ln3[0], ln3[1], out=t1)
-                skinny(t1, p + ".ff1", act=ops.ACT_RELU, out=ws["dffn"])
-                skinny(ws["dffn"], p + ".ff2", R=tb, out=ws["dz"][2], ln1=(P["dec.norm.g"], P["dec.norm.b"]), ln1_out=hs[l])
-                continue
-            if fused:
-                # Fused chain (made_dec_stage): every LayerNorm runs in the prologue of the Linear that consumes it, so a layer is
-                # 8 launches instead of 12 and no split-K partial sums go through HBM.  z[0..2]: the raw rows before norm 1 / 2 / 3.
-                z, hd = ws["dz"], D // H
-                if l > 0 or dec_early is None:
-                    self._dec_fused_query_side(ws, l, self._dec_first_rows(ws, video, music) if l == 0 else None)
-                ops.attention_wide(dq4, mempos3, mem3, dp4, scale=ca_scale, key_mask=fus_mask,
-                                   n_split=n_split, part_o=ws["part_o"], part_ml=ws["part_ml"])
-                dv = ws["dv"]
-                ops.linear(dpool[:, :D], P[p + ".ca.v.w"][:hd], None, M=B * Q, N=hd, K=D, batch=H, a_z_stride=D, w_z_stride=hd * D,
-                           segs=[Seg(out=dv, ldo=D, out_z_stride=hd)])                       # v_h = W_v,h pooled_h (b_v rides in ca.vo.b)
-                ops.linear(dv, P[p + ".ca.o.w"], P[p + ".ca.vo.b"], R=t1, out=z[1])
-                ops.dec_stage(z[1], P[p + ".ff1.w"], P[p + ".ff1.b"], ws["dffn"], ln=ln2, x_out=t2, act=ops.ACT_RELU)
-                ops.linear(ws["dffn"], P[p + ".ff2.w"], P[p + ".ff2.b"], R=t2, out=z[2])
-                if l == nd - 1:                                  # the last layer's norms have no consumer stage: one row kernel
-                    ops.splitk_finish(z[2].view(-1), 1, B * Q, D, None, ln1=ln3, ln1_out=tgt, ln2=(P["dec.norm.g"], P["dec.norm.b"]), ln2_out=hs[l])
-                continue
-            if l > 0 or dec_early is None:
-                self._decoder_query_side(ws, l, B)
-            ops.attention_wide(dq4, mempos3, mem3, dp4, scale=ca_scale, key_mask=fus_mask,
-                               n_split=n_split, part_o=ws["part_o"], part_ml=ws["part_ml"])
-            skinny(dpool, p + ".ca.vo", R=t1, ln1=ln2, ln1_out=t2)
-            skinny(t2, p + ".ff1", act=ops.ACT_RELU, out=ws["dffn"])
-            skinny(ws["dffn"], p + ".ff2", R=t2, ln1=ln3, ln1_out=tgt, ln2=(P["dec.norm.g"], P["dec.norm.b"]), ln2_out=hs[l])
-        out["hs"] = hs.view(nd, B, Q, D)
+    def _dec_layer_fused(self, k: "_Call", l: int, memory: Tensor) -> None:
+        """Fused chain (made_dec_stage): every LayerNorm runs in the prologue of the Linear that consumes it, so a layer is
+        8 launches instead of 12 and no split-K partial sums go through HBM.  z[0..2]: the raw rows before norm 1 / 2 / 3."""
+        c, P, ws = self.cfg, self.P, k.ws
+        p = f"detr_transformer.decoder.layers.{l}"
+        D, H, nd, rows = c.D, c.detr_nheads, c.detr_dec_layers, k.B * c.num_moment_queries
+        z, hd, dv, dpool, t2 = ws["dz"], D // H, ws["dv"], ws["dpool"], ws["t2"]
+        if l > 0:
+            self._dec_fused_query_side(ws, l, None)
+        self._dec_cross_attn(k, memory)
+        ops.linear(dpool[:, :D], P[p + ".ca.v.w"][:hd], None, M=rows, N=hd, K=D, batch=H, a_z_stride=D, w_z_stride=hd * D,
+                   segs=[Seg(out=dv, ldo=D, out_z_stride=hd)])                       # v_h = W_v,h pooled_h (b_v rides in ca.vo.b)
+        ops.linear(dv, P[p + ".ca.o.w"], P[p + ".ca.vo.b"], R=ws["t1"], out=z[1])
+        ops.dec_stage(z[1], P[p + ".ff1.w"], P[p + ".ff1.b"], ws["dffn"], ln=(P[p + ".ln2.g"], P[p + ".ln2.b"]), x_out=t2, act=ops.ACT_RELU)
+        ops.linear(ws["dffn"], P[p + ".ff2.w"], P[p + ".ff2.b"], R=t2, out=z[2])
+        if l == nd - 1:                                      # the last layer's norms have no consumer stage: one row kernel
+            ops.splitk_finish(z[2].view(-1), 1, rows, D, None, ln1=(P[p + ".ln3.g"], P[p + ".ln3.b"]), ln1_out=ws["tgt"],
+                              ln2=(P["dec.norm.g"], P["dec.norm.b"]), ln2_out=ws["hs"][l])
 
-        # ---- heads (K11) on all decoder layers at once.  (Running the class head and the query projection on the side stream
-        # beside the span head was tried: +150 us per step under graph replay, so the three chains stay on one stream.)
-        hs2 = hs.view(nd * B * Q, D)
+    def _dec_layer_splitk(self, k: "_Call", l: int, memory: Tensor) -> None:
+        """Post-norm layer as split-K Linears with the LayerNorms in their finishing pass (f32 parity mode, Q > 1, the pooled-track query)."""
+        P, ws = self.P, k.ws
+        p = f"detr_transformer.decoder.layers.{l}"
+        ln2, ln3 = [(P[p + f".ln{i}.g"], P[p + f".ln{i}.b"]) for i in (2, 3)]
+        t1, t2 = ws["t1"], ws["t2"]
+        if l > 0:
+            self._decoder_query_side(ws, l, k.B)
+        self._dec_cross_attn(k, memory)
+        self._skinny(ws, ws["dpool"], p + ".ca.vo", R=t1, ln1=ln2, ln1_out=t2)
+        self._skinny(ws, t2, p + ".ff1", act=ops.ACT_RELU, out=ws["dffn"])
+        self._skinny(ws, ws["dffn"], p + ".ff2", R=t2, ln1=ln3, ln1_out=ws["tgt"], ln2=(P["dec.norm.g"], P["dec.norm.b"]), ln2_out=ws["hs"][l])
+
+    def _short_cut(self, raw: Tensor, normed: Tensor, mq: Tensor, out: Optional[Tensor] = None) -> Tensor:
+        """audio_short_cut (reference model/model_Uni.py:144-145): normalize(normed + music), the sum through `raw`.  mq: `_music_per_query`."""
+        ops_train.add3(raw, normed, mq, b_mod=mq.numel())
+        return ops.l2norm_rows(raw, out_f32=out)
+
+    def _music_per_query(self, k: "_Call") -> Tensor:
+        Q = self.cfg.num_moment_queries
+        return k.music if Q == 1 else k.music[:, None, :].expand(k.B, Q, self.cfg.D).contiguous()
+
+    def _heads(self, k: "_Call") -> Dict[str, Tensor]:
+        """Heads (K11) on all decoder layers at once: class, span, the contrastive projections, the moment head.  (Running the class head
+        and the query projection on the side stream beside the span head was tried: +150 us per step under graph replay, so the three
+        chains stay on one stream.)"""
+        c, P, ws = self.cfg, self.P, k.ws
+        B, Tv, nd = k.B, k.frame.shape[1], c.detr_dec_layers
+        hs = ws["hs"]
+        hs2 = hs.view(-1, c.D)                                           # [nd * B * Q, D]
         logits, spans = ws["logits"], ws["spans"]
-        pq = vid_sum = None
         ops.linear(hs2, P["class_embed.w"], P["class_embed.b"], out=logits.view(-1, 2))
         if c.contrastive_align_loss:
-            ops.linear(hs2, P["proj_q.w"], P["proj_q.b"], out=ws["pq_raw"])
-            pq = ws["pq"]
-            ops.l2norm_rows(ws["pq_raw"], out_f32=pq.view(nd * B * Q, -1))
-            if c.audio_short_cut:                                    # reference model/model_Uni.py:144-145: normalize(pq + music)
-                from . import ops_train
-                mq = music if Q == 1 else music[:, None, :].expand(B, Q, D).contiguous()
-                ops_train.add3(ws["pq_raw"], pq, mq, b_mod=B * Q * D)
-                ops.l2norm_rows(ws["pq_raw"], out_f32=pq.view(nd * B * Q, -1))
+            pq_raw, pq2 = ws["pq_raw"], ws["pq"].view(hs2.shape[0], -1)
+            ops.linear(hs2, P["proj_q.w"], P["proj_q.b"], out=pq_raw)
+            ops.l2norm_rows(pq_raw, out_f32=pq2)
+            if c.audio_short_cut:
+                mq = self._music_per_query(k)
+                self._short_cut(pq_raw, pq2, mq, out=pq2)
                 if c.aux_loss and nd > 1:
                     # the auxiliary layers get the short-cut a SECOND time when their output dicts are built (reference
                     # model/model_Uni.py:166-169 adds the music vector to the already short-cut proj_queries[:-1])
-                    n_aux = (nd - 1) * B * Q
-                    ops_train.add3(ws["pq_raw"][:n_aux], pq.view(nd * B * Q, -1)[:n_aux], mq, b_mod=B * Q * D)
-                    ops.l2norm_rows(ws["pq_raw"][:n_aux], out_f32=pq.view(nd * B * Q, -1)[:n_aux])
+                    n_aux = (nd - 1) * B * c.num_moment_queries
+                    self._short_cut(pq_raw[:n_aux], pq2[:n_aux], mq, out=pq2[:n_aux])
         if hs2.shape[0] <= 1024:
-            skinny(hs2, "span_embed.0", act=ops.ACT_RELU, out=ws["h1"])
-            skinny(ws["h1"], "span_embed.1", act=ops.ACT_RELU, out=ws["h2"])
+            self._skinny(ws, hs2, "span_embed.0", act=ops.ACT_RELU, out=ws["h1"])
+            self._skinny(ws, ws["h1"], "span_embed.1", act=ops.ACT_RELU, out=ws["h2"])
             h2 = ws["h2"]
         else:
             h1 = ops.linear(hs2, P["span_embed.0.w"], P["span_embed.0.b"], act=ops.ACT_RELU, out=ws["h1"])
@@ -893,41 +944,38 @@ class MadeEngine:
             # the head predicts the centre only; the width is the video's share of the longest track (reference
             # model/model_Uni.py:135-136,280-282)
             ops.linear(h2, P["span_embed.2.w"], P["span_embed.2.b"], act=ops.ACT_SIGMOID, segs=[Seg(out=spans.view(-1, 2), ldo=2)])
-            spans[..., 1] = (v_duration.to(self.device, torch.float32) / c.max_m_duration).view(1, B, 1)
+            spans[..., 1] = (k.v_duration.to(self.device, torch.float32) / c.max_m_duration).view(1, B, 1)
         else:
             ops.linear(h2, P["span_embed.2.w"], P["span_embed.2.b"], act=ops.ACT_SIGMOID, out=spans.view(-1, 2))
-        out.update(pred_logits=logits[-1], pred_spans=spans[-1], logits_all=logits, spans_all=spans)
+        out = dict(pred_logits=logits[-1], pred_spans=spans[-1], logits_all=logits, spans_all=spans)
         if c.contrastive_align_loss:
-            self._frame_rows_linear(frame, P["proj_v.w"], P["proj_v.b"], ws["pv_raw"], B, Tv)
+            self._frame_rows_linear(k.frame, P["proj_v.w"], P["proj_v.b"], ws["pv_raw"], B, Tv)
             pv = ws["pv"]
             ops.l2norm_rows(ws["pv_raw"], out_f32=pv.view(B * Tv, -1))
-            vid_sum = ops.masked_mean(pv, None, out=ws["vid_sum"])
-            out.update(proj_queries=pq[-1], proj_vid_mem=pv, proj_queries_all=pq)
-
+            ops.masked_mean(pv, None, out=ws["vid_sum"])
+            out.update(proj_queries=ws["pq"][-1], proj_vid_mem=pv, proj_queries_all=ws["pq"])
         if c.moment_loss:                                                # reference model_Uni.py:152-159 (outputs only: no loss reads them)
-            last = hs[nd - 1]
-            m1 = ops.linear(last, P["moment_embed.0.w"], P["moment_embed.0.b"], act=ops.ACT_RELU)
+            m1 = ops.linear(hs[nd - 1], P["moment_embed.0.w"], P["moment_embed.0.b"], act=ops.ACT_RELU)
             m2 = ops.linear(m1, P["moment_embed.1.w"], P["moment_embed.1.b"], act=ops.ACT_RELU)
             m3 = ops.linear(m2, P["moment_embed.2.w"], P["moment_embed.2.b"], out_dtype=torch.float32)
             mf = ops.l2norm_rows(m3)
             if c.audio_short_cut:
-                from . import ops_train
-                mq = music if Q == 1 else music[:, None, :].expand(B, Q, D).contiguous()
-                ops_train.add3(m3, mf, mq, b_mod=B * Q * D)
-                mf = ops.l2norm_rows(m3)
-            out["moment_feats"] = mf.view(B, Q, D)
-        if not with_losses:
-            cur.wait_stream(side)
-            return out
-        # ---- matcher + set criterion (K12-K14), all layers in one launch each
+                mf = self._short_cut(m3, mf, self._music_per_query(k))
+            out["moment_feats"] = mf.view(B, c.num_moment_queries, c.D)
+        return out
+
+    def _criterion(self, k: "_Call", spans_target: Tensor) -> Dict[str, Tensor]:
+        """Matcher + set criterion (K12-K14) on the heads' outputs in the workspace, all layers in one launch each."""
+        c, P, ws = self.cfg, self.P, k.ws
+        nd, B, Q = c.detr_dec_layers, k.B, c.num_moment_queries
+        logits, spans = ws["logits"], ws["spans"]
+        pq, vid_sum = (ws["pq"], ws["vid_sum"]) if c.contrastive_align_loss else (None, None)
         tg = spans_target.contiguous()
         pi, ti, cnt, status, cost = ops.hungarian_match(logits.view(nd * B, Q, 2), spans.view(nd * B, Q, 2), tg, c.foreground_label)
         losses, total = ops.set_criterion(logits, spans, tg, pi, ti, cnt, pq, vid_sum, P["empty_weight"],
                                           c.foreground_label, P["crit_weights"])
-        out.update(matcher_pred_idx=pi.view(nd, B, -1), matcher_tgt_idx=ti.view(nd, B, -1), matcher_count=cnt.view(nd, B),
-                   matcher_status=status, criterion_losses=losses, localization_loss=total)
-        cur.wait_stream(side)
-        return out
+        return dict(matcher_pred_idx=pi.view(nd, B, -1), matcher_tgt_idx=ti.view(nd, B, -1), matcher_count=cnt.view(nd, B),
+                    matcher_status=status, criterion_losses=losses, localization_loss=total)
 
     # ------------------------------------------------------------------ grounding: towers once per item, localization per pair
     @torch.no_grad()
@@ -953,12 +1001,8 @@ class MadeEngine:
         for n0 in range(0, N, batch):
             B = min(batch, N - n0)
             m = masks[n0:n0 + B]
-            if which == "video":
-                ws = self._buffers(B, T, 1)
-                rows, order = ops.row_index(m, out=ws["rows_v"]), ops.batch_order(m, out=ws["order_v"])
-            else:
-                ws = self._buffers(B, 1, T)
-                rows, order = ops.row_index(m, out=ws["rows_a"]), ops.batch_order(m, out=ws["order_a"])
+            ws = self._buffers(B, T, 1) if which == "video" else self._buffers(B, 1, T)
+            rows, order = self._row_lists(m, ws, which[0])
             self._encode(feats[n0:n0 + B], m, which, ws, 0, rows=rows, order=order, out=(rec.tokens[n0:n0 + B], rec.vec[n0:n0 + B]))
         return rec
 
@@ -991,24 +1035,20 @@ class MadeEngine:
         if "pair_fm" not in ws:
             ws["pair_fm"] = torch.empty(B, Tv, device=dev, dtype=torch.float32)
             ws["pair_sm"] = torch.empty(B, Ta, device=dev, dtype=torch.float32)
-        fm, sm, fus, fus_mask = ws["pair_fm"], ws["pair_sm"], ws["fus"], ws["fus_mask"]
+        fm, sm, fus = ws["pair_fm"], ws["pair_sm"], ws["fus"]
         video, music_v = ws["video"], ws["music"]
         frame, seg = (fus[:, :Tv], fus[:, Tv:]) if concat else (ws["frame_buf"], ws["seg_buf"])
         cur = torch.cuda.current_stream()
         for p0 in range(0, P, B):
             ops.gather_pairs(vi[p0:p0 + B], mi[p0:p0 + B], videos.tokens, videos.mask, videos.vec, music.tokens, music.mask, music.vec,
                              frame, seg, fm, sm, video, music_v)
-            ops.concat_cols(fm if concat else None, sm, fus_mask)
-            pos = ops.sine_pe(fus_mask, self.P["dim_t"], out=ws["pos"])
-            rows_f = ops.row_index(fus_mask, out=ws["rows_f"])
-            order_f = ops.batch_order(fus_mask, out=ws["order_f"])
+            lists = self._fused_lists(ws, fm, sm)
             if not concat:
                 self._ca_fusion(ws, frame, seg, fm, sm, B, Tv, Ta)
             vdur = videos.duration[vi[p0:p0 + B].long()] if c.predict_center == 1 else None
+            k = _Call(ws, B, fm, sm, frame, seg, video, music_v, *lists, vdur)
             out: Dict[str, Tensor] = dict(video_feats=video, music_feats=music_v, frame_feats=frame, segment_feats=seg)
-            out = self._localize(ws, out, B, Tv, Ta, fm, sm, video, music_v, frame, pos, rows_f, order_f, None, None, None, vdur,
-                                 False, cur, cur)
-            yield p0, min(B, P - p0), out
+            yield p0, min(B, P - p0), self._after_fusion(k, out, cur, cur)
 
     @torch.no_grad()
     @_lib.scoped_f32_products
@@ -1083,29 +1123,18 @@ class MadeEngine:
     def _decoder_query_side(self, ws, l: int, B: int):
         """Decoder layer l up to the cross-attention: self-attention block over the queries (one folded Linear when Q = 1) ->
         ws["t1"], then the cross-attention query folded with W_k per head -> ws["dq_all"].  Reads ws["tgt"] only."""
-        c, P = self.cfg, self.P
-        Q, D, H = c.num_moment_queries, c.D, c.detr_nheads
+        P = self.P
         p = f"detr_transformer.decoder.layers.{l}"
-        ln1 = (P[p + ".ln1.g"], P[p + ".ln1.b"])
-        tgt, t1, qp = ws["tgt"], ws["t1"], P["query_embed"]
-        if Q == 1:
-            self._skinny(ws, tgt, p + ".sa.fold", R=tgt, ln1=ln1, ln1_out=t1)
-        else:
-            dqkv = ws["dqkv"]
-            ops.linear(tgt, P[p + ".sa.in.w"], P[p + ".sa.in.b"], A2=qp, a2_row_mod=Q,
-                       segs=[Seg(out=dqkv, col_begin=0, use_a2=True),
-                             Seg(out=dqkv[:, 2 * D:], col_begin=2 * D, ldo=dqkv.stride(0))])
-            d3 = dqkv.view(B, Q, 3 * D)
-            ops.attention(d3[:, :, :D], d3[:, :, D:2 * D], d3[:, :, 2 * D:], ws["datt"].view(B, Q, D), H)
-            self._skinny(ws, ws["datt"], p + ".sa.out", R=tgt, ln1=ln1, ln1_out=t1)
-        self._skinny(ws, t1, p + ".ca.qk", A2=qp, a2_row_mod=Q, out=ws["dq_all"])
+        tgt, t1 = ws["tgt"], ws["t1"]
+        self._dec_self_attn(ws, l, tgt, B, R=tgt, ln1=(P[p + ".ln1.g"], P[p + ".ln1.b"]), ln1_out=t1)
+        self._skinny(ws, t1, p + ".ca.qk", A2=P["query_embed"], a2_row_mod=self.cfg.num_moment_queries, out=ws["dq_all"])
 
-    def _regression_head(self, out, ws, mem3: Tensor, fus_mask: Tensor, spans_target: Tensor, v_duration, with_losses: bool, cur, side):
+    def _regression_head(self, k: "_Call", mem3: Tensor, spans_target: Optional[Tensor], with_losses: bool) -> Dict[str, Tensor]:
         """reference model/model_Uni.py:228-232,290-300: memory summed over all L positions / number of valid ones -> 3-layer
         ReLU MLP -> sigmoid; loss = 20 * L1.  The decoder's output is not used on this path, so it is not run."""
         c, P = self.cfg, self.P
-        B = mem3.shape[0]
-        fusion = ops.masked_mean(mem3, None) / fus_mask.sum(dim=1, keepdim=True)           # [B, D] f32
+        B, v_duration, out = k.B, k.v_duration, {}
+        fusion = ops.masked_mean(mem3, None) / k.ws["fus_mask"].sum(dim=1, keepdim=True)   # [B, D] f32
         h1 = ops.linear(fusion, P["reg_mlp.0.w"], P["reg_mlp.0.b"], act=ops.ACT_RELU)
         h2 = ops.linear(h1, P["reg_mlp.1.w"], P["reg_mlp.1.b"], act=ops.ACT_RELU)
         if c.predict_center == 1:
@@ -1121,7 +1150,6 @@ class MadeEngine:
             l1 = (out["pred_spans"] - tg).abs().mean()
             out["regression_loss_span"] = l1
             out["localization_loss"] = (l1 * 20).view(1)
-        cur.wait_stream(side)
         return out
 
     def _ca_fusion(self, ws, frame: Tensor, seg: Tensor, fm: Tensor, sm: Tensor, B: int, Tv: int, Ta: int) -> None:
@@ -1164,7 +1192,6 @@ class MadeEngine:
         elif c.vmr_loss == "dual_single_feature_fuse":
             # reference model_Uni.py:268-273: the pooled track vectors averaged with the track's own vector, then the music-pooling
             # similarity (metrics.py:10-24) -- cos(v_n, (pooled[m, n] + music[m]) / 2); the 1/2 cancels in the cosine
-            from . import ops_train
             B, D = video.shape
             fused = torch.empty(B * B, D, device=self.device, dtype=torch.float32)
             ops_train.add3(fused, pooled, music[:, None, :].expand(B, B, D).contiguous())        # rows (m, n): + music[m]
