@@ -1354,6 +1354,60 @@ int made_audio_fbank(const float* pcm, int64_t pcm_len, const MadeAudioSegDesc* 
 int made_ast_patches(const float* spec, int64_t n_segs, void* patches, int32_t patch_dtype, int64_t ld_patch, void* stream);
 
 /* ==========================================================================================
+ * Onsets and fitted moments (mgsv_amd/onsets.py, mgsv_amd/grounding.py fit_grounding; csrc/onsets.hip, csrc/fit.hip).  A track's
+ * attacks are found once, from made_audio_fbank's spectrogram of the whole track: block j of a track is the "segment" first =
+ * j * 1024 * 160, count = min(n16 - first, 1023 * 160 + 400), whose 1024 rows are the track's frames 1024 j .. 1024 j + 1023 (the
+ * fbank removes the mean per frame, so a frame does not depend on the segmentation).  A track of n16 samples has F = 1 + (n16 - 400)
+ * / 160 frames of 10 ms (0 below 400 samples); rows past F hold the pad value and are never read as signal.  The reference has no
+ * counterpart: it returns the regressed span as it is.
+ * ========================================================================================== */
+
+/* made_onset_strength: the spectral flux of N tracks.  logmel [N, F_ld, 128] f32 (16-byte aligned), n_frames [N] device int32, env
+ * [N, env_ld] f32:
+ *     env[t, f] = (1 / 128) * sum_b max(0, x[t, f, b] - x[t, f - lag, b])     for lag <= f < n_frames[t]
+ *     env[t, f] = 0                                                           for every other f < env_ld
+ * in the spectrogram's normalised units.  32 lanes per frame, two 16-byte loads per lane, the four differences of a lane added as
+ * (d0 + d1) + (d2 + d3) and the lanes by a fixed DPP tree: a frame's bits depend on its own 2 * 128 values only -- not on N, the
+ * track's place in the batch, F_ld or env_ld.  Rows >= n_frames[t] of logmel are not read.  No LDS, no atomics, no workspace.  A
+ * track with n_frames[t] > F_ld (or < 0) gets a NaN row.  lag in [1, 8]; N == 0 is a no-op.  Refused: negative sizes, lag out of
+ * range, null pointers (logmel may be NULL when F_ld == 0, env when env_ld == 0), a logmel that is not 16-byte aligned. */
+int made_onset_strength(const float* logmel, int64_t F_ld, const int32_t* n_frames, int64_t N, int32_t lag, float* env, int64_t env_ld,
+                        void* stream);
+
+/* made_onset_peaks: the onsets of N tracks from their envelopes env [N, env_ld] f32.  Frame f < n_frames[t] is an onset iff
+ *   1. env[f] > 0;
+ *   2. env[f] > env[g] for g in [f - w_max, f) and env[f] >= env[g] for g in (f, f + w_max], the windows clipped to [0, n_frames):
+ *      exact f32 comparisons; of equal neighbouring values the earlier wins;
+ *   3. env[f] >= s / n + delta, s the f32 sum in ascending frame order of env over [f - w_avg, f + w_avg] clipped to [0, n_frames)
+ *      and n the number of frames in it.
+ * count[t] int32 = the number of onsets; time[t * cap + i] f32, i < count[t] = the onsets ascending as (float)f * 0.01f seconds:
+ * the start of the first frame that shows the rise, at or before the attack.  Entries from count[t] on are not written.  Rule 2
+ * keeps two onsets w_max + 1 frames apart, so cap >= ceil(env_ld / (w_max + 1)) never overflows (a smaller cap is refused).  One
+ * workgroup per track walks tiles of 1024 frames with a 128-frame halo in LDS; the compaction is ordered (ballot, prefix popcount,
+ * a running offset): no atomics, no workspace, and a track's list does not depend on the other tracks.  A track with n_frames[t]
+ * > env_ld (or < 0) gets count -1 and no entries.  w_max in [1, 32], w_avg in [1, 128], delta finite and >= 0; N == 0 is a no-op.
+ * Refused: those ranges, negative sizes, null pointers (env may be NULL when env_ld == 0, time when cap == 0). */
+int made_onset_peaks(const float* env, int64_t env_ld, const int32_t* n_frames, int64_t N, int32_t w_max, int32_t w_avg, float delta,
+                     int64_t cap, float* time, int32_t* count, void* stream);
+
+/* made_fit_moments: E moments fitted to a wanted length, their track and its onsets; one thread per entry, every step one rounded
+ * f32 operation (no contraction), max(a, b) = a > b ? a : b and min(a, b) = a < b ? a : b.  start / end [E] f32 seconds on the
+ * track's axis, track [E] int32 (-1: none), want [E] f32 (NaN: keep the moment's own length), tlen [n_tracks] f32, onset_start
+ * [n_tracks + 1] int64 and onset_time [n_onsets] f32 the tracks' onsets as a CSR, strictly ascending inside a track, tol f32.
+ *   1. track outside [0, n_tracks), or start, end or tlen[track] NaN: out_start = out_end = shift = NaN, onset = -1.
+ *   2. T = tlen[track]; len = want if it is not NaN, else end - start; len = min(max(len, 0), T).
+ *   3. c = 0.5f * (start + end); s1 = c - 0.5f * len; s1 = min(max(s1, 0), T - len).
+ *   4. With tol > 0: among the track's onsets o with fabsf(o - s1) <= tol and o <= T - len the one with the smallest fabsf(o - s1),
+ *      of two equal ones the earlier (a binary search for the first o >= s1, then it and the one before): s2 = o and onset = its
+ *      index inside the track; without one, or with tol == 0, s2 = s1 and onset = -1.
+ *   5. out_start = s2, out_end = s2 + len, shift = s2 - start.
+ * onset_start / onset_time may be NULL with tol == 0 (length fitting alone).  E == 0 is a no-op.  Refused: tol negative or not
+ * finite, E or n_tracks negative or >= 2^31, n_onsets negative, null required pointers, tol > 0 without the table. */
+int made_fit_moments(const float* start, const float* end, const int32_t* track, const float* want, int64_t E, const float* tlen,
+                     int64_t n_tracks, const int64_t* onset_start, const float* onset_time, int64_t n_onsets, float tol, float* out_start,
+                     float* out_end, float* shift, int32_t* onset, void* stream);
+
+/* ==========================================================================================
  * Batches from a device-resident feature store (mgsv_amd/feature_store.py DeviceFeatureStore): a split's features stay on the
  * device in their storage format and every batch of the training / evaluation loop is assembled by one launch.  The reference
  * loads four files per sample in worker processes (dataloaders/dataloader_MGSV_EC_feature.py:57-67).

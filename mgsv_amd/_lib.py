@@ -345,6 +345,9 @@ SIGNATURES = {
     "made_audio_fbank": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, i32, vp, vp]),
     "made_ast_patches": (C.c_int, [vp, i64, vp, i32, i64, vp]),
     "made_gather_batch": (C.c_int, [C.POINTER(MadeGatherBatchArgs), vp]),
+    "made_onset_strength": (C.c_int, [vp, i64, vp, i64, i32, vp, i64, vp]),
+    "made_onset_peaks": (C.c_int, [vp, i64, vp, i64, i32, i32, f32, i64, vp, vp, vp]),
+    "made_fit_moments": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

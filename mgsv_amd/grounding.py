@@ -24,13 +24,17 @@ With `diversity` / `max_similarity` the selection returns a pool of P >= k group
 greedily -- score minus a penalty for the largest cosine with a group picked before, groups too close to a pick dropped -- so that
 near-duplicate tracks do not fill the top k; only the k kept are localized (`check_diversity`, `_diversify`).
 
+With `fit` (a `Fit`) the finished Grounding goes through `fit_grounding`, one made_fit_moments launch: every moment is given its
+video's length, kept inside its track and -- against the track's onsets (mgsv_amd/onsets.py) -- started on the nearest attack within
+a tolerance; the grounded moments stay in `raw_start` / `raw_end`.  Without it none of that code runs.
+
 A pair's localization depends on that pair's video and track only (every kernel after the towers computes a sample's rows
 independently of the rest of the batch), so the moment found in the ground-truth track is the one the batched evaluation scores.
 """
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
@@ -62,6 +66,10 @@ class Grounding:
     cand_score: Optional[Tensor] = None    # ... and their exact scores, f32 (NaN where there is no candidate)
     pool_rank: Optional[Tensor] = None     # grounded with diversity= / max_similarity=: [N_v, k] int32, every result's rank in the pool (-1: none) ...
     redundancy: Optional[Tensor] = None    # ... and its largest cosine with a result before it, f32 (NaN for the first result and where there is none)
+    raw_start: Optional[Tensor] = None     # fitted (fit=, `fit_grounding`): the moments as they were grounded, the shape of start (start / end are then the fitted ones) ...
+    raw_end: Optional[Tensor] = None
+    shift: Optional[Tensor] = None         # ... start - raw_start, f32 ...
+    onset: Optional[Tensor] = None         # ... and the onset the start was moved onto, int32 index inside the track's list (-1: not snapped)
 
     @property
     def k(self) -> int:
@@ -72,11 +80,12 @@ class Grounding:
         (music_ids indexed by track column; entries past the number of groups are left out).  Grounded over windows, music_ids is
         indexed by track and every track holds "moments": [{"start", "end", "confidence", "window_offset"}, ...] instead of one
         start / end / confidence.  Re-selected for diversity (`pool_rank` is set), every track also holds "pool_rank" and "redundancy"
-        (None for a video's first track, which has nothing before it)."""
+        (None for a video's first track, which has nothing before it).  Fitted (`raw_start` is set), every track's -- over windows
+        every moment's -- dict also holds "raw_start", "raw_end" and "snapped" (whether the start sits on an onset)."""
         if self.windows is not None:
             return self._window_records(video_ids, music_ids)
         tr, sc, st, en, cf = (t.cpu().numpy() for t in (self.track, self.score, self.start, self.end, self.confidence))
-        extra = self._diversity_fields()
+        extra, fitted = self._diversity_fields(), self._fit_fields()
         out = []
         for v, vid in enumerate(video_ids):
             ent = []
@@ -86,7 +95,7 @@ class Grounding:
                     continue
                 c = float(cf[v, j])
                 ent.append(dict(music_id=music_ids[m], score=float(sc[v, j]), start=float(st[v, j]), end=float(en[v, j]),
-                                confidence=None if math.isnan(c) else c, **extra(v, j)))
+                                confidence=None if math.isnan(c) else c, **fitted(v, j, 0), **extra(v, j)))
             out.append(dict(video_id=vid, tracks=ent))
         return out
 
@@ -97,11 +106,19 @@ class Grounding:
         pr, rd = self.pool_rank.cpu().numpy(), self.redundancy.cpu().numpy()
         return lambda v, j: dict(pool_rank=int(pr[v, j]), redundancy=None if math.isnan(rd[v, j]) else float(rd[v, j]))
 
+    def _fit_fields(self):
+        """f(v, j, i) -> {"raw_start", "raw_end", "snapped"} of moment i of result j of video v; nothing when the results were not fitted"""
+        if self.raw_start is None:
+            return lambda v, j, i: {}
+        Nv, k = self.track.shape
+        rs, re, on = (t.cpu().numpy().reshape(Nv, k, -1) for t in (self.raw_start, self.raw_end, self.onset))
+        return lambda v, j, i: dict(raw_start=float(rs[v, j, i]), raw_end=float(re[v, j, i]), snapped=bool(on[v, j, i] >= 0))
+
     def _window_records(self, video_ids: Sequence, music_ids: Sequence) -> List[dict]:
         tr, sc = self.track.cpu().numpy(), self.score.cpu().numpy()
         Nv, k = tr.shape
         st, en, cf, wi = (t.cpu().numpy().reshape(Nv, k, -1) for t in (self.start, self.end, self.confidence, self.window))
-        extra = self._diversity_fields()
+        extra, fitted = self._diversity_fields(), self._fit_fields()
         out = []
         for v, vid in enumerate(video_ids):
             ent = []
@@ -115,7 +132,7 @@ class Grounding:
                         continue
                     c = float(cf[v, j, i])
                     moms.append(dict(start=float(st[v, j, i]), end=float(en[v, j, i]), confidence=None if math.isnan(c) else c,
-                                     window_offset=float(self.windows.offset[wi[v, j, i]])))
+                                     window_offset=float(self.windows.offset[wi[v, j, i]]), **fitted(v, j, i)))
                 ent.append(dict(music_id=music_ids[m], score=float(sc[v, j]), moments=moms, **extra(v, j)))
             out.append(dict(video_id=vid, tracks=ent))
         return out
@@ -275,6 +292,117 @@ class _RowConstraints:
         return ops.eligibility(Nv, Nm, col_tags if self.all is not None else None, col_length if self.min is not None or self.max is not None else None,
                                col_key if self.start is not None else None, self.all, self.any, self.forbid, self.min, self.max,
                                self.start, self.keys, bits=bits, col_any=col_any, device=device)
+
+
+# ---------------------------------------------------------------------------------------------- fitted moments
+@dataclass
+class Fit:
+    """The optional last step of grounding: what a moment must look like to be laid under its video.
+    length: "video" (every moment as long as its video: `videos.duration`), None (a moment keeps its own length) or seconds, a
+    scalar or one entry per video.  snap: None, or the tolerance in seconds within which a moment's start is moved onto the nearest
+    onset of its track (an `Onsets` table is then needed).  At least one of the two must be given."""
+    length: object = None
+    snap: Optional[float] = None
+
+    def __post_init__(self):
+        if self.length is None and self.snap is None:
+            raise ValueError("Fit(): give length= or snap= (with neither there is nothing to fit)")
+        if isinstance(self.length, str) and self.length != "video":
+            raise ValueError(f"length = {self.length!r}: 'video', None or seconds")
+        if self.snap is not None:
+            self.snap = float(self.snap)
+            if not (math.isfinite(self.snap) and self.snap > 0.0):
+                raise ValueError(f"snap = {self.snap!r}: a tolerance in seconds, finite and > 0")
+
+
+def clamp_length(duration, n: int, max_m_duration: float) -> np.ndarray:
+    """f32 [n]: the length the moments of a column without windows are clamped to, min(max_m_duration, duration) (max_m_duration
+    where there is no duration) -- `_pair_moments`' bound"""
+    hi = np.full(n, np.float32(max_m_duration), np.float32)
+    if duration is None:
+        return hi
+    d = duration.detach().cpu().numpy() if isinstance(duration, Tensor) else np.asarray(duration)
+    return np.minimum(hi, d.astype(np.float32).reshape(-1))
+
+
+def _onsets_on(onsets, dev):
+    """the onset table's (start int64, time f32) on the device, uploaded once per (table, device)"""
+    cache = onsets.__dict__.setdefault("_device", {})
+    if str(dev) not in cache:
+        cache[str(dev)] = (torch.from_numpy(onsets.start).to(dev), torch.from_numpy(onsets.time).to(dev))
+    return cache[str(dev)]
+
+
+def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None, onsets=None, backend: Optional[str] = None) -> Grounding:
+    """`g` with every moment fitted (made_fit_moments; include/made_hip.h states the arithmetic): given the length `fit.length` asks
+    for -- centred on the grounded moment, clamped to the track -- and, with `fit.snap`, its start moved onto the track's nearest
+    onset within that tolerance that still leaves the moment inside the track.  start / end become the fitted values; raw_start /
+    raw_end keep the grounded ones, shift = start - raw_start, onset = the onset's index in the track's list (-1: not snapped).
+    Every other field is untouched, and so are entries without a track or a moment (NaN stays NaN).
+    video_duration [N_v] seconds (needed by length="video"); track_length f32 [tracks] in `g.track`'s numbering (needed always: the
+    bound the grounding clamped to); onsets: an `Onsets` table in the same numbering (needed by snap).  Entries are [N_v, k] or, over
+    windows with moments > 1, [N_v, k, n]: every moment of a track is fitted against that track, want is the video's value.
+    The window merge's suppression ran on the raw moments: two fitted moments of one track may overlap more than nms_iou.
+    backend None: the device kernel when `g` lives on a GPU, else the numpy restatement; "host": the restatement (same bits)."""
+    if g.raw_start is not None:
+        raise ValueError("this Grounding is fitted already (fit its raw_start / raw_end instead)")
+    Nv = g.track.shape[0]
+    shape = tuple(g.start.shape)
+    if track_length is None:
+        raise ValueError("fitting needs the tracks' length (track_length=...)")
+    tlen = np.ascontiguousarray((track_length.detach().cpu().numpy() if isinstance(track_length, Tensor) else np.asarray(track_length)),
+                                dtype=np.float32).reshape(-1)
+    if isinstance(fit.length, str):
+        if video_duration is None:
+            raise ValueError("Fit(length='video') needs the videos' durations (videos.duration is None)")
+        want = _seconds(video_duration, Nv, "video_duration")
+        if want.ndim != 1 or want.shape[0] != Nv:
+            raise ValueError(f"video_duration needs one entry per video ({Nv})")
+    elif fit.length is None:
+        want = np.full(Nv, np.nan, np.float32)
+    else:
+        want = _seconds(fit.length, Nv, "Fit.length")
+    tol = 0.0
+    if fit.snap is not None:
+        if onsets is None:
+            raise ValueError("Fit(snap=...) needs the tracks' onsets (onsets=..., or a library that carries them)")
+        if len(onsets) != len(tlen):
+            raise ValueError(f"the onset table holds {len(onsets)} tracks, there are {len(tlen)}")
+        tol = fit.snap
+    if backend is None:
+        backend = None if g.start.is_cuda else "host"
+    dev = g.start.device
+    expand = lambda t: t.reshape((Nv,) + (1,) * (len(shape) - 1)).expand(shape).contiguous().reshape(-1)
+    if backend == "host":
+        out = ops.fit_moments(g.start.reshape(-1), g.end.reshape(-1), _entry_tracks(g.track, shape), expand(torch.from_numpy(want)), tlen,
+                              None if tol == 0.0 else onsets.start, None if tol == 0.0 else onsets.time, tol, backend="host")
+        st, en, sh, on = (torch.from_numpy(a).to(dev).view(shape) for a in out)
+    else:
+        table = (None, None) if tol == 0.0 else _onsets_on(onsets, dev)
+        st, en, sh, on = (t.view(shape) for t in ops.fit_moments(
+            g.start.to(torch.float32).contiguous().reshape(-1), g.end.to(torch.float32).contiguous().reshape(-1),
+            _entry_tracks(g.track, shape), expand(torch.from_numpy(want).to(dev)), torch.from_numpy(tlen).to(dev), table[0], table[1], tol))
+    return replace(g, start=st, end=en, raw_start=g.start, raw_end=g.end, shift=sh, onset=on)
+
+
+def _check_fit(fit: Optional[Fit], videos: Encoded, onsets) -> None:
+    """the ValueErrors of `fit_grounding` that need no result, raised before anything is computed"""
+    if fit is None:
+        return
+    if not isinstance(fit, Fit):
+        raise TypeError(f"fit must be a Fit, got {type(fit).__name__}")
+    if isinstance(fit.length, str) and videos.duration is None:
+        raise ValueError("Fit(length='video') needs the videos' durations (videos.duration is None)")
+    if fit.snap is not None and onsets is None:
+        raise ValueError("Fit(snap=...) needs the tracks' onsets (onsets=..., or a library that carries them)")
+
+
+def _entry_tracks(track: Tensor, shape) -> Tensor:
+    """int32 [entries]: every entry's track -- `track` [N_v, k] repeated over a trailing moments dimension"""
+    t = track.to(torch.int32)
+    if len(shape) == 3:
+        t = t.unsqueeze(-1).expand(shape)
+    return t.contiguous().reshape(-1)
 
 
 @_lib.scoped_f32_products
@@ -572,7 +700,7 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
            pair_batch: int = 64, windows: Optional[Windows] = None, windows_per_track: int = 1, moments: int = 1,
            nms_iou: float = 0.5, constraints: Optional[Constraints] = None, tags=None, length=None,
            shortlist: Optional[int] = None, diversity: Optional[float] = None, max_similarity: Optional[float] = None,
-           pool: Optional[int] = None, candidates=None) -> Grounding:
+           pool: Optional[int] = None, candidates=None, fit: Optional[Fit] = None, onsets=None) -> Grounding:
     """Each video's best k tracks (groups of columns sharing a music id when group_id [N_m] is given) and the moment in each.
     constraints: per-video `Constraints` on the tracks' `tags` (int64 [tracks]) and `length` (f32 seconds [tracks]; default: the
     durations) -- the selection then runs on every row with its ineligible columns removed (made_eligibility, then the masked
@@ -595,12 +723,17 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     each video's best P groups, and made_mmr_select picks k of them greedily -- each time the group with the largest score - mu *
     (largest cosine of its representative column's `vec` with a group picked before), groups whose cosine with a pick exceeds tau
     dropped.  Only the k kept are localized; `score` stays the similarity, `Grounding.pool_rank` / `redundancy` [N_v, k] report each
-    result's rank in the pool and that largest cosine."""
+    result's rank in the pool and that largest cosine.
+    fit = Fit(length=, snap=) (default None: nothing below runs): the finished Grounding goes through `fit_grounding` -- every moment
+    given its video's length (or the seconds asked for), kept inside its track, its start moved onto the track's nearest onset
+    within `snap` seconds.  onsets: the `Onsets` table of the tracks, in `Grounding.track`'s numbering (mgsv_amd/onsets.py).  The
+    track length is what the moments were clamped to: min(max_m_duration, duration) per column, `default_length` over windows."""
     dev = engine.device
     Nv, Nm = len(videos), len(music)
     candidates = check_candidates(engine.cfg, candidates, Nv, shortlist, sims is not None)
     shortlist = check_shortlist(engine.cfg, shortlist, sims is not None)
     div = check_diversity(k, diversity, max_similarity, pool)
+    _check_fit(fit, videos, onsets)
     if shortlist is None and candidates is None:
         if sims is None:
             sims = similarity_matrix(engine, videos.vec, music.tokens, music.mask, music.vec)
@@ -641,8 +774,9 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
         tokens = music.tokens.to(dev, engine.tc).contiguous()
         cand = (ccol, _score_candidates(engine, video, ccol, ccos, _device_fetch(tokens, music.mask.to(dev, torch.float32).contiguous()), 4096))
     if windows is not None:
-        return _ground_windows(engine, videos, music, k, sims, group_id, pair_batch, windows, windows_per_track, moments, float(nms_iou),
-                               bits, cand, div)
+        g = _ground_windows(engine, videos, music, k, sims, group_id, pair_batch, windows, windows_per_track, moments, float(nms_iou),
+                            bits, cand, div)
+        return g if fit is None else fit_grounding(g, fit, videos.duration, default_length(music.duration, windows), onsets)
     gid, G = _group_tensor(group_id, Nm, dev)
     kk = max(1, min(int(k), G))
     ks = _pool_size(div, kk, G)
@@ -658,9 +792,10 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     mi = track.reshape(-1)
     mi = torch.where(mi < 0, torch.zeros_like(mi), mi)             # (no track: localized against track 0, reported as -1 / NaN)
     start, end, conf = _pair_moments(engine, videos, music, vi, mi, track.reshape(-1) < 0, pair_batch)
-    return Grounding(track=track, score=score, start=start.view(Nv, kk), end=end.view(Nv, kk), confidence=conf.view(Nv, kk),
-                     cand_col=None if cand is None else cand[0], cand_score=None if cand is None else cand[1],
-                     pool_rank=pool_rank, redundancy=redundancy)
+    g = Grounding(track=track, score=score, start=start.view(Nv, kk), end=end.view(Nv, kk), confidence=conf.view(Nv, kk),
+                  cand_col=None if cand is None else cand[0], cand_score=None if cand is None else cand[1],
+                  pool_rank=pool_rank, redundancy=redundancy)
+    return g if fit is None else fit_grounding(g, fit, videos.duration, clamp_length(music.duration, Nm, engine.cfg.max_m_duration), onsets)
 
 
 def _pad_pairs(vi: Tensor, mi: Tensor, min_pairs: int):
@@ -1238,7 +1373,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
                    moments: int = 1, nms_iou: float = 0.5, chunk_cols: int = 4096, video_batch: int = 1024, sims_fn=None,
                    timings: Optional[dict] = None, constraints: Optional[Constraints] = None, compact: Optional[bool] = None,
                    shortlist: Optional[int] = None, diversity: Optional[float] = None, max_similarity: Optional[float] = None,
-                   pool: Optional[int] = None, candidates=None) -> Grounding:
+                   pool: Optional[int] = None, candidates=None, fit: Optional[Fit] = None) -> Grounding:
     """`ground()` for a stored library (mgsv_amd.library.MusicLibrary: host arrays, a memory-mapped directory, or device tensors):
     the same Grounding, bit for bit, as
         ground(engine, videos, library.as_encoded(dev), k, group_id=library.group_id, windows=library.windows, ...)
@@ -1270,12 +1405,17 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     Host chunks and column sets are staged and uploaded as bytes and exponents -- half the traffic -- and one
     made_fp8_dequantize_rows launch widens each to bf16 on the compute stream in front of the kernels that read it; a device
     library's slices and listed columns are widened into a scratch buffer; localization and the shortlist's second stage gather
-    and widen the distinct selected columns (the whole library is never widened).  timings then receives dequantize_ms."""
+    and widen the distinct selected columns (the whole library is never widened).  timings then receives dequantize_ms.
+    fit = Fit(length=, snap=): `ground(..., fit=fit, onsets=library.onsets)` for the stored library, bit for bit, in every placement:
+    one made_fit_moments launch on the finished Grounding (`fit_grounding`) against `library.fit_length` and `library.onsets`.
+    fit None (the default): none of it runs."""
     c = engine.cfg
     dev = engine.device
     candidates = check_candidates(c, candidates, len(videos), shortlist, sims_fn is not None)
     shortlist = check_shortlist(c, shortlist, sims_fn is not None)
     div = check_diversity(k, diversity, max_similarity, pool)
+    if fit is not None:
+        _check_fit(fit, videos, library.onsets)
     if c.moment_query_type == "xpool":
         raise NotImplementedError("moment_query_type=xpool: the decoder query is the track's pooled vector averaged over the videos of "
                                   "the batch (reference model/model_Uni.py:222-223), a property of the batch with no per-pair meaning")
@@ -1375,11 +1515,13 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
             timings["dequantize_ms"] = deq.total_ms()
     cc, cs = (None, None) if cand is None else cand
     if windows is None:
-        return Grounding(track=rep, score=score, start=start, end=end, confidence=conf, cand_col=cc, cand_score=cs,
-                         pool_rank=pool_rank, redundancy=redundancy)
-    return Grounding(track=_window_tracks(rep, track_of_col), score=score, start=start, end=end, confidence=conf,
-                     window=torch.cat([p[3] for p in parts]), windows=windows, cand_col=cc, cand_score=cs,
-                     pool_rank=pool_rank, redundancy=redundancy)
+        g = Grounding(track=rep, score=score, start=start, end=end, confidence=conf, cand_col=cc, cand_score=cs,
+                      pool_rank=pool_rank, redundancy=redundancy)
+    else:
+        g = Grounding(track=_window_tracks(rep, track_of_col), score=score, start=start, end=end, confidence=conf,
+                      window=torch.cat([p[3] for p in parts]), windows=windows, cand_col=cc, cand_score=cs,
+                      pool_rank=pool_rank, redundancy=redundancy)
+    return g if fit is None else fit_grounding(g, fit, videos.duration, library.fit_length(c.max_m_duration), library.onsets)
 
 
 def moment_iou(start: Tensor, end: Tensor, gt_moment: Tensor, m_duration: Tensor, max_m_duration: float) -> Tensor:

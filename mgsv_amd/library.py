@@ -11,6 +11,9 @@ arrays tokens [N, S, D] (float32, or uint16 holding bf16 bit patterns), mask [N,
 source [N] int64, optionally duration [N] f32, win_track int32 / win_offset f32 / win_duration f32 [N], track_group [n_tracks]
 int32, and ids.json.  Optional track attributes for `ground_library(..., constraints=...)`: tags.npy int64 and length.npy f32, one
 entry per track, named by the manifest's "attributes" {tags, length, tag_names}; a manifest without that entry has none.
+Optional onsets for `ground_library(..., fit=Fit(snap=...))` (mgsv_amd/onsets.py): onset_start.npy int64 [n_tracks + 1] and
+onset_time.npy f32, the tracks' onsets as a CSR, and the manifest's "onsets" entry holding the detection parameters; a directory
+without them loads as a library without onsets.
 
 FP8 token storage (dtype "fp8"): tokens.npy is uint8 [N, S, D], one OCP e4m3fn byte per value, and tokens_exp.npy int8 [N, S] holds
 one power-of-two exponent per token row (the format: include/made_hip.h, csrc/fp8_format.h); the manifest says "dtype": "fp8" and
@@ -192,7 +195,7 @@ class MusicLibrary:
 
     def __init__(self, tokens, mask, vec, col_group, source, dtype: str, duration=None, windows: Optional[Windows] = None,
                  ids: Optional[Sequence] = None, group_id=None, tags=None, length=None, tag_names: Optional[Sequence[str]] = None,
-                 tokens_exp=None, compute: Optional[str] = None):
+                 tokens_exp=None, compute: Optional[str] = None, onsets=None):
         if dtype not in ("f32", "bf16", "fp8"):
             raise ValueError(f"dtype = {dtype!r}: a library holds f32, bf16 or fp8 tokens")
         self.tokens, self.mask, self.vec, self.duration = tokens, mask, vec, duration
@@ -240,6 +243,8 @@ class MusicLibrary:
                 raise ValueError(f"{name} needs one entry per track ({self.n_tracks}), got {len(a)}")
         if self.tag_names is not None and (len(self.tag_names) > 64 or len(set(self.tag_names)) != len(self.tag_names)):
             raise ValueError("tag_names: at most 64 distinct names, bit i <-> tag_names[i]")
+        self.onsets = None
+        self.set_onsets(onsets)
         self._device_attrs: Dict[str, tuple] = {}                  # ground_library's column attributes, uploaded once per device
         self._plans: Dict[int, dict] = {}
         self._stages: Dict[str, object] = {}                       # ground_library's pinned staging sets, reused across calls
@@ -281,6 +286,23 @@ class MusicLibrary:
             out |= 1 << table[n]
         return out
 
+    def set_onsets(self, onsets) -> None:
+        """Attach (or with None remove) the tracks' onset table, an `mgsv_amd.onsets.Onsets` with one entry per track in this
+        library's numbering (`ids`' order)."""
+        if onsets is not None and len(onsets) != self.n_tracks:
+            raise ValueError(f"onsets needs one entry per track ({self.n_tracks}), got {len(onsets)}")
+        self.onsets = onsets
+
+    def fit_length(self, max_m_duration: float) -> np.ndarray:
+        """f32 [tracks]: the length `ground_library` clamps a track's moments to, and `fit_grounding` fits them in: min(max_m_duration,
+        duration) per column without windows, the end of the track's last window with them (computed once)."""
+        key = ("fit_length", float(max_m_duration))
+        if key not in self._device_attrs:
+            from .grounding import clamp_length, default_length
+            self._device_attrs[key] = (default_length(None, self.windows) if self.windows is not None
+                                       else clamp_length(self.duration, len(self), max_m_duration))
+        return self._device_attrs[key]
+
     def track_length(self) -> Optional[np.ndarray]:
         """f32 [tracks]: `length`, or by default the column's duration / the end of the track's last window (None: neither)"""
         if self.length is not None:
@@ -316,11 +338,12 @@ class MusicLibrary:
     # ------------------------------------------------------------------ construction
     @classmethod
     def build(cls, music: Encoded, group_id=None, windows: Optional[Windows] = None, ids: Optional[Sequence] = None, tags=None,
-              length=None, tag_names: Optional[Sequence[str]] = None) -> "MusicLibrary":
+              length=None, tag_names: Optional[Sequence[str]] = None, onsets=None) -> "MusicLibrary":
         """A host library of an `Encoded` (device or host tensors).  group_id: one entry per column, or per TRACK with windows.
         Columns are reordered only if a group's columns are not contiguous: groups by first appearance, stable inside a group.
         The Windows keep their track numbering; only the per-column arrays are permuted (and `ids`, one per column, without
-        windows).  tags (int64) / length (f32 seconds): one entry per track, permuted like `ids`."""
+        windows).  tags (int64) / length (f32 seconds): one entry per track, permuted like `ids`.  onsets: an `Onsets` table
+        (mgsv_amd/onsets.py), one entry per track, permuted like `ids`, too."""
         N = len(music)
         gid = None if group_id is None else _host(group_id, np.int32).reshape(-1)
         if windows is not None:
@@ -349,6 +372,10 @@ class MusicLibrary:
         for name, a in (("tags", tags), ("length", length)):
             if a is not None and len(a) != (windows.n_tracks if windows is not None else N):
                 raise ValueError(f"{name} needs one entry per track")
+        if onsets is not None and len(onsets) != (windows.n_tracks if windows is not None else N):
+            raise ValueError("onsets needs one entry per track")
+        if windows is None and onsets is not None and not same:
+            onsets = onsets.take(order)
         if windows is None:
             if ids is not None and not same:
                 ids = [ids[i] for i in order]
@@ -357,7 +384,7 @@ class MusicLibrary:
             length = None if length is None else take(length)
         return cls(take(_tokens_to_host(music.tokens)), take(_host(music.mask, np.float32)), take(_host(music.vec, np.float32)),
                    take(col_group), order, _dtype_name(music.tokens.dtype), duration=dur, windows=win, ids=ids, group_id=gid,
-                   tags=tags, length=length, tag_names=tag_names)
+                   tags=tags, length=length, tag_names=tag_names, onsets=onsets)
 
     def to(self, device) -> "MusicLibrary":
         """The same library with tokens / mask / vec / duration as tensors on `device` (the host tables stay on the host)."""
@@ -367,7 +394,8 @@ class MusicLibrary:
         return MusicLibrary(tok, up(self.mask), up(self.vec), self.col_group, self.source, self.dtype,
                             duration=None if self.duration is None else up(self.duration), windows=self.windows, ids=self.ids,
                             group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
-                            tokens_exp=None if self.tokens_exp is None else up(self.tokens_exp), compute=self._compute_arg)
+                            tokens_exp=None if self.tokens_exp is None else up(self.tokens_exp), compute=self._compute_arg,
+                            onsets=self.onsets)
 
     def pin(self) -> "MusicLibrary":
         """The same library with tokens / mask / vec / duration copied into pinned host tensors: `ground_library` uploads its
@@ -377,7 +405,8 @@ class MusicLibrary:
         return MusicLibrary(tok.pin_memory(), pin(self.mask), pin(self.vec), self.col_group, self.source, self.dtype,
                             duration=None if self.duration is None else pin(self.duration), windows=self.windows, ids=self.ids,
                             group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
-                            tokens_exp=None if self.tokens_exp is None else pin(self.tokens_exp), compute=self._compute_arg)
+                            tokens_exp=None if self.tokens_exp is None else pin(self.tokens_exp), compute=self._compute_arg,
+                            onsets=self.onsets)
 
     @property
     def pinned(self) -> bool:
@@ -403,7 +432,7 @@ class MusicLibrary:
         """this library with other tokens"""
         return MusicLibrary(tokens, self.mask, self.vec, self.col_group, self.source, dtype, duration=self.duration, windows=self.windows,
                             ids=self.ids, group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
-                            tokens_exp=tokens_exp)
+                            tokens_exp=tokens_exp, onsets=self.onsets)
 
     def quantize(self, device=None) -> "MusicLibrary":
         """The FP8 library of a bf16 library: the same arrays with the tokens as e4m3fn bytes and one power-of-two exponent per
@@ -473,7 +502,8 @@ class MusicLibrary:
             sv("duration", self.duration)
         _write_tables(path, self.windows, self.group_id, self.ids)
         _write_manifest(path, self.dtype, len(self), self.S, self.D, self.duration is not None, self.windows, self.ids is not None,
-                        self.group_id is not None, _write_attributes(path, self.tags, self.length, self.tag_names), self._compute_arg)
+                        self.group_id is not None, _write_attributes(path, self.tags, self.length, self.tag_names), self._compute_arg,
+                        write_onsets(path, self.onsets))
 
     @classmethod
     def load(cls, path: str, mmap: bool = True) -> "MusicLibrary":
@@ -512,7 +542,7 @@ class MusicLibrary:
                    duration=ld("duration") if man["duration"] else None, windows=windows, ids=ids, group_id=group_id,
                    tags=np.load(os.path.join(path, "tags.npy")) if attr.get("tags") else None,
                    length=np.load(os.path.join(path, "length.npy")) if attr.get("length") else None, tag_names=attr.get("tag_names"),
-                   tokens_exp=tokens_exp, compute=man.get("compute") if man["dtype"] == "fp8" else None)
+                   tokens_exp=tokens_exp, compute=man.get("compute") if man["dtype"] == "fp8" else None, onsets=_read_onsets(path, man))
 
     # ------------------------------------------------------------------ the chunk plan
     def chunk_plan(self, chunk_cols: int) -> List[Tuple[int, int]]:
@@ -620,8 +650,30 @@ def _write_attributes(path: str, tags, length, tag_names) -> Optional[dict]:
     return dict(tags=tags is not None, length=length is not None, tag_names=None if tag_names is None else list(tag_names))
 
 
+def write_onsets(path: str, onsets) -> Optional[dict]:
+    """onset_start.npy / onset_time.npy and the manifest's "onsets" entry, the detection parameters (None, and no files, for a
+    library without onsets)"""
+    if onsets is None:
+        for name in ("onset_start.npy", "onset_time.npy"):         # (a table an earlier save left here is not this library's)
+            if os.path.isfile(os.path.join(path, name)):
+                os.remove(os.path.join(path, name))
+        return None
+    np.save(os.path.join(path, "onset_start.npy"), np.ascontiguousarray(onsets.start, dtype=np.int64))
+    np.save(os.path.join(path, "onset_time.npy"), np.ascontiguousarray(onsets.time, dtype=np.float32))
+    return dict(onsets.params)
+
+
+def _read_onsets(path: str, man: dict):
+    """the stored onset table, None when the directory has none"""
+    a, b = os.path.join(path, "onset_start.npy"), os.path.join(path, "onset_time.npy")
+    if not (os.path.isfile(a) and os.path.isfile(b)):
+        return None
+    from .onsets import Onsets
+    return Onsets(np.load(a), np.load(b), dict(man.get("onsets") or {}))
+
+
 def _write_manifest(path: str, dtype: str, N: int, S: int, D: int, duration: bool, windows: Optional[Windows], ids: bool,
-                    grouped: bool, attributes: Optional[dict] = None, compute: Optional[str] = None) -> None:
+                    grouped: bool, attributes: Optional[dict] = None, compute: Optional[str] = None, onsets: Optional[dict] = None) -> None:
     man = dict(format=FORMAT, version=VERSION, dtype=dtype, N=int(N), S=int(S), D=int(D), duration=bool(duration),
                windows=windows is not None, ids=bool(ids), grouped=bool(grouped),
                n_tracks=int(windows.n_tracks) if windows is not None else None)
@@ -629,6 +681,8 @@ def _write_manifest(path: str, dtype: str, N: int, S: int, D: int, duration: boo
         man["attributes"] = attributes
     if compute is not None:                                        # an FP8 library: the dtype its tokens are widened to
         man["compute"] = compute
+    if onsets is not None:                                         # the detection parameters of onset_start.npy / onset_time.npy
+        man["onsets"] = onsets
     with open(os.path.join(path, "manifest.json"), "w") as f:
         json.dump(man, f, indent=1)
         f.write("\n")

@@ -288,6 +288,49 @@ def _desc_tensor(a: np.ndarray, device) -> Tensor:
     return torch.from_numpy(a.view(np.uint8).reshape(len(a), a.dtype.itemsize)).to(device)
 
 
+# ------------------------------------------------------------------------------------------------ resample (the launch)
+def resample_tracks(tracks: Sequence, device, max_m_duration: float = 240, out_len: Optional[int] = None) -> Tuple[Tensor, List[int]]:
+    """Channel 0 of every (waveform, sr) at 16 kHz on `device`, zero-padded / truncated: (f32 [N, int(16000 max_m_duration)], the
+    resampled lengths before padding).  out_len: that many samples per row instead (whole tracks).  Needs no weights:
+    `MusicEncoder.resample` is this function, and mgsv_amd/onsets.py calls it without an encoder."""
+    dev = torch.device(device)
+    total = int(SR * max_m_duration) if out_len is None else int(out_len)
+    chans = [_channel0(w) for w, _ in tracks]
+    rates = [int(sr) for _, sr in tracks]
+    n = len(chans)
+    if n > TRACKS_MAX:
+        raise ValueError(f"{n} tracks in one call (at most {TRACKS_MAX})")
+    out = torch.empty(n, total, device=dev)
+    if n == 0:
+        return out, []
+    for sr in set(rates):
+        check_rate(sr)
+    lens = [int(c.shape[0]) for c in chans]
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    if all(c.device == dev for c in chans):
+        pcm = torch.cat([c.reshape(-1) for c in chans]) if n > 1 else chans[0].contiguous()
+    else:
+        pcm = torch.cat([c.reshape(-1).cpu() for c in chans]).to(dev)
+    if pcm.numel() == 0:
+        pcm = torch.zeros(1, device=dev)
+    desc = np.zeros(n, _RDESC)
+    blocks, where, pos = [], {}, 0
+    for i, sr in enumerate(rates):
+        if sr == SR:
+            desc[i] = (offs[i], lens[i], 0, 1, 1, 0, 0)
+            continue
+        o, m, width = resample_params(sr)
+        if sr not in where:
+            kt = np.ascontiguousarray(resample_taps(sr).T).reshape(-1)        # k-major
+            where[sr] = pos
+            blocks.append(kt)
+            pos += kt.size
+        desc[i] = (offs[i], lens[i], where[sr], o, m, width, 0)
+    taps = torch.from_numpy(np.concatenate(blocks) if blocks else np.zeros(1, np.float32)).to(dev)
+    ops.audio_resample(pcm, _desc_tensor(desc, dev), taps, out)
+    return out, [resampled_length(ln, sr) for ln, sr in zip(lens, rates)]
+
+
 # ------------------------------------------------------------------------------------------------ the encoder
 class MusicEncoder:
     """AST (AudioSet, DeiT-base distilled, input_tdim 1024) on gfx950, from decoded waveforms to [N, S, 768] f32 segment features.
@@ -363,42 +406,7 @@ class MusicEncoder:
     def resample(self, tracks: Sequence, max_m_duration: float = 240, out_len: Optional[int] = None) -> Tuple[Tensor, List[int]]:
         """Channel 0 of every (waveform, sr) at 16 kHz, zero-padded / truncated: (f32 [N, int(16000 max_m_duration)], the resampled
         lengths before padding).  out_len: that many samples per row instead (encode_windows: whole tracks)."""
-        dev = self.device
-        total = int(SR * max_m_duration) if out_len is None else int(out_len)
-        chans = [_channel0(w) for w, _ in tracks]
-        rates = [int(sr) for _, sr in tracks]
-        n = len(chans)
-        if n > TRACKS_MAX:
-            raise ValueError(f"{n} tracks in one call (at most {TRACKS_MAX})")
-        out = torch.empty(n, total, device=dev)
-        if n == 0:
-            return out, []
-        for sr in set(rates):
-            check_rate(sr)
-        lens = [int(c.shape[0]) for c in chans]
-        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-        if all(c.device == dev for c in chans):
-            pcm = torch.cat([c.reshape(-1) for c in chans]) if n > 1 else chans[0].contiguous()
-        else:
-            pcm = torch.cat([c.reshape(-1).cpu() for c in chans]).to(dev)
-        if pcm.numel() == 0:
-            pcm = torch.zeros(1, device=dev)
-        desc = np.zeros(n, _RDESC)
-        blocks, where, pos = [], {}, 0
-        for i, sr in enumerate(rates):
-            if sr == SR:
-                desc[i] = (offs[i], lens[i], 0, 1, 1, 0, 0)
-                continue
-            o, m, width = resample_params(sr)
-            if sr not in where:
-                kt = np.ascontiguousarray(resample_taps(sr).T).reshape(-1)        # k-major
-                where[sr] = pos
-                blocks.append(kt)
-                pos += kt.size
-            desc[i] = (offs[i], lens[i], where[sr], o, m, width, 0)
-        taps = torch.from_numpy(np.concatenate(blocks) if blocks else np.zeros(1, np.float32)).to(dev)
-        ops.audio_resample(pcm, _desc_tensor(desc, dev), taps, out)
-        return out, [resampled_length(ln, sr) for ln, sr in zip(lens, rates)]
+        return resample_tracks(tracks, self.device, max_m_duration, out_len)
 
     @torch.no_grad()
     def fbank_tracks(self, tracks: Sequence, stride: float = 2.5, filter: float = 4.0, max_m_duration: float = 240

@@ -1225,6 +1225,135 @@ def merge_moments(cand: Tensor, win_col: Tensor, win_score: Tensor, offset: Tens
     return start, end, conf, window
 
 
+def onset_strength(logmel: Tensor, n_frames: Tensor, lag: int = 2, env: Optional[Tensor] = None) -> Tensor:
+    """made_onset_strength: env [N, env_ld] f32, the spectral flux of logmel [N, F_ld, 128] f32 (contiguous) over `lag` frames:
+    the mean over the bins of max(0, x[f] - x[f - lag]) for lag <= f < n_frames[t] (int32 [N]), 0 elsewhere; a track with n_frames >
+    F_ld gets a NaN row.  env: a contiguous [N, env_ld] f32 tensor to write into (default: env_ld = F_ld)."""
+    assert logmel.dim() == 3 and logmel.shape[2] == 128 and logmel.dtype == torch.float32 and logmel.is_contiguous()
+    N, F_ld = logmel.shape[0], logmel.shape[1]
+    assert n_frames.dtype == torch.int32 and n_frames.is_contiguous() and n_frames.numel() == N
+    if env is None:
+        env = torch.empty(N, F_ld, device=logmel.device, dtype=torch.float32)
+    assert env.dim() == 2 and env.shape[0] == N and env.dtype == torch.float32 and env.is_contiguous()
+    check(lib().made_onset_strength(_p(logmel) if logmel.numel() else None, F_ld, _p(n_frames), N, int(lag),
+                                    _p(env) if env.numel() else None, env.shape[1], _stream()), "made_onset_strength")
+    return env
+
+
+def onset_peaks(env: Tensor, n_frames: Tensor, w_max: int = 5, w_avg: int = 50, delta: float = 0.05, time: Optional[Tensor] = None,
+                count: Optional[Tensor] = None):
+    """made_onset_peaks: (time [N, cap] f32, count [N] int32) of the envelopes env [N, env_ld] f32 (contiguous): the frames f <
+    n_frames[t] that are positive, a local maximum over w_max frames either side (the earlier of equal values) and at least delta
+    above the mean over w_avg frames either side, ascending, as f * 0.01 seconds.  Only time[t, :count[t]] is written.  time / count:
+    tensors to write into (default: new ones, cap = ceil(env_ld / (w_max + 1)), which cannot overflow)."""
+    assert env.dim() == 2 and env.dtype == torch.float32 and env.is_contiguous()
+    N, env_ld = env.shape
+    assert n_frames.dtype == torch.int32 and n_frames.is_contiguous() and n_frames.numel() == N
+    if time is None:
+        w = max(int(w_max), 1)
+        time = torch.empty(N, (env_ld + w) // (w + 1), device=env.device, dtype=torch.float32)
+    if count is None:
+        count = torch.empty(N, device=env.device, dtype=torch.int32)
+    assert time.dim() == 2 and time.shape[0] == N and time.dtype == torch.float32 and time.is_contiguous()
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == N
+    check(lib().made_onset_peaks(_p(env) if env.numel() else None, env_ld, _p(n_frames), N, int(w_max), int(w_avg), float(delta),
+                                 time.shape[1], _p(time) if time.numel() else None, _p(count), _stream()), "made_onset_peaks")
+    return time, count
+
+
+def fit_moments_host(start, end, track, want, tlen, onset_start=None, onset_time=None, tol: float = 0.0):
+    """made_fit_moments restated in numpy float32, one rounded operation per step (include/made_hip.h states the contract): the
+    same bits as the kernel.  Arrays of E entries -> (out_start, out_end, shift f32 [E], onset int32 [E])."""
+    import numpy as np
+    f32 = np.float32
+    tol = float(tol)
+    if not (math.isfinite(tol) and tol >= 0.0):
+        raise ValueError(f"tol = {tol!r}: must be finite and >= 0")
+    start, end, want = (np.ascontiguousarray(a, dtype=f32).reshape(-1) for a in (start, end, want))
+    track = np.ascontiguousarray(track).astype(np.int64).reshape(-1)
+    tlen = np.ascontiguousarray(tlen, dtype=f32).reshape(-1)
+    E, n_tracks = len(start), len(tlen)
+    assert len(end) == E and len(want) == E and len(track) == E
+    pmax = lambda a, b: np.where(a > b, a, b)
+    pmin = lambda a, b: np.where(a < b, a, b)
+    zero, half, nan = np.zeros(E, f32), f32(0.5), f32(np.nan)
+    in_range = (track >= 0) & (track < n_tracks)
+    tr = np.where(in_range, track, 0)
+    T = np.where(in_range, tlen[tr] if n_tracks else nan, nan).astype(f32)
+    none = np.isnan(start) | np.isnan(end) | np.isnan(T)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ln = np.where(np.isnan(want), end - start, want).astype(f32)
+        ln = pmin(pmax(ln, zero), T)
+        c = half * (start + end)
+        last = T - ln
+        s1 = pmin(pmax(c - half * ln, zero), last)
+        s2 = s1.copy()
+        which = np.full(E, -1, np.int32)
+        if tol > 0.0:
+            if onset_start is None or onset_time is None:
+                raise ValueError("tol > 0 needs the onset table")
+            ostart = np.ascontiguousarray(onset_start, dtype=np.int64).reshape(-1)
+            otime = np.ascontiguousarray(onset_time, dtype=f32).reshape(-1)
+            assert len(ostart) == n_tracks + 1
+            n = len(otime)
+            a = np.clip(ostart[tr], 0, n)
+            b = np.clip(np.maximum(ostart[tr + 1], a), 0, n)
+            a, b = np.where(none, 0, a), np.where(none, 0, b)
+            pad = np.concatenate([otime, np.zeros(1, f32)])          # (a read at n is masked out below)
+            lo, hi = a.copy(), b.copy()
+            while (lo < hi).any():                                 # the first onset >= s1, every entry's search in step
+                live = lo < hi
+                mid = lo + ((hi - lo) >> 1)
+                less = pad[np.minimum(mid, n)] < s1
+                lo = np.where(live & less, mid + 1, lo)
+                hi = np.where(live & ~less, mid, hi)
+            t32 = f32(tol)
+            ol = pad[np.clip(lo - 1, 0, n)]
+            dl = np.abs(ol - s1)
+            take_l = (lo > a) & (dl <= t32) & (ol <= last)
+            orr = pad[np.minimum(lo, n)]
+            dr = np.abs(orr - s1)
+            take_r = (lo < b) & (dr <= t32) & (orr <= last) & (~take_l | (dr < dl))
+            s2 = np.where(take_r, orr, np.where(take_l, ol, s1)).astype(f32)
+            which = np.where(take_r, lo - a, np.where(take_l, lo - 1 - a, -1)).astype(np.int32)
+        out_start = np.where(none, nan, s2).astype(f32)
+        out_end = np.where(none, nan, s2 + ln).astype(f32)
+        shift = np.where(none, nan, s2 - start).astype(f32)
+    return out_start, out_end, shift, np.where(none, -1, which).astype(np.int32)
+
+
+def fit_moments(start, end, track, want, tlen, onset_start=None, onset_time=None, tol: float = 0.0, backend: Optional[str] = None):
+    """made_fit_moments: every moment (start, end f32 [E], seconds on the axis of track [E] int32, -1: none) given the length want
+    [E] f32 (NaN: its own), kept inside [0, tlen[track]] and, with tol > 0, its start moved onto the track's nearest onset within
+    tol seconds that still leaves the moment inside the track (onset_start int64 [n_tracks + 1], onset_time f32: a CSR, ascending
+    inside a track) -> (out_start, out_end, shift f32 [E], onset int32 [E] the onset's index inside the track, -1: not snapped).
+    backend None: device tensors in and out, one launch.  backend "host": arrays or host tensors in, numpy arrays out, by
+    `fit_moments_host` -- the same bits, on any machine."""
+    if backend == "host":
+        host = lambda a: None if a is None else (a.detach().cpu().numpy() if isinstance(a, Tensor) else a)
+        return fit_moments_host(*(host(a) for a in (start, end, track, want, tlen, onset_start, onset_time)), tol=tol)
+    if backend is not None:
+        raise ValueError(f"backend = {backend!r}: None (the device) or 'host'")
+    for t in (start, end, want, tlen):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert track.dtype == torch.int32 and track.is_contiguous()
+    E = start.numel()
+    assert end.numel() == E and want.numel() == E and track.numel() == E
+    n_tracks, n_onsets = tlen.numel(), 0
+    if onset_start is not None:
+        assert onset_start.dtype == torch.int64 and onset_start.is_contiguous() and onset_start.numel() == n_tracks + 1
+        assert onset_time is not None and onset_time.dtype == torch.float32 and onset_time.is_contiguous()
+        n_onsets = onset_time.numel()
+    dev = start.device
+    out_start, out_end, shift = (torch.empty(E, device=dev, dtype=torch.float32) for _ in range(3))
+    onset = torch.empty(E, device=dev, dtype=torch.int32)
+    ptr = lambda t: _p(t) if t is not None and t.numel() else None
+    check(lib().made_fit_moments(ptr(start), ptr(end), ptr(track), ptr(want), E, ptr(tlen), n_tracks, _p(onset_start),
+                                 ptr(onset_time) if onset_start is not None else None, n_onsets, float(tol), ptr(out_start), ptr(out_end),
+                                 ptr(shift), ptr(onset), _stream()), "made_fit_moments")
+    return out_start, out_end, shift, onset
+
+
 def mmr_select(row: Tensor, score: Tensor, vec: Tensor, k: int, mu: float = 0.0, tau: float = float("inf")):
     """made_mmr_select: the greedy re-selection of k of every video's P pool slots -- row [Nv, P] int32 (the slot's row of vec, < 0:
     absent), score [Nv, P] f32, vec [n_rows, D] f32 contiguous -> (pos [Nv, k] int32 the picked slots in pick order, -1 past the last;
