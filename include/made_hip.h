@@ -844,14 +844,15 @@ int made_layernorm_bwd(const void* x, int32_t x_dtype, int64_t ldx, int64_t x_ro
 
 /* made_pool_bwd: backward of vec = normalize(masked_mean(local)) (reference model/model_Base.py:579-580,615-616) merged with
  *   the other gradients of `local`: out[b,t,:] = mask[b,t] * (in1[b,t,:] + in2[b,t,:] + dmean[b,:] / count_b),
- *   dmean = (dvec - vhat (vhat.dvec)) / max(|mean|, eps).  in1 / in2 may be NULL. */
+ *   dmean = (dvec - vhat (vhat.dvec)) / |mean|, and dvec / eps where |mean| < eps (F.normalize's clamp divides by a constant:
+ *   no projection term).  in1 / in2 may be NULL. */
 int made_pool_bwd(const float* mean, const float* dvec, const float* mask,
                   const void* in1, int32_t in1_dtype, int64_t in1_bs, int64_t in1_ld,
                   const void* in2, int32_t in2_dtype, int64_t in2_bs, int64_t in2_ld,
                   void* out, int32_t out_dtype, int64_t out_bs, int64_t out_ld,
                   int64_t B, int64_t T, int64_t D, float eps, void* stream);
 
-/* made_l2norm_bwd: y = x / max(|x|, eps)  ->  dx = (dy - yhat (yhat.dy)) / max(|x|, eps); dx f32 (stored or accumulated)
+/* made_l2norm_bwd: y = x / max(|x|, eps)  ->  dx = (dy - yhat (yhat.dy)) / |x|, and dy / eps where |x| < eps; dx f32 (stored or accumulated)
  *   and/or dx_alt in another dtype (always the plain gradient).  dy row of x row r is r / dy_rows_per (0 or 1: one each).  F.normalize at reference model/model_Uni.py:142-146, cosine at modules/loss.py:52-56. */
 int made_l2norm_bwd(const void* x, int32_t x_dtype, int64_t ldx, const float* dy, int64_t lddy, int64_t dy_rows_per,
                     float* dx, int64_t lddx, int32_t accumulate, void* dx_alt, int32_t alt_dtype, int64_t lddxa,
@@ -877,7 +878,7 @@ int made_xpool_tail_bwd(const void* y, int32_t y_dtype, int64_t ldy, const float
 
 /* made_softmax_bwd: softmax backward of the wide-head attention with materialised scores (few query rows per batch):
  *   P = softmax(scale*S + mask), Pd = dropout(P), dP = dropout'(dPd + extra[row]), dS = scale * P * (dP - sum_k P_k dP_k).
- *   Writes Pd and dS [rows, ldo] (columns L..ldo-1 zero) and dS^T [rows/rows_per_batch, L, ldt] in out_dtype; the products
+ *   Writes Pd and dS [rows, ldo] (columns L..ldo-1 zero, for any ldo >= L) and dS^T [rows/rows_per_batch, L, ldt] in out_dtype; the products
  *   dV = Pd^T dO, dK = dS^T Q and dQ = dS K are then made_gemm_tn calls.  mask row = row / rows_per_mask. */
 int made_softmax_bwd(const float* S, int64_t ld_s, const float* dP, int64_t ld_dp, const float* mask, int64_t rows_per_mask,
                      const float* extra, float scale, const MadeDropout* drop,

@@ -514,8 +514,8 @@ __global__ __launch_bounds__(RT) void pool_bwd_kernel(const PoolBwdArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) { nn += mv[i][j] * mv[i][j]; dot += mv[i][j] * gv[i][j]; }
     }
-    const float nrm = fmaxf(sqrtf(wave_sum(nn)), a.eps);
-    dot = wave_sum(dot) / (nrm * nrm);                       // (vhat . dvec) / nrm
+    const float nraw = sqrtf(wave_sum(nn)), nrm = fmaxf(nraw, a.eps);
+    dot = nraw < a.eps ? 0.f : wave_sum(dot) / (nrm * nrm);  // (vhat . dvec) / nrm; under the clamp the divisor is the constant eps: no projection
     const float inv = 1.f / (nrm * cnt);
     f32x4 dm[NV];                                            // dmean / count of this sample, this lane's columns
 #pragma unroll
@@ -583,8 +583,8 @@ __global__ __launch_bounds__(RT) void l2norm_bwd_kernel(const L2BwdArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) { nn += xv[i][j] * xv[i][j]; dot += xv[i][j] * gv[i][j]; }
     }
-    const float nrm = fmaxf(sqrtf(wave_sum(nn)), a.eps);
-    dot = wave_sum(dot) / (nrm * nrm);
+    const float nraw = sqrtf(wave_sum(nn)), nrm = fmaxf(nraw, a.eps);
+    dot = nraw < a.eps ? 0.f : wave_sum(dot) / (nrm * nrm);  // (under the clamp y = x / eps: dx = dy / eps, F.normalize's own gradient)
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int c = (i * WAVE + lane) * 4;
@@ -809,7 +809,8 @@ __global__ __launch_bounds__(RT) void softmax_bwd_kernel(const SmBwdArgs a) {
     const uint64_t base = (uint64_t)row * (uint64_t)a.L;
     const int64_t z = row / a.rpb, i = row % a.rpb;
     constexpr int SM_MAXC = 17;                              // rows of up to 1088 keys live in registers: ONE pass over S / dP / mask
-    if (a.L <= 64 * SM_MAXC) {
+    // (and ldo: the store loop of this form ends at column 64 * SM_MAXC, so a wider output row keeps its zero tail only in the form below)
+    if (a.L <= 64 * SM_MAXC && a.ldo <= 64 * SM_MAXC) {
         // (the three-pass form below reads S, dP and the mask with conditional 4-byte loads three times over: ~20 us for a 542-key row
         // of the decoder's memory-space attention, all of it latency)
         const int L = (int)a.L, nch = (L + 63) >> 6;
@@ -940,14 +941,21 @@ __global__ void add3_kernel(void* out, int odt, const void* a, int adt, const vo
 }
 
 // ---- out[c] += sum_rows x[row, c]  (f32 accumulate; gradient of a vector broadcast over rows) -------------------------
-__global__ __launch_bounds__(RT) void colsum_kernel(const void* x, int dt, int64_t ld, int64_t rows, int64_t cols, float* out) {
-    const int64_t c = (int64_t)blockIdx.x * RT + threadIdx.x;
-    if (c >= cols) return;
-    const int64_t per = (rows + gridDim.y - 1) / gridDim.y;
-    const int64_t r0 = (int64_t)blockIdx.y * per, r1 = r0 + per < rows ? r0 + per : rows;
+// A workgroup takes 64 columns and FOUR row slabs of `per` rows, one per wave; the four partials meet in LDS and leave as one atomic per
+// column.  (One slab per workgroup and 256 columns, the first form, ended in up to 512 same-address atomics per column: the chain of
+// rounded adds left the f32 sum of 5000 rows 3.3e-7 +- 1.6e-7 off float64, up to 8.3e-7, where a tree sum is at 1.9e-7.  The same
+// threads, rows per thread and 64-column wave loads as before, a quarter of the atomics.)
+__global__ __launch_bounds__(RT) void colsum_kernel(const void* x, int dt, int64_t ld, int64_t rows, int64_t cols, int64_t per, float* out) {
+    __shared__ float sm[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t c = (int64_t)blockIdx.x * 64 + lane;
+    const int64_t r0 = ((int64_t)blockIdx.y * 4 + wave) * per, r1 = r0 + per < rows ? r0 + per : rows;      // (r0 >= rows: an empty slab)
     float acc = 0.f;
-    for (int64_t r = r0; r < r1; ++r) acc += load_as_f32(x, dt, r * ld + c);
-    unsafeAtomicAdd(out + c, acc);
+    if (c < cols)
+        for (int64_t r = r0; r < r1; ++r) acc += load_as_f32(x, dt, r * ld + c);
+    sm[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && c < cols) unsafeAtomicAdd(out + c, (sm[0][lane] + sm[1][lane]) + (sm[2][lane] + sm[3][lane]));
 }
 
 inline unsigned blocks4(int64_t rows) { return (unsigned)((rows + 3) / 4); }
@@ -1037,8 +1045,10 @@ extern "C" int made_layernorm_bwd2(const void* xa, const float* gamma_a, int64_t
     a.drop_ld = drop_ld > 0 ? drop_ld : D;
     a.dgamma_a = dgamma_a; a.dbeta_a = dbeta_a; a.dgamma_b = dgamma_b; a.dbeta_b = dbeta_b;
     a.rows = rows; a.D = (int)D; a.eps = eps;
+    // every workgroup ends with 4 * D same-address atomics (flush_cols): at most 256 of them, as in made_layernorm_bwd.  With 1024 the f32
+    // parameter gradients of 4100 rows were 5.7e-7 +- 0.4e-7 off float64 (a chain of 1024 rounded adds per column; torch's tree sum: 1.2e-7)
     int64_t nb = (rows + 3) / 4;
-    if (nb > 1024) nb = 1024;
+    if (nb > 256) nb = 256;
     switch ((D + 255) / 256) {
         case 1: hipLaunchKernelGGL((layernorm_bwd2_kernel<1>), dim3((unsigned)nb), dim3(RT), 0, (hipStream_t)stream, a); break;
         case 2: hipLaunchKernelGGL((layernorm_bwd2_kernel<2>), dim3((unsigned)nb), dim3(RT), 0, (hipStream_t)stream, a); break;
@@ -1184,6 +1194,8 @@ extern "C" int made_colsum(const void* x, int32_t dtype, int64_t ld, int64_t row
     if (rows <= 0) return MADE_OK;
     int64_t ny = (rows + 7) / 8;                           // few rows per thread: the loads of a column run in parallel
     if (ny > 512) ny = 512;
-    hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((cols + RT - 1) / RT), (unsigned)ny), dim3(RT), 0, (hipStream_t)stream, x, dtype, ld, rows, cols, out);
+    const int64_t per = (rows + ny - 1) / ny;              // rows of a slab; four slabs to a workgroup
+    hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((cols + 63) / 64), (unsigned)((ny + 3) / 4)), dim3(RT), 0, (hipStream_t)stream, x, dtype, ld, rows,
+                       cols, per, out);
     return made_check_launch("made_colsum");
 }
