@@ -1408,6 +1408,42 @@ int made_fit_moments(const float* start, const float* end, const int32_t* track,
                      int64_t n_tracks, const int64_t* onset_start, const float* onset_time, int64_t n_onsets, float tol, float* out_start,
                      float* out_end, float* shift, int32_t* onset, void* stream);
 
+/* ---- Cut sync (mgsv_amd/grounding.py fit_grounding with Fit.cuts; csrc/sync.hip) -----------------------------------------------
+ * made_sync_moments: made_fit_moments for a video that is assembled from clips -- the start is chosen so that the video's cuts
+ * land on the track's onsets, and how well they do is reported.  start, end, track, want, tlen and the onset CSR are
+ * made_fit_moments' arguments.  video [E] int32 is the entry's video (negative or >= n_videos: no cuts); cut_start [n_videos + 1]
+ * int64 and cut_time [n_cuts] f32 are the videos' cuts as a CSR, seconds from the video's beginning, ascending inside a video.
+ * snap f32: how far the start may move from where made_fit_moments would put it without snapping; cut_tol f32: how near an onset a
+ * cut must fall to count.  Every step is one rounded f32 operation (no contraction), comparisons written out.
+ *   1. len, c, last = T - len and s1 exactly as made_fit_moments' steps 1 - 3; s1 is the unsnapped start.  A NaN start, end or
+ *      tlen[track], or a track outside [0, n_tracks): out_start = out_end = shift = sync = NaN, onset = anchor = hits = -1.
+ *   2. Anchors: A = [0] followed by the video's cuts c with c > 0 && c < len, in order (the one predicate drops a NaN, a cut that
+ *      is not positive and a cut outside the fitted moment).  At most the first 63 cuts of a row are read, so |A| <= 64: a safety
+ *      limit, not a feature -- the Python layer refuses a longer row.
+ *   3. Candidates: s1 itself, always; and for every anchor a = A[j] (j ascending) and every onset o of the track (index i
+ *      ascending) s = o - a when fabsf(s - s1) <= snap && s >= 0 && s <= last, all three on the rounded s.  For a fixed a each
+ *      test is monotone in o: the admitted onsets are one contiguous range, found by binary searches with the same predicate.
+ *   4. Score of a start s: sync(s) = the f32 sum, in the order of A from 0, of t(d_a); p = s + a, d_a the smaller of p - o_prev and
+ *      o_next - p for the onsets either side of p (o_next the first onset >= p by binary search, o_prev the one before it; a
+ *      side that does not exist is skipped); t(d) = d <= cut_tol ? 1 - d / cut_tol : 0; hits(s) = the number of anchors with d_a <=
+ *      cut_tol.  A track without onsets scores 0 and 0.
+ *   5. Choice, a strict order: larger sync, then smaller fabsf(s - s1), then smaller s, then smaller j, then smaller i; the s1
+ *      candidate carries j = +infinity.  So when s1 coincides with an (o, a) candidate the snapped description is reported, and
+ *      otherwise a start that need not move does not move.
+ *   6. out_start = s, out_end = s + len, shift = s - start; onset = i inside the track's list and anchor = j (both -1 when the
+ *      s1 candidate won; anchor 0: the start sits on the onset, j >= 1: anchor j, a cut, does); sync f32, hits int32.
+ * For a video without usable cuts (A = [0]) and an onset table without negative times, out_start, out_end, shift and onset are
+ * made_fit_moments(tol = snap)'s bit for bit.  One wave per entry, four entries per 256-thread workgroup; anchors and the candidate
+ * prefix in LDS, a butterfly reduction with the comparator of step 5 (strict, so the result does not depend on the reduction's
+ * shape); no atomics, no workspace, no scratch.  E == 0 is a no-op.  onset_time may be NULL with n_onsets == 0, cut_time with
+ * n_cuts == 0, cut_start with n_videos == 0, onset_start and tlen with n_tracks == 0.  Refused: E, n_tracks or n_videos outside
+ * [0, 2^31), negative n_onsets or n_cuts, snap or cut_tol not finite or not > 0, null required pointers. */
+int made_sync_moments(const float* start, const float* end, const int32_t* track, const int32_t* video, const float* want, int64_t E,
+                      const float* tlen, int64_t n_tracks, const int64_t* onset_start, const float* onset_time, int64_t n_onsets,
+                      const int64_t* cut_start, const float* cut_time, int64_t n_videos, int64_t n_cuts, float snap, float cut_tol,
+                      float* out_start, float* out_end, float* shift, int32_t* onset, int32_t* anchor, float* sync, int32_t* hits,
+                      void* stream);
+
 /* ==========================================================================================
  * Batches from a device-resident feature store (mgsv_amd/feature_store.py DeviceFeatureStore): a split's features stay on the
  * device in their storage format and every batch of the training / evaluation loop is assembled by one launch.  The reference

@@ -348,6 +348,7 @@ SIGNATURES = {
     "made_onset_strength": (C.c_int, [vp, i64, vp, i64, i32, vp, i64, vp]),
     "made_onset_peaks": (C.c_int, [vp, i64, vp, i64, i32, i32, f32, i64, vp, vp, vp]),
     "made_fit_moments": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp, vp]),
+    "made_sync_moments": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, i64, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -26,7 +26,9 @@ near-duplicate tracks do not fill the top k; only the k kept are localized (`che
 
 With `fit` (a `Fit`) the finished Grounding goes through `fit_grounding`, one made_fit_moments launch: every moment is given its
 video's length, kept inside its track and -- against the track's onsets (mgsv_amd/onsets.py) -- started on the nearest attack within
-a tolerance; the grounded moments stay in `raw_start` / `raw_end`.  Without it none of that code runs.
+a tolerance; the grounded moments stay in `raw_start` / `raw_end`.  Without it none of that code runs.  With `Fit.cuts` (where every
+video is cut) the launch is made_sync_moments instead: the start is chosen so that the video's beginning and its cuts land on attacks,
+and `anchor`, `sync` and `hits` say how well they do.
 
 A pair's localization depends on that pair's video and track only (every kernel after the towers computes a sample's rows
 independently of the rest of the batch), so the moment found in the ground-truth track is the one the batched evaluation scores.
@@ -70,6 +72,9 @@ class Grounding:
     raw_end: Optional[Tensor] = None
     shift: Optional[Tensor] = None         # ... start - raw_start, f32 ...
     onset: Optional[Tensor] = None         # ... and the onset the start was moved onto, int32 index inside the track's list (-1: not snapped)
+    anchor: Optional[Tensor] = None        # fitted with Fit.cuts: the anchor that sits on that onset, int32 (0: the video's beginning, j >= 1: its j-th cut inside the moment, -1: not snapped) ...
+    sync: Optional[Tensor] = None          # ... how well the beginning and the cuts land on onsets, f32 (each within cut_tol adds 1 - distance / cut_tol) ...
+    hits: Optional[Tensor] = None          # ... and how many of them land within cut_tol of one, int32 (-1 where there is no moment)
 
     @property
     def k(self) -> int:
@@ -81,7 +86,8 @@ class Grounding:
         indexed by track and every track holds "moments": [{"start", "end", "confidence", "window_offset"}, ...] instead of one
         start / end / confidence.  Re-selected for diversity (`pool_rank` is set), every track also holds "pool_rank" and "redundancy"
         (None for a video's first track, which has nothing before it).  Fitted (`raw_start` is set), every track's -- over windows
-        every moment's -- dict also holds "raw_start", "raw_end" and "snapped" (whether the start sits on an onset)."""
+        every moment's -- dict also holds "raw_start", "raw_end" and "snapped" (whether the start or a cut was put on an onset), and, fitted
+        to the video's cuts (`anchor` is set), "anchor", "sync" and "hits" beside them."""
         if self.windows is not None:
             return self._window_records(video_ids, music_ids)
         tr, sc, st, en, cf = (t.cpu().numpy() for t in (self.track, self.score, self.start, self.end, self.confidence))
@@ -107,12 +113,17 @@ class Grounding:
         return lambda v, j: dict(pool_rank=int(pr[v, j]), redundancy=None if math.isnan(rd[v, j]) else float(rd[v, j]))
 
     def _fit_fields(self):
-        """f(v, j, i) -> {"raw_start", "raw_end", "snapped"} of moment i of result j of video v; nothing when the results were not fitted"""
+        """f(v, j, i) -> {"raw_start", "raw_end", "snapped"} of moment i of result j of video v (and {"anchor", "sync", "hits"} when the
+        cuts were fitted); nothing when the results were not fitted"""
         if self.raw_start is None:
             return lambda v, j, i: {}
         Nv, k = self.track.shape
         rs, re, on = (t.cpu().numpy().reshape(Nv, k, -1) for t in (self.raw_start, self.raw_end, self.onset))
-        return lambda v, j, i: dict(raw_start=float(rs[v, j, i]), raw_end=float(re[v, j, i]), snapped=bool(on[v, j, i] >= 0))
+        plain = lambda v, j, i: dict(raw_start=float(rs[v, j, i]), raw_end=float(re[v, j, i]), snapped=bool(on[v, j, i] >= 0))
+        if self.anchor is None:
+            return plain
+        an, sy, hi = (t.cpu().numpy().reshape(Nv, k, -1) for t in (self.anchor, self.sync, self.hits))
+        return lambda v, j, i: dict(plain(v, j, i), anchor=int(an[v, j, i]), sync=float(sy[v, j, i]), hits=int(hi[v, j, i]))
 
     def _window_records(self, video_ids: Sequence, music_ids: Sequence) -> List[dict]:
         tr, sc = self.track.cpu().numpy(), self.score.cpu().numpy()
@@ -300,11 +311,25 @@ class Fit:
     """The optional last step of grounding: what a moment must look like to be laid under its video.
     length: "video" (every moment as long as its video: `videos.duration`), None (a moment keeps its own length) or seconds, a
     scalar or one entry per video.  snap: None, or the tolerance in seconds within which a moment's start is moved onto the nearest
-    onset of its track (an `Onsets` table is then needed).  At least one of the two must be given."""
+    onset of its track (an `Onsets` table is then needed).  At least one of the two must be given.
+    cuts: None, or where every video is cut -- one sequence of seconds from the video's beginning per video, strictly ascending,
+    finite and > 0, at most 63 a video (or an `onsets.Onsets` used as a plain CSR of times over videos).  The start is then chosen
+    within `snap` of the unsnapped one so that the video's beginning and its cuts land on onsets as well as they can
+    (made_sync_moments); a cut within cut_tol seconds of an onset counts.  Needs snap."""
     length: object = None
     snap: Optional[float] = None
+    cuts: object = None
+    cut_tol: float = 0.05
 
     def __post_init__(self):
+        self._cut_csr = None
+        self.cut_tol = float(self.cut_tol)
+        if not (math.isfinite(self.cut_tol) and self.cut_tol > 0.0):
+            raise ValueError(f"cut_tol = {self.cut_tol!r}: a tolerance in seconds, finite and > 0")
+        if self.cuts is not None:
+            if self.snap is None:
+                raise ValueError("Fit(cuts=...) needs snap= (how far a start may move to put the cuts on onsets)")
+            self._cut_csr = _cut_csr(self.cuts)
         if self.length is None and self.snap is None:
             raise ValueError("Fit(): give length= or snap= (with neither there is nothing to fit)")
         if isinstance(self.length, str) and self.length != "video":
@@ -313,6 +338,28 @@ class Fit:
             self.snap = float(self.snap)
             if not (math.isfinite(self.snap) and self.snap > 0.0):
                 raise ValueError(f"snap = {self.snap!r}: a tolerance in seconds, finite and > 0")
+
+
+def _cut_csr(cuts):
+    """(start int64 [N_v + 1], time f32) of `Fit.cuts`, checked: at most ops.SYNC_MAX_CUTS cuts a video, finite, > 0, strictly ascending"""
+    if hasattr(cuts, "start") and hasattr(cuts, "time"):
+        start = np.ascontiguousarray(cuts.start, dtype=np.int64).reshape(-1)
+        time = np.ascontiguousarray(cuts.time, dtype=np.float32).reshape(-1)
+        if len(start) < 1 or start[0] != 0 or start[-1] != len(time) or (np.diff(start) < 0).any():
+            raise ValueError("cuts: not a CSR of times over videos")
+    else:
+        rows = [np.asarray(r, dtype=np.float32).reshape(-1) for r in cuts]
+        start = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        time = np.concatenate(rows + [np.zeros(0, np.float32)]).astype(np.float32)
+    for v in range(len(start) - 1):
+        row = time[start[v]:start[v + 1]]
+        if len(row) > ops.SYNC_MAX_CUTS:
+            raise ValueError(f"cuts: video {v} has {len(row)} cuts, at most {ops.SYNC_MAX_CUTS} are supported")
+        if not (np.isfinite(row).all() and (row > 0).all()):
+            raise ValueError(f"cuts: video {v} holds a cut that is not finite or not > 0 (seconds from the video's beginning)")
+        if (np.diff(row) <= 0).any():
+            raise ValueError(f"cuts: video {v}'s cuts are not strictly ascending")
+    return start, time
 
 
 def clamp_length(duration, n: int, max_m_duration: float) -> np.ndarray:
@@ -343,6 +390,9 @@ def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None
     bound the grounding clamped to); onsets: an `Onsets` table in the same numbering (needed by snap).  Entries are [N_v, k] or, over
     windows with moments > 1, [N_v, k, n]: every moment of a track is fitted against that track, want is the video's value.
     The window merge's suppression ran on the raw moments: two fitted moments of one track may overlap more than nms_iou.
+    With `fit.cuts` (one row per video; made_sync_moments instead) the start is chosen within `fit.snap` of the unsnapped one so that
+    the video's beginning and its cuts land on onsets; an entry's video is its first index.  anchor, sync and hits are then set too:
+    the anchor that sits on `onset` (0: the beginning, j >= 1: a cut), the score and the number of anchors within `fit.cut_tol`.
     backend None: the device kernel when `g` lives on a GPU, else the numpy restatement; "host": the restatement (same bits)."""
     if g.raw_start is not None:
         raise ValueError("this Grounding is fitted already (fit its raw_start / raw_end instead)")
@@ -369,10 +419,25 @@ def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None
         if len(onsets) != len(tlen):
             raise ValueError(f"the onset table holds {len(onsets)} tracks, there are {len(tlen)}")
         tol = fit.snap
+    if fit._cut_csr is not None and len(fit._cut_csr[0]) - 1 != Nv:
+        raise ValueError(f"Fit.cuts holds {len(fit._cut_csr[0]) - 1} rows, there are {Nv} videos")
     if backend is None:
         backend = None if g.start.is_cuda else "host"
     dev = g.start.device
     expand = lambda t: t.reshape((Nv,) + (1,) * (len(shape) - 1)).expand(shape).contiguous().reshape(-1)
+    if fit._cut_csr is not None:
+        video = expand(torch.arange(Nv, dtype=torch.int32))
+        if backend == "host":
+            out = ops.sync_moments(g.start.reshape(-1), g.end.reshape(-1), _entry_tracks(g.track, shape), video, expand(torch.from_numpy(want)),
+                                   tlen, onsets.start, onsets.time, *fit._cut_csr, snap=tol, cut_tol=fit.cut_tol, backend="host")
+            out = [torch.from_numpy(a).to(dev) for a in out]
+        else:
+            out = ops.sync_moments(g.start.to(torch.float32).contiguous().reshape(-1), g.end.to(torch.float32).contiguous().reshape(-1),
+                                   _entry_tracks(g.track, shape), video.to(dev), expand(torch.from_numpy(want).to(dev)),
+                                   torch.from_numpy(tlen).to(dev), *_onsets_on(onsets, dev), *(torch.from_numpy(a).to(dev) for a in fit._cut_csr),
+                                   snap=tol, cut_tol=fit.cut_tol)
+        st, en, sh, on, an, sy, hi = (t.view(shape) for t in out)
+        return replace(g, start=st, end=en, raw_start=g.start, raw_end=g.end, shift=sh, onset=on, anchor=an, sync=sy, hits=hi)
     if backend == "host":
         out = ops.fit_moments(g.start.reshape(-1), g.end.reshape(-1), _entry_tracks(g.track, shape), expand(torch.from_numpy(want)), tlen,
                               None if tol == 0.0 else onsets.start, None if tol == 0.0 else onsets.time, tol, backend="host")
@@ -395,6 +460,8 @@ def _check_fit(fit: Optional[Fit], videos: Encoded, onsets) -> None:
         raise ValueError("Fit(length='video') needs the videos' durations (videos.duration is None)")
     if fit.snap is not None and onsets is None:
         raise ValueError("Fit(snap=...) needs the tracks' onsets (onsets=..., or a library that carries them)")
+    if fit._cut_csr is not None and len(fit._cut_csr[0]) - 1 != len(videos):
+        raise ValueError(f"Fit.cuts holds {len(fit._cut_csr[0]) - 1} rows, there are {len(videos)} videos")
 
 
 def _entry_tracks(track: Tensor, shape) -> Tensor:
@@ -726,7 +793,8 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     result's rank in the pool and that largest cosine.
     fit = Fit(length=, snap=) (default None: nothing below runs): the finished Grounding goes through `fit_grounding` -- every moment
     given its video's length (or the seconds asked for), kept inside its track, its start moved onto the track's nearest onset
-    within `snap` seconds.  onsets: the `Onsets` table of the tracks, in `Grounding.track`'s numbering (mgsv_amd/onsets.py).  The
+    within `snap` seconds (with `Fit.cuts`: chosen within `snap` so that the video's cuts land on onsets; `anchor`, `sync` and `hits`
+    are then set too).  onsets: the `Onsets` table of the tracks, in `Grounding.track`'s numbering (mgsv_amd/onsets.py).  The
     track length is what the moments were clamped to: min(max_m_duration, duration) per column, `default_length` over windows."""
     dev = engine.device
     Nv, Nm = len(videos), len(music)
@@ -1407,7 +1475,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     library's slices and listed columns are widened into a scratch buffer; localization and the shortlist's second stage gather
     and widen the distinct selected columns (the whole library is never widened).  timings then receives dequantize_ms.
     fit = Fit(length=, snap=): `ground(..., fit=fit, onsets=library.onsets)` for the stored library, bit for bit, in every placement:
-    one made_fit_moments launch on the finished Grounding (`fit_grounding`) against `library.fit_length` and `library.onsets`.
+    one made_fit_moments launch (made_sync_moments with `fit.cuts`) on the finished Grounding (`fit_grounding`) against `library.fit_length` and `library.onsets`.
     fit None (the default): none of it runs."""
     c = engine.cfg
     dev = engine.device

@@ -1354,6 +1354,120 @@ def fit_moments(start, end, track, want, tlen, onset_start=None, onset_time=None
     return out_start, out_end, shift, onset
 
 
+SYNC_MAX_CUTS = 63                       # cuts made_sync_moments reads of a video's row (one anchor per lane of a wave, anchor 0 the beginning)
+
+
+def _sync_params(snap, cut_tol):
+    snap, cut_tol = float(snap), float(cut_tol)
+    if not (math.isfinite(snap) and snap > 0.0):
+        raise ValueError(f"snap = {snap!r}: must be finite and > 0")
+    if not (math.isfinite(cut_tol) and cut_tol > 0.0):
+        raise ValueError(f"cut_tol = {cut_tol!r}: must be finite and > 0")
+    return snap, cut_tol
+
+
+def sync_moments_host(start, end, track, video, want, tlen, onset_start, onset_time, cut_start, cut_time, snap: float, cut_tol: float = 0.05):
+    """made_sync_moments restated in numpy float32, one rounded operation per step (include/made_hip.h states the contract): the
+    same bits as the kernel.  The front is `fit_moments_host`'s, vectorised over the entries; candidates, scores and the choice are
+    a loop over the entries, vectorised over an entry's candidates.  Arrays of E entries -> (out_start, out_end, shift f32 [E],
+    onset, anchor int32 [E], sync f32 [E], hits int32 [E])."""
+    import numpy as np
+    f32 = np.float32
+    snap, cut_tol = _sync_params(snap, cut_tol)
+    start, end, want = (np.ascontiguousarray(a, dtype=f32).reshape(-1) for a in (start, end, want))
+    track = np.ascontiguousarray(track).astype(np.int64).reshape(-1)
+    video = np.ascontiguousarray(video).astype(np.int64).reshape(-1)
+    tlen = np.ascontiguousarray(tlen, dtype=f32).reshape(-1)
+    ostart = np.ascontiguousarray(onset_start, dtype=np.int64).reshape(-1)
+    otime = np.ascontiguousarray(onset_time, dtype=f32).reshape(-1)
+    cstart = np.ascontiguousarray(cut_start, dtype=np.int64).reshape(-1)
+    ctime = np.ascontiguousarray(cut_time, dtype=f32).reshape(-1)
+    E, n_tracks, n_videos = len(start), len(tlen), len(cstart) - 1
+    assert len(end) == E and len(want) == E and len(track) == E and len(video) == E
+    assert len(ostart) == n_tracks + 1 and n_videos >= 0
+    pmax = lambda a, b: np.where(a > b, a, b)
+    pmin = lambda a, b: np.where(a < b, a, b)
+    zero, half, nan = np.zeros(E, f32), f32(0.5), f32(np.nan)
+    in_range = (track >= 0) & (track < n_tracks)
+    tr = np.where(in_range, track, 0)
+    T = np.where(in_range, tlen[tr] if n_tracks else nan, nan).astype(f32)
+    none = np.isnan(start) | np.isnan(end) | np.isnan(T)
+    out_start, out_end, shift, sync = (np.full(E, nan, f32) for _ in range(4))
+    onset, anchor, hits = (np.full(E, -1, np.int32) for _ in range(3))
+    snap32, tol32, one, inf = f32(snap), f32(cut_tol), f32(1), f32(np.inf)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ln = np.where(np.isnan(want), end - start, want).astype(f32)
+        ln = pmin(pmax(ln, zero), T)
+        c = half * (start + end)
+        last = T - ln
+        s1 = pmin(pmax(c - half * ln, zero), last)
+        for e in np.flatnonzero(~none):
+            oa = min(max(int(ostart[tr[e]]), 0), len(otime))
+            o = otime[oa:min(max(int(ostart[tr[e] + 1]), oa), len(otime))]
+            A = np.zeros(1, f32)
+            if 0 <= video[e] < n_videos:
+                ca = min(max(int(cstart[video[e]]), 0), len(ctime))
+                cuts = ctime[ca:min(max(int(cstart[video[e] + 1]), ca), len(ctime))][:SYNC_MAX_CUTS]
+                A = np.concatenate([A, cuts[(cuts > 0) & (cuts < ln[e])]]).astype(f32)
+            s = o[None, :] - A[:, None]                             # [anchors, onsets]: every start that puts an anchor on an onset
+            jj, ii = np.nonzero((np.abs(s - s1[e]) <= snap32) & (s >= 0) & (s <= last[e]))           # (row-major: j, then i, ascending)
+            cs = np.concatenate([s[jj, ii], s1[e:e + 1]]).astype(f32)                                 # the unsnapped start comes last, ...
+            cj = np.concatenate([jj, [np.iinfo(np.int64).max]])                                      # ... its anchor +infinity
+            ci = np.concatenate([ii, [-1]])
+            total, nhit = np.zeros(len(cs), f32), np.zeros(len(cs), np.int32)
+            if len(o):
+                for a in A:                                        # the score: f32 adds in the anchors' order
+                    p = cs + a
+                    nxt = np.searchsorted(o, p, side="left")       # the first onset >= p
+                    dl = np.where(nxt > 0, p - o[np.maximum(nxt, 1) - 1], inf).astype(f32)
+                    dr = np.where(nxt < len(o), o[np.minimum(nxt, len(o) - 1)] - p, inf).astype(f32)
+                    d = np.where(dr < dl, dr, dl)
+                    hit = d <= tol32
+                    total = total + np.where(hit, one - np.where(hit, d, f32(0)) / tol32, f32(0)).astype(f32)
+                    nhit += hit
+            dist = np.abs(cs - s1[e])
+            b = np.lexsort((ci, cj, cs, dist, -total))[0]           # larger sync, smaller distance, smaller s, smaller j, smaller i
+            out_start[e], out_end[e], shift[e] = cs[b], cs[b] + ln[e], cs[b] - start[e]
+            onset[e], anchor[e] = ci[b], (-1 if ci[b] < 0 else cj[b])
+            sync[e], hits[e] = total[b], nhit[b]
+    return out_start, out_end, shift, onset, anchor, sync, hits
+
+
+def sync_moments(start, end, track, video, want, tlen, onset_start, onset_time, cut_start, cut_time, snap: float, cut_tol: float = 0.05,
+                 backend: Optional[str] = None):
+    """made_sync_moments: `fit_moments` for videos assembled from clips.  video [E] int32 is every entry's video, cut_start int64
+    [n_videos + 1] / cut_time f32 the videos' cuts as a CSR (seconds from the video's beginning, ascending).  Among the unsnapped
+    start and every start within `snap` of it that puts the video's beginning or one of its cuts on an onset of the track, the one
+    whose anchors land best on onsets is taken (include/made_hip.h states the rule) -> (out_start, out_end, shift f32 [E], onset
+    int32 [E] the onset's index inside the track, anchor int32 [E] the anchor that sits on it (0: the beginning, j >= 1: a cut; both
+    -1: not snapped), sync f32 [E] the sum over the anchors of 1 - d / cut_tol for those within cut_tol of an onset, hits int32 [E]
+    their number).  backend None: device tensors in and out, one launch.  backend "host": arrays or host tensors in, numpy arrays
+    out, by `sync_moments_host` -- the same bits, on any machine."""
+    if backend == "host":
+        host = lambda a: a.detach().cpu().numpy() if isinstance(a, Tensor) else a
+        return sync_moments_host(*(host(a) for a in (start, end, track, video, want, tlen, onset_start, onset_time, cut_start, cut_time)),
+                                 snap=snap, cut_tol=cut_tol)
+    if backend is not None:
+        raise ValueError(f"backend = {backend!r}: None (the device) or 'host'")
+    for t in (start, end, want, tlen, onset_time, cut_time):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    for t in (track, video):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    E, n_tracks = start.numel(), tlen.numel()
+    assert end.numel() == E and want.numel() == E and track.numel() == E and video.numel() == E
+    assert onset_start.dtype == torch.int64 and onset_start.is_contiguous() and onset_start.numel() == n_tracks + 1
+    assert cut_start.dtype == torch.int64 and cut_start.is_contiguous() and cut_start.numel() >= 1
+    dev = start.device
+    out_start, out_end, shift, sync = (torch.empty(E, device=dev, dtype=torch.float32) for _ in range(4))
+    onset, anchor, hits = (torch.empty(E, device=dev, dtype=torch.int32) for _ in range(3))
+    ptr = lambda t: _p(t) if t.numel() else None
+    check(lib().made_sync_moments(ptr(start), ptr(end), ptr(track), ptr(video), ptr(want), E, ptr(tlen), n_tracks, _p(onset_start),
+                                  ptr(onset_time), onset_time.numel(), _p(cut_start), ptr(cut_time), cut_start.numel() - 1, cut_time.numel(),
+                                  float(snap), float(cut_tol), ptr(out_start), ptr(out_end), ptr(shift), ptr(onset), ptr(anchor), ptr(sync),
+                                  ptr(hits), _stream()), "made_sync_moments")
+    return out_start, out_end, shift, onset, anchor, sync, hits
+
+
 def mmr_select(row: Tensor, score: Tensor, vec: Tensor, k: int, mu: float = 0.0, tau: float = float("inf")):
     """made_mmr_select: the greedy re-selection of k of every video's P pool slots -- row [Nv, P] int32 (the slot's row of vec, < 0:
     absent), score [Nv, P] f32, vec [n_rows, D] f32 contiguous -> (pos [Nv, k] int32 the picked slots in pick order, -1 past the last;
