@@ -1444,6 +1444,62 @@ int made_sync_moments(const float* start, const float* end, const int32_t* track
                       float* out_start, float* out_end, float* shift, int32_t* onset, int32_t* anchor, float* sync, int32_t* hits,
                       void* stream);
 
+/* ---- Beat grids (mgsv_amd/beats.py; csrc/beats.hip) -----------------------------------------------------------------------------
+ * One tempo and the beat times of a track, from made_onset_strength's envelope (frames of 10 ms).  A beat list is "a CSR of
+ * ascending times per track": made_fit_moments and made_sync_moments take it where they take the onsets.
+ *
+ * made_tempo_autocorr: env [N, env_ld] f32 as made_onset_strength writes it, n_frames [N] device int32, 1 <= lag_min <= lag_max
+ * <= 256, n_lags = lag_max - lag_min + 1, weight [n_lags] device f32 (the tempo prior of the lags lag_min + j, rounded once by the
+ * host).  Outputs ac [N, n_lags + 1] f32, scale [N] f32, period [N] int32.  Per track t with nf = n_frames[t] and e = env[t]:
+ *   1. m = (the f32 sum of e[0 .. nf)) / (float)nf; x[f] = e[f] - m.
+ *   2. ac[t, 0] = sum_f x[f]^2.
+ *   3. ac[t, 1 + j] = sum_{f = l}^{nf - 1} x[f] * x[f - l] for l = lag_min + j (an empty sum, 0, when nf <= l).
+ *   4. scale[t] = 1.f / sqrtf(ac[t, 0] / (float)nf): the envelope's inverse standard deviation (three rounded operations).
+ *   5. score[j] = (ac[t, 1 + j] / (float)(nf - l)) * weight[j]: two rounded operations.
+ *   6. period[t] = the lag of the largest score, of equal scores the smaller lag.
+ * A track has no tempo -- period = -1, scale = NaN -- when nf <= lag_max, when ac[t, 0] is not > 0 (a NaN included), or when no
+ * score is > 0 (ac is still written).  A track with nf < 0 or nf > env_ld gets that and a NaN ac row; nothing of it is read.
+ * Summation order (f32, no contraction; it depends on nf alone, not on N or the track's place in the batch).  The mean: 1024
+ * chains, chain i adds e[i], e[i + 1024], ... ascending (ceil(nf / 1024) terms); the 64 chains of a wave meet in a tree of depth 6,
+ * the sixteen waves' totals are added in order (15 more additions).  A sum of steps 2 - 3: the track is cut into tiles of 1024
+ * frames; inside a tile 64 chains, chain i adding the products of the frames f0 + i, f0 + i + 64, ... ascending (16 terms; a frame
+ * outside [l, nf) adds +0), a tree of depth 6 over the chains, and the tiles' totals added ascending (ceil(nf / 1024) terms): a
+ * product passes through at most 16 + 6 + ceil(nf / 1024) additions.  One workgroup of sixteen waves per track; the tile and the
+ * 256 frames before it are staged in LDS as x; the waves split the lags; no atomics, no workspace.  N == 0 is a no-op.  Refused:
+ * negative sizes, lags outside the range, null pointers (env may be NULL when env_ld == 0), N >= 2^31, env_ld >= 2^24. */
+int made_tempo_autocorr(const float* env, int64_t env_ld, const int32_t* n_frames, int64_t N, int32_t lag_min, int32_t lag_max,
+                        const float* weight, float* ac, float* scale, int32_t* period, void* stream);
+
+/* made_beat_track: the beats of N tracks by Ellis's dynamic programme, every step one rounded f32 operation (no contraction).  env,
+ * n_frames as above; period [N] int32 and scale [N] f32 as made_tempo_autocorr writes them (any source will do); alpha f32 the
+ * tightness; outputs time [N, cap] f32, count [N] int32, cum [N, env_ld] f32, back [N, env_ld] int32.  With P = period[t]:
+ *   1. dlo = (P + 1) / 2 (integer division), dhi = 2 P.
+ *   2. pen[d] = -alpha * ((float)((d - P) * (d - P)) / (float)(d * P)) for d in [dlo, dhi]: the integers are exact, a division and
+ *      a product.  It is 0 at d = P, symmetric under d -> P^2 / d, and close to alpha * ln^2(d / P).
+ *   3. local[f] = e[f] * scale[t].
+ *   4. For f = 0 .. nf - 1: best = the largest cum[f - d] + pen[d] over d in [dlo, dhi] with f - d >= 0, of equal sums the smaller
+ *      d (a NaN sum is no candidate).  If there is a candidate and best > 0: cum[f] = local[f] + best, back[f] = f - d.  Otherwise
+ *      cum[f] = local[f], back[f] = -1: starting afresh is always allowed and costs nothing.
+ *   5. End frame = the argmax of cum over [max(0, nf - dhi), nf), of equal values the earlier frame (NaN is no candidate).
+ *   6. The beats are the chain end, back[end], back[back[end]], ... down to -1, written ascending as (float)f * 0.01f seconds to
+ *      time[t * cap + i]; count[t] = their number (0 when nf == 0).  Entries from count[t] on are not written; of a cum / back row
+ *      only [0, nf) is.
+ * Two beats are dlo frames apart or more, so a track has at most ceil(nf / dlo) beats.  Per track: period[t] == -1 gives count 0;
+ * nf outside [0, env_ld], a period outside {-1} and [2, 256], a scale that is not finite, or cap < ceil(nf / dlo) give count -1;
+ * in both cases nothing else of the track is written.  The host cannot see the periods: it refuses a cap < ceil(env_ld / 128),
+ * which no period makes safe; cap = env_ld / dlo_min + 1 for the smallest dlo the caller allows never overflows.
+ * One workgroup of sixteen waves per track.  Frame f reads frames <= f - dlo only, so the dlo frames f .. f + dlo - 1 are
+ * independent: that is the unit between two barriers.  A row of 16 lanes takes a frame (four frames a wave), its lanes the
+ * candidates d = dlo + lane, + 16, ... (at most 25), and two DPP maximum reductions over the row give the argmax under the strict
+ * order of step 4, which therefore does not depend on the reduction's shape.  The trailing 1024 values of cum, the envelope two
+ * tiles of 1024 frames ahead and the pen table live in LDS; cum and back in global memory are written, and back is read only by
+ * the backtrace: one thread's walk into LDS (the first 4096 beats; the rest by a second walk), written out in ascending order by
+ * all threads.  No atomics, no workspace.
+ * alpha finite and >= 0; N == 0 is a no-op.  Refused: negative sizes, such an alpha or cap, null pointers (env, cum and back may be
+ * NULL when env_ld == 0, time when cap == 0), N >= 2^31, env_ld >= 2^24. */
+int made_beat_track(const float* env, int64_t env_ld, const int32_t* n_frames, const int32_t* period, const float* scale, int64_t N,
+                    float alpha, int64_t cap, float* time, int32_t* count, float* cum, int32_t* back, void* stream);
+
 /* ==========================================================================================
  * Batches from a device-resident feature store (mgsv_amd/feature_store.py DeviceFeatureStore): a split's features stay on the
  * device in their storage format and every batch of the training / evaluation loop is assembled by one launch.  The reference

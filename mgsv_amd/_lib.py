@@ -347,6 +347,8 @@ SIGNATURES = {
     "made_gather_batch": (C.c_int, [C.POINTER(MadeGatherBatchArgs), vp]),
     "made_onset_strength": (C.c_int, [vp, i64, vp, i64, i32, vp, i64, vp]),
     "made_onset_peaks": (C.c_int, [vp, i64, vp, i64, i32, i32, f32, i64, vp, vp, vp]),
+    "made_tempo_autocorr": (C.c_int, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
+    "made_beat_track": (C.c_int, [vp, i64, vp, vp, vp, i64, f32, i64, vp, vp, vp, vp, vp]),
     "made_fit_moments": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp, vp]),
     "made_sync_moments": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, i64, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
 }

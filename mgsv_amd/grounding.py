@@ -28,7 +28,8 @@ With `fit` (a `Fit`) the finished Grounding goes through `fit_grounding`, one ma
 video's length, kept inside its track and -- against the track's onsets (mgsv_amd/onsets.py) -- started on the nearest attack within
 a tolerance; the grounded moments stay in `raw_start` / `raw_end`.  Without it none of that code runs.  With `Fit.cuts` (where every
 video is cut) the launch is made_sync_moments instead: the start is chosen so that the video's beginning and its cuts land on attacks,
-and `anchor`, `sync` and `hits` say how well they do.
+and `anchor`, `sync` and `hits` say how well they do.  With `Fit.grid = "beats"` the table of either launch is the track's beat grid
+(mgsv_amd/beats.py, `beats=`) instead of its onsets, and `tempo` is set.
 
 A pair's localization depends on that pair's video and track only (every kernel after the towers computes a sample's rows
 independently of the rest of the batch), so the moment found in the ground-truth track is the one the batched evaluation scores.
@@ -75,6 +76,7 @@ class Grounding:
     anchor: Optional[Tensor] = None        # fitted with Fit.cuts: the anchor that sits on that onset, int32 (0: the video's beginning, j >= 1: its j-th cut inside the moment, -1: not snapped) ...
     sync: Optional[Tensor] = None          # ... how well the beginning and the cuts land on onsets, f32 (each within cut_tol adds 1 - distance / cut_tol) ...
     hits: Optional[Tensor] = None          # ... and how many of them land within cut_tol of one, int32 (-1 where there is no moment)
+    tempo: Optional[Tensor] = None         # fitted with Fit.grid = "beats" (`onset` then indexes the track's beats): the track's tempo, f32 BPM, the shape of track (NaN: no track or no tempo)
 
     @property
     def k(self) -> int:
@@ -87,11 +89,12 @@ class Grounding:
         start / end / confidence.  Re-selected for diversity (`pool_rank` is set), every track also holds "pool_rank" and "redundancy"
         (None for a video's first track, which has nothing before it).  Fitted (`raw_start` is set), every track's -- over windows
         every moment's -- dict also holds "raw_start", "raw_end" and "snapped" (whether the start or a cut was put on an onset), and, fitted
-        to the video's cuts (`anchor` is set), "anchor", "sync" and "hits" beside them."""
+        to the video's cuts (`anchor` is set), "anchor", "sync" and "hits" beside them.  Fitted on the beat grid (`tempo` is set), every
+        track's dict also holds "grid": "beats" and "tempo" (BPM; None where the track has none)."""
         if self.windows is not None:
             return self._window_records(video_ids, music_ids)
         tr, sc, st, en, cf = (t.cpu().numpy() for t in (self.track, self.score, self.start, self.end, self.confidence))
-        extra, fitted = self._diversity_fields(), self._fit_fields()
+        extra, fitted, beat = self._diversity_fields(), self._fit_fields(), self._beat_fields()
         out = []
         for v, vid in enumerate(video_ids):
             ent = []
@@ -101,7 +104,7 @@ class Grounding:
                     continue
                 c = float(cf[v, j])
                 ent.append(dict(music_id=music_ids[m], score=float(sc[v, j]), start=float(st[v, j]), end=float(en[v, j]),
-                                confidence=None if math.isnan(c) else c, **fitted(v, j, 0), **extra(v, j)))
+                                confidence=None if math.isnan(c) else c, **fitted(v, j, 0), **beat(v, j), **extra(v, j)))
             out.append(dict(video_id=vid, tracks=ent))
         return out
 
@@ -111,6 +114,13 @@ class Grounding:
             return lambda v, j: {}
         pr, rd = self.pool_rank.cpu().numpy(), self.redundancy.cpu().numpy()
         return lambda v, j: dict(pool_rank=int(pr[v, j]), redundancy=None if math.isnan(rd[v, j]) else float(rd[v, j]))
+
+    def _beat_fields(self):
+        """f(v, j) -> {"grid", "tempo"} of result j of video v; nothing when the results were not fitted on the beat grid"""
+        if self.tempo is None:
+            return lambda v, j: {}
+        bpm = self.tempo.cpu().numpy()
+        return lambda v, j: dict(grid="beats", tempo=None if math.isnan(bpm[v, j]) else float(bpm[v, j]))
 
     def _fit_fields(self):
         """f(v, j, i) -> {"raw_start", "raw_end", "snapped"} of moment i of result j of video v (and {"anchor", "sync", "hits"} when the
@@ -129,7 +139,7 @@ class Grounding:
         tr, sc = self.track.cpu().numpy(), self.score.cpu().numpy()
         Nv, k = tr.shape
         st, en, cf, wi = (t.cpu().numpy().reshape(Nv, k, -1) for t in (self.start, self.end, self.confidence, self.window))
-        extra, fitted = self._diversity_fields(), self._fit_fields()
+        extra, fitted, beat = self._diversity_fields(), self._fit_fields(), self._beat_fields()
         out = []
         for v, vid in enumerate(video_ids):
             ent = []
@@ -144,7 +154,7 @@ class Grounding:
                     c = float(cf[v, j, i])
                     moms.append(dict(start=float(st[v, j, i]), end=float(en[v, j, i]), confidence=None if math.isnan(c) else c,
                                      window_offset=float(self.windows.offset[wi[v, j, i]]), **fitted(v, j, i)))
-                ent.append(dict(music_id=music_ids[m], score=float(sc[v, j]), moments=moms, **extra(v, j)))
+                ent.append(dict(music_id=music_ids[m], score=float(sc[v, j]), moments=moms, **beat(v, j), **extra(v, j)))
             out.append(dict(video_id=vid, tracks=ent))
         return out
 
@@ -315,14 +325,23 @@ class Fit:
     cuts: None, or where every video is cut -- one sequence of seconds from the video's beginning per video, strictly ascending,
     finite and > 0, at most 63 a video (or an `onsets.Onsets` used as a plain CSR of times over videos).  The start is then chosen
     within `snap` of the unsnapped one so that the video's beginning and its cuts land on onsets as well as they can
-    (made_sync_moments); a cut within cut_tol seconds of an onset counts.  Needs snap."""
+    (made_sync_moments); a cut within cut_tol seconds of an onset counts.  Needs snap.
+    grid: "onsets" (the default) or "beats" -- the table `snap` and `cuts` work on: the track's attacks (an `Onsets`), or its beat
+    grid (a `Beats`, mgsv_amd/beats.py: `beats=`, or a library that carries one), so that the start and the cuts land on the beat
+    and not on the nearest attack.  Nothing else about the launch changes; `Grounding.onset` then indexes the track's beats and
+    `Grounding.tempo` is set.  "beats" needs snap."""
     length: object = None
     snap: Optional[float] = None
     cuts: object = None
     cut_tol: float = 0.05
+    grid: str = "onsets"
 
     def __post_init__(self):
         self._cut_csr = None
+        if self.grid not in ("onsets", "beats"):
+            raise ValueError(f"grid = {self.grid!r}: 'onsets' or 'beats'")
+        if self.grid == "beats" and self.snap is None:
+            raise ValueError("Fit(grid='beats') needs snap= (how far a start may move to sit on a beat)")
         self.cut_tol = float(self.cut_tol)
         if not (math.isfinite(self.cut_tol) and self.cut_tol > 0.0):
             raise ValueError(f"cut_tol = {self.cut_tol!r}: a tolerance in seconds, finite and > 0")
@@ -380,7 +399,36 @@ def _onsets_on(onsets, dev):
     return cache[str(dev)]
 
 
-def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None, onsets=None, backend: Optional[str] = None) -> Grounding:
+def _fit_table(fit: Fit, onsets, beats, n_tracks: Optional[int]):
+    """the table `fit.snap` works on -- `onsets`, or with fit.grid == "beats" the beat grid's -- checked (None without snap)"""
+    if fit.snap is None:
+        return None
+    if fit.grid == "beats":
+        if beats is None:
+            raise ValueError("Fit(grid='beats') needs the tracks' beats (beats=..., or a library that carries them)")
+        if not (hasattr(beats, "table") and hasattr(beats, "tempo")):        # (by its fields: mgsv_amd/beats.py imports the audio front end, which grounding does not need)
+            raise TypeError(f"beats must be a Beats, got {type(beats).__name__}")
+        if n_tracks is not None and len(beats) != n_tracks:
+            raise ValueError(f"the beat table holds {len(beats)} tracks, there are {n_tracks}")
+        return beats.table
+    if onsets is None:
+        raise ValueError("Fit(snap=...) needs the tracks' onsets (onsets=..., or a library that carries them)")
+    if n_tracks is not None and len(onsets) != n_tracks:
+        raise ValueError(f"the onset table holds {len(onsets)} tracks, there are {n_tracks}")
+    return onsets
+
+
+def _track_tempo(track: Tensor, beats) -> Tensor:
+    """f32, the shape of track: beats.tempo[track], NaN where there is no track"""
+    tr = track.detach().cpu().numpy().astype(np.int64)      # (one read of track: the table lives on the host)
+    bpm = np.full(tr.shape, np.nan, np.float32)
+    if len(beats):
+        bpm[tr >= 0] = beats.tempo[tr[tr >= 0]]
+    return torch.from_numpy(bpm).to(track.device)
+
+
+def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None, onsets=None, backend: Optional[str] = None,
+                  beats=None) -> Grounding:
     """`g` with every moment fitted (made_fit_moments; include/made_hip.h states the arithmetic): given the length `fit.length` asks
     for -- centred on the grounded moment, clamped to the track -- and, with `fit.snap`, its start moved onto the track's nearest
     onset within that tolerance that still leaves the moment inside the track.  start / end become the fitted values; raw_start /
@@ -393,7 +441,9 @@ def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None
     With `fit.cuts` (one row per video; made_sync_moments instead) the start is chosen within `fit.snap` of the unsnapped one so that
     the video's beginning and its cuts land on onsets; an entry's video is its first index.  anchor, sync and hits are then set too:
     the anchor that sits on `onset` (0: the beginning, j >= 1: a cut), the score and the number of anchors within `fit.cut_tol`.
-    backend None: the device kernel when `g` lives on a GPU, else the numpy restatement; "host": the restatement (same bits)."""
+    backend None: the device kernel when `g` lives on a GPU, else the numpy restatement; "host": the restatement (same bits).
+    With `fit.grid == "beats"` the table is `beats.table` (a `Beats` in the same numbering) instead of `onsets`, which is then not
+    read: `onset` indexes the track's beats and `tempo` = beats.tempo[track] is set."""
     if g.raw_start is not None:
         raise ValueError("this Grounding is fitted already (fit its raw_start / raw_end instead)")
     Nv = g.track.shape[0]
@@ -414,11 +464,9 @@ def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None
         want = _seconds(fit.length, Nv, "Fit.length")
     tol = 0.0
     if fit.snap is not None:
-        if onsets is None:
-            raise ValueError("Fit(snap=...) needs the tracks' onsets (onsets=..., or a library that carries them)")
-        if len(onsets) != len(tlen):
-            raise ValueError(f"the onset table holds {len(onsets)} tracks, there are {len(tlen)}")
+        onsets = _fit_table(fit, onsets, beats, len(tlen))
         tol = fit.snap
+    on_beats = dict(tempo=_track_tempo(g.track, beats)) if fit.snap is not None and fit.grid == "beats" else {}
     if fit._cut_csr is not None and len(fit._cut_csr[0]) - 1 != Nv:
         raise ValueError(f"Fit.cuts holds {len(fit._cut_csr[0]) - 1} rows, there are {Nv} videos")
     if backend is None:
@@ -437,7 +485,7 @@ def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None
                                    torch.from_numpy(tlen).to(dev), *_onsets_on(onsets, dev), *(torch.from_numpy(a).to(dev) for a in fit._cut_csr),
                                    snap=tol, cut_tol=fit.cut_tol)
         st, en, sh, on, an, sy, hi = (t.view(shape) for t in out)
-        return replace(g, start=st, end=en, raw_start=g.start, raw_end=g.end, shift=sh, onset=on, anchor=an, sync=sy, hits=hi)
+        return replace(g, start=st, end=en, raw_start=g.start, raw_end=g.end, shift=sh, onset=on, anchor=an, sync=sy, hits=hi, **on_beats)
     if backend == "host":
         out = ops.fit_moments(g.start.reshape(-1), g.end.reshape(-1), _entry_tracks(g.track, shape), expand(torch.from_numpy(want)), tlen,
                               None if tol == 0.0 else onsets.start, None if tol == 0.0 else onsets.time, tol, backend="host")
@@ -447,10 +495,10 @@ def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None
         st, en, sh, on = (t.view(shape) for t in ops.fit_moments(
             g.start.to(torch.float32).contiguous().reshape(-1), g.end.to(torch.float32).contiguous().reshape(-1),
             _entry_tracks(g.track, shape), expand(torch.from_numpy(want).to(dev)), torch.from_numpy(tlen).to(dev), table[0], table[1], tol))
-    return replace(g, start=st, end=en, raw_start=g.start, raw_end=g.end, shift=sh, onset=on)
+    return replace(g, start=st, end=en, raw_start=g.start, raw_end=g.end, shift=sh, onset=on, **on_beats)
 
 
-def _check_fit(fit: Optional[Fit], videos: Encoded, onsets) -> None:
+def _check_fit(fit: Optional[Fit], videos: Encoded, onsets, beats=None, n_tracks: Optional[int] = None) -> None:
     """the ValueErrors of `fit_grounding` that need no result, raised before anything is computed"""
     if fit is None:
         return
@@ -458,7 +506,9 @@ def _check_fit(fit: Optional[Fit], videos: Encoded, onsets) -> None:
         raise TypeError(f"fit must be a Fit, got {type(fit).__name__}")
     if isinstance(fit.length, str) and videos.duration is None:
         raise ValueError("Fit(length='video') needs the videos' durations (videos.duration is None)")
-    if fit.snap is not None and onsets is None:
+    if fit.grid == "beats":
+        _fit_table(fit, onsets, beats, n_tracks)
+    elif fit.snap is not None and onsets is None:
         raise ValueError("Fit(snap=...) needs the tracks' onsets (onsets=..., or a library that carries them)")
     if fit._cut_csr is not None and len(fit._cut_csr[0]) - 1 != len(videos):
         raise ValueError(f"Fit.cuts holds {len(fit._cut_csr[0]) - 1} rows, there are {len(videos)} videos")
@@ -767,7 +817,7 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
            pair_batch: int = 64, windows: Optional[Windows] = None, windows_per_track: int = 1, moments: int = 1,
            nms_iou: float = 0.5, constraints: Optional[Constraints] = None, tags=None, length=None,
            shortlist: Optional[int] = None, diversity: Optional[float] = None, max_similarity: Optional[float] = None,
-           pool: Optional[int] = None, candidates=None, fit: Optional[Fit] = None, onsets=None) -> Grounding:
+           pool: Optional[int] = None, candidates=None, fit: Optional[Fit] = None, onsets=None, beats=None) -> Grounding:
     """Each video's best k tracks (groups of columns sharing a music id when group_id [N_m] is given) and the moment in each.
     constraints: per-video `Constraints` on the tracks' `tags` (int64 [tracks]) and `length` (f32 seconds [tracks]; default: the
     durations) -- the selection then runs on every row with its ineligible columns removed (made_eligibility, then the masked
@@ -794,14 +844,15 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     fit = Fit(length=, snap=) (default None: nothing below runs): the finished Grounding goes through `fit_grounding` -- every moment
     given its video's length (or the seconds asked for), kept inside its track, its start moved onto the track's nearest onset
     within `snap` seconds (with `Fit.cuts`: chosen within `snap` so that the video's cuts land on onsets; `anchor`, `sync` and `hits`
-    are then set too).  onsets: the `Onsets` table of the tracks, in `Grounding.track`'s numbering (mgsv_amd/onsets.py).  The
+    are then set too).  onsets: the `Onsets` table of the tracks, in `Grounding.track`'s numbering (mgsv_amd/onsets.py); beats: their
+    `Beats` (mgsv_amd/beats.py), the table `Fit(grid="beats")` works on instead -- `tempo` is then set too.  The
     track length is what the moments were clamped to: min(max_m_duration, duration) per column, `default_length` over windows."""
     dev = engine.device
     Nv, Nm = len(videos), len(music)
     candidates = check_candidates(engine.cfg, candidates, Nv, shortlist, sims is not None)
     shortlist = check_shortlist(engine.cfg, shortlist, sims is not None)
     div = check_diversity(k, diversity, max_similarity, pool)
-    _check_fit(fit, videos, onsets)
+    _check_fit(fit, videos, onsets, beats, windows.n_tracks if windows is not None else Nm)
     if shortlist is None and candidates is None:
         if sims is None:
             sims = similarity_matrix(engine, videos.vec, music.tokens, music.mask, music.vec)
@@ -844,7 +895,7 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     if windows is not None:
         g = _ground_windows(engine, videos, music, k, sims, group_id, pair_batch, windows, windows_per_track, moments, float(nms_iou),
                             bits, cand, div)
-        return g if fit is None else fit_grounding(g, fit, videos.duration, default_length(music.duration, windows), onsets)
+        return g if fit is None else fit_grounding(g, fit, videos.duration, default_length(music.duration, windows), onsets, beats=beats)
     gid, G = _group_tensor(group_id, Nm, dev)
     kk = max(1, min(int(k), G))
     ks = _pool_size(div, kk, G)
@@ -863,7 +914,7 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     g = Grounding(track=track, score=score, start=start.view(Nv, kk), end=end.view(Nv, kk), confidence=conf.view(Nv, kk),
                   cand_col=None if cand is None else cand[0], cand_score=None if cand is None else cand[1],
                   pool_rank=pool_rank, redundancy=redundancy)
-    return g if fit is None else fit_grounding(g, fit, videos.duration, clamp_length(music.duration, Nm, engine.cfg.max_m_duration), onsets)
+    return g if fit is None else fit_grounding(g, fit, videos.duration, clamp_length(music.duration, Nm, engine.cfg.max_m_duration), onsets, beats=beats)
 
 
 def _pad_pairs(vi: Tensor, mi: Tensor, min_pairs: int):
@@ -1475,7 +1526,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     library's slices and listed columns are widened into a scratch buffer; localization and the shortlist's second stage gather
     and widen the distinct selected columns (the whole library is never widened).  timings then receives dequantize_ms.
     fit = Fit(length=, snap=): `ground(..., fit=fit, onsets=library.onsets)` for the stored library, bit for bit, in every placement:
-    one made_fit_moments launch (made_sync_moments with `fit.cuts`) on the finished Grounding (`fit_grounding`) against `library.fit_length` and `library.onsets`.
+    one made_fit_moments launch (made_sync_moments with `fit.cuts`) on the finished Grounding (`fit_grounding`) against `library.fit_length` and `library.onsets` (`library.beats` with `Fit(grid="beats")`).
     fit None (the default): none of it runs."""
     c = engine.cfg
     dev = engine.device
@@ -1483,7 +1534,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     shortlist = check_shortlist(c, shortlist, sims_fn is not None)
     div = check_diversity(k, diversity, max_similarity, pool)
     if fit is not None:
-        _check_fit(fit, videos, library.onsets)
+        _check_fit(fit, videos, library.onsets, library.beats, library.n_tracks)
     if c.moment_query_type == "xpool":
         raise NotImplementedError("moment_query_type=xpool: the decoder query is the track's pooled vector averaged over the videos of "
                                   "the batch (reference model/model_Uni.py:222-223), a property of the batch with no per-pair meaning")
@@ -1589,7 +1640,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
         g = Grounding(track=_window_tracks(rep, track_of_col), score=score, start=start, end=end, confidence=conf,
                       window=torch.cat([p[3] for p in parts]), windows=windows, cand_col=cc, cand_score=cs,
                       pool_rank=pool_rank, redundancy=redundancy)
-    return g if fit is None else fit_grounding(g, fit, videos.duration, library.fit_length(c.max_m_duration), library.onsets)
+    return g if fit is None else fit_grounding(g, fit, videos.duration, library.fit_length(c.max_m_duration), library.onsets, beats=library.beats)
 
 
 def moment_iou(start: Tensor, end: Tensor, gt_moment: Tensor, m_duration: Tensor, max_m_duration: float) -> Tensor:

@@ -122,16 +122,11 @@ def track_spectrogram(pcm16: torch.Tensor, n16: Sequence[int], tables=None):
     return spec.view(n, n_blocks * music.ROWS, music.MELS), torch.tensor(frames, dtype=torch.int32, device=dev)
 
 
-@torch.no_grad()
-def detect_onsets(tracks: Sequence, device="cuda:0", max_seconds: Optional[float] = None, lag: int = 2, w_max: int = 5,
-                  w_avg: int = 50, delta: float = 0.05, timings: Optional[dict] = None) -> Onsets:
-    """The onsets of every (waveform, sr) of `tracks` (as `MusicEncoder.encode_tracks` takes them: float32 [C, n] or [n], channel 0
-    is read), over the whole track or its first max_seconds.  Tracks run in groups of consecutive tracks whose spectrogram holds at
-    most SPEC_BUDGET floats (one track alone may exceed it); per group: one resample launch, made_audio_fbank over the blocks,
-    made_onset_strength, made_onset_peaks, one read of the counts and times.  A track shorter than 400 samples has no onsets.
-    timings: a dict that receives the milliseconds of the four phases (this synchronises; for measurements)."""
-    lag, w_max, w_avg, delta = _check_params(lag, w_max, w_avg, delta)
-    dev = torch.device(device)
+def _envelopes(tracks: Sequence, dev, max_seconds: Optional[float], lag: int, timed: bool):
+    """The front end `detect_onsets` and mgsv_amd/beats.py share: the tracks in groups of consecutive tracks whose spectrogram holds
+    at most SPEC_BUDGET floats (one track alone may exceed it); per group one resample launch, made_audio_fbank over the blocks and
+    made_onset_strength.  Yields (env [n, env_ld] f32, frames [n] int32, ev) per group: ev is None or, timed, the four events
+    recorded before, between and after the three phases -- the consumer appends its own with `_mark`."""
     chans = [music._channel0(w) for w, _ in tracks]
     n16 = [music.resampled_length(int(c.shape[0]), sr) for c, (_, sr) in zip(chans, tracks)]
     if max_seconds is not None:
@@ -142,45 +137,84 @@ def detect_onsets(tracks: Sequence, device="cuda:0", max_seconds: Optional[float
     blocks = [max(1, -(-n_frames_of(x) // music.ROWS)) for x in n16]
     tables = tuple(torch.from_numpy(t).to(dev) for t in music.fbank_tables()) if tracks else None
     per_block = music.ROWS * music.MELS
-    marks = []
-    counts: List[np.ndarray] = []
-    times: List[np.ndarray] = []
     t0 = 0
     while t0 < len(tracks):
         t1, most = t0 + 1, blocks[t0]
         while t1 < len(tracks) and (t1 - t0 + 1) * max(most, blocks[t1]) * per_block <= SPEC_BUDGET and t1 - t0 < music.TRACKS_MAX:
             most = max(most, blocks[t1])
             t1 += 1
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timings is not None else None
-        if ev:
-            ev[0].record()
+        ev = [] if timed else None
+        _mark(ev)
         longest = max(1, max(n16[t0:t1]))
         pcm16, _ = music.resample_tracks(tracks[t0:t1], dev, out_len=longest)
-        if ev:
-            ev[1].record()
+        _mark(ev)
         spec, frames = track_spectrogram(pcm16, n16[t0:t1], tables)
-        if ev:
-            ev[2].record()
+        _mark(ev)
         env = ops.onset_strength(spec, frames, lag)
-        if ev:
-            ev[3].record()
-        time, count = ops.onset_peaks(env, frames, w_max, w_avg, delta)
-        if ev:
-            ev[4].record()
-            marks.append(ev)
-        c = count.cpu().numpy().astype(np.int64)
-        assert (c >= 0).all()
-        tm = time.cpu().numpy()
-        counts.append(c)
-        times.append(np.concatenate([tm[i, :c[i]] for i in range(len(c))]) if len(c) else np.zeros(0, np.float32))
+        _mark(ev)
+        yield env, frames, ev
         t0 = t1
-    if timings is not None:
-        torch.cuda.synchronize()
-        for j, name in enumerate(("resample_ms", "fbank_ms", "strength_ms", "peaks_ms")):
-            timings[name] = sum(e[j].elapsed_time(e[j + 1]) for e in marks)
-        timings["groups"] = len(marks)
-    start = np.zeros(len(tracks) + 1, np.int64)
+
+
+def _mark(ev: Optional[list]) -> None:
+    """record one more event on the current stream (nothing when the run is not timed)"""
+    if ev is not None:
+        ev.append(torch.cuda.Event(enable_timing=True))
+        ev[-1].record()
+
+
+def _read_lists(time: torch.Tensor, count: torch.Tensor):
+    """(counts int64 [n], the rows' first count[i] times one after the other, f32) of a group: one read of each tensor"""
+    c = count.cpu().numpy().astype(np.int64)
+    assert (c >= 0).all()
+    tm = time.cpu().numpy()
+    return c, (np.concatenate([tm[i, :c[i]] for i in range(len(c))]) if len(c) else np.zeros(0, np.float32))
+
+
+def _phase_timings(timings: Optional[dict], marks: list, names: Sequence[str]) -> None:
+    """timings[name j] = the milliseconds between the events j and j + 1, summed over the groups (this synchronises)"""
+    if timings is None:
+        return
+    torch.cuda.synchronize()
+    for j, name in enumerate(names):
+        timings[name] = sum(e[j].elapsed_time(e[j + 1]) for e in marks)
+    timings["groups"] = len(marks)
+
+
+def _csr(n: int, counts: List[np.ndarray], times: List[np.ndarray]):
+    """(start int64 [n + 1], time f32) of the groups' lists"""
+    start = np.zeros(n + 1, np.int64)
     if counts:
         np.cumsum(np.concatenate(counts), out=start[1:])
-    return Onsets(start, np.concatenate(times) if times else np.zeros(0, np.float32),
-                  dict(lag=lag, w_max=w_max, w_avg=w_avg, delta=delta, frame_seconds=FRAME_SECONDS, max_seconds=max_seconds))
+    return start, (np.concatenate(times) if times else np.zeros(0, np.float32))
+
+
+def _onset_params(lag, w_max, w_avg, delta, max_seconds) -> dict:
+    return dict(lag=lag, w_max=w_max, w_avg=w_avg, delta=delta, frame_seconds=FRAME_SECONDS, max_seconds=max_seconds)
+
+
+ONSET_PHASES = ("resample_ms", "fbank_ms", "strength_ms", "peaks_ms")
+
+
+@torch.no_grad()
+def detect_onsets(tracks: Sequence, device="cuda:0", max_seconds: Optional[float] = None, lag: int = 2, w_max: int = 5,
+                  w_avg: int = 50, delta: float = 0.05, timings: Optional[dict] = None) -> Onsets:
+    """The onsets of every (waveform, sr) of `tracks` (as `MusicEncoder.encode_tracks` takes them: float32 [C, n] or [n], channel 0
+    is read), over the whole track or its first max_seconds.  Tracks run in groups of consecutive tracks whose spectrogram holds at
+    most SPEC_BUDGET floats (one track alone may exceed it); per group: one resample launch, made_audio_fbank over the blocks,
+    made_onset_strength, made_onset_peaks, one read of the counts and times.  A track shorter than 400 samples has no onsets.
+    timings: a dict that receives the milliseconds of the four phases (this synchronises; for measurements)."""
+    lag, w_max, w_avg, delta = _check_params(lag, w_max, w_avg, delta)
+    marks = []
+    counts: List[np.ndarray] = []
+    times: List[np.ndarray] = []
+    for env, frames, ev in _envelopes(tracks, torch.device(device), max_seconds, lag, timings is not None):
+        time, count = ops.onset_peaks(env, frames, w_max, w_avg, delta)
+        _mark(ev)
+        if ev:
+            marks.append(ev)
+        c, tm = _read_lists(time, count)
+        counts.append(c)
+        times.append(tm)
+    _phase_timings(timings, marks, ONSET_PHASES)
+    return Onsets(*_csr(len(tracks), counts, times), _onset_params(lag, w_max, w_avg, delta, max_seconds))

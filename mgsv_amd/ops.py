@@ -1261,6 +1261,59 @@ def onset_peaks(env: Tensor, n_frames: Tensor, w_max: int = 5, w_avg: int = 50, 
     return time, count
 
 
+BEAT_MAX_LAG = 256                       # the longest period made_tempo_autocorr and made_beat_track take, frames of 10 ms
+
+
+def tempo_autocorr(env: Tensor, n_frames: Tensor, lag_min: int, lag_max: int, weight: Tensor):
+    """made_tempo_autocorr: (ac [N, n_lags + 1] f32, scale [N] f32, period [N] int32) of the envelopes env [N, env_ld] f32
+    (contiguous), n_lags = lag_max - lag_min + 1: ac[:, 0] the sum of squares of the mean-removed envelope over n_frames[t] frames,
+    ac[:, 1 + j] its autocorrelation at lag lag_min + j, scale the inverse standard deviation, period the lag with the largest
+    (ac / (nf - l)) * weight[j] (weight [n_lags] f32 on the device; the smaller of equal ones).  A track without a tempo (nf <=
+    lag_max, no variance, no positive score) gets period -1 and scale NaN."""
+    assert env.dim() == 2 and env.dtype == torch.float32 and env.is_contiguous()
+    N, env_ld = env.shape
+    n_lags = int(lag_max) - int(lag_min) + 1
+    assert n_frames.dtype == torch.int32 and n_frames.is_contiguous() and n_frames.numel() == N
+    assert weight.dtype == torch.float32 and weight.is_contiguous() and weight.numel() == max(n_lags, 0) and weight.device == env.device
+    ac = torch.empty(N, max(n_lags, 0) + 1, device=env.device, dtype=torch.float32)
+    scale = torch.empty(N, device=env.device, dtype=torch.float32)
+    period = torch.empty(N, device=env.device, dtype=torch.int32)
+    check(lib().made_tempo_autocorr(_p(env) if env.numel() else None, env_ld, _p(n_frames), N, int(lag_min), int(lag_max), _p(weight),
+                                    _p(ac), _p(scale), _p(period), _stream()), "made_tempo_autocorr")
+    return ac, scale, period
+
+
+def beat_track(env: Tensor, n_frames: Tensor, period: Tensor, scale: Tensor, alpha: float = 100.0, period_min: int = 2,
+               cap: Optional[int] = None, time: Optional[Tensor] = None, count: Optional[Tensor] = None, cum: Optional[Tensor] = None,
+               back: Optional[Tensor] = None):
+    """made_beat_track: (time [N, cap] f32, count [N] int32, cum [N, env_ld] f32, back [N, env_ld] int32) of the envelopes env [N,
+    env_ld] f32 (contiguous) with the periods period [N] int32 (frames; -1: no tempo, count 0) and scale [N] f32: Ellis's dynamic
+    programme (include/made_hip.h states every step), the beats ascending as f * 0.01 seconds in time[t, :count[t]].  Only [0,
+    n_frames[t]) of a cum / back row is written.  count -1: a track that was refused (its frames, period, scale or cap).  alpha: the
+    tightness -- 100 is librosa's, for an envelope of unit deviation; nobody has tuned it on real music.  period_min: the smallest
+    period the caller's tracks hold; the default cap, env_ld // dlo_min + 1 with dlo_min = (period_min + 1) // 2, cannot overflow.
+    time / count / cum / back: tensors to write into (default: new ones; time's second size is then the cap)."""
+    assert env.dim() == 2 and env.dtype == torch.float32 and env.is_contiguous()
+    N, env_ld = env.shape
+    for t, dt in ((n_frames, torch.int32), (period, torch.int32), (scale, torch.float32)):
+        assert t.dtype == dt and t.is_contiguous() and t.numel() == N and t.device == env.device
+    if cap is None:
+        cap = env_ld // max((int(period_min) + 1) // 2, 1) + 1
+    if time is None:
+        time = torch.empty(N, max(int(cap), 0), device=env.device, dtype=torch.float32)
+    count = torch.empty(N, device=env.device, dtype=torch.int32) if count is None else count
+    cum = torch.empty(N, env_ld, device=env.device, dtype=torch.float32) if cum is None else cum
+    back = torch.empty(N, env_ld, device=env.device, dtype=torch.int32) if back is None else back
+    assert time.dim() == 2 and time.shape[0] == N and time.dtype == torch.float32 and time.is_contiguous()
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == N
+    assert tuple(cum.shape) == (N, env_ld) and cum.dtype == torch.float32 and cum.is_contiguous()
+    assert tuple(back.shape) == (N, env_ld) and back.dtype == torch.int32 and back.is_contiguous()
+    check(lib().made_beat_track(_p(env) if env.numel() else None, env_ld, _p(n_frames), _p(period), _p(scale), N, float(alpha), time.shape[1],
+                                _p(time) if time.numel() else None, _p(count), _p(cum) if cum.numel() else None,
+                                _p(back) if back.numel() else None, _stream()), "made_beat_track")
+    return time, count, cum, back
+
+
 def fit_moments_host(start, end, track, want, tlen, onset_start=None, onset_time=None, tol: float = 0.0):
     """made_fit_moments restated in numpy float32, one rounded operation per step (include/made_hip.h states the contract): the
     same bits as the kernel.  Arrays of E entries -> (out_start, out_end, shift f32 [E], onset int32 [E])."""
