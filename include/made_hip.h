@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MADE_ABI_VERSION 8
+#define MADE_ABI_VERSION 9
 
 enum MadeDtype { MADE_F32 = 0, MADE_BF16 = 1 };
 
@@ -91,13 +91,13 @@ enum MadeStatus {
 };
 
 int         made_abi_version(void);
-/* f32 products of every kernel that multiplies f32 operands (MadeDtype MADE_F32 compute): mode 0 = exact (v_mfma_f32_32x32x2_f32, 157 TFLOP/s
- * peak), mode 1 = split-bf16: each operand as hi + lo bf16 halves and a . b ~ hi.hi + hi.lo + lo.hi on the bf16 matrix pipe (three products at
- * 16x the f32 rate; the operands' last 7 mantissa bits are dropped: relative 8e-6 per operand, f32 accumulation, storage and elementwise
- * steps unchanged).  Process-wide, read when a launch is issued; the reference's arithmetic is fp32 throughout (train-MaDe.py:237), its
- * tolerance <= 1e-4 on logits / spans -- the engine's "f32x3" mode is held to that gate by the same tests as "f32". */
-int         made_set_f32_products(int mode);
-int         made_get_f32_products(void);
+/* f32 products (the `f32_products` field of MadeLinearArgs, MadeAttnArgs, MadeWideAttnArgs, MadeAttnBwdArgs and MadeGemmTNArgs): how THAT call
+ * multiplies f32 operands (MadeDtype MADE_F32 compute).  0 = exact (v_mfma_f32_32x32x2_f32, 157 TFLOP/s peak); 1 = split-bf16: each operand as
+ * hi + lo bf16 halves and a . b ~ hi.hi + hi.lo + lo.hi on the bf16 matrix pipe (three products at 16x the f32 rate; the operands' last 7
+ * mantissa bits are dropped: relative 8e-6 per operand, f32 accumulation, storage and elementwise steps unchanged); any other value is
+ * MADE_ERR_INVALID_ARG.  The field has no effect on a call that multiplies no f32 operands (bf16 compute).  The library keeps no mode of
+ * its own: every launch is what its arguments say.  The reference's arithmetic is fp32 throughout (train-MaDe.py:237), its tolerance
+ * <= 1e-4 on logits / spans -- the engine's "f32x3" mode is held to that gate by the same tests as "f32". */
 const char* made_last_error(void);
 /* fills name (<= name_len chars), compute-unit count and 1 if the device is gfx950 */
 int         made_device_info(char* name, int name_len, int* cu_count, int* is_gfx950);
@@ -115,7 +115,7 @@ int         made_device_info(char* name, int name_len, int* cu_count, int* is_gf
  *   A' = (A + A2[row % a2_row_mod]) for column segments flagged use_a2 (or A2 itself when a2_replace is set),
  *   else A; rows of A whose a_row_mask is 0 are read as zero.  W is [N,K] row-major (nn.Linear layout), K contiguous.
  *   Compute type = w_dtype: MADE_BF16 -> v_mfma_f32_32x32x16_bf16, MADE_F32 -> v_mfma_f32_32x32x2_f32
- *   (exact f32 FMA chain); accumulation is always f32.
+ *   (exact f32 FMA chain; three bf16 products on split operands when f32_products = 1); accumulation is always f32.
  *   The N columns are split into up to 4 segments, each with its own output tensor; a segment may
  *   be written transposed per batch (out[b][n][t], t = row % rows_per_batch) which is the layout
  *   made_attention wants for V.  `batch` > 1 runs independent problems (grid.z) with the given
@@ -174,6 +174,7 @@ typedef struct MadeLinearArgs {
        for problem z of a batched call -- the value-projection bias of the memory-space cross-attention, whose dropped attention
        weights no longer sum to 1 (reference music_detr/transformer.py:293-296 under dropout; replaces a made_head_bias launch) */
     const float* bias_row_scale; int64_t bias_z_stride;
+    int32_t      f32_products; int32_t _pad;                /* 0 = exact f32 products, 1 = split-bf16 (see "f32 products" above) */
 } MadeLinearArgs;
 
 int made_linear(const MadeLinearArgs* args, void* stream);
@@ -288,7 +289,7 @@ typedef struct MadeAttnArgs {
     int64_t B, H, Lq, Lk;
     int64_t q_bs, ldq, k_bs, ldk, v_bs, ldv, o_bs, ldo;
     const float* key_mask; const float* q_mask;
-    float scale; int32_t _pad;
+    float scale; int32_t f32_products;   /* 0 = exact f32 products, 1 = split-bf16 (see "f32 products" above) */
     const float* q_skip_mask;  /* [B, Lq] or NULL: queries that are 0 here are padding whose output nobody reads; 32-query
                                   groups (and whole workgroups) made only of them are skipped and their O rows left untouched */
     /* training path */
@@ -333,7 +334,7 @@ typedef struct MadeWideAttnArgs {
     int32_t dtype; int32_t o_dtype;
     int64_t B, NQ1, NQ2, L, D;
     int64_t q_bs, q_s1, q_s2, k_bs, ldk, kadd_bs, ldkadd, v_bs, ldv, o_bs, o_s1, o_s2;
-    float scale; int32_t _pad;
+    float scale; int32_t f32_products;   /* 0 = exact f32 products, 1 = split-bf16 (see "f32 products" above) */
     int64_t n_split;           /* > 1: keys are split over grid.z (few queries, long memory: fills the chip) and */
     float*  part_o;            /*      the slices are merged by a second launch; [B, n_split, NQ, D] f32 */
     float*  part_ml;           /*      [B, n_split, NQ, 4] f32 (running max, sum, sum of the dropped weights, unused) */
@@ -751,7 +752,7 @@ typedef struct MadeAttnBwdArgs {
     int64_t B, H, Lq, Lk;
     int64_t q_bs, ldq, k_bs, ldk, v_bs, ldv, o_bs, ldo, do_bs, lddo, dq_bs, lddq, dk_bs, lddk, dv_bs, lddv;
     const float* key_mask; const float* q_skip_mask;
-    float scale; int32_t _pad;
+    float scale; int32_t f32_products;   /* 0 = exact f32 products, 1 = split-bf16 (see "f32 products" above) */
     MadeDropout drop;
     const int32_t* batch_order; /* [B] or NULL: issue order of the batch, as in MadeAttnArgs */
     const uint32_t* keep_bits; int64_t ld_bits;   /* NULL, or the forward's dropout decisions (MadeAttnArgs.keep_bits; bf16 path): the
@@ -782,6 +783,7 @@ typedef struct MadeGemmTNArgs {
                                                        whose rows are all masked are skipped without being loaded */
     const int32_t* row_index; const int32_t* n_rows; /* optional row gather (unbatched calls): the reduction runs over the
                                                        *n_rows rows row_index[0..] only (made_row_index); row_mask is not needed */
+    int32_t f32_products; int32_t _pad;             /* 0 = exact f32 products, 1 = split-bf16 (see "f32 products" above) */
 } MadeGemmTNArgs;
 
 int made_gemm_tn(const MadeGemmTNArgs* args, void* stream);

@@ -22,7 +22,7 @@ def variant_env(name: str, default: str = "") -> str:
 
 
 LIB_PATH = os.environ.get("MADE_LIB_PATH") or os.path.join(_HERE, "libmade_hip.so")
-ABI_VERSION = 8                          # include/made_hip.h MADE_ABI_VERSION the ctypes mirrors in this file were written for
+ABI_VERSION = 9                          # include/made_hip.h MADE_ABI_VERSION the ctypes mirrors in this file were written for
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_QUICKGELU, ACT_SIGMOID = 0, 1, 2, 3, 4
@@ -67,7 +67,7 @@ class MadeLinearArgs(C.Structure):
                 ("seg", MadeLinearSeg * 4),
                 ("G", vp), ("g_dtype", i32), ("gate", i32), ("ldg", i64), ("gate_scale", f32), ("z_dtype", i32),
                 ("Zout", vp), ("ldz", i64), ("drop", MadeDropout), ("drop_ld", i64), ("row_index", vp), ("n_rows", vp),
-                ("bias_row_scale", vp), ("bias_z_stride", i64)]
+                ("bias_row_scale", vp), ("bias_z_stride", i64), ("f32_products", i32), ("_pad", i32)]
 
 
 class MadeFinishArgs(C.Structure):
@@ -106,7 +106,7 @@ class MadeAttnArgs(C.Structure):
                 ("q_bs", i64), ("ldq", i64), ("k_bs", i64), ("ldk", i64),
                 ("v_bs", i64), ("ldv", i64), ("o_bs", i64), ("ldo", i64),
                 ("key_mask", vp), ("q_mask", vp),
-                ("scale", f32), ("_pad", i32),
+                ("scale", f32), ("f32_products", i32),
                 ("q_skip_mask", vp),
                 ("lse", vp), ("drop", MadeDropout), ("batch_order", vp), ("keep_bits", vp), ("ld_bits", i64)]
 
@@ -117,7 +117,7 @@ class MadeAttnBwdArgs(C.Structure):
                 ("B", i64), ("H", i64), ("Lq", i64), ("Lk", i64),
                 ("q_bs", i64), ("ldq", i64), ("k_bs", i64), ("ldk", i64), ("v_bs", i64), ("ldv", i64), ("o_bs", i64), ("ldo", i64),
                 ("do_bs", i64), ("lddo", i64), ("dq_bs", i64), ("lddq", i64), ("dk_bs", i64), ("lddk", i64), ("dv_bs", i64), ("lddv", i64),
-                ("key_mask", vp), ("q_skip_mask", vp), ("scale", f32), ("_pad", i32), ("drop", MadeDropout),
+                ("key_mask", vp), ("q_skip_mask", vp), ("scale", f32), ("f32_products", i32), ("drop", MadeDropout),
                 ("batch_order", vp), ("keep_bits", vp), ("ld_bits", i64)]
 
 
@@ -160,7 +160,7 @@ class MadeWideAttnArgs(C.Structure):
                 ("B", i64), ("NQ1", i64), ("NQ2", i64), ("L", i64), ("D", i64),
                 ("q_bs", i64), ("q_s1", i64), ("q_s2", i64), ("k_bs", i64), ("ldk", i64), ("kadd_bs", i64), ("ldkadd", i64),
                 ("v_bs", i64), ("ldv", i64), ("o_bs", i64), ("o_s1", i64), ("o_s2", i64),
-                ("scale", f32), ("_pad", i32),
+                ("scale", f32), ("f32_products", i32),
                 ("n_split", i64), ("part_o", vp), ("part_ml", vp), ("drop", MadeDropout), ("sum_out", vp),
                 ("lse_out", vp)]
 
@@ -180,7 +180,7 @@ class MadeGemmTNArgs(C.Structure):
                 ("row_mask", vp), ("mask_zs1", i64), ("mask_zs2", i64),
                 ("alpha", f32), ("accumulate", i32), ("split_m", i64),
                 ("colsum", vp), ("colsum_zs1", i64), ("colsum_zs2", i64), ("row_group_valid", vp),
-                ("row_index", vp), ("n_rows", vp)]
+                ("row_index", vp), ("n_rows", vp), ("f32_products", i32), ("_pad", i32)]
 
 
 class MadeGemmTNProblem(C.Structure):
@@ -233,8 +233,6 @@ class MadeGatherBatchArgs(C.Structure):
 # name -> (restype, argtypes); every symbol include/made_hip.h declares
 SIGNATURES = {
     "made_abi_version": (C.c_int, []),
-    "made_set_f32_products": (C.c_int, [C.c_int]),
-    "made_get_f32_products": (C.c_int, []),
     "made_last_error": (C.c_char_p, []),
     "made_device_info": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "made_tape_begin": (C.c_int, []),
@@ -383,24 +381,6 @@ def check(status: int, what: str = "") -> None:
     if status != 0:
         msg = lib().made_last_error().decode("utf-8", "replace")
         raise MadeError(f"{what or 'libmade_hip'} failed (status {status}): {msg}")
-
-
-def scoped_f32_products(fn):
-    """Decorator of an entry point whose first argument is an engine / encoder: the library's process-wide f32 product mode
-    (made_set_f32_products) is that object's `_f32_products` (0 when it has none) for the duration of the call and what it was before
-    afterwards -- an "f32x3" engine's split-bf16 mode never outlives the engine's own launches."""
-    import functools
-
-    @functools.wraps(fn)
-    def run(owner, *args, **kw):
-        l = lib()
-        before = int(l.made_get_f32_products())
-        check(l.made_set_f32_products(int(getattr(owner, "_f32_products", 0))), "made_set_f32_products")
-        try:
-            return fn(owner, *args, **kw)
-        finally:
-            check(l.made_set_f32_products(before), "made_set_f32_products")
-    return run
 
 
 def device_info():

@@ -26,7 +26,7 @@ template <typename TC> struct Frag;
 template <> struct Frag<float>  { typedef f32x4  type; };
 template <> struct Frag<bf16_t> { typedef bf16x8 type; };
 
-template <typename TC, int HD, bool X3 = false>        // X3 (f32 only): split-bf16 products (common.h, made_set_f32_products)
+template <typename TC, int HD, bool X3 = false>        // X3 (f32 only): split-bf16 products (common.h; the arguments' f32_products)
 __global__ __launch_bounds__(NTHREADS, (HD <= 64 ? 2 : 1)) void attention_kernel(const MadeAttnArgs a) {
     typedef typename Frag<TC>::type frag_t;
     constexpr int SZ = (int)sizeof(TC);
@@ -412,15 +412,15 @@ int launch_attention(const MadeAttnArgs& a, hipStream_t st) {
     dim3 grid((unsigned)(((a.Lq + BQ - 1) / BQ) * 8 * ((a.H * a.B + 7) / 8))), block(NTHREADS);
     switch (a.hd) {
         case 32:
-            if (sizeof(TC) == 4 && g_made_f32_products) hipLaunchKernelGGL((attention_kernel<TC, 32, sizeof(TC) == 4>), grid, block, 0, st, a);
+            if (sizeof(TC) == 4 && a.f32_products) hipLaunchKernelGGL((attention_kernel<TC, 32, sizeof(TC) == 4>), grid, block, 0, st, a);
             else hipLaunchKernelGGL((attention_kernel<TC, 32>), grid, block, 0, st, a);
             break;
         case 64:
-            if (sizeof(TC) == 4 && g_made_f32_products) hipLaunchKernelGGL((attention_kernel<TC, 64, sizeof(TC) == 4>), grid, block, 0, st, a);
+            if (sizeof(TC) == 4 && a.f32_products) hipLaunchKernelGGL((attention_kernel<TC, 64, sizeof(TC) == 4>), grid, block, 0, st, a);
             else hipLaunchKernelGGL((attention_kernel<TC, 64>), grid, block, 0, st, a);
             break;
         case 128:
-            if (sizeof(TC) == 4 && g_made_f32_products) hipLaunchKernelGGL((attention_kernel<TC, 128, sizeof(TC) == 4>), grid, block, 0, st, a);
+            if (sizeof(TC) == 4 && a.f32_products) hipLaunchKernelGGL((attention_kernel<TC, 128, sizeof(TC) == 4>), grid, block, 0, st, a);
             else hipLaunchKernelGGL((attention_kernel<TC, 128>), grid, block, 0, st, a);
             break;
         default:
@@ -438,6 +438,7 @@ extern "C" int made_attention(const MadeAttnArgs* args, void* stream) {
     MADE_REQUIRE(a.Q && a.K && a.V && a.O, "made_attention: null tensor");
     MADE_REQUIRE(a.B >= 0 && a.H > 0 && a.Lq >= 0 && a.Lk > 0, "made_attention: bad dims");
     MADE_REQUIRE(a.dtype == MADE_F32 || a.dtype == MADE_BF16, "made_attention: bad dtype %d", a.dtype);
+    MADE_REQUIRE(a.f32_products == 0 || a.f32_products == 1, "made_attention: f32_products %d not in {0, 1}", a.f32_products);
     if (a.keep_bits)
         MADE_REQUIRE(a.ld_bits >= 32 * ((a.Lq + 31) / 32) && a.ld_bits % 32 == 0 && ((uintptr_t)a.keep_bits % 8) == 0,
                      "made_attention: keep_bits rows need ld_bits = a multiple of 32 >= Lq (%lld words per key tile) and 8-byte alignment", (long long)(32 * ((a.Lq + 31) / 32)));

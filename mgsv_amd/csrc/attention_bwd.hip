@@ -38,7 +38,7 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* tile, int P, int 
 }
 
 // ---------------------------------------------------------------------------------------------- dQ
-template <typename TC, int HD, bool X3 = false>        // X3 (f32 only): split-bf16 products (common.h, made_set_f32_products)
+template <typename TC, int HD, bool X3 = false>        // X3 (f32 only): split-bf16 products (common.h; the arguments' f32_products)
 __global__ __launch_bounds__(NTH, (sizeof(TC) == 2 && HD <= 64) ? 2 : 1) void attn_bwd_dq_kernel(const MadeAttnBwdArgs a) {
     typedef typename Frag<TC>::type frag_t;
     constexpr int SZ = (int)sizeof(TC);
@@ -708,7 +708,7 @@ int launch_bwd_hd(const MadeAttnBwdArgs& a, dim3 gq, dim3 gk, size_t lds_q, size
         }
         attr_done = true;
     }
-    if (sizeof(TC) == 4 && g_made_f32_products) {
+    if (sizeof(TC) == 4 && a.f32_products) {
         static bool attr3 = false;
         if (!attr3) {
             hipError_t e1 = hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<TC, HD, sizeof(TC) == 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDyn);
@@ -752,6 +752,7 @@ extern "C" int made_attention_bwd(const MadeAttnBwdArgs* args, void* stream) {
     MADE_REQUIRE(a.Q && a.K && a.V && a.O && a.dO && a.dQ && a.dK && a.dV && a.lse && a.delta, "made_attention_bwd: null tensor");
     MADE_REQUIRE(a.B >= 0 && a.H > 0 && a.Lq >= 0 && a.Lk > 0, "made_attention_bwd: bad dims");
     MADE_REQUIRE(a.dtype == MADE_F32 || a.dtype == MADE_BF16, "made_attention_bwd: bad dtype %d", a.dtype);
+    MADE_REQUIRE(a.f32_products == 0 || a.f32_products == 1, "made_attention_bwd: f32_products %d not in {0, 1}", a.f32_products);
     MADE_REQUIRE(a.drop.p >= 0.f && a.drop.p < 1.f, "made_attention_bwd: dropout p out of [0,1)");
     if (a.keep_bits)
         MADE_REQUIRE(a.ld_bits >= 32 * ((a.Lq + 31) / 32) && a.ld_bits % 32 == 0 && ((uintptr_t)a.keep_bits % 8) == 0,

@@ -46,7 +46,7 @@ template <> struct Frag<bf16_t> { typedef bf16x8 type; };
 // (include/made_hip.h) instead of (sample, blockIdx.z-th equal slice): sample, first tile, tile count, slice index, the sample's first
 // valid key and the valid-key bits of its tiles arrive with one 64-byte load, so the scan of the sample's whole key mask (a dependent
 // global round trip, ballots and two barriers in front of the first tile) goes; a.n_split is the slice capacity of part_o / part_ml.
-template <typename TC, int D, bool DB, int NSL, bool X3 = false, bool PLAN = false>      // X3 (f32 only): split-bf16 products (common.h, made_set_f32_products)
+template <typename TC, int D, bool DB, int NSL, bool X3 = false, bool PLAN = false>      // X3 (f32 only): split-bf16 products (common.h; the arguments' f32_products)
 __global__ __launch_bounds__(NTHREADS) void attention_wide_kernel(const MadeWideAttnArgs a, const int32_t* __restrict__ plan) {
     static_assert(!PLAN || (DB && sizeof(TC) == 2 && NSL == 4 && !X3), "the planned launch: LDS-DMA variant, one query tile");
     typedef typename Frag<TC>::type frag_t;
@@ -589,7 +589,7 @@ int launch_wide(const MadeWideAttnArgs& a, hipStream_t st) {
     const int64_t qtiles = (nq + WQB - 1) / WQB;
     const bool batch_fast = qtiles > 1 && qtiles <= 8 && qtiles != a.B;       // see the kernel: which index runs fastest
     dim3 grid((unsigned)(batch_fast ? a.B : qtiles), (unsigned)(batch_fast ? qtiles : a.B), (unsigned)nsplit), block(NTHREADS);
-    if (SZ == 4 && g_made_f32_products) hipLaunchKernelGGL((attention_wide_kernel<TC, D, DB, NSL, SZ == 4>), grid, block, lds_bytes, st, a, (const int32_t*)nullptr);
+    if (SZ == 4 && a.f32_products) hipLaunchKernelGGL((attention_wide_kernel<TC, D, DB, NSL, SZ == 4>), grid, block, lds_bytes, st, a, (const int32_t*)nullptr);
     else hipLaunchKernelGGL((attention_wide_kernel<TC, D, DB, NSL>), grid, block, lds_bytes, st, a, (const int32_t*)nullptr);
     int rc = made_check_launch("made_attention_wide");
     if (rc != MADE_OK || nsplit == 1) return rc;
@@ -790,6 +790,7 @@ extern "C" int made_attention_wide_planned(const MadeWideAttnArgs* args, const v
     MADE_REQUIRE(a.Q && a.K && a.V && a.O, "made_attention_wide_planned: null tensor");
     MADE_REQUIRE(a.B >= 0 && a.NQ1 >= 0 && a.NQ2 > 0 && a.L > 0, "made_attention_wide_planned: bad dims");
     MADE_REQUIRE(a.o_dtype == MADE_F32 || a.o_dtype == MADE_BF16, "made_attention_wide_planned: bad o_dtype %d", a.o_dtype);
+    MADE_REQUIRE(a.f32_products == 0 || a.f32_products == 1, "made_attention_wide_planned: f32_products %d not in {0, 1}", a.f32_products);    // (bf16 only: checked, never read)
     MADE_UNSUPPORTED(a.dtype == MADE_BF16 && (a.D == 256 || a.D == 512) && a.Kadd == nullptr && a.key_mask != nullptr && a.NQ1 * a.NQ2 <= WQ,
                      "made_attention_wide_planned: bf16, D in {256, 512}, no Kadd, a key mask and at most %d query rows per sample", WQ);
     MADE_UNSUPPORTED(a.B <= n_slots && n_slots <= PLAN_T, "made_attention_wide_planned: B <= n_slots <= %d", PLAN_T);
@@ -811,6 +812,7 @@ extern "C" int made_attention_wide(const MadeWideAttnArgs* args, void* stream) {
     MADE_REQUIRE(a.Q && a.K && a.V && a.O, "made_attention_wide: null tensor");
     MADE_REQUIRE(a.B >= 0 && a.NQ1 >= 0 && a.NQ2 > 0 && a.L > 0, "made_attention_wide: bad dims");
     MADE_REQUIRE(a.dtype == MADE_F32 || a.dtype == MADE_BF16, "made_attention_wide: bad dtype %d", a.dtype);
+    MADE_REQUIRE(a.f32_products == 0 || a.f32_products == 1, "made_attention_wide: f32_products %d not in {0, 1}", a.f32_products);
     MADE_REQUIRE(a.o_dtype == MADE_F32 || a.o_dtype == MADE_BF16, "made_attention_wide: bad o_dtype %d", a.o_dtype);
     MADE_UNSUPPORTED(a.D == 128 || a.D == 256 || a.D == 512, "made_attention_wide: D=%lld not in {128, 256, 512}", (long long)a.D);
     MADE_UNSUPPORTED(a.B <= 65535, "made_attention_wide: B too large for the grid");

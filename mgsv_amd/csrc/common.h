@@ -131,12 +131,11 @@ __host__ __device__ __forceinline__ int made_keep_slot(int q) { return 2 * ((q &
 // made_attention_bwd's single-pass kernel (attention_bwd_fused.hip): MADE_OK after launching, a HIP error, or -1000 when it does not apply
 int made_attention_bwd_fused_try(const MadeAttnBwdArgs& a, hipStream_t st);
 
-// ---- f32 products on the bf16 matrix pipe (made_set_f32_products(1); engine dtype "f32x3") ----------------------------------------
+// ---- f32 products on the bf16 matrix pipe (`f32_products` = 1 in a launch's arguments; engine dtype "f32x3") ----------------------
 // v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate (157 TFLOP/s).  With x = hi + lo + O(2^-17 |x|) (hi = bf16(x), lo = bf16(x - hi))
 // a . b ~ hi.hi + hi.lo + lo.hi: three v_mfma_f32_32x32x8_bf16 (32 cycles each) replace four f32 MFMAs (64 cycles each) per 8-deep
 // step on the SAME fragment layout (lane half hh holds k = 4 hh .. 4 hh + 3 in both), f32 accumulation as before.  Storage, statistics and
 // every elementwise step stay f32; only the products lose the operands' last 7 bits (relative 8e-6 per operand, random sign).
-extern int g_made_f32_products;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 struct SplitF32x4 { s16x4 hi, lo; };
 __device__ __forceinline__ SplitF32x4 made_split4(const f32x4 x) {

@@ -25,7 +25,7 @@ template <> struct TnCfg<bf16_t> { static constexpr int BM = 64, ROW = 128 * 2 +
 // f32: the two reduction rows a wave reads per MFMA must sit 32 banks apart
 template <> struct TnCfg<float>  { static constexpr int BM = 32, ROW = 128 * 4 + 128, CPR = 32; typedef f32x4 frag_t; };
 
-template <typename TC, bool X3 = false>        // X3 (f32 only): split-bf16 products (common.h, made_set_f32_products)
+template <typename TC, bool X3 = false>        // X3 (f32 only): split-bf16 products (common.h; the arguments' f32_products)
 __global__ __launch_bounds__(TNT) void gemm_tn_kernel(const MadeGemmTNArgs a) {
     typedef TnCfg<TC> Cfg;
     typedef typename Cfg::frag_t frag_t;
@@ -291,6 +291,7 @@ extern "C" int made_gemm_tn(const MadeGemmTNArgs* args, void* stream) {
     MADE_REQUIRE(a.M >= 0 && a.N > 0 && a.K > 0, "made_gemm_tn: bad dims");
     MADE_REQUIRE(a.ab_dtype == MADE_F32 || a.ab_dtype == MADE_BF16, "made_gemm_tn: bad operand dtype %d", a.ab_dtype);
     MADE_REQUIRE(a.c_dtype == MADE_F32 || a.c_dtype == a.ab_dtype, "made_gemm_tn: C must be f32 or the operand dtype");
+    MADE_REQUIRE(a.f32_products == 0 || a.f32_products == 1, "made_gemm_tn: f32_products %d not in {0, 1}", a.f32_products);
     if (a.batch1 <= 0) a.batch1 = 1;
     if (a.batch2 <= 0) a.batch2 = 1;
     if (a.split_m <= 0) a.split_m = 1;
@@ -325,7 +326,7 @@ extern "C" int made_gemm_tn(const MadeGemmTNArgs* args, void* stream) {
     }
     dim3 grid((unsigned)tiles, (unsigned)a.split_m, (unsigned)nz);
     if (a.ab_dtype == MADE_BF16) hipLaunchKernelGGL(gemm_tn_kernel<bf16_t>, grid, dim3(TNT), 0, st, a);
-    else if (g_made_f32_products) hipLaunchKernelGGL((gemm_tn_kernel<float, true>), grid, dim3(TNT), 0, st, a);
+    else if (a.f32_products) hipLaunchKernelGGL((gemm_tn_kernel<float, true>), grid, dim3(TNT), 0, st, a);
     else hipLaunchKernelGGL(gemm_tn_kernel<float>, grid, dim3(TNT), 0, st, a);
     return made_check_launch("made_gemm_tn");
 }

@@ -260,7 +260,7 @@ __device__ __forceinline__ void epilogue8(const MadeLinearArgs& a, int m, int n,
     }
 }
 
-template <typename TA, typename TC, bool X3 = false>      // X3 (f32 compute only): split-bf16 products (common.h, made_set_f32_products)
+template <typename TA, typename TC, bool X3 = false>      // X3 (f32 compute only): split-bf16 products (common.h; the arguments' f32_products)
 __global__ __launch_bounds__(NTHREADS, 2) void linear_kernel(const MadeLinearArgs a) {
     typedef typename Frag<TC>::type frag_t;
     constexpr int PER16 = elem_traits<TC>::per16;
@@ -1503,6 +1503,12 @@ static void launch_t16(const MadeLinearArgs& a, hipStream_t st) {
     else hipLaunchKernelGGL((linear_t16_kernel<TRAIN, 8>), g, block, 0, st, a);
 }
 
+template <int BMT, bool X3>                                // the f32 LDS-DMA kernel: X3 = the arguments' f32_products
+static void launch_glds_f32(const MadeLinearArgs& a, bool train, dim3 grid, hipStream_t st) {
+    if (train) hipLaunchKernelGGL((linear_glds_kernel<1, true, BMT, float, X3>), grid, dim3(NTHREADS), 0, st, a);
+    else hipLaunchKernelGGL((linear_glds_kernel<1, false, BMT, float, X3>), grid, dim3(NTHREADS), 0, st, a);
+}
+
 }  // namespace
 
 // tuning knob for the micro-benchmarks and tests: MADE_LINEAR_TILE=64|128 forces the single-stage direct-to-LDS kernels of round 1,
@@ -1627,6 +1633,7 @@ static int linear_validate(const MadeLinearArgs& a) {
     MADE_REQUIRE(a.nseg >= 1 && a.nseg <= 4, "made_linear: nseg=%d out of range", a.nseg);
     MADE_REQUIRE(a.batch >= 1 && a.batch <= 65535, "made_linear: batch=%lld out of range", (long long)a.batch);
     MADE_REQUIRE(a.w_dtype == MADE_F32 || a.w_dtype == MADE_BF16, "made_linear: bad w_dtype %d", a.w_dtype);
+    MADE_REQUIRE(a.f32_products == 0 || a.f32_products == 1, "made_linear: f32_products %d not in {0, 1}", a.f32_products);
     MADE_UNSUPPORTED(!(a.a_dtype == MADE_BF16 && a.w_dtype == MADE_F32),
                      "made_linear: bf16 activations with f32 weights are not supported");
     const int per16 = a.w_dtype == MADE_F32 ? 4 : 8;
@@ -1716,13 +1723,11 @@ extern "C" int made_linear(const MadeLinearArgs* args, void* stream) {
             break;
         case MADE_LINEAR_GLDS64_F32: {
             dim3 g((unsigned)(((a.M + 63) / 64) * ((a.N + BN - 1) / BN)), 1, (unsigned)a.batch);
-            if (train) { if (g_made_f32_products) hipLaunchKernelGGL((linear_glds_kernel<1, true, 64, float, true>), g, block, 0, st, a); else hipLaunchKernelGGL((linear_glds_kernel<1, true, 64, float>), g, block, 0, st, a); }
-            else { if (g_made_f32_products) hipLaunchKernelGGL((linear_glds_kernel<1, false, 64, float, true>), g, block, 0, st, a); else hipLaunchKernelGGL((linear_glds_kernel<1, false, 64, float>), g, block, 0, st, a); }
+            if (a.f32_products) launch_glds_f32<64, true>(a, train, g, st); else launch_glds_f32<64, false>(a, train, g, st);
             break;
         }
         case MADE_LINEAR_GLDS128_F32:
-            if (train) { if (g_made_f32_products) hipLaunchKernelGGL((linear_glds_kernel<1, true, 128, float, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((linear_glds_kernel<1, true, 128, float>), grid, block, 0, st, a); }
-            else { if (g_made_f32_products) hipLaunchKernelGGL((linear_glds_kernel<1, false, 128, float, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((linear_glds_kernel<1, false, 128, float>), grid, block, 0, st, a); }
+            if (a.f32_products) launch_glds_f32<128, true>(a, train, grid, st); else launch_glds_f32<128, false>(a, train, grid, st);
             break;
         case MADE_LINEAR_BIG256:
         case MADE_LINEAR_BIG128: {                         // persistent: one workgroup per CU (a multiple of 8: one eighth per XCD)
@@ -1762,7 +1767,7 @@ extern "C" int made_linear(const MadeLinearArgs* args, void* stream) {
         }
         case MADE_LINEAR_GENERAL_F32IN: hipLaunchKernelGGL((linear_kernel<float, bf16_t>), grid, block, 0, st, a); break;
         case MADE_LINEAR_GENERAL_BF16: hipLaunchKernelGGL((linear_kernel<bf16_t, bf16_t>), grid, block, 0, st, a); break;
-        default: if (g_made_f32_products) hipLaunchKernelGGL((linear_kernel<float, float, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((linear_kernel<float, float>), grid, block, 0, st, a); break;
+        default: if (a.f32_products) hipLaunchKernelGGL((linear_kernel<float, float, true>), grid, block, 0, st, a); else hipLaunchKernelGGL((linear_kernel<float, float>), grid, block, 0, st, a); break;
     }
     return made_check_launch("made_linear");
 }

@@ -18,6 +18,7 @@ Data layout in HBM (B = batch, L = T_v + T_a under concat fusion, D = dim_input)
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 from dataclasses import dataclass
@@ -71,8 +72,12 @@ class MadeEngine:
         self.tc = torch.bfloat16 if dtype == "bf16" else torch.float32
         self.dtype_name = dtype
         # "f32x3": f32 storage and elementwise arithmetic like "f32"; the matrix products run as three bf16 products on split operands
-        # (made_set_f32_products(1): include/made_hip.h) instead of the exact-f32 MFMA at 1/16 of the bf16 rate
-        self._f32_products = 1 if dtype == "f32x3" else 0
+        # (f32_products = 1 in each launch's arguments: include/made_hip.h) instead of the exact-f32 MFMA at 1/16 of the bf16 rate.
+        # Decided here, once: every matrix product of the engine is issued through these four names.
+        self._linear, self._linear_splitk, self._attention, self._attention_wide = ops.linear, ops.linear_splitk, ops.attention, ops.attention_wide
+        if dtype == "f32x3":
+            self._linear, self._linear_splitk = functools.partial(ops.linear, split=True), functools.partial(ops.linear_splitk, split=True)
+            self._attention, self._attention_wide = functools.partial(ops.attention, split=True), functools.partial(ops.attention_wide, split=True)
         self._check_supported()
         self._ws: Dict[tuple, Dict[str, Tensor]] = {}
         self._side: Optional[torch.cuda.Stream] = None       # the second stream, created on first use (_side_stream)
@@ -330,13 +335,13 @@ class MadeEngine:
         D = self.cfg.D
         qkv = ws["qkv"][:B * T]
         if pos is None:
-            ops.linear(x, w_in, b_in, out=qkv, rows=rows)
+            self._linear(x, w_in, b_in, out=qkv, rows=rows)
         else:                                       # q and k are projected from x + pos (given precomputed), v from x
-            ops.linear(x, w_in, b_in, A2=pos, a2_replace=True, rows=rows,
+            self._linear(x, w_in, b_in, A2=pos, a2_replace=True, rows=rows,
                        segs=[Seg(out=qkv, col_begin=0, use_a2=True), Seg(out=qkv[:, 2 * D:], col_begin=2 * D, ldo=qkv.stride(0))])
         q3 = qkv.view(B, T, 3 * D)
         att = ws["att"][:B * T]
-        ops.attention(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], att.view(B, T, D), H, key_mask=key_mask,
+        self._attention(q3[:, :, :D], q3[:, :, D:2 * D], q3[:, :, 2 * D:], att.view(B, T, D), H, key_mask=key_mask,
                       q_skip_mask=key_mask if skip is not None else None, order=order)
         return att
 
@@ -373,12 +378,12 @@ class MadeEngine:
         # and the attention skip them; valid rows are bit-identical to the dense computation
         if self.tc == torch.bfloat16:       # mask + f32->bf16 once, then the direct-to-LDS GEMM
             xin = ops.cast_mask_rows(feats.view(nrow, Kin), mflat, ws["xin"][:nrow * Kin].view(nrow, Kin))
-            x = ops.linear(xin, P[proj + ".w"], P[proj + ".b"], act=act, R=P[pe][:T], r_row_mod=T, out=ws["x0"][:nrow], rows=rows)
+            x = self._linear(xin, P[proj + ".w"], P[proj + ".b"], act=act, R=P[pe][:T], r_row_mod=T, out=ws["x0"][:nrow], rows=rows)
         else:
-            x = ops.linear(feats.view(nrow, Kin), P[proj + ".w"], P[proj + ".b"], a_row_mask=mflat, act=act,
+            x = self._linear(feats.view(nrow, Kin), P[proj + ".w"], P[proj + ".b"], a_row_mask=mflat, act=act,
                            R=P[pe][:T], r_row_mod=T, out=ws["x0"][:nrow], rows=rows)
         x = self._temporal_layers(x, B, T, mask, mod, depth, ws, rows, order)
-        ops.linear(x, P[mod + ".final.w"], P[mod + ".final.b"], out_row_mask=mflat, tile_skip_mask=mflat,
+        self._linear(x, P[mod + ".final.w"], P[mod + ".final.b"], out_row_mask=mflat, tile_skip_mask=mflat,
                    segs=[Seg(out=local, ldo=local.stride(1), rows_per_batch=T, out_batch_stride=local.stride(0))])
         ops.masked_mean(local, mask, out=mean)
         ops.l2norm_rows(mean, out_f32=vec)
@@ -392,10 +397,10 @@ class MadeEngine:
             p = f"{mod}.layers.{l}"
             x1 = ops.layernorm(x, P[p + ".ln1.g"], P[p + ".ln1.b"], out=ws["x1"][:nrow], row_skip=mflat)
             att = self._mha_block(x1, B, T, P[p + ".in.w"], P[p + ".in.b"], mask, ws, c.SA_temporal_heads, skip=mflat, rows=rows, order=order)
-            x2 = ops.linear(att, P[p + ".out.w"], P[p + ".out.b"], R=x1, out=ws["x2"][:nrow], rows=rows)
+            x2 = self._linear(att, P[p + ".out.w"], P[p + ".out.b"], R=x1, out=ws["x2"][:nrow], rows=rows)
             x3 = ops.layernorm(x2, P[p + ".ln2.g"], P[p + ".ln2.b"], out=ws["x3"][:nrow], row_skip=mflat)
-            h = ops.linear(x3, P[p + ".ff1.w"], P[p + ".ff1.b"], act=ops.ACT_GELU, out=ws["ffn"][:nrow, :c.temporal_ffn_dim], rows=rows)
-            x = ops.linear(h, P[p + ".ff2.w"], P[p + ".ff2.b"], R=x3, out=ws["x0"][:nrow], rows=rows)
+            h = self._linear(x3, P[p + ".ff1.w"], P[p + ".ff1.b"], act=ops.ACT_GELU, out=ws["ffn"][:nrow, :c.temporal_ffn_dim], rows=rows)
+            x = self._linear(h, P[p + ".ff2.w"], P[p + ".ff2.b"], R=x3, out=ws["x0"][:nrow], rows=rows)
         return x
 
     def _encode_mlp(self, feats: Tensor, mask: Tensor, which: str, ws, local: Tensor, mean: Tensor, vec: Tensor) -> None:
@@ -412,14 +417,14 @@ class MadeEngine:
         act = ops.ACT_QUICKGELU if c.with_act_after_proj else ops.ACT_NONE
         if self.tc == torch.bfloat16:
             xin = ops.cast_mask_rows(feats.view(nrow, Kin), mflat, ws["xin"][:nrow * Kin].view(nrow, Kin))
-            x = ops.linear(xin, P[proj + ".w"], P[proj + ".b"], act=act, out=ws["x0"][:nrow])
+            x = self._linear(xin, P[proj + ".w"], P[proj + ".b"], act=act, out=ws["x0"][:nrow])
         else:
-            x = ops.linear(feats.view(nrow, Kin), P[proj + ".w"], P[proj + ".b"], a_row_mask=mflat, act=act, out=ws["x0"][:nrow])
-        h = ops.linear(x, P[key + ".0.w"], P[key + ".0.b"], out=ws["ffn"][:nrow, :1024])
+            x = self._linear(feats.view(nrow, Kin), P[proj + ".w"], P[proj + ".b"], a_row_mask=mflat, act=act, out=ws["x0"][:nrow])
+        h = self._linear(x, P[key + ".0.w"], P[key + ".0.b"], out=ws["ffn"][:nrow, :1024])
         ops.row_affine(h, P[key + ".1.scale"], P[key + ".1.shift"], act=ops.ACT_RELU)
-        y = ops.linear(h, P[key + ".3.w"], P[key + ".3.b"], out=ws["x1"][:nrow])
+        y = self._linear(h, P[key + ".3.w"], P[key + ".3.b"], out=ws["x1"][:nrow])
         ops.row_affine(y, P[key + ".4.scale"], P[key + ".4.shift"], act=ops.ACT_RELU)
-        ops.linear(y, P[key + ".6.w"], P[key + ".6.b"], out_row_mask=mflat,
+        self._linear(y, P[key + ".6.w"], P[key + ".6.b"], out_row_mask=mflat,
                    segs=[Seg(out=local, ldo=local.stride(1), rows_per_batch=T, out_batch_stride=local.stride(0))])
         ops.masked_mean(local, mask, out=mean)
         ops.l2norm_rows(mean, out_f32=vec)
@@ -444,12 +449,12 @@ class MadeEngine:
         seg = Seg(out=x3d[:, 1:], ldo=D, rows_per_batch=T, out_batch_stride=T1 * D)
         if self.tc == torch.bfloat16:
             xin = ops.cast_mask_rows(feats.view(B * T, Kin), mask.reshape(-1), ws["xin"][:B * T * Kin].view(B * T, Kin))
-            ops.linear(xin, P[proj + ".w"], P[proj + ".b"], act=act, R=P[pe][1:T1], r_row_mod=T, segs=[seg])
+            self._linear(xin, P[proj + ".w"], P[proj + ".b"], act=act, R=P[pe][1:T1], r_row_mod=T, segs=[seg])
         else:
-            ops.linear(feats.view(B * T, Kin), P[proj + ".w"], P[proj + ".b"], a_row_mask=mask.reshape(-1), act=act,
+            self._linear(feats.view(B * T, Kin), P[proj + ".w"], P[proj + ".b"], a_row_mask=mask.reshape(-1), act=act,
                        R=P[pe][1:T1], r_row_mod=T, segs=[seg])
         x = self._temporal_layers(x, B, T1, mask1, mod, depth, ws, rows1, order1)
-        y = ops.linear(x, P[mod + ".final.w"], P[mod + ".final.b"], out_row_mask=mask1.reshape(-1), out=ws["x1"][:B * T1])
+        y = self._linear(x, P[mod + ".final.w"], P[mod + ".final.b"], out_row_mask=mask1.reshape(-1), out=ws["x1"][:B * T1])
         y3 = y.view(B, T1, D)
         ops.l2norm_rows(y3[:, 0], out_f32=vec)
         local.copy_(y3[:, 1:])
@@ -482,13 +487,13 @@ class MadeEngine:
         rows = n * S
         skip = mask.reshape(-1) if mask is not None else None           # masked segments are never attended to
         ops.layernorm(seg, P[tower + ".ln1.g"], P[tower + ".ln1.b"], out=s1[:rows], row_skip=skip)   # [n,S,D] view -> compact rows
-        ops.linear(s1[:rows], P[tower + ".kv.w"], P[tower + ".kv.b"], tile_skip_mask=skip,
+        self._linear(s1[:rows], P[tower + ".kv.w"], P[tower + ".kv.b"], tile_skip_mask=skip,
                    segs=[Seg(out=kbuf, col_begin=0), Seg(out=ubuf, col_begin=D)])
         if not hoist:
             return kbuf[:rows].view(n, S, D), ubuf[:rows].view(n, S, D)
-        ops.linear(ubuf[:rows], P[tower + ".out.w"], P[tower + ".out.b"], out=u2[:rows, :D], tile_skip_mask=skip)
+        self._linear(ubuf[:rows], P[tower + ".out.w"], P[tower + ".out.b"], out=u2[:rows, :D], tile_skip_mask=skip)
         if fold:
-            ops.linear(u2[:rows, :D], P[tower + ".linf.w"], None, out=u2[:rows, D:], tile_skip_mask=skip)
+            self._linear(u2[:rows, :D], P[tower + ".linf.w"], None, out=u2[:rows, D:], tile_skip_mask=skip)
         return kbuf[:rows].view(n, S, D), u2[:rows].view(n, S, -1)
 
     def _xpool_chunks(self, tower: str, seg: Tensor, seg_mask: Optional[Tensor], bufs: tuple, pairs) -> None:
@@ -514,7 +519,7 @@ class MadeEngine:
             sims_out = torch.empty(Nv, Nm, device=dev, dtype=torch.float32)
         path = self._xpool_path(Nv, S, D, pooled_out)
         v1 = ops.layernorm(video, P[tower + ".ln1.g"], P[tower + ".ln1.b"], out_dtype=tc)
-        q = ops.linear(v1, P[tower + ".q.w"], P[tower + ".q.b"])
+        q = self._linear(v1, P[tower + ".q.w"], P[tower + ".q.b"])
         scale = 1.0 / math.sqrt(D)
         ln2, ln3 = [(P[tower + f".ln{i}.g"], P[tower + f".ln{i}.b"]) for i in (2, 3)]
         E = lambda *shape, dtype=tc: torch.empty(shape, device=dev, dtype=dtype)
@@ -553,7 +558,7 @@ class MadeEngine:
 
             def pairs(m0, n, K, U, mask):
                 ops.xpool_attention(q, K, U, mask, xh[:n * Nv].view(n, Nv, D), scale=scale, ws=iws)
-                ops.linear(xh[:n * Nv], P[tower + ".linf.w"], P[tower + ".linf.b"], out=y[:n * Nv])
+                self._linear(xh[:n * Nv], P[tower + ".linf.w"], P[tower + ".linf.b"], out=y[:n * Nv])
                 ops.xpool_tail(y[:n * Nv], ln3[0], ln3[1], video, sims_out[:, m0:m0 + n], n, Nv)
         else:
             if chunk_m is None:
@@ -576,10 +581,10 @@ class MadeEngine:
                 else:
                     # n_split=1: splitting the keys over workgroups + a merge launch is no faster here and costs the other stream CUs
                     # (1.2 % of the eval throughput with two batches in flight)
-                    ops.attention_wide(q.view(1, Nv, 1, D), K, U, o[:rows].view(n, Nv, 1, D), scale=scale, key_mask=mask, shared_q=True, n_split=1)
-                a2 = o[:rows] if hoist else ops.linear(o[:rows], P[tower + ".out.w"], P[tower + ".out.b"], out=o2[:rows])
+                    self._attention_wide(q.view(1, Nv, 1, D), K, U, o[:rows].view(n, Nv, 1, D), scale=scale, key_mask=mask, shared_q=True, n_split=1)
+                a2 = o[:rows] if hoist else self._linear(o[:rows], P[tower + ".out.w"], P[tower + ".out.b"], out=o2[:rows])
                 a3 = ops.layernorm(a2, ln2[0], ln2[1], out=o3[:rows])
-                y = ops.linear(a3, P[tower + ".lin.w"], P[tower + ".lin.b"], R=a3, out=o2[:rows] if hoist else o[:rows])
+                y = self._linear(a3, P[tower + ".lin.w"], P[tower + ".lin.b"], R=a3, out=o2[:rows] if hoist else o[:rows])
                 ops.xpool_tail(y, ln3[0], ln3[1], video, sims_out[:, m0:m0 + n], n, Nv,
                                pooled_out=pooled_out[m0 * Nv:(m0 + n) * Nv] if pooled_out is not None else None)
         self._xpool_chunks(tower, seg, seg_mask, bufs, pairs)
@@ -603,7 +608,7 @@ class MadeEngine:
         cache = {} if cache is None else cache
         if "q" not in cache:
             v1 = ops.layernorm(video, P[tower + ".ln1.g"], P[tower + ".ln1.b"], out_dtype=tc)
-            cache["q"] = ops.linear(v1, P[tower + ".q.w"], P[tower + ".q.b"])
+            cache["q"] = self._linear(v1, P[tower + ".q.w"], P[tower + ".q.b"])
             cache["vn"] = ops.l2norm_rows(video)
         K, UU = self._xpool_tracks(tower, seg, seg_mask, self._xpool_track_bufs(U, S, D, hoist=True, fold=True))
         return ops.xpool_sims_pairs(cache["q"], K, UU, seg_mask, P[tower + ".linf.b"], P[tower + ".linf.rs"],
@@ -611,7 +616,7 @@ class MadeEngine:
                                     max_count=max_count)
 
     def dual_sims(self, video: Tensor, music: Tensor, out: Optional[Tensor] = None, add: Optional[Tensor] = None, splitk: bool = True) -> Tensor:
-        """cos(v, m) (reference modules/loss.py:52-56), always with the exact-f32 MFMA; `add` is summed in.  splitk False: never the
+        """cos(v, m) (reference modules/loss.py:52-56), always on f32 operands, a bf16 engine's too (exact-f32 MFMA; split products in an "f32x3" engine); `add` is summed in.  splitk False: never the
         in-batch split-K form, whose sums are ordered differently (the shortlist's cosines, which must not depend on the chunking)."""
         vn = ops.l2norm_rows(video)
         mn = ops.l2norm_rows(music)
@@ -621,37 +626,27 @@ class MadeEngine:
                 out = torch.empty(Nv, Nm, device=vn.device, dtype=torch.float32)
             split = max(2, min(16, D // 32))
             wsp = torch.empty(split * Nv * Nm, device=vn.device, dtype=torch.float32)
-            ops.linear_splitk(vn, mn, None, wsp, split, R=add, out=out)
+            self._linear_splitk(vn, mn, None, wsp, split, R=add, out=out)
             return out
-        return ops.linear(vn, mn, None, R=add, out=out, out_dtype=torch.float32)
+        return self._linear(vn, mn, None, R=add, out=out, out_dtype=torch.float32)
 
-    def _set_products(self) -> None:
-        """the library's process-wide f32 product mode <- this engine's (read by the f32 kernels' launchers; a bf16 engine issues f32
-        launches too and sets the exact mode).  The entry points are scoped (_lib.scoped_f32_products): the mode they leave behind is the one
-        they found."""
-        _lib.check(_lib.lib().made_set_f32_products(self._f32_products), "made_set_f32_products")
-
-    @_lib.scoped_f32_products
     def retrieval_sim_matrix(self, video_embeds: Tensor, segment_embeds: Tensor, segment_masks: Tensor,
                              music_embeds: Tensor, chunk_m: Optional[int] = None, out: Optional[Tensor] = None,
                              single_out: Optional[Tensor] = None) -> Tensor:
         """reference test-MaDe.py:386-403: sim[Nv, Nm] = single (X-Pool) + dual (cosine).  out / single_out: [Nv, Nm] f32 views
         (two different buffers) that receive the sum / the X-Pool term instead of new tensors."""
-        self._set_products()
         seg = segment_embeds.to(self.tc) if segment_embeds.dtype != self.tc else segment_embeds
         single = self.xpool_sims(video_embeds, seg, segment_masks if self.cfg.fusion_mask == 1 else None, sims_out=single_out, chunk_m=chunk_m)
         return self.dual_sims(video_embeds, music_embeds, out=out, add=single)
 
     # ------------------------------------------------------------------ full forward
     @torch.no_grad()
-    @_lib.scoped_f32_products
     def forward(self, frame_feats: Tensor, segment_feats: Tensor, frame_masks: Tensor, segment_masks: Tensor,
                 spans_target: Tensor, with_losses: bool = True, want_pooled: bool = False,
                 v_duration: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """reference model/model_Uni.py:177-322 in eval mode.  This function is the schedule only -- which stage runs on which stream and
         who waits for whom (its tail, shared with `localize_pairs`, is `_after_fusion`); the launches are the stages'."""
         c = self.cfg
-        self._set_products()
         if c.predict_center == 1 and v_duration is None:
             raise ValueError("predict_center=1 needs v_duration (reference model/model_Uni.py:280-282)")
         B, Tv, _ = frame_feats.shape
@@ -783,10 +778,10 @@ class MadeEngine:
         p = f"detr_transformer.encoder.layers.{l}"
         att = self._mha_block(src, B, L, P[p + ".in.w"], P[p + ".in.b"], ws["fus_mask"], ws, c.detr_nheads, pos=ws["srcpos"], skip=fskip,
                               rows=enc_rows, order=k.order_f)
-        x = ops.linear(att, P[p + ".out.w"], P[p + ".out.b"], R=src, out=ws["x1"][:rows], rows=enc_rows)
+        x = self._linear(att, P[p + ".out.w"], P[p + ".out.b"], R=src, out=ws["x1"][:rows], rows=enc_rows)
         s1 = ops.layernorm(x, P[p + ".ln1.g"], P[p + ".ln1.b"], out=ws["x2"][:rows], row_skip=fskip)
-        h = ops.linear(s1, P[p + ".ff1.w"], P[p + ".ff1.b"], act=ops.ACT_RELU, out=ws["ffn"][:rows, :c.detr_dim_feedforward], rows=enc_rows)
-        x = ops.linear(h, P[p + ".ff2.w"], P[p + ".ff2.b"], R=s1, out=ws["x1"][:rows], rows=enc_rows)
+        h = self._linear(s1, P[p + ".ff1.w"], P[p + ".ff1.b"], act=ops.ACT_RELU, out=ws["ffn"][:rows, :c.detr_dim_feedforward], rows=enc_rows)
+        x = self._linear(h, P[p + ".ff2.w"], P[p + ".ff2.b"], R=s1, out=ws["x1"][:rows], rows=enc_rows)
         # the norm that produces the next src also emits src + pos (next layer's q/k input, decoder's keys)
         src = ws["x3" if l % 2 == 0 else "x0"][:rows]
         ops.layernorm_add(x, P[p + ".ln2.g"], P[p + ".ln2.b"], k.pos.view(rows, D), src, ws["srcpos"], row_skip=fskip)
@@ -803,10 +798,10 @@ class MadeEngine:
         ops.layernorm_add(x, P[p + ".ln1.g"], P[p + ".ln1.b"], k.pos.view(rows, D), n1, srcpos, row_skip=fskip)
         att = self._mha_block(n1, B, L, P[p + ".in.w"], P[p + ".in.b"], ws["fus_mask"], ws, c.detr_nheads, pos=srcpos, skip=fskip,
                               rows=enc_rows, order=k.order_f)
-        xa = ops.linear(att, P[p + ".out.w"], P[p + ".out.b"], R=x, out=ws["x1"][:rows], rows=enc_rows)
+        xa = self._linear(att, P[p + ".out.w"], P[p + ".out.b"], R=x, out=ws["x1"][:rows], rows=enc_rows)
         n2 = ops.layernorm(xa, P[p + ".ln2.g"], P[p + ".ln2.b"], out=ws["x2"][:rows], row_skip=fskip)
-        h = ops.linear(n2, P[p + ".ff1.w"], P[p + ".ff1.b"], act=ops.ACT_RELU, out=ws["ffn"][:rows, :c.detr_dim_feedforward], rows=enc_rows)
-        return ops.linear(h, P[p + ".ff2.w"], P[p + ".ff2.b"], R=xa, out=ws["x0"][:rows], rows=enc_rows)
+        h = self._linear(n2, P[p + ".ff1.w"], P[p + ".ff1.b"], act=ops.ACT_RELU, out=ws["ffn"][:rows, :c.detr_dim_feedforward], rows=enc_rows)
+        return self._linear(h, P[p + ".ff2.w"], P[p + ".ff2.b"], R=xa, out=ws["x0"][:rows], rows=enc_rows)
 
     def _dec_open(self, k: "_Call", pooled: Optional[Tensor]) -> None:
         """The initial decoder queries and layer 0 up to its cross-attention: what the decoder reads of the towers only.  (The pre-norm
@@ -837,10 +832,10 @@ class MadeEngine:
         if Q == 1:
             return self._skinny(ws, x, p + ".sa.fold", **to)
         dqkv = ws["dqkv"]
-        ops.linear(x, P[p + ".sa.in.w"], P[p + ".sa.in.b"], A2=P["query_embed"], a2_row_mod=Q,
+        self._linear(x, P[p + ".sa.in.w"], P[p + ".sa.in.b"], A2=P["query_embed"], a2_row_mod=Q,
                    segs=[Seg(out=dqkv, col_begin=0, use_a2=True), Seg(out=dqkv[:, 2 * D:], col_begin=2 * D, ldo=dqkv.stride(0))])
         d3 = dqkv.view(B, Q, 3 * D)
-        ops.attention(d3[:, :, :D], d3[:, :, D:2 * D], d3[:, :, 2 * D:], ws["datt"].view(B, Q, D), c.detr_nheads)
+        self._attention(d3[:, :, :D], d3[:, :, D:2 * D], d3[:, :, 2 * D:], ws["datt"].view(B, Q, D), c.detr_nheads)
         self._skinny(ws, ws["datt"], p + ".sa.out", **to)
 
     def _dec_cross_attn(self, k: "_Call", memory: Tensor) -> None:
@@ -848,7 +843,7 @@ class MadeEngine:
         c, ws = self.cfg, k.ws
         B, Q, H, D = k.B, c.num_moment_queries, c.detr_nheads, c.D
         heads = lambda t: t.view(B, Q, H, D).permute(0, 2, 1, 3)         # [B, H, Q, D] view: row (b,q), head-major columns
-        ops.attention_wide(heads(ws["dq_all"]), ws["srcpos"].view(memory.shape), memory, heads(ws["dpool"]), scale=1.0 / math.sqrt(D // H),
+        self._attention_wide(heads(ws["dq_all"]), ws["srcpos"].view(memory.shape), memory, heads(ws["dpool"]), scale=1.0 / math.sqrt(D // H),
                            key_mask=ws["fus_mask"], n_split=max(1, min(8, 256 // max(B, 1))), part_o=ws["part_o"], part_ml=ws["part_ml"])
 
     def _dec_layer_pre_norm(self, k: "_Call", l: int, memory: Tensor) -> None:
@@ -880,11 +875,11 @@ class MadeEngine:
         if l > 0:
             self._dec_fused_query_side(ws, l, None)
         self._dec_cross_attn(k, memory)
-        ops.linear(dpool[:, :D], P[p + ".ca.v.w"][:hd], None, M=rows, N=hd, K=D, batch=H, a_z_stride=D, w_z_stride=hd * D,
+        self._linear(dpool[:, :D], P[p + ".ca.v.w"][:hd], None, M=rows, N=hd, K=D, batch=H, a_z_stride=D, w_z_stride=hd * D,
                    segs=[Seg(out=dv, ldo=D, out_z_stride=hd)])                       # v_h = W_v,h pooled_h (b_v rides in ca.vo.b)
-        ops.linear(dv, P[p + ".ca.o.w"], P[p + ".ca.vo.b"], R=ws["t1"], out=z[1])
+        self._linear(dv, P[p + ".ca.o.w"], P[p + ".ca.vo.b"], R=ws["t1"], out=z[1])
         ops.dec_stage(z[1], P[p + ".ff1.w"], P[p + ".ff1.b"], ws["dffn"], ln=(P[p + ".ln2.g"], P[p + ".ln2.b"]), x_out=t2, act=ops.ACT_RELU)
-        ops.linear(ws["dffn"], P[p + ".ff2.w"], P[p + ".ff2.b"], R=t2, out=z[2])
+        self._linear(ws["dffn"], P[p + ".ff2.w"], P[p + ".ff2.b"], R=t2, out=z[2])
         if l == nd - 1:                                      # the last layer's norms have no consumer stage: one row kernel
             ops.splitk_finish(z[2].view(-1), 1, rows, D, None, ln1=(P[p + ".ln3.g"], P[p + ".ln3.b"]), ln1_out=ws["tgt"],
                               ln2=(P["dec.norm.g"], P["dec.norm.b"]), ln2_out=ws["hs"][l])
@@ -920,10 +915,10 @@ class MadeEngine:
         hs = ws["hs"]
         hs2 = hs.view(-1, c.D)                                           # [nd * B * Q, D]
         logits, spans = ws["logits"], ws["spans"]
-        ops.linear(hs2, P["class_embed.w"], P["class_embed.b"], out=logits.view(-1, 2))
+        self._linear(hs2, P["class_embed.w"], P["class_embed.b"], out=logits.view(-1, 2))
         if c.contrastive_align_loss:
             pq_raw, pq2 = ws["pq_raw"], ws["pq"].view(hs2.shape[0], -1)
-            ops.linear(hs2, P["proj_q.w"], P["proj_q.b"], out=pq_raw)
+            self._linear(hs2, P["proj_q.w"], P["proj_q.b"], out=pq_raw)
             ops.l2norm_rows(pq_raw, out_f32=pq2)
             if c.audio_short_cut:
                 mq = self._music_per_query(k)
@@ -938,15 +933,15 @@ class MadeEngine:
             self._skinny(ws, ws["h1"], "span_embed.1", act=ops.ACT_RELU, out=ws["h2"])
             h2 = ws["h2"]
         else:
-            h1 = ops.linear(hs2, P["span_embed.0.w"], P["span_embed.0.b"], act=ops.ACT_RELU, out=ws["h1"])
-            h2 = ops.linear(h1, P["span_embed.1.w"], P["span_embed.1.b"], act=ops.ACT_RELU, out=ws["h2"])
+            h1 = self._linear(hs2, P["span_embed.0.w"], P["span_embed.0.b"], act=ops.ACT_RELU, out=ws["h1"])
+            h2 = self._linear(h1, P["span_embed.1.w"], P["span_embed.1.b"], act=ops.ACT_RELU, out=ws["h2"])
         if c.predict_center == 1:
             # the head predicts the centre only; the width is the video's share of the longest track (reference
             # model/model_Uni.py:135-136,280-282)
-            ops.linear(h2, P["span_embed.2.w"], P["span_embed.2.b"], act=ops.ACT_SIGMOID, segs=[Seg(out=spans.view(-1, 2), ldo=2)])
+            self._linear(h2, P["span_embed.2.w"], P["span_embed.2.b"], act=ops.ACT_SIGMOID, segs=[Seg(out=spans.view(-1, 2), ldo=2)])
             spans[..., 1] = (k.v_duration.to(self.device, torch.float32) / c.max_m_duration).view(1, B, 1)
         else:
-            ops.linear(h2, P["span_embed.2.w"], P["span_embed.2.b"], act=ops.ACT_SIGMOID, out=spans.view(-1, 2))
+            self._linear(h2, P["span_embed.2.w"], P["span_embed.2.b"], act=ops.ACT_SIGMOID, out=spans.view(-1, 2))
         out = dict(pred_logits=logits[-1], pred_spans=spans[-1], logits_all=logits, spans_all=spans)
         if c.contrastive_align_loss:
             self._frame_rows_linear(k.frame, P["proj_v.w"], P["proj_v.b"], ws["pv_raw"], B, Tv)
@@ -955,9 +950,9 @@ class MadeEngine:
             ops.masked_mean(pv, None, out=ws["vid_sum"])
             out.update(proj_queries=ws["pq"][-1], proj_vid_mem=pv, proj_queries_all=ws["pq"])
         if c.moment_loss:                                                # reference model_Uni.py:152-159 (outputs only: no loss reads them)
-            m1 = ops.linear(hs[nd - 1], P["moment_embed.0.w"], P["moment_embed.0.b"], act=ops.ACT_RELU)
-            m2 = ops.linear(m1, P["moment_embed.1.w"], P["moment_embed.1.b"], act=ops.ACT_RELU)
-            m3 = ops.linear(m2, P["moment_embed.2.w"], P["moment_embed.2.b"], out_dtype=torch.float32)
+            m1 = self._linear(hs[nd - 1], P["moment_embed.0.w"], P["moment_embed.0.b"], act=ops.ACT_RELU)
+            m2 = self._linear(m1, P["moment_embed.1.w"], P["moment_embed.1.b"], act=ops.ACT_RELU)
+            m3 = self._linear(m2, P["moment_embed.2.w"], P["moment_embed.2.b"], out_dtype=torch.float32)
             mf = ops.l2norm_rows(m3)
             if c.audio_short_cut:
                 mf = self._short_cut(m3, mf, self._music_per_query(k))
@@ -988,9 +983,7 @@ class MadeEngine:
         """The music temporal tower only over [N, T_a, ast_dim] features."""
         return self._encode_items(segment_feats, segment_masks, m_duration, "audio", batch)
 
-    @_lib.scoped_f32_products
     def _encode_items(self, feats: Tensor, masks: Tensor, duration: Optional[Tensor], which: str, batch: int) -> "Encoded":
-        self._set_products()
         dev, D = self.device, self.cfg.D
         N, T, _ = feats.shape
         feats = feats.to(dev, torch.float32).contiguous()
@@ -1016,7 +1009,6 @@ class MadeEngine:
                                       "the batch (reference model/model_Uni.py:222-223), a property of the batch with no per-pair meaning")
         if c.predict_center == 1 and videos.duration is None:
             raise ValueError("predict_center=1 needs the videos' durations (encode_videos(..., v_duration=...))")
-        self._set_products()
         dev = self.device
         vi = torch.as_tensor(vi).to(dev, torch.int32).reshape(-1).contiguous()
         mi = torch.as_tensor(mi).to(dev, torch.int32).reshape(-1).contiguous()
@@ -1051,7 +1043,6 @@ class MadeEngine:
             yield p0, min(B, P - p0), self._after_fusion(k, out, cur, cur)
 
     @torch.no_grad()
-    @_lib.scoped_f32_products
     def localize_pairs(self, videos: "Encoded", music: "Encoded", vi, mi, pair_batch: int = 64) -> Dict[str, Optional[Tensor]]:
         """Moment localization of arbitrary (video vi[p], track mi[p]) pairs from per-item tower outputs (encode_videos /
         encode_music): per batch of pairs one made_gather_pairs, then the eval path after the towers (fusion, DETR, heads) -- no
@@ -1075,7 +1066,7 @@ class MadeEngine:
         slab = 64 if self.tc == torch.bfloat16 else 32
         tiles = ((A.shape[0] + 127) // 128) * ((N + 127) // 128)
         split = max(2, min(192 // max(tiles, 1), (K + slab - 1) // slab, 32, dws.numel() // (A.shape[0] * N)))
-        ops.linear_splitk(A, W, P[wkey + ".b"], dws, split, **kw)
+        self._linear_splitk(A, W, P[wkey + ".b"], dws, split, **kw)
 
     def _fused_decoder(self) -> bool:
         """The fused decoder chain (made_dec_stage) covers the scripts' configuration: bf16, one moment query, queries from the clip
@@ -1135,14 +1126,14 @@ class MadeEngine:
         c, P = self.cfg, self.P
         B, v_duration, out = k.B, k.v_duration, {}
         fusion = ops.masked_mean(mem3, None) / k.ws["fus_mask"].sum(dim=1, keepdim=True)   # [B, D] f32
-        h1 = ops.linear(fusion, P["reg_mlp.0.w"], P["reg_mlp.0.b"], act=ops.ACT_RELU)
-        h2 = ops.linear(h1, P["reg_mlp.1.w"], P["reg_mlp.1.b"], act=ops.ACT_RELU)
+        h1 = self._linear(fusion, P["reg_mlp.0.w"], P["reg_mlp.0.b"], act=ops.ACT_RELU)
+        h2 = self._linear(h1, P["reg_mlp.1.w"], P["reg_mlp.1.b"], act=ops.ACT_RELU)
         if c.predict_center == 1:
             spans = torch.empty(B, 2, device=self.device, dtype=torch.float32)
-            ops.linear(h2, P["reg_mlp.2.w"], P["reg_mlp.2.b"], act=ops.ACT_SIGMOID, segs=[Seg(out=spans, ldo=2)])
+            self._linear(h2, P["reg_mlp.2.w"], P["reg_mlp.2.b"], act=ops.ACT_SIGMOID, segs=[Seg(out=spans, ldo=2)])
             spans[:, 1] = v_duration.to(self.device, torch.float32) / c.max_m_duration
         else:
-            spans = ops.linear(h2, P["reg_mlp.2.w"], P["reg_mlp.2.b"], act=ops.ACT_SIGMOID, out_dtype=torch.float32)
+            spans = self._linear(h2, P["reg_mlp.2.w"], P["reg_mlp.2.b"], act=ops.ACT_SIGMOID, out_dtype=torch.float32)
         out["pred_spans"] = spans.view(B, 1, 2)
         if with_losses:
             tg = spans_target.to(torch.float32)
@@ -1162,16 +1153,16 @@ class MadeEngine:
         x = seg.reshape(B * Ta, D)
         nx = ops.layernorm(x, P["ca.lnq.g"], P["ca.lnq.b"], out=ws["ca_nx"])
         nc = ops.layernorm(frame.reshape(B * Tv, D), P["ca.lnc.g"], P["ca.lnc.b"], out=ws["ca_nc"])
-        q = ops.linear(nx, P["ca.q.w"], None, out=ws["ca_q"])
-        kv = ops.linear(nc, P["ca.kv.w"], None, out=ws["ca_kv"])
+        q = self._linear(nx, P["ca.q.w"], None, out=ws["ca_q"])
+        kv = self._linear(nc, P["ca.kv.w"], None, out=ws["ca_kv"])
         kv3 = kv.view(B, Tv, 2 * inner)
-        ops.attention(q.view(B, Ta, inner), kv3[:, :, :inner], kv3[:, :, inner:], ws["ca_att"].view(B, Ta, inner), Hc,
+        self._attention(q.view(B, Ta, inner), kv3[:, :, :inner], kv3[:, :, inner:], ws["ca_att"].view(B, Ta, inner), Hc,
                       key_mask=fm, q_mask=sm, scale=c.ca_dim_head ** -0.5)
-        ax = ops.linear(ws["ca_att"], P["ca.out.w"], P["ca.out.b"], R=x, out=ws["ca_x"])
+        ax = self._linear(ws["ca_att"], P["ca.out.w"], P["ca.out.b"], R=x, out=ws["ca_x"])
         nf = ops.layernorm(ax, P["ca.lnf.g"], P["ca.lnf.b"], out=ws["ca_nx"])
-        h = ops.linear(nf, P["ca.ff1.w"], P["ca.ff1.b"], act=ops.ACT_GELU, out=ws["ca_h"])
-        y = ops.linear(h, P["ca.ff2.w"], P["ca.ff2.b"], R=ax, out=ws["ca_y"])
-        ops.linear(y, P["ca.final.w"], P["ca.final.b"], out_row_mask=sm.reshape(-1), out=ws["fus"].view(B * Ta, D))
+        h = self._linear(nf, P["ca.ff1.w"], P["ca.ff1.b"], act=ops.ACT_GELU, out=ws["ca_h"])
+        y = self._linear(h, P["ca.ff2.w"], P["ca.ff2.b"], R=ax, out=ws["ca_y"])
+        self._linear(y, P["ca.final.w"], P["ca.final.b"], out_row_mask=sm.reshape(-1), out=ws["fus"].view(B * Ta, D))
 
     def _retrieval_loss(self, ws: Dict[str, Tensor], video: Tensor, music: Tensor, row_exclude: Optional[Tensor] = None,
                         pooled: Optional[Tensor] = None) -> None:
@@ -1199,7 +1190,7 @@ class MadeEngine:
             vn = ops.l2norm_rows(video)
             sims = torch.empty(B, B, device=self.device, dtype=torch.float32)
             # sims[n, m] = <fn[m, n, :], vn[n, :]>: one row-vector product per video, batched over the videos
-            ops.linear(fn.view(B, B * D)[:, :D], vn, None, M=B, N=1, K=D, batch=B, a_z_stride=D, w_z_stride=D,     # rows m of video 0, stride B*D
+            self._linear(fn.view(B, B * D)[:, :D], vn, None, M=B, N=1, K=D, batch=B, a_z_stride=D, w_z_stride=D,     # rows m of video 0, stride B*D
                        segs=[Seg(out=sims, ldo=1, out_z_stride=B)])
             ws["sims_fused"], ws["ff_fused"], ws["ff_fn"], ws["ff_vn"] = sims, fused, fn, vn      # (the training path's backward reads them)
             ops.clip_loss(sims, ls, rl, weight=wgt)
@@ -1212,7 +1203,7 @@ class MadeEngine:
         row block would waste launches, so express the view as A with rows_per_batch addressing on the OUTPUT
         side only when possible; here rows are gathered by a batched launch (grid.z = B)."""
         D = frame.shape[2]
-        ops.linear(frame[0], w, b, M=Tv, batch=B, a_z_stride=frame.stride(0), w_z_stride=0,
+        self._linear(frame[0], w, b, M=Tv, batch=B, a_z_stride=frame.stride(0), w_z_stride=0,
                    segs=[Seg(out=out, ldo=out.stride(0), out_z_stride=Tv * out.stride(0))])
 
     # ------------------------------------------------------------------ conveniences

@@ -302,11 +302,6 @@ class FrameEncoder:
                         "pooled": torch.empty(B, WIDTH, device=dev, dtype=tc), "feat": torch.empty(B, EMBED, device=dev)}
         return self._ws
 
-    _f32_products = 0                                        # exact f32 products (made_set_f32_products), scoped to the entry points
-
-    def _set_products(self) -> None:
-        _lib.check(_lib.lib().made_set_f32_products(self._f32_products), "made_set_f32_products")
-
     def tower(self, patches: Tensor, out: Tensor) -> Tensor:
         """The tower over one chunk of patch rows [chunk * 49, 3072] -> out [chunk, 512] f32."""
         P, ws, B = self.P, self._workspace(), self.chunk
@@ -323,11 +318,9 @@ class FrameEncoder:
         return ops.linear(ws["pooled"], P["proj"], None, out=out)
 
     @torch.no_grad()
-    @_lib.scoped_f32_products
     def encode(self, frames) -> Tensor:
         """[N, 512] f32 features of N frames: a uint8 [N, H, W, 3] tensor / array (device-resident tensors are read in place) or a
         sequence of [H, W, 3] uint8 frames of any sizes."""
-        self._set_products()
         buf, desc, coef = pack_frames(frames, self.device)
         n = desc.shape[0]
         out = torch.empty(n, EMBED, device=self.device)

@@ -522,7 +522,6 @@ def _entry_tracks(track: Tensor, shape) -> Tensor:
     return t.contiguous().reshape(-1)
 
 
-@_lib.scoped_f32_products
 def similarity_matrix(engine: MadeEngine, video: Tensor, seg: Tensor, seg_mask: Tensor, music: Tensor, out: Optional[Tensor] = None,
                       single_out: Optional[Tensor] = None) -> Tensor:
     """[N_v, N_m] f32 similarities by the configuration's vmr loss, the branch the evaluation ranks with (reference
@@ -812,7 +811,6 @@ def _device_fetch_fp8(library, deq: "_Dequantize"):
 
 
 @torch.no_grad()
-@_lib.scoped_f32_products
 def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Optional[Tensor] = None, group_id=None,
            pair_batch: int = 64, windows: Optional[Windows] = None, windows_per_track: int = 1, moments: int = 1,
            nms_iou: float = 0.5, constraints: Optional[Constraints] = None, tags=None, length=None,
@@ -872,7 +870,6 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
             bits = rc.bits(Nv, Nm, *attrs, device=dev)
     cand = None
     if candidates is not None:
-        engine._set_products()
         video = videos.vec.to(dev, torch.float32).contiguous()
         ccol = _normalize_candidates(candidates, Nm, dev)
         if constraints is not None:
@@ -884,7 +881,6 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
         fetch = _device_fetch(tokens, music.mask.to(dev, torch.float32).contiguous())
         cand = (ccol, _score_candidates(engine, video, ccol, ccos, fetch, 4096, csr=csr))
     if shortlist is not None:
-        engine._set_products()
         R = min(shortlist, Nm)
         video = videos.vec.to(dev, torch.float32).contiguous()
         empty = (torch.empty(Nv, 0, 1, device=dev, dtype=torch.int32), torch.empty(Nv, 0, 1, device=dev, dtype=torch.float32))
@@ -1417,7 +1413,6 @@ def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w
     columns alone (a host library reads `vec` at those columns only)."""
     dev = engine.device
     Nv, N = len(videos), len(library)
-    engine._set_products()
     cur = torch.cuda.current_stream()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timings is not None else None
     if ev:
@@ -1487,7 +1482,6 @@ def _select_shortlisted(engine: MadeEngine, videos: Encoded, library, kk: int, w
 
 
 @torch.no_grad()
-@_lib.scoped_f32_products
 def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_batch: int = 64, windows_per_track: int = 1,
                    moments: int = 1, nms_iou: float = 0.5, chunk_cols: int = 4096, video_batch: int = 1024, sims_fn=None,
                    timings: Optional[dict] = None, constraints: Optional[Constraints] = None, compact: Optional[bool] = None,

@@ -384,11 +384,6 @@ class MusicEncoder:
                         "feat": torch.empty(B, WIDTH, device=dev)}
         return self._ws
 
-    _f32_products = 0                                        # exact f32 products (made_set_f32_products), scoped to the entry points
-
-    def _set_products(self) -> None:
-        _lib.check(_lib.lib().made_set_f32_products(self._f32_products), "made_set_f32_products")
-
     def tower(self, patches: Tensor, out: Tensor) -> Tensor:
         """The tower over one chunk of patch rows [chunk * 1212, 256] -> out [chunk, 768] f32."""
         P, ws, B = self.P, self._workspace(), self.chunk
@@ -433,12 +428,10 @@ class MusicEncoder:
 
     # -------------------------------------------------------------------------------------------- spectrograms -> features
     @torch.no_grad()
-    @_lib.scoped_f32_products
     def encode_spectrograms(self, spec: Tensor) -> Tensor:
         """[S', 768] f32 features of normalised spectrograms spec [S', 1024, 128] f32 (the reference's `audio` rows)."""
         if spec.dim() != 3 or tuple(spec.shape[1:]) != (ROWS, MELS):
             raise ValueError(f"spectrograms must be [S, {ROWS}, {MELS}], got {tuple(spec.shape)}")
-        self._set_products()
         spec = spec.to(self.device, torch.float32).contiguous()
         n = spec.shape[0]
         out = torch.empty(n, WIDTH, device=self.device)
@@ -451,14 +444,12 @@ class MusicEncoder:
         return out
 
     @torch.no_grad()
-    @_lib.scoped_f32_products
     def encode_tracks(self, tracks: Sequence, stride: float = 2.5, filter: float = 4.0, max_m_duration: float = 240
                       ) -> Tuple[Tensor, Tensor, Tensor]:
         """(feats [N, S, 768] f32, mask [N, S] f32, m_duration [N] f64) of N tracks, each (waveform, sr) with a float32 [C, n] or [n]
         waveform (array or tensor).  Only the valid prefix of each track's segments is encoded; masked rows are zero."""
         first, count, _, _ = segment_table(0, stride, filter, 0, max_m_duration)
         S = len(first)
-        self._set_products()
         pcm16, n16 = self.resample(tracks, max_m_duration)
         N, total = pcm16.shape
         masks = np.zeros((N, S), np.float32)
@@ -481,7 +472,6 @@ class MusicEncoder:
 
     # -------------------------------------------------------------------------------------------- whole tracks -> windows
     @torch.no_grad()
-    @_lib.scoped_f32_products
     def encode_windows(self, tracks: Sequence, stride: float = 2.5, filter: float = 4.0, window: float = 240, hop: float = 120,
                        group_samples: int = 1 << 26):
         """(feats [Nw, S, 768] f32, mask [Nw, S] f32, Windows) of N whole tracks cut into overlapping windows of `window` seconds every
@@ -492,7 +482,6 @@ class MusicEncoder:
         groups whose padded [n, longest] buffer holds at most group_samples floats (one track alone may exceed it)."""
         from .windows import library_descriptors, window_table
         S = len(segment_table(0, stride, filter, 0, window)[0])
-        self._set_products()
         dev = self.device
         chans = [_channel0(w) for w, _ in tracks]
         n16 = [resampled_length(int(c.shape[0]), sr) for c, (_, sr) in zip(chans, tracks)]

@@ -165,8 +165,9 @@ def linear(A: Tensor, W: Tensor, bias: Optional[Tensor] = None, *, out: Optional
            tile_skip_mask: Optional[Tensor] = None, batch: int = 1, a_z_stride: int = 0, w_z_stride: int = 0, M: Optional[int] = None,
            N: Optional[int] = None, K: Optional[int] = None, gate: int = 0, G: Optional[Tensor] = None, gate_scale: float = 1.0,
            Zout: Optional[Tensor] = None, drop=None, drop_ld: Optional[int] = None, rows=None, drop_col_div: int = 1,
-           bias_row_scale: Optional[Tensor] = None, bias_z_stride: int = 0) -> Tensor:
+           bias_row_scale: Optional[Tensor] = None, bias_z_stride: int = 0, split: bool = False) -> Tensor:
     """out = act(A' W^T + bias) (+R).  A [M,K] (row stride free, unit inner stride), W [N,K].
+    split: f32 products as three bf16 products on split operands (MadeLinearArgs.f32_products; no effect on bf16 weights).
     Training extras: Zout receives the pre-activation; gate/G multiply by act'(G) * gate_scale; drop = (seed, site, p)
     applies the stateless dropout of include/made_hip.h after act/gate (element index row * drop_ld + col)."""
     assert A.dim() == 2 and W.dim() == 2 and A.stride(1) == 1 and W.stride(1) == 1
@@ -184,7 +185,7 @@ def linear(A: Tensor, W: Tensor, bias: Optional[Tensor] = None, *, out: Optional
     a.bias = _p(_f32(bias, "bias"))
     a.M, a.N, a.K = M, N, K
     a.batch, a.a_z_stride, a.w_z_stride = batch, a_z_stride, w_z_stride
-    a.act = act
+    a.act, a.f32_products = act, 1 if split else 0
     if R is not None:
         assert R.dim() == 2 and R.stride(1) == 1
         a.R, a.r_dtype, a.ldr, a.r_row_mod = _p(R), dt_of(R), R.stride(0), r_row_mod
@@ -266,10 +267,10 @@ def batch_order(mask: Tensor, out: Optional[Tensor] = None) -> Tensor:
 def linear_splitk(A: Tensor, W: Tensor, bias: Optional[Tensor], ws: Tensor, split_k: int, *, A2: Optional[Tensor] = None,
                   a2_row_mod: int = 0, act: int = ACT_NONE, R: Optional[Tensor] = None, r_row_mod: int = 0,
                   out: Optional[Tensor] = None, ln1=None, ln1_out: Optional[Tensor] = None, ln2=None,
-                  ln2_out: Optional[Tensor] = None, eps: float = 1e-5) -> None:
+                  ln2_out: Optional[Tensor] = None, eps: float = 1e-5, split: bool = False) -> None:
     """Skinny Linear (few rows, e.g. the decoder's B*Q): K is split over grid.z so the launch fills the chip, the raw f32
     partials land in `ws` ([>= split_k*M*N] f32) and made_splitk_finish sums them and applies bias / act / residual, then
-    optionally LayerNorm (ln1 = (gamma, beta)) and a second LayerNorm on top (ln2)."""
+    optionally LayerNorm (ln1 = (gamma, beta)) and a second LayerNorm on top (ln2).  split: as in linear."""
     assert A.dim() == 2 and W.dim() == 2 and A.stride(1) == 1 and W.stride(1) == 1
     M, K = A.shape
     N = W.shape[0]
@@ -281,7 +282,7 @@ def linear_splitk(A: Tensor, W: Tensor, bias: Optional[Tensor], ws: Tensor, spli
         a.A2, a.lda2, a.a2_row_mod = _p(A2), A2.stride(0), a2_row_mod
     a.W, a.ldw = _p(W), W.stride(0)
     a.M, a.N, a.K = M, N, K
-    a.batch = 1
+    a.batch, a.f32_products = 1, 1 if split else 0
     a.nseg, a.split_k, a.split_ws = 1, max(split_k, 2), _p(ws)
     sg = a.seg[0]
     sg.col_begin, sg.out, sg.out_dtype, sg.ldo, sg.use_a2 = 0, _p(ws), F32, N, 1 if use_a2 else 0
@@ -366,9 +367,10 @@ def dec_stage(Zin: Tensor, W: Tensor, bias: Optional[Tensor], out: Tensor, *, ln
 def attention(Q: Tensor, K: Tensor, V: Tensor, O: Tensor, H: int, *, key_mask: Optional[Tensor] = None,
               q_mask: Optional[Tensor] = None, scale: Optional[float] = None, Lk: Optional[int] = None,
               q_skip_mask: Optional[Tensor] = None, lse: Optional[Tensor] = None, drop=None,
-              order: Optional[Tensor] = None, keep_bits: Optional[Tensor] = None) -> Tensor:
+              order: Optional[Tensor] = None, keep_bits: Optional[Tensor] = None, split: bool = False) -> Tensor:
     """softmax(Q K^T scale + mask) V.  Q [B,Lq,H*hd], K / V [B,Lk,H*hd], O [B,Lq,H*hd]
     (any batch/row strides, unit inner stride).  Lk defaults to K.shape[1].
+    split: f32 products as three bf16 products on split operands (MadeAttnArgs.f32_products; no effect on bf16 tensors).
     Training: lse [B,H,Lq] f32 receives the log-sum-exp, drop = (seed, site, p) drops attention weights; keep_bits
     (int32, shape attention_bits_shape(B, H, Lq, Lk)) receives the decisions, one bit per score, for attention_bwd."""
     assert Q.dim() == 3 and K.dim() == 3 and V.dim() == 3 and O.dim() == 3
@@ -388,6 +390,7 @@ def attention(Q: Tensor, K: Tensor, V: Tensor, O: Tensor, H: int, *, key_mask: O
     a.q_mask = _p(_f32(q_mask, "q_mask"))
     a.q_skip_mask = _p(_f32(q_skip_mask, "q_skip_mask"))
     a.scale = (1.0 / math.sqrt(hd)) if scale is None else scale
+    a.f32_products = 1 if split else 0
     if order is not None:                       # issue order of the batch (batch_order): longest sample first
         assert order.dtype == torch.int32 and order.numel() == B and order.is_contiguous()
         a.batch_order = _p(order)
@@ -468,10 +471,12 @@ def wide_slice_plan(key_mask: Tensor, *, n_slots: int, max_slices: int = 8, orde
 def attention_wide(Q: Tensor, K: Tensor, V: Tensor, O: Tensor, *, scale: float, Kadd: Optional[Tensor] = None,
                    key_mask: Optional[Tensor] = None, shared_q: bool = False, n_split: int = 1,
                    part_o: Optional[Tensor] = None, part_ml: Optional[Tensor] = None, drop=None,
-                   sum_out: Optional[Tensor] = None, lse_out: Optional[Tensor] = None, plan: Optional[WidePlan] = None) -> Tensor:
+                   sum_out: Optional[Tensor] = None, lse_out: Optional[Tensor] = None, plan: Optional[WidePlan] = None,
+                   split: bool = False) -> Tensor:
     """Single-head attention with head dim = D.  Q [B|1, NQ1, NQ2, D], K/Kadd/V [B, L, D], O [B, NQ1, NQ2, D]
     (strided views fine, unit inner stride).  shared_q: the same queries for every batch entry (Q.shape[0] == 1).
-    plan (wide_slice_plan of the same key_mask): the launch follows the plan and n_split is the slice capacity of part_o / part_ml."""
+    plan (wide_slice_plan of the same key_mask): the launch follows the plan and n_split is the slice capacity of part_o / part_ml.
+    split: f32 products as three bf16 products on split operands (MadeWideAttnArgs.f32_products; no effect on bf16 tensors, planned launches among them)."""
     assert Q.dim() == 4 and O.dim() == 4 and K.dim() == 3 and V.dim() == 3
     assert Q.stride(3) == 1 and O.stride(3) == 1 and K.stride(2) == 1 and V.stride(2) == 1
     assert Q.dtype == K.dtype == V.dtype
@@ -488,7 +493,7 @@ def attention_wide(Q: Tensor, K: Tensor, V: Tensor, O: Tensor, *, scale: float, 
         assert Kadd.dim() == 3 and Kadd.stride(2) == 1 and Kadd.dtype == K.dtype
         a.Kadd, a.kadd_bs, a.ldkadd = _p(Kadd), Kadd.stride(0), Kadd.stride(1)
     a.o_bs, a.o_s1, a.o_s2 = O.stride(0), O.stride(1), O.stride(2)
-    a.scale = scale
+    a.scale, a.f32_products = scale, 1 if split else 0
     nq = a.NQ1 * a.NQ2
     if plan is not None:
         assert key_mask is not None and (plan.B, plan.L) == (B, L) and n_split >= plan.max_slices, "the plan is not this call's"

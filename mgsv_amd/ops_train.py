@@ -52,9 +52,10 @@ def gemm_tn(A: Tensor, B: Tensor, Cout: Tensor, *, alpha: float = 1.0, accumulat
             row_mask: Optional[Tensor] = None, row_groups: Optional[Tensor] = None, rows=None, colsum: Optional[Tensor] = None,
             batch: Pair = (1, 1),
             a_zs: Pair = (0, 0), b_zs: Pair = (0, 0), c_zs: Pair = (0, 0), mask_zs: Pair = (0, 0),
-            colsum_zs: Pair = (0, 0)) -> Tensor:
+            colsum_zs: Pair = (0, 0), split: bool = False) -> Tensor:
     """Cout[N,K] (+)= alpha * A[M,N]^T B[M,K]  (made_gemm_tn).  A, B, Cout are the 2-D views of batch element 0; the
-    *_zs pairs are the element strides of the two batch levels.  colsum[N] += alpha * column sums of A."""
+    *_zs pairs are the element strides of the two batch levels.  colsum[N] += alpha * column sums of A.
+    split: f32 products as three bf16 products on split operands (MadeGemmTNArgs.f32_products; no effect on bf16 operands)."""
     M, N = A.shape
     K = B.shape[1]
     assert B.shape[0] == M and tuple(Cout.shape) == (N, K), (A.shape, B.shape, Cout.shape)
@@ -87,6 +88,7 @@ def gemm_tn(A: Tensor, B: Tensor, Cout: Tensor, *, alpha: float = 1.0, accumulat
         a.row_index, a.n_rows = _p(rows[0]), _p(rows[1])
     a.mask_zs1, a.mask_zs2 = mask_zs
     a.alpha, a.accumulate, a.split_m = float(alpha), int(bool(accumulate)), int(split_m)
+    a.f32_products = 1 if split else 0
     a.colsum = _p(_f32(colsum, "colsum"))
     a.colsum_zs1, a.colsum_zs2 = colsum_zs
     flops = 2.0 * M * N * K * nz
@@ -164,9 +166,10 @@ def dropout_desc(seed: int, site: int, p: float) -> MadeDropout:
 
 def attention_bwd(Q: Tensor, K: Tensor, V: Tensor, O: Tensor, dO: Tensor, dQ: Tensor, dK: Tensor, dV: Tensor, lse: Tensor,
                   delta: Tensor, H: int, *, key_mask: Optional[Tensor] = None, q_skip_mask: Optional[Tensor] = None,
-                  scale: Optional[float] = None, drop=None, order: Optional[Tensor] = None, keep_bits: Optional[Tensor] = None) -> None:
+                  scale: Optional[float] = None, drop=None, order: Optional[Tensor] = None, keep_bits: Optional[Tensor] = None,
+                  split: bool = False) -> None:
     """Gradients of ops.attention (made_attention_bwd).  All [B, L, H*hd] views with unit inner stride.  keep_bits: the decisions the
-    forward call stored (same mask as re-drawing it; bf16 path)."""
+    forward call stored (same mask as re-drawing it; bf16 path).  split: as in ops.attention (MadeAttnBwdArgs.f32_products)."""
     import math
     for t in (Q, K, V, O, dO, dQ, dK, dV):
         assert t.dim() == 3 and t.stride(2) == 1 and t.dtype == Q.dtype
@@ -187,6 +190,7 @@ def attention_bwd(Q: Tensor, K: Tensor, V: Tensor, O: Tensor, dO: Tensor, dQ: Te
         assert order.dtype == torch.int32 and order.numel() == a.B and order.is_contiguous()
         a.batch_order = _p(order)
     a.scale = (1.0 / math.sqrt(hd)) if scale is None else scale
+    a.f32_products = 1 if split else 0
     if drop is not None and drop[2] > 0.0:
         set_drop(a.drop, drop)
         if keep_bits is not None:

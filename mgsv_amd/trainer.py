@@ -639,7 +639,6 @@ class MadeTrainer(MadeEngine):
         zero_grad: also clear `flat_grad` for the backward pass that follows, on the second stream (backward() then skips its own fill).
         This function is the schedule only -- which stage runs on which stream and who waits for whom; the launches are the stages'."""
         c = self.cfg
-        self._set_products()
         if c.predict_center == 1 and v_duration is None:
             raise ValueError("predict_center=1 needs v_duration (reference model/model_Uni.py:280-282)")
         self.seed = int(seed)
@@ -1302,7 +1301,6 @@ class MadeTrainer(MadeEngine):
         of them waits for it until the end of the backward pass): optimizer_step(part="early") there applies the matching + detection
         groups' update under the temporal encoders' backward, which reads none of their weights (opt-in, see _early_opt_ok).
         This function is the schedule only -- which stage runs on which stream and who waits for whom; the launches are the stages'."""
-        self._set_products()
         c = self.cfg
         B, Tv, Ta = self._shape
         ws, tw = self._buffers(B, Tv, Ta), self._train_buffers(B, Tv, Ta)

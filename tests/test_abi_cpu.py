@@ -29,7 +29,9 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(raw, n), f"{n} declared in made_hip.h but not exported"
     assert set(names) == set(_lib.SIGNATURES), "ctypes binding and header disagree"
-    assert _lib.lib().made_abi_version() == _lib.ABI_VERSION == 8
+    assert _lib.lib().made_abi_version() == _lib.ABI_VERSION == 9
+    for gone in ("made_set_f32_products", "made_get_f32_products"):           # version 9: the f32 product mode is a field of each launch's arguments
+        assert not hasattr(raw, gone), f"{gone} is still exported: the library keeps no product mode of its own"
 
 
 def _all_structs():
@@ -102,6 +104,30 @@ def test_argument_validation_without_gpu():
     assert l.made_attention(C.byref(a), None) == -1
     with pytest.raises(_lib.MadeError):
         _lib.check(-1, "x")
+
+
+def test_f32_products_outside_0_1_is_refused_before_any_launch():
+    """f32_products is 0 (exact) or 1 (split-bf16): anything else is MADE_ERR_INVALID_ARG with a message naming the field.  The pointers are
+    placeholders (aligned, never dereferenced: the check comes before the launch); dimensions and dtypes pass the checks ahead of it."""
+    l = _lib.lib()
+    p = 0x1000
+    lin = _lib.MadeLinearArgs()
+    lin.A, lin.W, lin.M, lin.N, lin.K, lin.nseg, lin.batch = p, p, 4, 4, 4, 1, 1
+    att = _lib.MadeAttnArgs()
+    att.Q, att.K, att.V, att.O, att.B, att.H, att.Lq, att.Lk, att.hd = p, p, p, p, 1, 1, 4, 4, 32
+    wide = _lib.MadeWideAttnArgs()
+    wide.Q, wide.K, wide.V, wide.O, wide.B, wide.NQ1, wide.NQ2, wide.L, wide.D = p, p, p, p, 1, 1, 1, 4, 256
+    bwd = _lib.MadeAttnBwdArgs()
+    for k in ("Q", "K", "V", "O", "dO", "dQ", "dK", "dV", "lse", "delta"):
+        setattr(bwd, k, p)
+    bwd.B, bwd.H, bwd.Lq, bwd.Lk, bwd.hd = 1, 1, 4, 4, 32
+    tn = _lib.MadeGemmTNArgs()
+    tn.A, tn.B, tn.C, tn.M, tn.N, tn.K = p, p, p, 4, 4, 4
+    for fn, a in ((l.made_linear, lin), (l.made_attention, att), (l.made_attention_wide, wide), (l.made_attention_bwd, bwd), (l.made_gemm_tn, tn)):
+        for bad in (2, -1):
+            a.f32_products = bad
+            assert fn(C.byref(a), None) == -1, (fn.__name__, bad)
+            assert b"f32_products" in l.made_last_error(), l.made_last_error()
 
 
 def test_product_path_refuses_cpu_tensors():

@@ -186,7 +186,7 @@ def test_groups_on_the_host_backend():
 def test_binding_lists_the_entry_point():
     assert "made_cosine_join" in _lib.SIGNATURES
     assert hasattr(_lib.lib(), "made_cosine_join")
-    assert _lib.lib().made_abi_version() == 8
+    assert _lib.lib().made_abi_version() == 9
 
 
 def test_cosine_join_argument_validation_without_gpu():

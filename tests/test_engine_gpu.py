@@ -71,7 +71,7 @@ def _cases():
 @pytest.mark.parametrize("name", list(_cases()))
 def test_f32_forward_matches_oracle(name, dtype):
     """dtype "f32": exact-f32 MFMA.  "f32x3" (round 6): the same f32 engine with every matrix product as three bf16 products on split operands
-    (made_set_f32_products(1), csrc/common.h) -- held to the SAME 1e-4 gate on every output."""
+    (f32_products = 1 in each launch's arguments, csrc/common.h) -- held to the SAME 1e-4 gate on every output."""
     cfg, B, Tv, Ta = _cases()[name]
     sd = synth.make_state_dict(cfg, seed=0)
     inp = synth.make_inputs(cfg, B, Tv, Ta, seed=1, min_len_v=min(5, Tv), min_len_a=min(12, Ta))
@@ -489,31 +489,130 @@ def test_two_batches_in_flight_match_one_at_a_time():
 
 
 def test_f32x3_engine_leaves_the_exact_product_mode_behind():
-    """made_set_f32_products is process-wide: an "f32x3" engine switches every f32 product to three bf16 products on split operands for its own
-    launches only.  A bare f32 ops.linear gives the same bits before and after such an engine's forward, and the mode reads 0 (exact) after the
-    call and after a bf16 engine's forward that follows."""
-    from mgsv_amd import _lib, ops
+    """The f32 product mode is an argument of each launch (f32_products), never a state of the library: an "f32x3" engine runs every f32 product
+    of its own as three bf16 products on split operands, and nobody else's.  A bare f32 ops.linear gives the same bits before such an engine's
+    forward, after it, and after a bf16 engine's forward that follows; the same product with split=True differs from them."""
+    from mgsv_amd import ops
+    g = torch.Generator(device="cuda").manual_seed(7)
+    x = torch.randn(300, 256, device="cuda", generator=g)
+    w = torch.randn(128, 256, device="cuda", generator=g) / 16
+    bias = torch.randn(128, device="cuda", generator=g)
+    before = ops.linear(x, w, bias).clone()
+    cfg = cfg_native()
+    sd = synth.make_state_dict(cfg, seed=0)
+    inp = synth.make_inputs(cfg, 2, 20, 40, seed=1)
+    MadeEngine(cfg, sd, dtype="f32x3").forward_numpy(inp)
+    after = ops.linear(x, w, bias).clone()
+    torch.cuda.synchronize()
+    assert torch.equal(before, after), float((before - after).abs().max())
+    MadeEngine(cfg, sd, dtype="bf16").forward_numpy(inp)
+    after_bf16 = ops.linear(x, w, bias).clone()
+    split = ops.linear(x, w, bias, split=True).clone()
+    torch.cuda.synchronize()
+    assert torch.equal(before, after_bf16), float((before - after_bf16).abs().max())
+    assert not torch.equal(before, split)                                        # (the two modes do differ on this product: the checks above can fail)
+
+
+def _device_inputs(cfg, B=2, Tv=20, Ta=40, seed=1):
+    inp = synth.make_inputs(cfg, B, Tv, Ta, seed=seed)
+    return {k: torch.from_numpy(v).cuda() for k, v in inp.items() if isinstance(v, np.ndarray)}
+
+
+def test_every_f32_product_of_an_f32x3_engine_is_a_split_one(monkeypatch):
+    """Every made_linear / made_attention / made_attention_wide launch of every entry point carries the engine's mode: f32_products = 1 on each
+    f32-compute launch of an "f32x3" engine, 0 on each launch of an "f32" engine.  (A call site that bypassed the engine's bound ops would only
+    run slower and still meet the 1e-4 gates: this is the test that sees it.)"""
+    from mgsv_amd import _lib
+    from mgsv_amd.grounding import ground
     l = _lib.lib()
-    _lib.check(l.made_set_f32_products(0), "made_set_f32_products")              # the library's default, whatever ran before this test
-    try:
-        g = torch.Generator(device="cuda").manual_seed(7)
-        x = torch.randn(300, 256, device="cuda", generator=g)
-        w = torch.randn(128, 256, device="cuda", generator=g) / 16
-        bias = torch.randn(128, device="cuda", generator=g)
-        before = ops.linear(x, w, bias).clone()
-        cfg = cfg_native()
-        sd = synth.make_state_dict(cfg, seed=0)
-        inp = synth.make_inputs(cfg, 2, 20, 40, seed=1)
-        MadeEngine(cfg, sd, dtype="f32x3").forward_numpy(inp)
-        assert l.made_get_f32_products() == 0
-        after = ops.linear(x, w, bias).clone()
-        torch.cuda.synchronize()
-        assert torch.equal(before, after), float((before - after).abs().max())
-        MadeEngine(cfg, sd, dtype="bf16").forward_numpy(inp)
-        assert l.made_get_f32_products() == 0
-        _lib.check(l.made_set_f32_products(1), "made_set_f32_products")          # (the two modes do differ on this product: the check above can fail)
-        split = ops.linear(x, w, bias).clone()
-        torch.cuda.synchronize()
-        assert not torch.equal(before, split)
-    finally:
-        _lib.check(l.made_set_f32_products(0), "made_set_f32_products")
+    seen = []                                                                    # (compute dtype, f32_products) of each launch
+    for name, dtype_field in (("made_linear", "w_dtype"), ("made_attention", "dtype"), ("made_attention_wide", "dtype")):
+        def recording(args, stream, _real=getattr(l, name), _field=dtype_field):
+            seen.append((getattr(args._obj, _field), args._obj.f32_products))
+            return _real(args, stream)
+        monkeypatch.setattr(l, name, recording)
+    cfg = cfg_native()
+    sd = synth.make_state_dict(cfg, seed=0)
+    t = _device_inputs(cfg)
+    B = t["frame_feats"].shape[0]
+    for dtype, want in (("f32x3", 1), ("f32", 0)):
+        eng = MadeEngine(cfg, sd, dtype=dtype)
+        V = eng.encode_videos(t["frame_feats"], t["frame_masks"], t["v_duration"])
+        M = eng.encode_music(t["segment_feats"], t["segment_masks"])
+        entry_points = {
+            "forward": lambda: eng.forward(t["frame_feats"], t["segment_feats"], t["frame_masks"], t["segment_masks"], t["spans_target"],
+                                           v_duration=t["v_duration"]),
+            "retrieval_sim_matrix": lambda: eng.retrieval_sim_matrix(V.vec, M.tokens, M.mask, M.vec),
+            "xpool_sims": lambda: eng.xpool_sims(V.vec, M.tokens, M.mask),
+            "dual_sims": lambda: eng.dual_sims(V.vec, M.vec),
+            "encode_videos": lambda: eng.encode_videos(t["frame_feats"], t["frame_masks"], t["v_duration"]),
+            "encode_music": lambda: eng.encode_music(t["segment_feats"], t["segment_masks"]),
+            "localize_pairs": lambda: eng.localize_pairs(V, M, torch.arange(B), torch.arange(B)),
+            "ground": lambda: ground(eng, V, M, 1),
+        }
+        for entry, run in entry_points.items():
+            del seen[:]
+            run()
+            torch.cuda.synchronize()
+            assert seen, (dtype, entry)                                          # the entry point did go through the recorded launches
+            f32 = [mode for compute, mode in seen if compute == _lib.F32]
+            assert f32 and all(mode == want for mode in f32), (dtype, entry, seen)
+            if dtype == "f32":
+                assert all(mode == 0 for _, mode in seen), (entry, seen)
+
+
+def test_two_engines_of_different_modes_do_not_see_each_other():
+    """An "f32" and an "f32x3" engine on the same weights and batch, each on a stream of its own: alternated from one thread, then driven from
+    two threads started together, every output of every round is bit for bit what that engine gives alone -- and the two engines' outputs
+    differ from each other, so a mode that leaked from one to the other would show.  (The threaded half is the one that discriminates: with a
+    mode kept in the library, two threads of different modes race.)"""
+    import threading
+    cfg = cfg_native()
+    sd = synth.make_state_dict(cfg, seed=0)
+    t = _device_inputs(cfg)
+    keys = ["pred_logits", "pred_spans", "sims_single", "sims_dual", "video_feats", "music_feats"]
+    engines = [MadeEngine(cfg, sd, dtype="f32"), MadeEngine(cfg, sd, dtype="f32x3")]
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+
+    def step(i):
+        with torch.cuda.stream(streams[i]):
+            o = engines[i].forward(t["frame_feats"], t["segment_feats"], t["frame_masks"], t["segment_masks"], t["spans_target"],
+                                   v_duration=t["v_duration"])
+            got = {k: o[k].clone() for k in keys}
+        streams[i].synchronize()
+        return got
+
+    torch.cuda.synchronize()
+    solo = [step(0), step(1)]                                                    # (also every launcher's one-time set-up, before any thread)
+    assert any(not torch.equal(solo[0][k], solo[1][k]) for k in keys)
+
+    def same(i, got, what):
+        for k in keys:
+            assert torch.equal(got[k], solo[i][k]), f"{what}, {engines[i].dtype_name}: {k} differs from the engine's solo run"
+
+    for r in range(3):                                                           # one thread, alternating
+        for i in range(2):
+            same(i, step(i), f"alternating round {r}")
+
+    start = threading.Barrier(2)
+    results, errors = [[], []], []
+
+    def drive(i):
+        try:
+            start.wait()
+            for _ in range(3):
+                results[i].append(step(i))
+        except BaseException as ex:                                              # reported by the test's own thread below
+            errors.append((i, ex))
+
+    threads = [threading.Thread(target=drive, args=(i,)) for i in range(2)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    torch.cuda.synchronize()
+    assert not errors, errors
+    for i in range(2):
+        assert len(results[i]) == 3
+        for r, got in enumerate(results[i]):
+            same(i, got, f"threaded round {r}")

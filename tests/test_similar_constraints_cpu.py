@@ -273,7 +273,7 @@ def test_candidates_refusals_without_a_device():
 def test_binding_declares_the_extended_entry_points():
     assert {"made_cosine_topk_ex", "made_cosine_topk_ex_ws_bytes"} <= set(_lib.SIGNATURES)
     l = _lib.lib()
-    assert hasattr(l, "made_cosine_topk_ex") and hasattr(l, "made_cosine_topk_ex_ws_bytes") and l.made_abi_version() == 8
+    assert hasattr(l, "made_cosine_topk_ex") and hasattr(l, "made_cosine_topk_ex_ws_bytes") and l.made_abi_version() == 9
 
 
 def test_extended_workspace_rule_and_argument_checks_without_gpu():

@@ -182,7 +182,7 @@ def test_value_errors():
 def test_binding_lists_the_entry_points():
     assert {"made_cosine_topk", "made_cosine_topk_ws_bytes"} <= set(_lib.SIGNATURES)
     assert hasattr(_lib.lib(), "made_cosine_topk") and hasattr(_lib.lib(), "made_cosine_topk_ws_bytes")
-    assert _lib.lib().made_abi_version() == 8
+    assert _lib.lib().made_abi_version() == 9
 
 
 def test_workspace_bytes_and_the_clamp_of_the_splits():

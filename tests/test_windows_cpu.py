@@ -176,7 +176,7 @@ def test_new_entry_points_are_declared_bound_and_exported():
         assert re.search(r"\bint " + name + r"\s*\(", code), name
         assert name in _lib.SIGNATURES and hasattr(raw, name), name
     assert "windows.hip" in open(os.path.join(ROOT, "mgsv_amd", "csrc", "Makefile")).read()
-    assert _lib.lib().made_abi_version() == 8
+    assert _lib.lib().made_abi_version() == 9
 
 
 def test_argument_validation_without_gpu():

@@ -139,7 +139,6 @@ def main():
             res["resample_ms"] = round(timed(lambda: enc.resample(tracks), a.reps), 3)
             res["fbank_ms"] = round(timed(fbank, a.reps), 3)
             res["patches_ms"] = round(timed(patches, a.reps), 3)
-        enc._set_products()
         tms = timed(tower, reps)
         n_run = len(descs) * C                                     # segments the chunks compute (the last chunk padded)
         res[f"{dt}_tower_ms"] = round(tms, 2)
