@@ -158,6 +158,74 @@ LINEAR_VARIANTS = {0: "linear_f32", 1: "linear_f32in_bf16", 2: "linear_kernel<bf
 LINEAR_LOG = None                                             # a list: every linear() call appends its form (tools/linear_calls.py)
 
 
+def _host_ptr(t: Optional[Tensor]):
+    """data pointer of a tensor on any device: for argument structs that are looked at (made_linear_variant) and never launched"""
+    return None if t is None else t.data_ptr()
+
+
+def linear_args(A: Tensor, W: Tensor, bias: Optional[Tensor] = None, *, out: Optional[Tensor] = None,
+                segs: Optional[Sequence[Seg]] = None, A2: Optional[Tensor] = None, a2_row_mod: int = 0,
+                a2_replace: bool = False, a_row_mask: Optional[Tensor] = None, act: int = ACT_NONE, R: Optional[Tensor] = None,
+                r_row_mod: int = 0, out_row_mask: Optional[Tensor] = None, out_dtype: Optional[torch.dtype] = None,
+                tile_skip_mask: Optional[Tensor] = None, batch: int = 1, a_z_stride: int = 0, w_z_stride: int = 0, M: Optional[int] = None,
+                N: Optional[int] = None, K: Optional[int] = None, gate: int = 0, G: Optional[Tensor] = None, gate_scale: float = 1.0,
+                Zout: Optional[Tensor] = None, drop=None, drop_ld: Optional[int] = None, rows=None, drop_col_div: int = 1,
+                bias_row_scale: Optional[Tensor] = None, bias_z_stride: int = 0, split: bool = False, launchable: bool = True):
+    """(MadeLinearArgs, segs) of a linear() call: every field filled, nothing launched (linear() calls this, then made_linear).
+    launchable=False takes tensors of any device, for a made_linear_variant question asked without a GPU; such arguments are
+    never handed to made_linear."""
+    ptr = _p if launchable else _host_ptr
+    assert A.dim() == 2 and W.dim() == 2 and A.stride(1) == 1 and W.stride(1) == 1
+    M = A.shape[0] if M is None else M
+    K = A.shape[1] if K is None else K
+    N = W.shape[0] if N is None else N
+    a = MadeLinearArgs()
+    a.A, a.a_dtype, a.w_dtype, a.lda = ptr(A), dt_of(A), dt_of(W), A.stride(0)
+    if A2 is not None:
+        assert A2.dim() == 2 and A2.stride(1) == 1 and A2.dtype == A.dtype
+        a.A2, a.lda2, a.a2_row_mod = ptr(A2), A2.stride(0), a2_row_mod
+        a.a2_replace = 1 if a2_replace else 0
+    a.a_row_mask = ptr(_f32(a_row_mask, "a_row_mask"))
+    a.W, a.ldw = ptr(W), W.stride(0)
+    a.bias = ptr(_f32(bias, "bias"))
+    a.M, a.N, a.K = M, N, K
+    a.batch, a.a_z_stride, a.w_z_stride = batch, a_z_stride, w_z_stride
+    a.act, a.f32_products = act, 1 if split else 0
+    if R is not None:
+        assert R.dim() == 2 and R.stride(1) == 1
+        a.R, a.r_dtype, a.ldr, a.r_row_mod = ptr(R), dt_of(R), R.stride(0), r_row_mod
+    a.out_row_mask = ptr(_f32(out_row_mask, "out_row_mask"))
+    a.tile_skip_mask = ptr(_f32(tile_skip_mask, "tile_skip_mask"))
+    if gate:
+        assert G is not None and G.dim() == 2 and G.stride(1) == 1
+        a.G, a.g_dtype, a.gate, a.ldg, a.gate_scale = ptr(G), dt_of(G), gate, G.stride(0), float(gate_scale)
+    if Zout is not None:
+        assert Zout.dim() == 2 and Zout.stride(1) == 1
+        a.Zout, a.z_dtype, a.ldz = ptr(Zout), dt_of(Zout), Zout.stride(0)
+    if drop is not None and drop[2] > 0.0:
+        set_drop(a.drop, drop)
+        a.drop_ld = N if drop_ld is None else drop_ld
+        a.drop_col_div = int(drop_col_div)
+    if rows is not None:                                      # row gather: (row_index int32 [M], n_rows int32 [1]) from row_index()
+        a.row_index, a.n_rows = ptr(rows[0]), ptr(rows[1])
+    if bias_row_scale is not None:                            # bias[z * bias_z_stride + col] * bias_row_scale[row, z] (tiny-M kernel)
+        assert tuple(bias_row_scale.shape) == (M, batch)
+        a.bias_row_scale, a.bias_z_stride = ptr(_f32(bias_row_scale, "bias_row_scale")), bias_z_stride
+    if segs is None:
+        if out is None:
+            out = torch.empty((M, N) if batch == 1 else (batch, M, N), device=A.device, dtype=out_dtype or W.dtype)
+        segs = [Seg(out=out, out_z_stride=(out.stride(0) if (batch > 1 and out.dim() == 3) else 0))]
+    a.nseg = len(segs)
+    for i, s in enumerate(segs):
+        sg = a.seg[i]
+        sg.col_begin, sg.out, sg.out_dtype = s.col_begin, ptr(s.out), dt_of(s.out)
+        sg.transposed = 1 if s.transposed else 0
+        sg.ldo = s.ldo if s.ldo is not None else s.out.stride(-2)
+        sg.rows_per_batch, sg.out_batch_stride, sg.out_z_stride = s.rows_per_batch, s.out_batch_stride, s.out_z_stride
+        sg.use_a2 = 1 if s.use_a2 else 0
+    return a, segs
+
+
 def linear(A: Tensor, W: Tensor, bias: Optional[Tensor] = None, *, out: Optional[Tensor] = None,
            segs: Optional[Sequence[Seg]] = None, A2: Optional[Tensor] = None, a2_row_mod: int = 0,
            a2_replace: bool = False, a_row_mask: Optional[Tensor] = None, act: int = ACT_NONE, R: Optional[Tensor] = None,
@@ -170,55 +238,11 @@ def linear(A: Tensor, W: Tensor, bias: Optional[Tensor] = None, *, out: Optional
     split: f32 products as three bf16 products on split operands (MadeLinearArgs.f32_products; no effect on bf16 weights).
     Training extras: Zout receives the pre-activation; gate/G multiply by act'(G) * gate_scale; drop = (seed, site, p)
     applies the stateless dropout of include/made_hip.h after act/gate (element index row * drop_ld + col)."""
-    assert A.dim() == 2 and W.dim() == 2 and A.stride(1) == 1 and W.stride(1) == 1
-    M = A.shape[0] if M is None else M
-    K = A.shape[1] if K is None else K
-    N = W.shape[0] if N is None else N
-    a = MadeLinearArgs()
-    a.A, a.a_dtype, a.w_dtype, a.lda = _p(A), dt_of(A), dt_of(W), A.stride(0)
-    if A2 is not None:
-        assert A2.dim() == 2 and A2.stride(1) == 1 and A2.dtype == A.dtype
-        a.A2, a.lda2, a.a2_row_mod = _p(A2), A2.stride(0), a2_row_mod
-        a.a2_replace = 1 if a2_replace else 0
-    a.a_row_mask = _p(_f32(a_row_mask, "a_row_mask"))
-    a.W, a.ldw = _p(W), W.stride(0)
-    a.bias = _p(_f32(bias, "bias"))
-    a.M, a.N, a.K = M, N, K
-    a.batch, a.a_z_stride, a.w_z_stride = batch, a_z_stride, w_z_stride
-    a.act, a.f32_products = act, 1 if split else 0
-    if R is not None:
-        assert R.dim() == 2 and R.stride(1) == 1
-        a.R, a.r_dtype, a.ldr, a.r_row_mod = _p(R), dt_of(R), R.stride(0), r_row_mod
-    a.out_row_mask = _p(_f32(out_row_mask, "out_row_mask"))
-    a.tile_skip_mask = _p(_f32(tile_skip_mask, "tile_skip_mask"))
-    if gate:
-        assert G is not None and G.dim() == 2 and G.stride(1) == 1
-        a.G, a.g_dtype, a.gate, a.ldg, a.gate_scale = _p(G), dt_of(G), gate, G.stride(0), float(gate_scale)
-    if Zout is not None:
-        assert Zout.dim() == 2 and Zout.stride(1) == 1
-        a.Zout, a.z_dtype, a.ldz = _p(Zout), dt_of(Zout), Zout.stride(0)
-    if drop is not None and drop[2] > 0.0:
-        set_drop(a.drop, drop)
-        a.drop_ld = N if drop_ld is None else drop_ld
-        a.drop_col_div = int(drop_col_div)
-    if rows is not None:                                      # row gather: (row_index int32 [M], n_rows int32 [1]) from row_index()
-        a.row_index, a.n_rows = _p(rows[0]), _p(rows[1])
-    if bias_row_scale is not None:                            # bias[z * bias_z_stride + col] * bias_row_scale[row, z] (tiny-M kernel)
-        assert tuple(bias_row_scale.shape) == (M, batch)
-        a.bias_row_scale, a.bias_z_stride = _p(_f32(bias_row_scale, "bias_row_scale")), bias_z_stride
-    if segs is None:
-        if out is None:
-            out = torch.empty((M, N) if batch == 1 else (batch, M, N), device=A.device,
-                              dtype=out_dtype or W.dtype)
-        segs = [Seg(out=out, out_z_stride=(out.stride(0) if (batch > 1 and out.dim() == 3) else 0))]
-    a.nseg = len(segs)
-    for i, s in enumerate(segs):
-        sg = a.seg[i]
-        sg.col_begin, sg.out, sg.out_dtype = s.col_begin, _p(s.out), dt_of(s.out)
-        sg.transposed = 1 if s.transposed else 0
-        sg.ldo = s.ldo if s.ldo is not None else s.out.stride(-2)
-        sg.rows_per_batch, sg.out_batch_stride, sg.out_z_stride = s.rows_per_batch, s.out_batch_stride, s.out_z_stride
-        sg.use_a2 = 1 if s.use_a2 else 0
+    a, segs = linear_args(A, W, bias, out=out, segs=segs, A2=A2, a2_row_mod=a2_row_mod, a2_replace=a2_replace, a_row_mask=a_row_mask, act=act, R=R,
+                          r_row_mod=r_row_mod, out_row_mask=out_row_mask, out_dtype=out_dtype, tile_skip_mask=tile_skip_mask, batch=batch,
+                          a_z_stride=a_z_stride, w_z_stride=w_z_stride, M=M, N=N, K=K, gate=gate, G=G, gate_scale=gate_scale, Zout=Zout, drop=drop,
+                          drop_ld=drop_ld, rows=rows, drop_col_div=drop_col_div, bias_row_scale=bias_row_scale, bias_z_stride=bias_z_stride, split=split)
+    M, N, K = a.M, a.N, a.K
     esz = 4 if a.w_dtype == F32 else 2
     kind = "linear_" + ("f32" if a.w_dtype == F32 else ("bf16" if a.a_dtype == BF16 else "f32in_bf16"))
     if _timer is not None and kind == "linear_bf16":          # timed runs label the launch with the kernel it dispatches to
@@ -264,6 +288,28 @@ def batch_order(mask: Tensor, out: Optional[Tensor] = None) -> Tensor:
     return out
 
 
+def linear_splitk_args(A: Tensor, W: Tensor, ws: Tensor, split_k: int, *, A2: Optional[Tensor] = None, a2_row_mod: int = 0,
+                       split: bool = False, launchable: bool = True) -> MadeLinearArgs:
+    """the MadeLinearArgs of linear_splitk's made_linear launch (nothing launched; launchable as in linear_args)"""
+    ptr = _p if launchable else _host_ptr
+    assert A.dim() == 2 and W.dim() == 2 and A.stride(1) == 1 and W.stride(1) == 1
+    M, K = A.shape
+    N = W.shape[0]
+    assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= split_k * M * N
+    a = MadeLinearArgs()
+    a.A, a.a_dtype, a.w_dtype, a.lda = ptr(A), dt_of(A), dt_of(W), A.stride(0)
+    use_a2 = A2 is not None
+    if use_a2:
+        a.A2, a.lda2, a.a2_row_mod = ptr(A2), A2.stride(0), a2_row_mod
+    a.W, a.ldw = ptr(W), W.stride(0)
+    a.M, a.N, a.K = M, N, K
+    a.batch, a.f32_products = 1, 1 if split else 0
+    a.nseg, a.split_k, a.split_ws = 1, max(split_k, 2), ptr(ws)
+    sg = a.seg[0]
+    sg.col_begin, sg.out, sg.out_dtype, sg.ldo, sg.use_a2 = 0, ptr(ws), F32, N, 1 if use_a2 else 0
+    return a
+
+
 def linear_splitk(A: Tensor, W: Tensor, bias: Optional[Tensor], ws: Tensor, split_k: int, *, A2: Optional[Tensor] = None,
                   a2_row_mod: int = 0, act: int = ACT_NONE, R: Optional[Tensor] = None, r_row_mod: int = 0,
                   out: Optional[Tensor] = None, ln1=None, ln1_out: Optional[Tensor] = None, ln2=None,
@@ -271,21 +317,8 @@ def linear_splitk(A: Tensor, W: Tensor, bias: Optional[Tensor], ws: Tensor, spli
     """Skinny Linear (few rows, e.g. the decoder's B*Q): K is split over grid.z so the launch fills the chip, the raw f32
     partials land in `ws` ([>= split_k*M*N] f32) and made_splitk_finish sums them and applies bias / act / residual, then
     optionally LayerNorm (ln1 = (gamma, beta)) and a second LayerNorm on top (ln2).  split: as in linear."""
-    assert A.dim() == 2 and W.dim() == 2 and A.stride(1) == 1 and W.stride(1) == 1
-    M, K = A.shape
-    N = W.shape[0]
-    assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= split_k * M * N
-    a = MadeLinearArgs()
-    a.A, a.a_dtype, a.w_dtype, a.lda = _p(A), dt_of(A), dt_of(W), A.stride(0)
-    use_a2 = A2 is not None
-    if use_a2:
-        a.A2, a.lda2, a.a2_row_mod = _p(A2), A2.stride(0), a2_row_mod
-    a.W, a.ldw = _p(W), W.stride(0)
-    a.M, a.N, a.K = M, N, K
-    a.batch, a.f32_products = 1, 1 if split else 0
-    a.nseg, a.split_k, a.split_ws = 1, max(split_k, 2), _p(ws)
-    sg = a.seg[0]
-    sg.col_begin, sg.out, sg.out_dtype, sg.ldo, sg.use_a2 = 0, _p(ws), F32, N, 1 if use_a2 else 0
+    a = linear_splitk_args(A, W, ws, split_k, A2=A2, a2_row_mod=a2_row_mod, split=split)
+    M, N, K = a.M, a.N, a.K
     esz = 4 if a.w_dtype == F32 else 2
     _timed("linear_splitk_f32" if a.w_dtype == F32 else "linear_kernel<bf16,bf16>", 2.0 * M * N * K, M * K * esz + N * K * esz + M * N * 4 * a.split_k,
            lambda: check(lib().made_linear(C.byref(a), _stream()), "made_linear(split_k)"), f"M={M} N={N} K={K} split={a.split_k}")

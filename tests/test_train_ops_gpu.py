@@ -546,7 +546,7 @@ def test_set_criterion_bwd(T, Q, G):
         assert float((got.cpu() - ref).abs().max()) <= 2e-5 * max(float(ref.abs().max()), 1e-3), name
 
 
-@pytest.mark.parametrize("Bn,N", [(9, 384), (60, 640), (200, 1280)])     # skinny / 64-row-tile / 128-row-tile kernels in bf16
+@pytest.mark.parametrize("Bn,N", [(9, 384), (60, 640), (200, 1280)])     # bf16: linear_tiny_kernel (64 x 32 tiles) / linear_glds_kernel<1,.,64> / <1,.,128>, gathered or not
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_row_gather_linear_and_gemm_tn_bit_identical_on_valid_rows(T, dtype, Bn, N):
     """rows=(row_index, n_rows): the GEMMs touch the valid tokens only; their results equal the ungathered call bit for bit,
