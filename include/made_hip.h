@@ -1502,6 +1502,68 @@ int made_tempo_autocorr(const float* env, int64_t env_ld, const int32_t* n_frame
 int made_beat_track(const float* env, int64_t env_ld, const int32_t* n_frames, const int32_t* period, const float* scale, int64_t N,
                     float alpha, int64_t cap, float* time, int32_t* count, float* cum, int32_t* back, void* stream);
 
+/* ---- Cuts (mgsv_amd/cuts.py; csrc/cuts.hip) -------------------------------------------------------------------------------------
+ * Where a video's shots change, from its decoded frames: the list made_sync_moments takes as cut_start / cut_time.  A video is F
+ * frames of one size H x W, RGB uint8 interleaved [H, W, 3]; P = H * W, 1 <= P <= 2^24; videos of mixed sizes may share a call.
+ * Everything below is integer arithmetic, every division an integer floor division: no order of additions can change a bit.
+ * The reference has no counterpart.
+ *
+ * Signature (made_frame_hist).  For the pixel at row r, column c of frame f:
+ *   1. luma Y = (77 R + 150 G + 29 B + 128) >> 8                       (0 .. 255);
+ *   2. bin b = Y >> 2                                                  (64 bins);
+ *   3. cell = 4 * (4 r / H) + (4 c / W)                                (a 4 x 4 grid; cells are empty when H or W is below 4).
+ * hist[f, cell, b] (uint32 [n_frames, 16, 64]) counts the pixels of frame f with that cell and bin; a frame's counts sum to P.
+ *
+ * Distance (made_hist_distance).  D[0] = 0; D[f] = sum over cell, b of |hist[f] - hist[f - 1]| (uint32), so 0 <= D[f] <= 2 P; a
+ * frame whose first_of_video flag is set (the first frame of every video, wherever it sits in the batch) has D = 0.
+ *
+ * Pick (made_cut_peaks).  Frame f of video v (F = n_frames[v] frames, D = its row) is a cut iff, in int64 arithmetic,
+ *   1. D[f] >= thr[v] and D[f] > 0 (thr a per-video device uint32: the host's ceil(threshold * 2 P));
+ *   2. D[f] > D[g] for g in [f - w_max, f) and D[f] >= D[g] for g in (f, f + w_max], the windows clipped to [0, F): of equal
+ *      neighbours the earlier wins;
+ *   3. 256 * D[f] * n >= ratio_q8 * S, S the sum of D over [f - w_avg, f + w_avg] clipped to [1, F) without f itself and n the
+ *      number of frames in it (D[0] is 0 by definition, not a measurement: it is left out); with n == 0 the test passes.  This
+ *      rejects sustained motion and shake, where every distance is large -- and a real cut inside such a stretch.
+ * ------------------------------------------------------------------------------------------------------------------------------- */
+
+/* One frame of made_frame_hist's packed input. */
+typedef struct MadeCutFrameDesc {
+    int64_t offset;        /* byte offset of the frame's first pixel in `frames` (RGB, 3 bytes per pixel, rows of 3 W bytes, no gaps) */
+    int32_t H, W;          /* rows and columns */
+} MadeCutFrameDesc;
+
+/* made_frame_hist: the signatures of n_frames frames.  frames: device bytes, frames_len of them; desc [n_frames] device array;
+ * hist [n_frames, 16, 64] uint32, every word of which is written (zeroed by an asynchronous memset on the stream, then counted
+ * into) and nothing beyond.  A frame is one contiguous byte range; a workgroup takes chunks of 16 384 consecutive pixels, a lane
+ * 16 pixels (48 bytes) at a time: three 16-byte loads when the frame's first byte is 16-byte aligned, twelve dword loads when it
+ * is 4-byte aligned, byte loads otherwise and for the frame's last partial step -- all fill the same twelve words, so the counts
+ * do not depend on the path; nothing outside [offset, offset + 3 P) is read.  (r, c) comes from one division per lane and step,
+ * then an increment with wrap (with W >= 64 the 16 pixels change their cell once at most, which is looked up once).  A lane merges
+ * runs of equal (cell, bin) among its 16 pixels into one add of the run's length, to the wave's own 1024-word LDS histogram (folding
+ * the lanes of a wave that share a target bought nothing on top of that and was taken out).  The workgroups of a frame (ceil(mean P /
+ * 16 384) each, from frames_len / n_frames: the host cannot see the descriptors) add their non-zero counts into hist with integer
+ * global atomics.  A descriptor with H or W < 1, P > 2^24, offset < 0 or offset + 3 P > frames_len leaves a zero signature and
+ * reads nothing.  n_frames == 0 is a no-op.  Refused: negative sizes, n_frames >= 2^21, frames_len < 3, null pointers. */
+int made_frame_hist(const uint8_t* frames, int64_t frames_len, const MadeCutFrameDesc* desc, int64_t n_frames, uint32_t* hist,
+                    void* stream);
+
+/* made_hist_distance: D [n_frames] uint32 of hist [n_frames, 16, 64] uint32 (16-byte aligned) by the rule above; first_of_video
+ * [n_frames] device uint8, non-zero forces D = 0 (frame 0 needs no flag).  One wave per frame: four 16-byte loads of either
+ * signature per lane, an integer DPP sum.  No LDS, no atomics.  n_frames == 0 is a no-op.  Refused: a negative n_frames or one
+ * >= 2^31, null pointers, a hist that is not 16-byte aligned. */
+int made_hist_distance(const uint32_t* hist, const uint8_t* first_of_video, int64_t n_frames, uint32_t* D, void* stream);
+
+/* made_cut_peaks: the cuts of N videos from their distances D [N, D_ld] uint32 by the rule above; n_frames [N] device int32, thr
+ * [N] device uint32.  count[v] int32 = the number of cuts; frame[v * cap + i] int32, i < count[v] = the cut frames ascending;
+ * strength[v * cap + i] uint32 = D[frame].  Entries from count[v] on are not written.  Rule 2 keeps two cuts w_max + 1 frames
+ * apart, so cap >= ceil(D_ld / (w_max + 1)) never overflows (a smaller cap is refused).  One workgroup per video walks tiles of
+ * 1024 frames with a 128-frame halo in LDS; the compaction is ordered (ballot, prefix popcount, a running offset): no atomics, no
+ * workspace, and a video's list does not depend on the other videos.  A video with n_frames[v] > D_ld (or < 0) gets count -1 and
+ * no entries.  w_max in [1, 64], w_avg in [1, 128], ratio_q8 in [0, 65535]; N == 0 is a no-op.  Refused: those ranges, negative
+ * sizes, N or D_ld >= 2^31, null pointers (D may be NULL when D_ld == 0, frame and strength when cap == 0). */
+int made_cut_peaks(const uint32_t* D, int64_t D_ld, const int32_t* n_frames, int64_t N, const uint32_t* thr, int32_t w_max,
+                   int32_t w_avg, int32_t ratio_q8, int64_t cap, int32_t* frame, uint32_t* strength, int32_t* count, void* stream);
+
 /* ==========================================================================================
  * Batches from a device-resident feature store (mgsv_amd/feature_store.py DeviceFeatureStore): a split's features stay on the
  * device in their storage format and every batch of the training / evaluation loop is assembled by one launch.  The reference

@@ -218,6 +218,10 @@ class MadeAudioSegDesc(C.Structure):
     _fields_ = [("first", i64), ("count", i64)]
 
 
+class MadeCutFrameDesc(C.Structure):
+    _fields_ = [("offset", i64), ("H", i32), ("W", i32)]
+
+
 GATHER_MAX_ARRAYS = 8
 GATHER_F32, GATHER_BF16, GATHER_U8 = 0, 1, 2
 
@@ -347,6 +351,9 @@ SIGNATURES = {
     "made_onset_peaks": (C.c_int, [vp, i64, vp, i64, i32, i32, f32, i64, vp, vp, vp]),
     "made_tempo_autocorr": (C.c_int, [vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
     "made_beat_track": (C.c_int, [vp, i64, vp, vp, vp, i64, f32, i64, vp, vp, vp, vp, vp]),
+    "made_frame_hist": (C.c_int, [vp, i64, vp, i64, vp, vp]),
+    "made_hist_distance": (C.c_int, [vp, vp, i64, vp, vp]),
+    "made_cut_peaks": (C.c_int, [vp, i64, vp, i64, vp, i32, i32, i32, i64, vp, vp, vp, vp]),
     "made_fit_moments": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp, vp]),
     "made_sync_moments": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i64, i64, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
 }

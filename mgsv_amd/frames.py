@@ -395,3 +395,24 @@ def decode_frame(path: str) -> np.ndarray:
 def load_video_frames(frame_dir: str, video_start: float, video_end: float, max_v_frames: int) -> List[np.ndarray]:
     """The frames of one video the reference's loader selects, decoded: a list of uint8 [H, W, 3] arrays."""
     return [decode_frame(p) for p in frame_paths(frame_dir, video_start, video_end, max_v_frames)]
+
+
+def load_frame_sequence(frame_dir: str, first: int = 0, last: Optional[int] = None) -> np.ndarray:
+    """The frames `{first}.jpg` .. `{last}.jpg` of a directory in NUMERIC order (10.jpg after 2.jpg), decoded by `decode_frame`:
+    uint8 [F, H, W, 3], what `cuts.detect_cuts` takes for one video (`ffmpeg -vf fps=...` into a directory writes such files).
+    last = None: up to the largest number present.  A missing number or a frame of another size is an error."""
+    numbers = sorted(int(n[:-4]) for n in os.listdir(frame_dir) if n.endswith(".jpg") and n[:-4].isdigit())
+    first = int(first)
+    if last is None:
+        last = numbers[-1] if numbers else first - 1
+    want = list(range(first, int(last) + 1))
+    missing = sorted(set(want) - set(numbers))
+    if missing:
+        raise RuntimeError(f"{frame_dir}: {missing[0]}.jpg is missing")
+    frames = []
+    for i in want:
+        fr = decode_frame(os.path.join(frame_dir, f"{i}.jpg"))
+        if frames and fr.shape != frames[0].shape:
+            raise ValueError(f"{frame_dir}: {i}.jpg is {fr.shape[0]} x {fr.shape[1]}, the frames before it {frames[0].shape[0]} x {frames[0].shape[1]}")
+        frames.append(fr)
+    return np.stack(frames) if frames else np.zeros((0, 1, 1, 3), np.uint8)

@@ -1299,6 +1299,68 @@ def onset_peaks(env: Tensor, n_frames: Tensor, w_max: int = 5, w_avg: int = 50, 
     return time, count
 
 
+CUT_CELLS, CUT_BINS = 16, 64             # made_frame_hist's signature: a 64-bin luma histogram in each cell of a 4 x 4 grid
+CUT_MAX_PIXELS = 1 << 24                 # H * W of a frame made_frame_hist takes
+
+
+def frame_hist(frames: Tensor, desc: Tensor, hist: Optional[Tensor] = None) -> Tensor:
+    """made_frame_hist: hist [n, 16, 64] uint32 (held as int32: the same bits, counts stay below 2^31), the signatures of the n
+    frames of `desc` -- per cell of a 4 x 4 grid the 64-bin histogram of the luma (77 R + 150 G + 29 B + 128) >> 8.  frames: uint8
+    bytes holding every frame (any shape, contiguous); desc: uint8 [n, 16] or int64 [n, 2] device rows laid out as MadeCutFrameDesc.
+    A descriptor that does not fit `frames` or whose size is out of range leaves a zero signature.  hist: a contiguous int32 tensor
+    of n * 1024 words to write into (default: a new one)."""
+    assert frames.dtype == torch.uint8 and frames.is_contiguous()
+    assert desc.is_contiguous() and desc.numel() * desc.element_size() % C.sizeof(_lib.MadeCutFrameDesc) == 0
+    n = desc.numel() * desc.element_size() // C.sizeof(_lib.MadeCutFrameDesc)
+    if hist is None:
+        hist = torch.empty(n, CUT_CELLS, CUT_BINS, device=frames.device, dtype=torch.int32)
+    assert hist.dtype == torch.int32 and hist.is_contiguous() and hist.numel() == n * CUT_CELLS * CUT_BINS
+    check(lib().made_frame_hist(_p(frames) if frames.numel() else None, frames.numel(), _p(desc) if n else None, n,
+                                _p(hist) if n else None, _stream()), "made_frame_hist")
+    return hist
+
+
+def hist_distance(hist: Tensor, first_of_video: Tensor, D: Optional[Tensor] = None) -> Tensor:
+    """made_hist_distance: D [n] uint32 (held as int32), D[f] = sum |hist[f] - hist[f - 1]| over the 1024 words of the signatures
+    hist [n, 16, 64] int32 (contiguous); D[0] = 0 and D[f] = 0 wherever first_of_video [n] uint8 is non-zero."""
+    assert hist.dtype == torch.int32 and hist.is_contiguous() and hist.numel() % (CUT_CELLS * CUT_BINS) == 0
+    n = hist.numel() // (CUT_CELLS * CUT_BINS)
+    assert first_of_video.dtype == torch.uint8 and first_of_video.is_contiguous() and first_of_video.numel() == n
+    if D is None:
+        D = torch.empty(n, device=hist.device, dtype=torch.int32)
+    assert D.dtype == torch.int32 and D.is_contiguous() and D.numel() == n
+    check(lib().made_hist_distance(_p(hist) if n else None, _p(first_of_video) if n else None, n, _p(D) if n else None, _stream()),
+          "made_hist_distance")
+    return D
+
+
+def cut_peaks(D: Tensor, n_frames: Tensor, thr: Tensor, w_max: int = 8, w_avg: int = 32, ratio_q8: int = 768, frame: Optional[Tensor] = None,
+              strength: Optional[Tensor] = None, count: Optional[Tensor] = None):
+    """made_cut_peaks: (frame [N, cap] int32, strength [N, cap] int32 holding uint32 bits, count [N] int32) of the distances D
+    [N, D_ld] int32 (uint32 bits, contiguous): the frames f < n_frames[v] with D[f] > 0, D[f] >= thr[v] (int32 [N], uint32 bits), a
+    local maximum over w_max frames either side (the earlier of equal values) and 256 D[f] n >= ratio_q8 S, S the sum and n the
+    number of the other frames within w_avg of f, frame 0 left out; ascending.  Only [v, :count[v]] is written.  frame / strength /
+    count: tensors to write into (default: new ones, cap = ceil(D_ld / (w_max + 1)), which cannot overflow)."""
+    assert D.dim() == 2 and D.dtype == torch.int32 and D.is_contiguous()
+    N, D_ld = D.shape
+    for t in (n_frames, thr):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == N
+    w = max(int(w_max), 1)
+    if frame is None:
+        frame = torch.empty(N, (D_ld + w) // (w + 1), device=D.device, dtype=torch.int32)
+    if strength is None:
+        strength = torch.empty(N, frame.shape[1], device=D.device, dtype=torch.int32)
+    if count is None:
+        count = torch.empty(N, device=D.device, dtype=torch.int32)
+    for t in (frame, strength):
+        assert t.dim() == 2 and t.shape[0] == N and t.shape[1] == frame.shape[1] and t.dtype == torch.int32 and t.is_contiguous()
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() == N
+    check(lib().made_cut_peaks(_p(D) if D.numel() else None, D_ld, _p(n_frames), N, _p(thr), int(w_max), int(w_avg), int(ratio_q8),
+                               frame.shape[1], _p(frame) if frame.numel() else None, _p(strength) if strength.numel() else None,
+                               _p(count), _stream()), "made_cut_peaks")
+    return frame, strength, count
+
+
 BEAT_MAX_LAG = 256                       # the longest period made_tempo_autocorr and made_beat_track take, frames of 10 ms
 
 
