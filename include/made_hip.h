@@ -1502,6 +1502,67 @@ int made_tempo_autocorr(const float* env, int64_t env_ld, const int32_t* n_frame
 int made_beat_track(const float* env, int64_t env_ld, const int32_t* n_frames, const int32_t* period, const float* scale, int64_t N,
                     float alpha, int64_t cap, float* time, int32_t* count, float* cum, int32_t* back, void* stream);
 
+/* ---- Bar grids (mgsv_amd/bars.py; csrc/bars.hip) --------------------------------------------------------------------------------
+ * The metre, the phase and the downbeats of a track, from its log-mel spectrogram and its beat list.  A downbeat list is again "a
+ * CSR of ascending times per track": made_fit_moments and made_sync_moments take it where they take the onsets or the beats.
+ *
+ * made_beat_sync_mean: the mean spectrum of every beat's interval.  spec [N, spec_ld, 128] f32 (made_audio_fbank's rows, one track
+ * after the other), n_frames [N] device int32, time [N, cap] f32 and count [N] int32 as made_beat_track writes them (any ascending
+ * list will do), beat_start [N + 1] device int64 the exclusive prefix of the counts; output B [total_beats, 128] f32, track t's
+ * beat k in row beat_start[t] + k.  Per track with n = count[t], nf = n_frames[t]:
+ *   1. b_k = (int)(time_k * 100.0f + 0.5f), two rounded operations, kept inside [0, nf] (a NaN or negative time gives 0, a frame
+ *      >= nf gives nf).  For every f < 2^20 this inverts made_beat_track's (float)f * 0.01f exactly.
+ *   2. The interval of beat k is [b_k, e_k): e_k = b_{k+1} for k < n - 1; e_{n-1} = b_{n-1} + (b_{n-1} - b_{n-2}) for n >= 2 and
+ *      b_0 + 1 for n == 1, clipped to nf.  Its length is L = e_k - b_k.
+ *   3. B[k, m] = (the f32 sum of spec[f, m] over b_k <= f < e_k) / (float)L; a row of +0 when L <= 0 (an empty interval, or a list
+ *      that does not ascend).
+ * Summation order (f32; it depends on L alone, not on N, k, cap or the track's place in the batch): a bin has 8 chains, chain c
+ * adding the frames b_k + c, b_k + c + 8, ... ascending from +0 (ceil((L - c) / 8) terms), and the chains meet in the tree
+ * ((c0 + c2) + (c4 + c6)) + ((c1 + c3) + (c5 + c7)).  A value passes through at most ceil(L / 8) + 2 rounded additions (the first
+ * term of a chain is added to +0, which is exact) and the division: depth = ceil(L / 8) + 3, and |B - exact| <= depth * 2^-24 *
+ * sum|x| / L to first order.
+ * A track with count <= 0 or count > cap, nf outside [0, spec_ld], or beat_start[t + 1] - beat_start[t] != count[t] (or rows
+ * outside [0, total_beats)) writes nothing.  A wave takes a beat: lanes own four bins with one 16-byte load per frame, the two
+ * halves of the wave the even and the odd frames, four loads in flight per lane; an interval of any length is walked by its one
+ * wave.  The spectrogram is read once; no atomics, no workspace, no scratch.  N == 0 is a no-op.  Refused: negative sizes, spec_ld
+ * >= 2^20 (step 1), N or total_beats >= 2^31, null pointers (spec may be NULL when spec_ld == 0, time when cap == 0, B when
+ * total_beats == 0). */
+int made_beat_sync_mean(const float* spec, int64_t spec_ld, const int32_t* n_frames, const float* time, int64_t cap, const int32_t* count,
+                        const int64_t* beat_start, int64_t N, int64_t total_beats, float* B, void* stream);
+
+/* made_bar_pick: metre, phase and downbeats of N tracks.  B, beat_start, time / cap as above (track t has n = beat_start[t + 1] -
+ * beat_start[t] beats); metre_mask: bit m set for every metre m that is tried, a non-empty set of integers in [2, 8] passed by
+ * value; low_bins in [0, 128], low_weight f32 >= 0, min_bars >= 1, min_strength f32 >= 0.  Outputs evidence [total_beats] f32,
+ * metre / phase [N] int32, strength [N] f32, down_time [N, cap_d] f32, down_count [N] int32.  Every step below is one rounded f32
+ * operation unless it says otherwise (no contraction).  Per track:
+ *   1. e[0] = 0; for k >= 1, e[k] = (1/128) * sum_m w_m * max(0, B[k, m] - B[k-1, m]), w_m = 1.f + low_weight for m < low_bins and
+ *      1 otherwise (a NaN difference adds 0): the energy that arrives at beat k against the beat before it.  The 128 terms meet as
+ *      t[l] + t[l + 64] for l = 0 .. 63, then in a tree of depth 6 over l (pairs l ^ 1, l ^ 2, rotations by 4 and 8 inside each 16,
+ *      then the four sixteens), then the exact product with 2^-7: a term passes through a subtraction, a product and 7 additions
+ *      (with w_m's own rounding: depth 10).
+ *   2. tot = e[1] + e[2] + ... + e[n - 1], one chain, ascending, from +0.  mean_all = tot / (float)(n - 1).
+ *   3. For every metre m of the set and every phase phi in [0, m): the members are the beats k >= 1 with k % m == phi, cnt their
+ *      number, s their sum (one chain, ascending, from +0); score = s / (float)cnt - mean_all.  (m, phi) is a candidate iff cnt >=
+ *      min_bars and the score is not NaN.
+ *   4. The pick is the candidate with the largest score, of equal scores the smaller m, then the smaller phi.  strength = score /
+ *      mean_all.
+ *   5. No metre -- metre = 0, phase = -1, strength = NaN, down_count = 0 -- when n < 2, when there is no candidate, when mean_all is
+ *      not > 0, or when strength < min_strength or is NaN.
+ *   6. Otherwise metre = m, phase = phi, and the downbeats are the beats phi, phi + m, ... < n (beat 0 when phi == 0), written
+ *      ascending with the beats' own f32 times to down_time[t * cap_d + i]; down_count = their number, or -1 (and no time written)
+ *      when it exceeds cap_d.  Entries from down_count on are not written.
+ * A track whose list does not fit its arrays (n < 0, n > cap, rows outside [0, total_beats)) gets metre 0, phase -1, strength NaN,
+ * down_count -1 and no evidence.  One workgroup of sixteen waves per track: waves take the beats of step 1 and keep e in LDS for
+ * n <= 4096 (a longer track reads it back from `evidence` after a fence and a barrier); one thread per chain walks steps 2 - 3 (at
+ * most 36 chains); one thread walks the candidates in (m, phi) order with a strict >, so the pick does not depend on any
+ * reduction's shape.  No atomics, no workspace, no scratch.  N == 0 is a no-op.  Refused: negative sizes, a metre_mask that is 0
+ * or has a bit outside 2 .. 8, low_bins outside [0, 128], low_weight or min_strength negative or not finite, min_bars < 1, cap_d <
+ * ceil(cap / 2) (every second beat may be a downbeat), N or total_beats >= 2^31, null pointers (B and evidence may be NULL when
+ * total_beats == 0, time when cap == 0, down_time when cap_d == 0). */
+int made_bar_pick(const float* B, const int64_t* beat_start, const float* time, int64_t cap, int64_t N, int64_t total_beats,
+                  int32_t metre_mask, int32_t low_bins, float low_weight, int32_t min_bars, float min_strength, float* evidence,
+                  int32_t* metre, int32_t* phase, float* strength, float* down_time, int64_t cap_d, int32_t* down_count, void* stream);
+
 /* ---- Cuts (mgsv_amd/cuts.py; csrc/cuts.hip) -------------------------------------------------------------------------------------
  * Where a video's shots change, from its decoded frames: the list made_sync_moments takes as cut_start / cut_time.  A video is F
  * frames of one size H x W, RGB uint8 interleaved [H, W, 3]; P = H * W, 1 <= P <= 2^24; videos of mixed sizes may share a call.

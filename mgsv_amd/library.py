@@ -17,6 +17,10 @@ without them loads as a library without onsets.
 Optional beat grids for `ground_library(..., fit=Fit(snap=..., grid="beats"))` (mgsv_amd/beats.py): beat_start.npy int64 [n_tracks + 1]
 and beat_time.npy f32, the tracks' beats as a CSR, beat_tempo.npy f32 [n_tracks] (BPM, NaN: no tempo), and the manifest's "beats"
 entry holding the detection parameters; a directory without them loads as a library without beats.
+Optional bar grids for `ground_library(..., fit=Fit(snap=..., grid="downbeats"))` (mgsv_amd/bars.py): bar_start.npy int64 [n_tracks
++ 1] and bar_time.npy f32, the tracks' downbeats as a CSR, bar_metre.npy int32 [n_tracks] (0: no metre), bar_phase.npy int32 and
+bar_strength.npy f32, and the manifest's "bars" entry holding the detection parameters; a directory without them loads as a library
+without bars.
 
 FP8 token storage (dtype "fp8"): tokens.npy is uint8 [N, S, D], one OCP e4m3fn byte per value, and tokens_exp.npy int8 [N, S] holds
 one power-of-two exponent per token row (the format: include/made_hip.h, csrc/fp8_format.h); the manifest says "dtype": "fp8" and
@@ -198,7 +202,7 @@ class MusicLibrary:
 
     def __init__(self, tokens, mask, vec, col_group, source, dtype: str, duration=None, windows: Optional[Windows] = None,
                  ids: Optional[Sequence] = None, group_id=None, tags=None, length=None, tag_names: Optional[Sequence[str]] = None,
-                 tokens_exp=None, compute: Optional[str] = None, onsets=None, beats=None):
+                 tokens_exp=None, compute: Optional[str] = None, onsets=None, beats=None, bars=None):
         if dtype not in ("f32", "bf16", "fp8"):
             raise ValueError(f"dtype = {dtype!r}: a library holds f32, bf16 or fp8 tokens")
         self.tokens, self.mask, self.vec, self.duration = tokens, mask, vec, duration
@@ -250,6 +254,8 @@ class MusicLibrary:
         self.set_onsets(onsets)
         self.beats = None
         self.set_beats(beats)
+        self.bars = None
+        self.set_bars(bars)
         self._device_attrs: Dict[str, tuple] = {}                  # ground_library's column attributes, uploaded once per device
         self._plans: Dict[int, dict] = {}
         self._stages: Dict[str, object] = {}                       # ground_library's pinned staging sets, reused across calls
@@ -305,6 +311,13 @@ class MusicLibrary:
             raise ValueError(f"beats needs one entry per track ({self.n_tracks}), got {len(beats)}")
         self.beats = beats
 
+    def set_bars(self, bars) -> None:
+        """Attach (or with None remove) the tracks' bar grids, an `mgsv_amd.bars.Bars` with one entry per track in this library's
+        numbering (`ids`' order)."""
+        if bars is not None and len(bars) != self.n_tracks:
+            raise ValueError(f"bars needs one entry per track ({self.n_tracks}), got {len(bars)}")
+        self.bars = bars
+
     def fit_length(self, max_m_duration: float) -> np.ndarray:
         """f32 [tracks]: the length `ground_library` clamps a track's moments to, and `fit_grounding` fits them in: min(max_m_duration,
         duration) per column without windows, the end of the track's last window with them (computed once)."""
@@ -350,12 +363,14 @@ class MusicLibrary:
     # ------------------------------------------------------------------ construction
     @classmethod
     def build(cls, music: Encoded, group_id=None, windows: Optional[Windows] = None, ids: Optional[Sequence] = None, tags=None,
-              length=None, tag_names: Optional[Sequence[str]] = None, onsets=None, beats=None) -> "MusicLibrary":
+              length=None, tag_names: Optional[Sequence[str]] = None, onsets=None, beats=None,
+              bars=None) -> "MusicLibrary":
         """A host library of an `Encoded` (device or host tensors).  group_id: one entry per column, or per TRACK with windows.
         Columns are reordered only if a group's columns are not contiguous: groups by first appearance, stable inside a group.
         The Windows keep their track numbering; only the per-column arrays are permuted (and `ids`, one per column, without
         windows).  tags (int64) / length (f32 seconds): one entry per track, permuted like `ids`.  onsets: an `Onsets` table
-        (mgsv_amd/onsets.py), one entry per track, permuted like `ids`, too; beats: a `Beats` (mgsv_amd/beats.py), likewise."""
+        (mgsv_amd/onsets.py), one entry per track, permuted like `ids`, too; beats: a `Beats` (mgsv_amd/beats.py), likewise; bars: a `Bars`
+        (mgsv_amd/bars.py), likewise."""
         N = len(music)
         gid = None if group_id is None else _host(group_id, np.int32).reshape(-1)
         if windows is not None:
@@ -392,6 +407,10 @@ class MusicLibrary:
             raise ValueError("beats needs one entry per track")
         if windows is None and beats is not None and not same:
             beats = beats.take(order)
+        if bars is not None and len(bars) != (windows.n_tracks if windows is not None else N):
+            raise ValueError("bars needs one entry per track")
+        if windows is None and bars is not None and not same:
+            bars = bars.take(order)
         if windows is None:
             if ids is not None and not same:
                 ids = [ids[i] for i in order]
@@ -400,7 +419,7 @@ class MusicLibrary:
             length = None if length is None else take(length)
         return cls(take(_tokens_to_host(music.tokens)), take(_host(music.mask, np.float32)), take(_host(music.vec, np.float32)),
                    take(col_group), order, _dtype_name(music.tokens.dtype), duration=dur, windows=win, ids=ids, group_id=gid,
-                   tags=tags, length=length, tag_names=tag_names, onsets=onsets, beats=beats)
+                   tags=tags, length=length, tag_names=tag_names, onsets=onsets, beats=beats, bars=bars)
 
     def to(self, device) -> "MusicLibrary":
         """The same library with tokens / mask / vec / duration as tensors on `device` (the host tables stay on the host)."""
@@ -411,7 +430,7 @@ class MusicLibrary:
                             duration=None if self.duration is None else up(self.duration), windows=self.windows, ids=self.ids,
                             group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
                             tokens_exp=None if self.tokens_exp is None else up(self.tokens_exp), compute=self._compute_arg,
-                            onsets=self.onsets, beats=self.beats)
+                            onsets=self.onsets, beats=self.beats, bars=self.bars)
 
     def pin(self) -> "MusicLibrary":
         """The same library with tokens / mask / vec / duration copied into pinned host tensors: `ground_library` uploads its
@@ -422,7 +441,7 @@ class MusicLibrary:
                             duration=None if self.duration is None else pin(self.duration), windows=self.windows, ids=self.ids,
                             group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
                             tokens_exp=None if self.tokens_exp is None else pin(self.tokens_exp), compute=self._compute_arg,
-                            onsets=self.onsets, beats=self.beats)
+                            onsets=self.onsets, beats=self.beats, bars=self.bars)
 
     @property
     def pinned(self) -> bool:
@@ -448,7 +467,7 @@ class MusicLibrary:
         """this library with other tokens"""
         return MusicLibrary(tokens, self.mask, self.vec, self.col_group, self.source, dtype, duration=self.duration, windows=self.windows,
                             ids=self.ids, group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
-                            tokens_exp=tokens_exp, onsets=self.onsets, beats=self.beats)
+                            tokens_exp=tokens_exp, onsets=self.onsets, beats=self.beats, bars=self.bars)
 
     def quantize(self, device=None) -> "MusicLibrary":
         """The FP8 library of a bf16 library: the same arrays with the tokens as e4m3fn bytes and one power-of-two exponent per
@@ -519,7 +538,7 @@ class MusicLibrary:
         _write_tables(path, self.windows, self.group_id, self.ids)
         _write_manifest(path, self.dtype, len(self), self.S, self.D, self.duration is not None, self.windows, self.ids is not None,
                         self.group_id is not None, _write_attributes(path, self.tags, self.length, self.tag_names), self._compute_arg,
-                        write_onsets(path, self.onsets), write_beats(path, self.beats))
+                        write_onsets(path, self.onsets), write_beats(path, self.beats), write_bars(path, self.bars))
 
     @classmethod
     def load(cls, path: str, mmap: bool = True) -> "MusicLibrary":
@@ -559,7 +578,7 @@ class MusicLibrary:
                    tags=np.load(os.path.join(path, "tags.npy")) if attr.get("tags") else None,
                    length=np.load(os.path.join(path, "length.npy")) if attr.get("length") else None, tag_names=attr.get("tag_names"),
                    tokens_exp=tokens_exp, compute=man.get("compute") if man["dtype"] == "fp8" else None, onsets=_read_onsets(path, man),
-                   beats=_read_beats(path, man))
+                   beats=_read_beats(path, man), bars=_read_bars(path, man))
 
     # ------------------------------------------------------------------ the chunk plan
     def chunk_plan(self, chunk_cols: int) -> List[Tuple[int, int]]:
@@ -717,9 +736,39 @@ def _read_beats(path: str, man: dict):
     return Beats(Onsets(np.load(files[0]), np.load(files[1]), dict(params)), np.load(files[2]), params)
 
 
+BAR_FILES = ("bar_start.npy", "bar_time.npy", "bar_metre.npy", "bar_phase.npy", "bar_strength.npy")
+
+
+def write_bars(path: str, bars) -> Optional[dict]:
+    """bar_start.npy / bar_time.npy / bar_metre.npy / bar_phase.npy / bar_strength.npy and the manifest's "bars" entry, the detection
+    parameters (None, and no files, for a library without bars)"""
+    if bars is None:
+        for name in BAR_FILES:                                     # (a table an earlier save left here is not this library's)
+            if os.path.isfile(os.path.join(path, name)):
+                os.remove(os.path.join(path, name))
+        return None
+    np.save(os.path.join(path, "bar_start.npy"), np.ascontiguousarray(bars.table.start, dtype=np.int64))
+    np.save(os.path.join(path, "bar_time.npy"), np.ascontiguousarray(bars.table.time, dtype=np.float32))
+    np.save(os.path.join(path, "bar_metre.npy"), np.ascontiguousarray(bars.metre, dtype=np.int32))
+    np.save(os.path.join(path, "bar_phase.npy"), np.ascontiguousarray(bars.phase, dtype=np.int32))
+    np.save(os.path.join(path, "bar_strength.npy"), np.ascontiguousarray(bars.strength, dtype=np.float32))
+    return dict(bars.params)
+
+
+def _read_bars(path: str, man: dict):
+    """the stored bar grids, None when the directory has none"""
+    files = [os.path.join(path, name) for name in BAR_FILES]
+    if not all(os.path.isfile(f) for f in files):
+        return None
+    from .bars import Bars
+    from .onsets import Onsets
+    params = dict(man.get("bars") or {})
+    return Bars(Onsets(np.load(files[0]), np.load(files[1]), dict(params)), np.load(files[2]), np.load(files[3]), np.load(files[4]), params)
+
+
 def _write_manifest(path: str, dtype: str, N: int, S: int, D: int, duration: bool, windows: Optional[Windows], ids: bool,
                     grouped: bool, attributes: Optional[dict] = None, compute: Optional[str] = None, onsets: Optional[dict] = None,
-                    beats: Optional[dict] = None) -> None:
+                    beats: Optional[dict] = None, bars: Optional[dict] = None) -> None:
     man = dict(format=FORMAT, version=VERSION, dtype=dtype, N=int(N), S=int(S), D=int(D), duration=bool(duration),
                windows=windows is not None, ids=bool(ids), grouped=bool(grouped),
                n_tracks=int(windows.n_tracks) if windows is not None else None)
@@ -731,6 +780,8 @@ def _write_manifest(path: str, dtype: str, N: int, S: int, D: int, duration: boo
         man["onsets"] = onsets
     if beats is not None:                                          # the detection parameters of beat_start.npy / beat_time.npy / beat_tempo.npy
         man["beats"] = beats
+    if bars is not None:                                           # the detection parameters of bar_start.npy ... bar_strength.npy
+        man["bars"] = bars
     with open(os.path.join(path, "manifest.json"), "w") as f:
         json.dump(man, f, indent=1)
         f.write("\n")

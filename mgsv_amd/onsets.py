@@ -122,11 +122,12 @@ def track_spectrogram(pcm16: torch.Tensor, n16: Sequence[int], tables=None):
     return spec.view(n, n_blocks * music.ROWS, music.MELS), torch.tensor(frames, dtype=torch.int32, device=dev)
 
 
-def _envelopes(tracks: Sequence, dev, max_seconds: Optional[float], lag: int, timed: bool):
+def _envelopes(tracks: Sequence, dev, max_seconds: Optional[float], lag: int, timed: bool, with_spec: bool = False):
     """The front end `detect_onsets` and mgsv_amd/beats.py share: the tracks in groups of consecutive tracks whose spectrogram holds
     at most SPEC_BUDGET floats (one track alone may exceed it); per group one resample launch, made_audio_fbank over the blocks and
     made_onset_strength.  Yields (env [n, env_ld] f32, frames [n] int32, ev) per group: ev is None or, timed, the four events
-    recorded before, between and after the three phases -- the consumer appends its own with `_mark`."""
+    recorded before, between and after the three phases -- the consumer appends its own with `_mark`.  with_spec (mgsv_amd/bars.py):
+    (env, frames, ev, spec) instead, spec [n, spec_ld, 128] f32 the group's spectrogram that env was computed from."""
     chans = [music._channel0(w) for w, _ in tracks]
     n16 = [music.resampled_length(int(c.shape[0]), sr) for c, (_, sr) in zip(chans, tracks)]
     if max_seconds is not None:
@@ -152,7 +153,7 @@ def _envelopes(tracks: Sequence, dev, max_seconds: Optional[float], lag: int, ti
         _mark(ev)
         env = ops.onset_strength(spec, frames, lag)
         _mark(ev)
-        yield env, frames, ev
+        yield (env, frames, ev, spec) if with_spec else (env, frames, ev)
         t0 = t1
 
 

@@ -1414,6 +1414,155 @@ def beat_track(env: Tensor, n_frames: Tensor, period: Tensor, scale: Tensor, alp
     return time, count, cum, back
 
 
+BAR_METRES = (2, 3, 4)                   # the metres made_bar_pick tries by default; any distinct integers in [2, 8]
+BAR_MAX_FRAMES = 1 << 20                 # spec_ld made_beat_sync_mean takes: a beat's frame is recovered from its f32 time
+
+
+def beat_sync_mean(spec: Tensor, n_frames: Tensor, time: Tensor, count: Tensor, beat_start: Tensor, total_beats: Optional[int] = None,
+                   B: Optional[Tensor] = None) -> Tensor:
+    """made_beat_sync_mean: B [total_beats, 128] f32, the mean of spec [N, spec_ld, 128] f32 (contiguous, as `track_spectrogram`
+    returns it) over every beat's interval of frames -- from the beat's frame (int)(time * 100 + 0.5) to the next beat's, the last
+    one as long as the one before it (one frame for a single beat), clipped to n_frames[t]; an empty interval gives a row of zeros.
+    time [N, cap] f32 / count [N] int32: the beat lists as `beat_track` writes them (any ascending list); beat_start [N + 1] int64
+    on the device: the exclusive prefix of the counts, so that B is packed.  A track with count <= 0, with n_frames outside [0,
+    spec_ld] or whose count is not beat_start's writes nothing.  total_beats: the rows of B (default: read from beat_start[-1],
+    which synchronises); B: a contiguous [total_beats, 128] f32 tensor to write into."""
+    assert spec.dim() == 3 and spec.shape[2] == 128 and spec.dtype == torch.float32 and spec.is_contiguous()
+    N, spec_ld = spec.shape[0], spec.shape[1]
+    assert time.dim() == 2 and time.shape[0] == N and time.dtype == torch.float32 and time.is_contiguous()
+    for t, n in ((n_frames, N), (count, N)):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n and t.device == spec.device
+    assert beat_start.dtype == torch.int64 and beat_start.is_contiguous() and beat_start.numel() == N + 1 and beat_start.device == spec.device
+    if B is None:
+        total_beats = int(beat_start[-1]) if total_beats is None else int(total_beats)
+        B = torch.empty(max(total_beats, 0), 128, device=spec.device, dtype=torch.float32)
+    assert B.dim() == 2 and B.shape[1] == 128 and B.dtype == torch.float32 and B.is_contiguous()
+    check(lib().made_beat_sync_mean(_p(spec) if spec.numel() else None, spec_ld, _p(n_frames), _p(time) if time.numel() else None, time.shape[1],
+                                    _p(count), _p(beat_start), N, B.shape[0], _p(B) if B.numel() else None, _stream()), "made_beat_sync_mean")
+    return B
+
+
+def _bar_params(metres, low_bins, low_weight, min_bars, min_strength):
+    """(metres tuple ascending, mask, low_bins, low_weight, min_bars, min_strength), checked"""
+    try:
+        ms = [int(m) for m in metres]
+        exact = all(float(m) == int(m) for m in metres)
+    except (TypeError, ValueError):
+        raise ValueError(f"metres = {metres!r}: a sequence of integers in [2, 8]")
+    if not ms or not exact or len(set(ms)) != len(ms) or min(ms) < 2 or max(ms) > 8:
+        raise ValueError(f"metres = {metres!r}: a non-empty sequence of distinct integers in [2, 8]")
+    low_bins, min_bars, low_weight, min_strength = int(low_bins), int(min_bars), float(low_weight), float(min_strength)
+    if not 0 <= low_bins <= 128:
+        raise ValueError(f"low_bins = {low_bins}: must lie in [0, 128]")
+    if not (math.isfinite(low_weight) and low_weight >= 0):
+        raise ValueError(f"low_weight = {low_weight}: must be finite and >= 0")
+    if min_bars < 1:
+        raise ValueError(f"min_bars = {min_bars}: must be >= 1")
+    if not (math.isfinite(min_strength) and min_strength >= 0):
+        raise ValueError(f"min_strength = {min_strength}: must be finite and >= 0")
+    ms = tuple(sorted(ms))
+    return ms, sum(1 << m for m in ms), low_bins, low_weight, min_bars, min_strength
+
+
+def bar_pick_host(evidence, beat_start, time, metres=BAR_METRES, min_bars: int = 4, min_strength: float = 0.0, cap_d: Optional[int] = None):
+    """Steps 2 - 6 of made_bar_pick restated in numpy float32 on a given `evidence` [total_beats] (include/made_hip.h states the
+    contract): the same bits as the kernel.  beat_start int64 [N + 1], time f32 [N, cap] -> (metre, phase int32 [N], strength f32
+    [N], down_time f32 [N, cap_d] (NaN past a track's downbeats: the kernel leaves those entries unwritten), down_count int32 [N])."""
+    import numpy as np
+    f32 = np.float32
+    ms, _, _, _, min_bars, min_strength = _bar_params(metres, 0, 0.0, min_bars, min_strength)
+    ev = np.ascontiguousarray(evidence, dtype=f32).reshape(-1)
+    start = np.ascontiguousarray(beat_start, dtype=np.int64).reshape(-1)
+    time = np.ascontiguousarray(time, dtype=f32)
+    assert time.ndim == 2 and len(start) == time.shape[0] + 1
+    N, cap = time.shape
+    cap_d = (cap + 1) // 2 if cap_d is None else int(cap_d)
+    if cap_d < (cap + 1) // 2:
+        raise ValueError(f"cap_d = {cap_d}: must be >= ceil(cap / 2) = {(cap + 1) // 2}")
+    metre, phase, count = np.zeros(N, np.int32), np.full(N, -1, np.int32), np.zeros(N, np.int32)
+    strength, down = np.full(N, np.nan, f32), np.full((N, cap_d), np.nan, f32)
+    chain = lambda a: np.add.accumulate(np.concatenate([np.zeros(1, f32), a]), dtype=f32)[-1]      # one f32 chain, ascending, from +0
+    for t in range(N):
+        r0, r1 = int(start[t]), int(start[t + 1])
+        n = r1 - r0
+        if r0 < 0 or n < 0 or r1 > len(ev) or n > cap:
+            count[t] = -1
+            continue
+        if n < 2:
+            continue
+        e = ev[r0:r1]
+        with np.errstate(all="ignore"):
+            mean_all = chain(e[1:]) / f32(n - 1)
+            best, bm, bphi = f32(0), 0, -1
+            for m in ms:
+                for phi in range(m):
+                    members = e[(m if phi == 0 else phi)::m]
+                    if len(members) < min_bars:
+                        continue
+                    score = f32(chain(members) / f32(len(members)) - mean_all)
+                    if np.isnan(score):
+                        continue
+                    if bm == 0 or score > best:
+                        best, bm, bphi = score, m, phi
+            if bm == 0:
+                continue
+            st = f32(best / mean_all)
+            if not mean_all > 0 or not st >= f32(min_strength):
+                continue
+        metre[t], phase[t], strength[t] = bm, bphi, st
+        beats = np.arange(bphi, n, bm)
+        if len(beats) > cap_d:
+            count[t] = -1
+            continue
+        count[t] = len(beats)
+        down[t, :len(beats)] = time[t, beats]
+    return metre, phase, strength, down, count
+
+
+def bar_pick(B, beat_start, time, metres=BAR_METRES, low_bins: int = 16, low_weight: float = 1.0, min_bars: int = 4, min_strength: float = 0.0,
+             cap_d: Optional[int] = None, backend: Optional[str] = None, evidence=None, down_time: Optional[Tensor] = None):
+    """made_bar_pick: the metre, the phase and the downbeats of N tracks from their beat-synchronous spectra B [total_beats, 128]
+    f32 (`beat_sync_mean`), beat_start [N + 1] int64 and the beat times time [N, cap] f32 -> (evidence [total_beats] f32, metre,
+    phase int32 [N], strength f32 [N], down_time [N, cap_d] f32, down_count int32 [N]).  evidence[k] is the weighted mean over the
+    bins of the positive part of B[k] - B[k - 1] (the bins below low_bins weigh 1 + low_weight), 0 at a track's first beat; every
+    (metre, phase) is scored by the mean evidence of its beats minus the mean of all, the largest score wins (of equal scores the
+    smaller metre, then the smaller phase), strength = score / mean.  A track without a metre (fewer than two beats, no phase with
+    min_bars members, no evidence, strength < min_strength) has metre 0, phase -1, strength NaN and no downbeats.  Only
+    down_time[t, :down_count[t]] is written; cap_d defaults to ceil(cap / 2), which cannot overflow.  The defaults are a starting
+    value that nobody has tuned on real music.  backend None: device tensors in and out, one launch.  backend "host": steps 2 - 6 on
+    a given `evidence` (B is not read and may be None) by `bar_pick_host`, arrays or host tensors in, numpy arrays out -- the same
+    bits, on any machine.  evidence / down_time: device tensors to write into (default: new ones; down_time's second size is then cap_d)."""
+    if backend == "host":
+        if evidence is None:
+            raise ValueError("backend='host' restates the pick on a given evidence (evidence=...)")
+        host = lambda a: a.detach().cpu().numpy() if isinstance(a, Tensor) else a
+        return (host(evidence),) + bar_pick_host(host(evidence), host(beat_start), host(time), metres, min_bars, min_strength, cap_d)
+    if backend is not None:
+        raise ValueError(f"backend = {backend!r}: None (the device) or 'host'")
+    _, mask, low_bins, low_weight, min_bars, min_strength = _bar_params(metres, low_bins, low_weight, min_bars, min_strength)
+    assert B.dim() == 2 and B.shape[1] == 128 and B.dtype == torch.float32 and B.is_contiguous()
+    assert time.dim() == 2 and time.dtype == torch.float32 and time.is_contiguous() and time.device == B.device
+    N, cap = time.shape
+    assert beat_start.dtype == torch.int64 and beat_start.is_contiguous() and beat_start.numel() == N + 1 and beat_start.device == B.device
+    total = B.shape[0]
+    if down_time is not None:
+        assert down_time.dim() == 2 and down_time.shape[0] == N and down_time.dtype == torch.float32 and down_time.is_contiguous()
+        cap_d = down_time.shape[1]
+    cap_d = (cap + 1) // 2 if cap_d is None else int(cap_d)
+    dev = B.device
+    if evidence is None:
+        evidence = torch.empty(total, device=dev, dtype=torch.float32)
+    assert evidence.dtype == torch.float32 and evidence.is_contiguous() and evidence.numel() == total and evidence.device == dev
+    metre, phase, down_count = (torch.empty(N, device=dev, dtype=torch.int32) for _ in range(3))
+    strength = torch.empty(N, device=dev, dtype=torch.float32)
+    if down_time is None:
+        down_time = torch.empty(N, max(cap_d, 0), device=dev, dtype=torch.float32)
+    check(lib().made_bar_pick(_p(B) if total else None, _p(beat_start), _p(time) if time.numel() else None, cap, N, total, mask, low_bins,
+                              low_weight, min_bars, min_strength, _p(evidence) if total else None, _p(metre), _p(phase), _p(strength),
+                              _p(down_time) if down_time.numel() else None, cap_d, _p(down_count), _stream()), "made_bar_pick")
+    return evidence, metre, phase, strength, down_time, down_count
+
+
 def fit_moments_host(start, end, track, want, tlen, onset_start=None, onset_time=None, tol: float = 0.0):
     """made_fit_moments restated in numpy float32, one rounded operation per step (include/made_hip.h states the contract): the
     same bits as the kernel.  Arrays of E entries -> (out_start, out_end, shift f32 [E], onset int32 [E])."""
