@@ -767,7 +767,10 @@ int made_attention_bwd(const MadeAttnBwdArgs* args, void* stream);
  * backward (batched).  Batch index z = z1 * batch2 + z2 with independent element strides per level (a C stride of 0 sums
  * the batch into one C).  split_m > 1 splits the reduction over workgroups; partial tiles are combined with f32 atomic
  * adds, so it requires accumulate = 1 and an f32 C that the caller has initialised (gradients are zeroed once per step).
- * Rows whose row_mask is 0 are read as zero in BOTH operands (padded tokens may hold stale data). */
+ * Rows whose row_mask is 0 are read as zero in BOTH operands (padded tokens may hold stale data).
+ * M == 0 adds nothing and stores nothing (C is not cleared, whatever `accumulate` says), and so does an EMPTY ROW LIST (*n_rows == 0),
+ * in every kernel of made_gemm_tn and made_gemm_tn_grouped: callers zero gradients once per step.  (A row mask that is zero
+ * everywhere is a reduction over M rows of zeros: a plain store then writes zeros.) */
 typedef struct MadeGemmTNArgs {
     const void* A; const void* B; void* C;
     int32_t ab_dtype; int32_t c_dtype;             /* MadeDtype; C is f32 or the operand dtype */
@@ -787,6 +790,19 @@ typedef struct MadeGemmTNArgs {
 } MadeGemmTNArgs;
 
 int made_gemm_tn(const MadeGemmTNArgs* args, void* stream);
+
+/* Which kernel made_gemm_tn dispatches these arguments to, or the (negative) MadeStatus with which made_gemm_tn would refuse them.
+ * Nothing is launched and no pointer is dereferenced (the pointers' alignment is looked at), so the question can be asked without a GPU.
+ * M == 0, which launches nothing, reports the tiled kernel of its dtype. */
+enum MadeGemmTNVariant {
+    MADE_GEMM_TN_SMALL = 0,        /* gemm_tn_small_kernel: one thread per C element; operands that 16-byte chunks cannot address */
+    MADE_GEMM_TN_TILED_BF16 = 1,   /* gemm_tn_kernel<bf16>: 128 x 128 tiles, register-staged slabs of 64 rows, every option */
+    MADE_GEMM_TN_TILED_F32 = 2,    /* gemm_tn_kernel<float>: slabs of 32 rows, exact f32 products */
+    MADE_GEMM_TN_TILED_F32X3 = 3,  /* gemm_tn_kernel<float, X3>: the same with split-bf16 products (f32_products = 1) */
+    MADE_GEMM_TN_GLDS = 4          /* gemm_tn_glds_kernel: bf16, N and K multiples of 128, unbatched, M >= 256, no row mask (or a row list),
+                                      at most 4096 rows per workgroup: slabs go global -> LDS directly */
+};
+int made_gemm_tn_variant(const MadeGemmTNArgs* args);
 
 /* made_gemm_tn_grouped: up to 8 weight gradients that reduce over the same rows -- the Linears of one transformer layer
  * (reference music_detr/transformer.py:191-210, model/model_Base.py:64-91: dW_i += alpha * dY_i^T X_i, db_i += alpha * colsum(dY_i)) --

@@ -313,6 +313,7 @@ SIGNATURES = {
     "made_recall_ranks": (C.c_int, [vp, i64, vp, vp, i64, i64, i64, vp, vp, vp]),
     "made_span_iou": (C.c_int, [vp, vp, vp, vp, i64, i64, i32, f32, vp, vp, vp]),
     "made_gemm_tn": (C.c_int, [C.POINTER(MadeGemmTNArgs), vp]),
+    "made_gemm_tn_variant": (C.c_int, [C.POINTER(MadeGemmTNArgs)]),
     "made_gemm_tn_grouped": (C.c_int, [C.POINTER(MadeGemmTNGroup), vp]),
     "made_gemm_tn_grouped_workspace": (i64, [C.POINTER(MadeGemmTNGroup)]),
     "made_concat_cols": (C.c_int, [vp, i64, vp, i64, vp, i64, vp]),

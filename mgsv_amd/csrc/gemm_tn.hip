@@ -258,11 +258,13 @@ __global__ __launch_bounds__(256) void gemm_tn_small_kernel(const MadeGemmTNArgs
     const int64_t n = active ? e / a.K : 0, k = active ? e % a.K : 0;
     int64_t Mv = a.M;
     if (a.n_rows) { const int64_t nv = *a.n_rows; Mv = nv < a.M ? nv : a.M; }
+    if (Mv <= 0) return;                                  // an empty row list adds nothing and stores nothing, as M == 0 (include/made_hip.h)
     const int64_t per = (Mv + gridDim.y - 1) / gridDim.y;
     const int64_t m0 = (int64_t)blockIdx.y * per, m1 = m0 + per < Mv ? m0 + per : Mv;
     const float* maskg = a.row_mask ? a.row_mask + z1 * a.mask_zs1 + z2 * a.mask_zs2 : nullptr;
     const int64_t ao = z1 * a.a_zs1 + z2 * a.a_zs2, bo = z1 * a.b_zs1 + z2 * a.b_zs2;
-    float acc = 0.f, cs = 0.f;
+    float acc = 0.f;
+    double cs = 0.0;                                        // (a serial f32 sum of the rows measured 2 - 7 x the error of a pairwise one: docs/EXPERIMENTS.md 3o)
     for (int64_t ml = m0; ml < m1; ++ml) {
         const int64_t m = a.row_index ? (int64_t)a.row_index[ml] : ml;
         if (maskg && maskg[m] == 0.f) continue;
@@ -277,16 +279,17 @@ __global__ __launch_bounds__(256) void gemm_tn_small_kernel(const MadeGemmTNArgs
     } else {
         ((bf16_t*)a.C)[co] = (bf16_t)(acc * a.alpha);
     }
-    if (a.colsum && k == 0) unsafeAtomicAdd(a.colsum + z1 * a.colsum_zs1 + z2 * a.colsum_zs2 + n, cs * a.alpha);
+    if (a.colsum && k == 0) unsafeAtomicAdd(a.colsum + z1 * a.colsum_zs1 + z2 * a.colsum_zs2 + n, (float)cs * a.alpha);
 }
 
 }  // namespace
 
-int made_gemm_tn_fast(const MadeGemmTNArgs& a, hipStream_t st);      // gemm_tn_glds.hip
+bool made_gemm_tn_fast_applies(const MadeGemmTNArgs& a);             // gemm_tn_glds.hip
+int made_gemm_tn_fast(const MadeGemmTNArgs& a, hipStream_t st);
 
-extern "C" int made_gemm_tn(const MadeGemmTNArgs* args, void* stream) {
-    MADE_REQUIRE(args != nullptr, "made_gemm_tn: null args");
-    MadeGemmTNArgs a = *args;
+// which kernel made_gemm_tn runs for these arguments, or why it refuses them (one place: the launcher and made_gemm_tn_variant both ask
+// here); `a` leaves with its defaults filled in (batch, split_m) and the flags a row list overrides dropped.  Nothing is dereferenced.
+static int pick_variant(MadeGemmTNArgs& a) {
     MADE_REQUIRE(a.A && a.B && a.C, "made_gemm_tn: null tensor");
     MADE_REQUIRE(a.M >= 0 && a.N > 0 && a.K > 0, "made_gemm_tn: bad dims");
     MADE_REQUIRE(a.ab_dtype == MADE_F32 || a.ab_dtype == MADE_BF16, "made_gemm_tn: bad operand dtype %d", a.ab_dtype);
@@ -303,8 +306,8 @@ extern "C" int made_gemm_tn(const MadeGemmTNArgs* args, void* stream) {
     MADE_REQUIRE((a.row_index == nullptr) == (a.n_rows == nullptr), "made_gemm_tn: row_index and n_rows come together");
     MADE_UNSUPPORTED(a.row_index == nullptr || nz == 1, "made_gemm_tn: row gather is for unbatched calls");
     if (a.row_index) a.row_group_valid = nullptr;
-    if (a.M == 0) return MADE_OK;                                   /* nothing to add (C is not cleared: callers zero gradients) */
-    hipStream_t st = (hipStream_t)stream;
+    // (M == 0 launches nothing and is accepted whatever the strides: the code is the tiled kernel's)
+    if (a.M == 0) return a.ab_dtype == MADE_BF16 ? MADE_GEMM_TN_TILED_BF16 : (a.f32_products ? MADE_GEMM_TN_TILED_F32X3 : MADE_GEMM_TN_TILED_F32);
     const int per16 = a.ab_dtype == MADE_F32 ? 4 : 8;
     const int64_t n_up = (a.N + per16 - 1) / per16 * per16, k_up = (a.K + per16 - 1) / per16 * per16;
     const bool aligned = a.lda % per16 == 0 && a.ldb % per16 == 0 && n_up <= a.lda && k_up <= a.ldb &&
@@ -312,21 +315,41 @@ extern "C" int made_gemm_tn(const MadeGemmTNArgs* args, void* stream) {
                          ((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.B % 16) == 0;
     if (!aligned) {
         MADE_UNSUPPORTED(a.N * a.K <= (1 << 20), "made_gemm_tn: unaligned operands are only supported for small outputs");
+        return MADE_GEMM_TN_SMALL;
+    }
+    const int64_t tiles = ((a.N + TBN - 1) / TBN) * ((a.K + TBK - 1) / TBK);
+    MADE_UNSUPPORTED(tiles < (1LL << 31), "made_gemm_tn: too many tiles");
+    if (made_gemm_tn_fast_applies(a)) return MADE_GEMM_TN_GLDS;      // direct-to-LDS two-stage kernel when the shapes allow
+    if (a.ab_dtype == MADE_BF16) return MADE_GEMM_TN_TILED_BF16;
+    return a.f32_products ? MADE_GEMM_TN_TILED_F32X3 : MADE_GEMM_TN_TILED_F32;
+}
+
+extern "C" int made_gemm_tn_variant(const MadeGemmTNArgs* args) {
+    MADE_REQUIRE(args != nullptr, "made_gemm_tn: null args");
+    MadeGemmTNArgs a = *args;
+    return pick_variant(a);
+}
+
+extern "C" int made_gemm_tn(const MadeGemmTNArgs* args, void* stream) {
+    MADE_REQUIRE(args != nullptr, "made_gemm_tn: null args");
+    MadeGemmTNArgs a = *args;
+    const int variant = pick_variant(a);
+    if (variant < 0) return variant;
+    if (a.M == 0) return MADE_OK;                                   /* nothing to add (C is not cleared: callers zero gradients) */
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nz = a.batch1 * a.batch2;
+    if (variant == MADE_GEMM_TN_SMALL) {
         int sy = (int)a.split_m;
         if (!a.accumulate) sy = 1;
         dim3 grid((unsigned)((a.N * a.K + 255) / 256), (unsigned)sy, (unsigned)nz);
         hipLaunchKernelGGL(gemm_tn_small_kernel, grid, dim3(256), 0, st, a);
         return made_check_launch("made_gemm_tn(small)");
     }
+    if (variant == MADE_GEMM_TN_GLDS) return made_gemm_tn_fast(a, st);
     const int64_t tiles = ((a.N + TBN - 1) / TBN) * ((a.K + TBK - 1) / TBK);
-    MADE_UNSUPPORTED(tiles < (1LL << 31), "made_gemm_tn: too many tiles");
-    {
-        const int rc = made_gemm_tn_fast(a, st);                     // direct-to-LDS 3-stage kernel when the shapes allow
-        if (rc != 1) return rc;
-    }
     dim3 grid((unsigned)tiles, (unsigned)a.split_m, (unsigned)nz);
-    if (a.ab_dtype == MADE_BF16) hipLaunchKernelGGL(gemm_tn_kernel<bf16_t>, grid, dim3(TNT), 0, st, a);
-    else if (a.f32_products) hipLaunchKernelGGL((gemm_tn_kernel<float, true>), grid, dim3(TNT), 0, st, a);
+    if (variant == MADE_GEMM_TN_TILED_BF16) hipLaunchKernelGGL(gemm_tn_kernel<bf16_t>, grid, dim3(TNT), 0, st, a);
+    else if (variant == MADE_GEMM_TN_TILED_F32X3) hipLaunchKernelGGL((gemm_tn_kernel<float, true>), grid, dim3(TNT), 0, st, a);
     else hipLaunchKernelGGL(gemm_tn_kernel<float>, grid, dim3(TNT), 0, st, a);
     return made_check_launch("made_gemm_tn");
 }

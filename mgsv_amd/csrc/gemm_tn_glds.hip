@@ -700,13 +700,17 @@ extern "C" int made_gemm_tn_grouped(const MadeGemmTNGroup* group, void* stream) 
 }
 
 
-// called by made_gemm_tn after validation; returns MADE_ERR_UNSUPPORTED-like sentinel 1 when the fast path does not apply
+// whether the direct-to-LDS kernel serves these (validated, defaults filled in) arguments: asked by made_gemm_tn's one dispatch function
+bool made_gemm_tn_fast_applies(const MadeGemmTNArgs& a) {
+    return a.ab_dtype == MADE_BF16 && a.N % GT_BN == 0 && a.K % GT_BK == 0 && a.lda % 8 == 0 && a.ldb % 8 == 0 &&
+           a.batch1 * a.batch2 == 1 && (a.row_mask == nullptr || a.row_index != nullptr) &&
+           ((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.B % 16) == 0 && a.M >= 4 * GT_BM &&
+           ((a.M + GT_BM - 1) / GT_BM + a.split_m - 1) / a.split_m * GT_BM <= GT_MAX_ROWS;
+}
+
+// called by made_gemm_tn for the arguments made_gemm_tn_fast_applies accepted
 int made_gemm_tn_fast(const MadeGemmTNArgs& a, hipStream_t st) {
-    const bool ok = a.ab_dtype == MADE_BF16 && a.N % GT_BN == 0 && a.K % GT_BK == 0 && a.lda % 8 == 0 && a.ldb % 8 == 0 &&
-                    a.batch1 * a.batch2 == 1 && (a.row_mask == nullptr || a.row_index != nullptr) &&
-                    ((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.B % 16) == 0 && a.M >= 4 * GT_BM &&
-                    ((a.M + GT_BM - 1) / GT_BM + a.split_m - 1) / a.split_m * GT_BM <= GT_MAX_ROWS;
-    if (!ok) return 1;
+    MADE_REQUIRE(made_gemm_tn_fast_applies(a), "made_gemm_tn(glds): arguments the direct-to-LDS kernel does not serve");
     const int64_t tiles = (a.N / GT_BN) * (a.K / GT_BK);
     dim3 grid((unsigned)(a.split_m >= 8 ? 8 * tiles * ((a.split_m + 7) / 8) : tiles * a.split_m), 1, 1);
     static const bool once = hipFuncSetAttribute((const void*)gemm_tn_glds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GT_LDS) == hipSuccess;

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib, tape as _tape
 from ._lib import BF16, F32, MadeAttnBwdArgs, MadeDropout, MadeGemmTNArgs, MadeGemmTNGroup, check, lib
-from .ops import _f32, _p, _stream, _timed, dt_of, set_drop
+from .ops import _f32, _host_ptr, _p, _stream, _timed, dt_of, set_drop
 
 Tensor = torch.Tensor
 Pair = Tuple[int, int]
@@ -48,14 +48,24 @@ def _tn_splits(tiles: int, nslab: int, gathered: bool, cap: int) -> int:
     return best
 
 
-def gemm_tn(A: Tensor, B: Tensor, Cout: Tensor, *, alpha: float = 1.0, accumulate: bool = False, split_m: Optional[int] = None,
-            row_mask: Optional[Tensor] = None, row_groups: Optional[Tensor] = None, rows=None, colsum: Optional[Tensor] = None,
-            batch: Pair = (1, 1),
-            a_zs: Pair = (0, 0), b_zs: Pair = (0, 0), c_zs: Pair = (0, 0), mask_zs: Pair = (0, 0),
-            colsum_zs: Pair = (0, 0), split: bool = False) -> Tensor:
-    """Cout[N,K] (+)= alpha * A[M,N]^T B[M,K]  (made_gemm_tn).  A, B, Cout are the 2-D views of batch element 0; the
-    *_zs pairs are the element strides of the two batch levels.  colsum[N] += alpha * column sums of A.
-    split: f32 products as three bf16 products on split operands (MadeGemmTNArgs.f32_products; no effect on bf16 operands)."""
+# made_gemm_tn_variant codes (include/made_hip.h: MadeGemmTNVariant) -> kernel symbols
+GEMM_TN_VARIANTS = {0: "gemm_tn_small_kernel", 1: "gemm_tn_kernel<bf16>", 2: "gemm_tn_kernel<float>", 3: "gemm_tn_kernel<float,X3>",
+                    4: "gemm_tn_glds_kernel"}
+
+# None, or a list: every gemm_tn / gemm_tn_grouped call appends the form of the call it launches -- gemm_tn: (kernel symbol of
+# made_gemm_tn_variant on ITS arguments, split_m); gemm_tn_grouped: ("grouped128" | "grouped256_atomic" | "grouped256_ws", split_m, grid)
+GEMM_TN_LOG = None
+
+
+def gemm_tn_args(A: Tensor, B: Tensor, Cout: Tensor, *, alpha: float = 1.0, accumulate: bool = False, split_m: Optional[int] = None,
+                 row_mask: Optional[Tensor] = None, row_groups: Optional[Tensor] = None, rows=None, colsum: Optional[Tensor] = None,
+                 batch: Pair = (1, 1),
+                 a_zs: Pair = (0, 0), b_zs: Pair = (0, 0), c_zs: Pair = (0, 0), mask_zs: Pair = (0, 0),
+                 colsum_zs: Pair = (0, 0), split: bool = False, launchable: bool = True) -> MadeGemmTNArgs:
+    """the MadeGemmTNArgs of a gemm_tn() call: every field filled, nothing launched (gemm_tn() calls this, then made_gemm_tn).
+    launchable=False takes tensors of any device, for a made_gemm_tn_variant question asked without a GPU; such arguments are never
+    handed to made_gemm_tn."""
+    ptr = _p if launchable else _host_ptr
     M, N = A.shape
     K = B.shape[1]
     assert B.shape[0] == M and tuple(Cout.shape) == (N, K), (A.shape, B.shape, Cout.shape)
@@ -74,7 +84,7 @@ def gemm_tn(A: Tensor, B: Tensor, Cout: Tensor, *, alpha: float = 1.0, accumulat
                 # (at least eight slabs per split: fewer do not pay for a tile of atomic adds -- one slab per split until round 6: 4.70 against 4.72 ms)
                 split_m = max(1, min(512 // max(tiles, 1), ((M + slab - 1) // slab) // 8, 256))
     a = MadeGemmTNArgs()
-    a.A, a.B, a.C = _p(A), _p(B), _p(Cout)
+    a.A, a.B, a.C = ptr(A), ptr(B), ptr(Cout)
     a.ab_dtype, a.c_dtype = dt_of(A), dt_of(Cout)
     a.M, a.N, a.K = M, N, K
     a.lda, a.ldb, a.ldc = A.stride(0), B.stride(0), Cout.stride(0)
@@ -82,15 +92,26 @@ def gemm_tn(A: Tensor, B: Tensor, Cout: Tensor, *, alpha: float = 1.0, accumulat
     a.a_zs1, a.a_zs2 = a_zs
     a.b_zs1, a.b_zs2 = b_zs
     a.c_zs1, a.c_zs2 = c_zs
-    a.row_mask = _p(_f32(row_mask, "row_mask"))
-    a.row_group_valid = _p(_f32(row_groups, "row_groups")) if (row_mask is not None and nz == 1) else None
+    a.row_mask = ptr(_f32(row_mask, "row_mask"))
+    a.row_group_valid = ptr(_f32(row_groups, "row_groups")) if (row_mask is not None and nz == 1) else None
     if rows is not None and nz == 1:                          # (row_index int32 [M], n_rows int32 [1]) from ops.row_index
-        a.row_index, a.n_rows = _p(rows[0]), _p(rows[1])
+        a.row_index, a.n_rows = ptr(rows[0]), ptr(rows[1])
     a.mask_zs1, a.mask_zs2 = mask_zs
     a.alpha, a.accumulate, a.split_m = float(alpha), int(bool(accumulate)), int(split_m)
     a.f32_products = 1 if split else 0
-    a.colsum = _p(_f32(colsum, "colsum"))
+    a.colsum = ptr(_f32(colsum, "colsum"))
     a.colsum_zs1, a.colsum_zs2 = colsum_zs
+    return a
+
+
+def gemm_tn(A: Tensor, B: Tensor, Cout: Tensor, *, rows=None, batch: Pair = (1, 1), **kw) -> Tensor:
+    """Cout[N,K] (+)= alpha * A[M,N]^T B[M,K]  (made_gemm_tn; the keywords are gemm_tn_args').  A, B, Cout are the 2-D views of batch
+    element 0; the *_zs pairs are the element strides of the two batch levels.  colsum[N] += alpha * column sums of A.
+    split: f32 products as three bf16 products on split operands (MadeGemmTNArgs.f32_products; no effect on bf16 operands)."""
+    a = gemm_tn_args(A, B, Cout, rows=rows, batch=batch, **kw)
+    M, N, K, nz = a.M, a.N, a.K, batch[0] * batch[1]
+    if GEMM_TN_LOG is not None:
+        GEMM_TN_LOG.append((GEMM_TN_VARIANTS.get(lib().made_gemm_tn_variant(C.byref(a)), "?"), int(a.split_m)))
     flops = 2.0 * M * N * K * nz
     nbytes = float((M * N + M * K) * A.element_size() * nz + N * K * Cout.element_size())
     _timed("made_gemm_tn", flops, nbytes, lambda: check(lib().made_gemm_tn(C.byref(a), _stream()), "made_gemm_tn"),
@@ -103,12 +124,20 @@ def gemm_tn_grouped_workspace(device, nbytes: int) -> Tensor:
     return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
 
 
-def gemm_tn_grouped(problems, rows=None, alpha: float = 1.0, split_m: Optional[int] = None, workspace=None) -> None:
+def _tn256_grid(tiles256: int, M: int) -> int:
+    """workgroups of the 256 x 256-tile form (csrc/gemm_tn_glds.hip t2_shape): 8 XCDs x the (tile, slab) units of an XCD, at most 32 each"""
+    return 8 * min(32, max(1, (((M + 63) // 64 + 7) // 8) * tiles256))
+
+
+def gemm_tn_grouped(problems, rows=None, alpha: float = 1.0, split_m: Optional[int] = None, workspace=None,
+                    tile_size: Optional[int] = None) -> None:
     """Several weight gradients over the same rows in one launch (made_gemm_tn_grouped).  problems: list of (dY [M, N], X [M, K],
     dW [N, K] f32, db [N] f32 or None); bf16 operands, N and K multiples of 128.  rows = (row_index, n_rows) or None.
     workspace: a callable nbytes -> uint8 tensor (gemm_tn_grouped_workspace; the caller keeps one per stream) -- with it the 256 x 256-tile
-    form exchanges the tile partials through it instead of adding them to dW with atomics (include/made_hip.h: MadeGemmTNGroup.workspace)."""
-    assert 1 <= len(problems) <= 8
+    form exchanges the tile partials through it instead of adding them to dW with atomics (include/made_hip.h: MadeGemmTNGroup.workspace).
+    tile_size: None -- 256 x 256 tiles where every N and K is a multiple of 256 and 4096 <= M <= 36864, 128 x 128 otherwise; 128 or 256 --
+    that form, for any M the library accepts (the parity suite's way to the 256-tile kernel's small-M dealing; the trainer does not pass it)."""
+    assert 1 <= len(problems) <= 8 and tile_size in (None, 128, 256)
     M = problems[0][0].shape[0]
     g = MadeGemmTNGroup()
     g.n_problems, g.alpha, g.M = len(problems), float(alpha), M
@@ -126,11 +155,16 @@ def gemm_tn_grouped(problems, rows=None, alpha: float = 1.0, split_m: Optional[i
         nbytes += float(M * (N + K) * 2 + N * K * 4)
     if rows is not None:
         g.row_index, g.n_rows = _p(rows[0]), _p(rows[1])
-    big = (all(pr[0].shape[1] % 256 == 0 and pr[1].shape[1] % 256 == 0 for pr in problems) and 4096 <= M <= 36864
-           and _lib.variant_env("MADE_TN_TILE", "256") == "256")
+    if tile_size is None:
+        big = (all(pr[0].shape[1] % 256 == 0 and pr[1].shape[1] % 256 == 0 for pr in problems) and 4096 <= M <= 36864
+               and _lib.variant_env("MADE_TN_TILE", "256") == "256")
+    else:
+        big = tile_size == 256
+    form = "grouped128"
     if big:
         # 256 x 256 tiles, one eight-wave workgroup per CU, the (tile, slab) units dealt out evenly by the kernel itself
         g.tile_size = 256
+        form = "grouped256_atomic"
         if split_m is None:
             split_m = 1
         # the tile partials meet in a workspace instead of being added to the gradients with atomics (MADE_TN256_ATOMIC_FLUSH=1, measurement knob: the atomics)
@@ -141,9 +175,13 @@ def gemm_tn_grouped(problems, rows=None, alpha: float = 1.0, split_m: Optional[i
                 assert ws.dtype == torch.uint8 and ws.numel() >= need and ws.is_contiguous()
                 _tape.keep(ws)                                # (a tape recorded outside TrainStepGraph has no other owner for it)
                 g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel()
+                form = "grouped256_ws"
     if split_m is None:
         split_m = _tn_splits(tiles, (M + 63) // 64, rows is not None, 64)
     g.split_m = int(split_m)
+    if GEMM_TN_LOG is not None:
+        sp = g.split_m
+        GEMM_TN_LOG.append((form, sp, _tn256_grid(tiles // 4, M) if big else (8 * tiles * ((sp + 7) // 8) if sp >= 8 else tiles * sp)))
     _timed("made_gemm_tn", flops, nbytes, lambda: check(lib().made_gemm_tn_grouped(C.byref(g), _stream()), "made_gemm_tn_grouped"),
            ("rows", rows[1], M) if rows is not None else f"grouped x{len(problems)} M={M}")
 
