@@ -547,7 +547,12 @@ int made_masked_softmax(const float* logits, int64_t ld_logits, const float* mas
  * :172-178 (LayerNorm2, linear_proj with residual, LayerNorm3) and modules/metrics.py:19-24 (cosine) -- no [Nm*Nv, D]
  * tensor is ever written.  Q = q_proj(LN1(video)) [Nv, D]; K = k_proj(LN1(seg)), U [Nm, S, D] (rows at m*{k,u}_bs + s*ld);
  * key_mask [Nm, S] f32 or NULL; vn = video / |video| [Nv, D] f32.  A track with no valid segment gives NaN, like the
- * reference's softmax over -inf.  LayerNorm variances are taken in one pass (E[x^2] - E[x]^2, f32): a bf16-path kernel. */
+ * reference's softmax over -inf.  LayerNorm variances are taken in one pass (E[x^2] - E[x]^2, f32): a bf16-path kernel.
+ * Rounding points (everything else is f32; tests/xpool_ref.py restates this list): the probabilities exp2(s - m) before the P.U product
+ * (their denominator is the f32 sum of the unrounded ones); o^ = O / l before the Linear, AFTER LayerNorm2's sums were taken from the
+ * f32 o^ (so k2 = -mean rstd belongs to the unrounded row: with value rows that share an offset the two no longer cancel, see
+ * docs/EXPERIMENTS.md 3p); the folded weight W'' = (W + I) diag(g2) (Av, Bv are f32 sums over the given W); g3 vn in the cosine's
+ * numerator (the per-video sums over g3 vn are f32). */
 typedef struct MadeXpoolFusedArgs {
     const void* Q; int64_t ldq;
     const void* K; const void* U; int64_t k_bs, ldk, u_bs, ldu;
@@ -578,7 +583,9 @@ int made_xpool_fused(const MadeXpoolFusedArgs* args, void* stream);
  * residual of modules/transformer.py:176 costs nothing.  Two passes per track with the probabilities parked in LDS (bf16), K / U rows
  * through LDS-DMA; S <= 512 segments.  Q [Nv, D], K / U [Nm, S, D] (rows at m * {k,u}_bs + s * ld{k,u}), all bf16; key_mask [Nm, S] f32
  * or NULL; ws: Nm * 32 ints (valid range and one bit per segment of every track), 16-byte aligned.  A track without a valid segment
- * gives NaN rows, like the reference's softmax over -inf. */
+ * gives NaN rows, like the reference's softmax over -inf.
+ * Rounding points: the probabilities before the P.U product (denominator: the f32 sum of the unrounded ones) and the bf16 output rows;
+ * mean and the one-pass variance are f32 sums over the f32 o. */
 typedef struct MadeXpoolAttnArgs {
     const void* Q; int64_t ldq;
     const void* K; const void* U; int64_t k_bs, ldk, u_bs, ldu;
@@ -604,7 +611,11 @@ int made_xpool_attention(const MadeXpoolAttnArgs* args, void* stream);
  * bytes, 16-byte aligned (per-video terms of LayerNorm3 + cosine -- since round 5 with a second, bf16 copy of g3 * vn in the order the 64-video kernel's lanes
  * read it; Nv * ldq * 2 and Nv * (1.5 D + 4) * 4 must stay below 4 GB -- filled when prepare_ws != 0; 32 ints per track, rebuilt by every call).
  * Two kernels serve the call: 32 videos per workgroup (the default) and 64 (MADE_XPOOL_SIMS_PQ=64: the same sums in the same order, results equal to 1e-7).
- * A track without a valid segment gives NaN, like the reference's softmax over -inf. */
+ * A track without a valid segment gives NaN, like the reference's softmax over -inf.
+ * Rounding points of both kernels (everything else is f32): the probabilities before the two P.V products (denominator: the f32 sum of the
+ * unrounded ones; LayerNorm2's sums are taken from the f32 o); g3 vn in the sum over g3 vn z; and the seven sums that are LINEAR in z --
+ * sum z c for c = 1, Bv, Av, g3^2, g3^2 Bv, g3^2 Av, g3 b3 -- go through the matrix pipe: there z (before the division by l: values of at
+ * most max|u''|) AND the seven constant vectors are bf16.  The sums over z^2 and the per-model / per-video constants are f32. */
 typedef struct MadeXpoolSimsArgs {
     const void* Q; int64_t ldq;
     const void* K; const void* UU; int64_t k_bs, ldk, u_bs, ldu;
@@ -653,7 +664,10 @@ int     made_xpool_sims_pairs(const MadeXpoolPairsArgs* args, void* stream);
  * the bf16 probabilities between them; replaces made_attention_wide's key split + merge on this shape.  Q [Nv <= 64, D], K / U [Nm, S <= 512, D]
  * (rows at m * {k,u}_bs + s * ld{k,u}), bf16, D = 256 / 512; key_mask [Nm, S] f32 or NULL; out[m * o_bs + n * ldo + d] bf16 or f32;
  * ws: made_xpool_inbatch_ws_bytes(Nm, S) bytes, 16-byte aligned (a larger workspace may be reused for a smaller call).  A track without a valid
- * segment gives NaN rows (the reference's softmax).  (Round 5's opt-in one-launch form -- both roles in one workgroup, the probabilities handed
+ * segment gives NaN rows (the reference's softmax).  Rounding points: per 32-segment tile p~ = exp2(s - ceil(tile maximum)) in bf16 (the
+ * denominator sums the ROUNDED p~, in f32); a tile's p~ is brought to the track's reference by an exact power of two 2^-k, k clamped to 255,
+ * on the bf16 exponent field: a value that leaves the normal range becomes +0 or a bf16 subnormal (weight below 2^-126); the output rows when bf16.
+ * (Round 5's opt-in one-launch form -- both roles in one workgroup, the probabilities handed
  * over inside the launch -- was 4 % faster alone and is gone: docs/EXPERIMENTS.md.) */
 typedef struct MadeXpoolInbatchArgs {
     const void* Q; int64_t ldq;
@@ -667,6 +681,33 @@ typedef struct MadeXpoolInbatchArgs {
 
 int     made_xpool_inbatch(const MadeXpoolInbatchArgs* args, void* stream);
 int64_t made_xpool_inbatch_ws_bytes(int64_t Nm, int64_t S);
+
+/* How made_xpool_sims / made_xpool_fused / made_xpool_attention cut these arguments into workgroups: the launch calls the same function, so
+ * the answer IS the dispatch.  Returns MADE_OK or the status with which the launch would refuse the arguments; nothing is launched and no
+ * pointer is dereferenced (their alignment is looked at), so the question can be asked without a GPU.  Nv == 0 or Nm == 0 (nothing is
+ * launched) reports chunks = 0.  Measurement knobs (honoured under MADE_DEBUG_VARIANTS only): MADE_XPOOL_SIMS_PQ=64 the 64-video kernel;
+ * MADE_XPOOL_SIMS_PER / MADE_XPOOL_FUSED_PER / MADE_XPOOL_ATTN_PER = n > 0: exactly n tracks per chunk (clamped to the kernel's track
+ * table: 464 / 440 for the 32- / 64-video sims kernel, 1024 for made_xpool_fused; to Nm for made_xpool_attention, which has none). */
+enum MadeXpoolKernel {
+    MADE_XPOOL_KERNEL_SIMS32 = 0,   /* xpool_sims32_kernel: 32 videos, four waves, two workgroups per CU */
+    MADE_XPOOL_KERNEL_SIMS64 = 1,   /* xpool_sims64_kernel: 64 videos (MADE_XPOOL_SIMS_PQ=64) */
+    MADE_XPOOL_KERNEL_FUSED = 2,    /* xpool_fused_persist_kernel: 64 videos, attention + linear waves */
+    MADE_XPOOL_KERNEL_ATTN256 = 3,  /* xpool_attn_kernel<256> */
+    MADE_XPOOL_KERNEL_ATTN512 = 4   /* xpool_attn_kernel<512> */
+};
+typedef struct MadeXpoolPlan {
+    int32_t kernel;             /* MadeXpoolKernel */
+    int32_t videos_per_wg;      /* 32 or 64 */
+    int32_t video_tiles;        /* ceil(Nv / videos_per_wg) */
+    int32_t tracks_per_chunk;   /* tracks a workgroup walks (the last chunk may be shorter) */
+    int32_t chunks;             /* chunks that hold a track: ceil(Nm / tracks_per_chunk) */
+    int32_t chunks_launched;    /* >= chunks: made_xpool_sims pads to a multiple of 8 from 8 chunks on (the padded workgroups exit at once) */
+    int32_t xcd_order;          /* 1: chunk c is walked by the workgroups of XCD c % 8 (made_xpool_sims with chunks_launched % 8 == 0) */
+    int32_t _pad;
+} MadeXpoolPlan;
+int made_xpool_sims_plan(const MadeXpoolSimsArgs* args, MadeXpoolPlan* plan);
+int made_xpool_fused_plan(const MadeXpoolFusedArgs* args, MadeXpoolPlan* plan);
+int made_xpool_attention_plan(const MadeXpoolAttnArgs* args, MadeXpoolPlan* plan);
 
 /* made_row_affine: out[r, :] = act(x[r, :] * scale[r % period] + shift[r % period]), act = none | ReLU.  Eval-mode
  * BatchNorm1d of the EmbeddingNet aggregator (reference model/model_Base.py:224-229): its input is [B, T, F], so the

@@ -154,6 +154,11 @@ class MadeXpoolInbatchArgs(C.Structure):
                 ("Nv", i64), ("Nm", i64), ("S", i64), ("D", i64), ("scale", f32), ("_pad2", i32), ("ws", vp)]
 
 
+class MadeXpoolPlan(C.Structure):
+    _fields_ = [("kernel", i32), ("videos_per_wg", i32), ("video_tiles", i32), ("tracks_per_chunk", i32), ("chunks", i32),
+                ("chunks_launched", i32), ("xcd_order", i32), ("_pad", i32)]
+
+
 class MadeWideAttnArgs(C.Structure):
     _fields_ = [("Q", vp), ("K", vp), ("Kadd", vp), ("V", vp), ("O", vp), ("key_mask", vp),
                 ("dtype", i32), ("o_dtype", i32),
@@ -306,6 +311,9 @@ SIGNATURES = {
     "made_xpool_attention": (C.c_int, [C.POINTER(MadeXpoolAttnArgs), vp]),
     "made_xpool_sims": (C.c_int, [C.POINTER(MadeXpoolSimsArgs), vp]),
     "made_xpool_sims_ws_bytes": (C.c_int64, [i64, i64, i64]),
+    "made_xpool_sims_plan": (C.c_int, [C.POINTER(MadeXpoolSimsArgs), C.POINTER(MadeXpoolPlan)]),
+    "made_xpool_fused_plan": (C.c_int, [C.POINTER(MadeXpoolFusedArgs), C.POINTER(MadeXpoolPlan)]),
+    "made_xpool_attention_plan": (C.c_int, [C.POINTER(MadeXpoolAttnArgs), C.POINTER(MadeXpoolPlan)]),
     "made_xpool_sims_pairs": (C.c_int, [C.POINTER(MadeXpoolPairsArgs), vp]),
     "made_xpool_inbatch": (C.c_int, [C.POINTER(MadeXpoolInbatchArgs), vp]),
     "made_xpool_inbatch_ws_bytes": (C.c_int64, [i64, i64]),

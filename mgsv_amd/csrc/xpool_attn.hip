@@ -1301,7 +1301,8 @@ __global__ __launch_bounds__(256) void xpool_sims_prep_kernel(const float* vn, i
 
 }  // namespace
 
-extern "C" int made_xpool_attention(const MadeXpoolAttnArgs* args, void* stream) {
+// The arguments made_xpool_attention accepts and how it cuts them into workgroups (made_xpool_attention_plan; the launch calls it too)
+static int xpool_attention_plan(const MadeXpoolAttnArgs* args, MadeXpoolPlan& p) {
     MADE_REQUIRE(args != nullptr, "made_xpool_attention: null args");
     const MadeXpoolAttnArgs& a = *args;
     MADE_REQUIRE(a.Q && a.K && a.U && a.out && a.ws, "made_xpool_attention: null pointer");
@@ -1315,17 +1316,41 @@ extern "C" int made_xpool_attention(const MadeXpoolAttnArgs* args, void* stream)
     MADE_UNSUPPORTED((uint64_t)a.S * (uint64_t)a.ldk * 2 < (1ull << 32) && (uint64_t)a.S * (uint64_t)a.ldu * 2 < (1ull << 32) &&
                      (uint64_t)(a.Nv + 64) * (uint64_t)a.ldo * 2 < (1ull << 32),
                      "made_xpool_attention: a track's K / U rows and its Nv output rows must each span less than 4 GB");
+    p = MadeXpoolPlan{};
+    p.kernel = a.D == 512 ? MADE_XPOOL_KERNEL_ATTN512 : MADE_XPOOL_KERNEL_ATTN256;
+    p.videos_per_wg = XA_PQ;
     if (a.Nv == 0 || a.Nm == 0) return MADE_OK;
-    hipStream_t st = (hipStream_t)stream;
-    int* info = (int*)a.ws;
-    hipLaunchKernelGGL(xpool_attn_info_kernel, dim3((unsigned)((a.Nm + 3) / 4)), dim3(256), 0, st, a.key_mask, a.S, a.Nm, info);
     // chunks of tracks per video tile: about four workgroups per CU over the launch, whole tracks
     const int64_t nvt = (a.Nv + XA_PQ - 1) / XA_PQ;
     int64_t chunks = (1024 + nvt - 1) / nvt;
     if (chunks > a.Nm) chunks = a.Nm;
     if (chunks < 1) chunks = 1;
-    const int per = (int)((a.Nm + chunks - 1) / chunks);
-    dim3 grid((unsigned)nvt, (unsigned)((a.Nm + per - 1) / per));
+    int64_t per = (a.Nm + chunks - 1) / chunks;
+    // MADE_XPOOL_ATTN_PER: exactly that many tracks per chunk (the kernel has no per-chunk table: any count up to Nm)
+    const char* knob = made_variant_env("MADE_XPOOL_ATTN_PER");
+    if (knob && atoi(knob) > 0) per = atoi(knob) < a.Nm ? atoi(knob) : a.Nm;
+    p.video_tiles = (int32_t)nvt;
+    p.tracks_per_chunk = (int32_t)per;
+    p.chunks = p.chunks_launched = (int32_t)((a.Nm + per - 1) / per);
+    return MADE_OK;
+}
+
+extern "C" int made_xpool_attention_plan(const MadeXpoolAttnArgs* args, MadeXpoolPlan* plan) {
+    MADE_REQUIRE(plan != nullptr, "made_xpool_attention_plan: null plan");
+    return xpool_attention_plan(args, *plan);
+}
+
+extern "C" int made_xpool_attention(const MadeXpoolAttnArgs* args, void* stream) {
+    MadeXpoolPlan pl;
+    const int prc = xpool_attention_plan(args, pl);
+    if (prc != MADE_OK) return prc;
+    const MadeXpoolAttnArgs& a = *args;
+    if (a.Nv == 0 || a.Nm == 0) return MADE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    int* info = (int*)a.ws;
+    hipLaunchKernelGGL(xpool_attn_info_kernel, dim3((unsigned)((a.Nm + 3) / 4)), dim3(256), 0, st, a.key_mask, a.S, a.Nm, info);
+    const int per = pl.tracks_per_chunk;
+    dim3 grid((unsigned)pl.video_tiles, (unsigned)pl.chunks_launched);
     const int rc = a.D == 512 ? launch_xpool_attn<512>(a, info, grid, per, st) : launch_xpool_attn<256>(a, info, grid, per, st);
     if (rc != MADE_OK) return rc;
     return made_check_launch("made_xpool_attention");
@@ -1333,7 +1358,10 @@ extern "C" int made_xpool_attention(const MadeXpoolAttnArgs* args, void* stream)
 
 extern "C" int64_t made_xpool_sims_ws_bytes(int64_t Nv, int64_t Nm, int64_t D) { return (xs_ws_info(Nv, D) + Nm * XA_INFO) * 4; }
 
-extern "C" int made_xpool_sims(const MadeXpoolSimsArgs* args, void* stream) {
+static bool xpool_dbg_is(int v) { const char* e = made_variant_env("MADE_XPOOL_DBG"); return e && atoi(e) == v; }
+
+// The arguments made_xpool_sims accepts, the kernel that serves them and its chunks of tracks (made_xpool_sims_plan; the launch calls it too)
+static int xpool_sims_plan(const MadeXpoolSimsArgs* args, MadeXpoolPlan& p) {
     MADE_REQUIRE(args != nullptr, "made_xpool_sims: null args");
     const MadeXpoolSimsArgs& a = *args;
     MADE_REQUIRE(a.Q && a.K && a.UU && a.av && a.bv && a.ln3_g && a.ln3_b && a.vn && a.sims && a.ws, "made_xpool_sims: null pointer");
@@ -1351,6 +1379,60 @@ extern "C" int made_xpool_sims(const MadeXpoolSimsArgs* args, void* stream) {
                      "made_xpool_sims: value rows hold u | u'' (ldu >= 2 D); a track's K / value rows must each span less than 4 GB");
     MADE_UNSUPPORTED((uint64_t)a.Nv * (uint64_t)a.ldq * 2 < (1ull << 32) && (uint64_t)a.Nv * (uint64_t)(a.D + 4 + a.D / 2) * 4 + 64 < (1ull << 32),
                      "made_xpool_sims: Q and the per-video workspace rows are addressed with 32-bit byte offsets (Nv * ldq * 2 and Nv * (1.5 D + 4) * 4 below 4 GB)");
+    constexpr int D = 256;
+    // the retrieval set's tracks: 32 videos (MADE_XPOOL_SIMS_PQ=64: round 5's 64-video kernel -- half the LDS-DMA bytes per pair, the same speed
+    // within 1.2 %: the comment in front of it) and four waves per workgroup, two workgroups per CU; at most MAX_TRACKS per chunk (the track table
+    // in LDS), as few partial rounds of the chip as possible
+    const bool pq64 = made_variant_env("MADE_XPOOL_SIMS_PQ") && atoi(made_variant_env("MADE_XPOOL_SIMS_PQ")) == 64;
+    // MADE_XPOOL_DBG=32 / 64: the phase-stamp build of the 32- / 64-video kernel (tools/xpool_sims_stamps.py)
+    const bool use64 = (pq64 && !xpool_dbg_is(32)) || xpool_dbg_is(64);
+    p = MadeXpoolPlan{};
+    p.kernel = use64 ? MADE_XPOOL_KERNEL_SIMS64 : MADE_XPOOL_KERNEL_SIMS32;
+    p.videos_per_wg = use64 ? 64 : 32;
+    if (a.Nv == 0 || a.Nm == 0) return MADE_OK;
+    const int64_t nvt32 = use64 ? (a.Nv + 63) / 64 : (a.Nv + 31) / 32;
+    const int64_t max_tracks = use64 ? Xs64<D>::MAX_TRACKS : Xs32<D>::MAX_TRACKS;
+    int64_t per32;
+    const char* knob = made_variant_env("MADE_XPOOL_SIMS_PER");
+    if (knob && atoi(knob) > 0) {
+        // exactly that many tracks per chunk, up to the track table
+        per32 = atoi(knob) < max_tracks ? atoi(knob) : max_tracks;
+    } else {
+        // Chunks of at most 64 tracks: the workgroups of an XCD walk a chunk together and share its rows through that XCD's L2 -- the shorter the
+        // chunk, the less they drift apart.  53 k x 4 k (profiles/r04_ao_*): 464 tracks per chunk 56.4 ms with 66 GB of L2 misses per launch, 128: 56.2 ms /
+        // 56 GB, 64: 57.2 ms / 31 GB, 32: 59.2 ms / 26 GB (a workgroup's prologue -- Q, g3 vn, the constant fragments -- costs about two tracks).
+        const int64_t max_per = 64 < max_tracks ? 64 : max_tracks;
+        const int64_t c_lo = (a.Nm + max_per - 1) / max_per;
+        double best = 1e30; int64_t bc = c_lo;
+        for (int64_t cch = c_lo; cch <= c_lo + 24 && cch <= a.Nm; ++cch) {
+            const int64_t pr = (a.Nm + cch - 1) / cch, rounds = (nvt32 * ((a.Nm + pr - 1) / pr) + 511) / 512;
+            const double cost = (double)rounds * (double)(pr + 2);
+            if (cost < best) { best = cost; bc = cch; }
+        }
+        if (bc >= 8) bc = (bc + 7) / 8 * 8;                              // whole chunks per XCD (see the kernel's workgroup order)
+        per32 = (a.Nm + bc - 1) / bc;
+    }
+    const int64_t live = (a.Nm + per32 - 1) / per32;
+    int64_t nch = live;
+    if (nch >= 8) nch = (nch + 7) / 8 * 8;                          // (chunks behind the last track exit at once)
+    p.video_tiles = (int32_t)nvt32;
+    p.tracks_per_chunk = (int32_t)per32;
+    p.chunks = (int32_t)live;
+    p.chunks_launched = (int32_t)nch;
+    p.xcd_order = (nch & 7) == 0 ? 1 : 0;
+    return MADE_OK;
+}
+
+extern "C" int made_xpool_sims_plan(const MadeXpoolSimsArgs* args, MadeXpoolPlan* plan) {
+    MADE_REQUIRE(plan != nullptr, "made_xpool_sims_plan: null plan");
+    return xpool_sims_plan(args, *plan);
+}
+
+extern "C" int made_xpool_sims(const MadeXpoolSimsArgs* args, void* stream) {
+    MadeXpoolPlan pl;
+    const int prc = xpool_sims_plan(args, pl);
+    if (prc != MADE_OK) return prc;
+    const MadeXpoolSimsArgs& a = *args;
     if (a.Nv == 0 || a.Nm == 0) return MADE_OK;
     hipStream_t st = (hipStream_t)stream;
     constexpr int D = 256;
@@ -1359,10 +1441,6 @@ extern "C" int made_xpool_sims(const MadeXpoolSimsArgs* args, void* stream) {
         hipLaunchKernelGGL(xpool_sims_prep_kernel<D>, dim3((unsigned)((a.Nv + 3) / 4)), dim3(256), 0, st, a.vn, a.ldvn, a.ln3_g, a.ln3_b, a.av, a.bv, wsf, a.Nv);
     int* info = (int*)(wsf + xs_ws_info(a.Nv, D));
     hipLaunchKernelGGL(xpool_attn_info_kernel, dim3((unsigned)((a.Nm + 3) / 4)), dim3(256), 0, st, a.key_mask, a.S, a.Nm, info);
-    // the retrieval set's tracks: 32 videos (MADE_XPOOL_SIMS_PQ=64: round 5's 64-video kernel -- half the LDS-DMA bytes per pair, the same speed
-    // within 1.2 %: the comment in front of it) and four waves per workgroup, two workgroups per CU; at most MAX_TRACKS per chunk (the track table
-    // in LDS), as few partial rounds of the chip as possible
-    const bool pq64 = made_variant_env("MADE_XPOOL_SIMS_PQ") && atoi(made_variant_env("MADE_XPOOL_SIMS_PQ")) == 64;
     static bool attr32 = false;
     if (!attr32) {
         hipError_t e = hipFuncSetAttribute((const void*)xpool_sims32_kernel<D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
@@ -1372,29 +1450,10 @@ extern "C" int made_xpool_sims(const MadeXpoolSimsArgs* args, void* stream) {
         if (e != hipSuccess) { made_set_error("made_xpool_sims: cannot reserve 80 KB of LDS: %s", hipGetErrorString(e)); return MADE_ERR_HIP; }
         attr32 = true;
     }
-    // MADE_XPOOL_DBG=32: the phase-stamp build of the 32-video kernel (tools/xpool_sims_stamps.py): workgroup (0, 0) writes cycle stamps into the sims buffer, no similarity is written
-    const bool stamps32 = made_variant_env("MADE_XPOOL_DBG") && atoi(made_variant_env("MADE_XPOOL_DBG")) == 32;
-    const bool stamps64 = made_variant_env("MADE_XPOOL_DBG") && atoi(made_variant_env("MADE_XPOOL_DBG")) == 64;      // the same for the 64-video kernel
-    const bool use64 = (pq64 && !stamps32) || stamps64;
-    const int64_t nvt32 = use64 ? (a.Nv + 63) / 64 : (a.Nv + 31) / 32;
-    // Chunks of at most 64 tracks: the workgroups of an XCD walk a chunk together and share its rows through that XCD's L2 -- the shorter the
-    // chunk, the less they drift apart.  53 k x 4 k (profiles/r04_ao_*): 464 tracks per chunk 56.4 ms with 66 GB of L2 misses per launch, 128: 56.2 ms /
-    // 56 GB, 64: 57.2 ms / 31 GB, 32: 59.2 ms / 26 GB (a workgroup's prologue -- Q, g3 vn, the constant fragments -- costs about two tracks).
-    int64_t max_per = 64;
-    if (made_variant_env("MADE_XPOOL_SIMS_PER") && atoi(made_variant_env("MADE_XPOOL_SIMS_PER")) > 0) max_per = atoi(made_variant_env("MADE_XPOOL_SIMS_PER"));
-    const int64_t max_tracks = use64 ? Xs64<D>::MAX_TRACKS : Xs32<D>::MAX_TRACKS;
-    if (max_per > max_tracks) max_per = max_tracks;
-    const int64_t c_lo = (a.Nm + max_per - 1) / max_per;
-    double best = 1e30; int64_t bc = c_lo;
-    for (int64_t cch = c_lo; cch <= c_lo + 24 && cch <= a.Nm; ++cch) {
-        const int64_t pr = (a.Nm + cch - 1) / cch, rounds = (nvt32 * ((a.Nm + pr - 1) / pr) + 511) / 512;
-        const double cost = (double)rounds * (double)(pr + 2);
-        if (cost < best) { best = cost; bc = cch; }
-    }
-    if (bc >= 8) bc = (bc + 7) / 8 * 8;                              // whole chunks per XCD (see the kernel's workgroup order)
-    const int per32 = (int)((a.Nm + bc - 1) / bc);
-    int nch = (int)((a.Nm + per32 - 1) / per32);
-    if (nch >= 8) nch = (nch + 7) / 8 * 8;                          // (chunks behind the last track exit at once)
+    // MADE_XPOOL_DBG=32 / 64: workgroup (0, 0) writes cycle stamps into the sims buffer, no similarity is written
+    const bool use64 = pl.kernel == MADE_XPOOL_KERNEL_SIMS64, stamps32 = xpool_dbg_is(32), stamps64 = xpool_dbg_is(64);
+    const int per32 = pl.tracks_per_chunk, nch = pl.chunks_launched;
+    const int64_t nvt32 = pl.video_tiles;
     dim3 g32((unsigned)(nvt32 * nch));
     if (use64 && stamps64) hipLaunchKernelGGL((xpool_sims64_kernel<D, true>), g32, dim3(256), Xs64<D>::TBL_OFF + per32 * 32, st, a, (const int*)info, per32, (int)nvt32, nch);
     else if (use64) hipLaunchKernelGGL((xpool_sims64_kernel<D, false>), g32, dim3(256), Xs64<D>::TBL_OFF + per32 * 32, st, a, (const int*)info, per32, (int)nvt32, nch);

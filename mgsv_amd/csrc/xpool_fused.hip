@@ -620,7 +620,8 @@ __global__ __launch_bounds__(XT) void xpool_prep_kernel(const float* vn, int64_t
 
 }  // namespace
 
-extern "C" int made_xpool_fused(const MadeXpoolFusedArgs* args, void* stream) {
+// The arguments made_xpool_fused accepts and its chunks of tracks (made_xpool_fused_plan; the launch calls it too)
+static int xpool_fused_plan(const MadeXpoolFusedArgs* args, MadeXpoolPlan& p) {
     MADE_REQUIRE(args != nullptr, "made_xpool_fused: null args");
     const MadeXpoolFusedArgs& a = *args;
     MADE_REQUIRE(a.Q && a.K && a.U && a.ln2_g && a.ln2_b && a.Wl && a.bl && a.ln3_g && a.ln3_b && a.vn && a.sims && a.ws,
@@ -633,6 +634,44 @@ extern "C" int made_xpool_fused(const MadeXpoolFusedArgs* args, void* stream) {
                      a.ldvn % 4 == 0 && ((uintptr_t)a.ws % 16) == 0 && ((uintptr_t)a.Q % 16) == 0 && ((uintptr_t)a.K % 16) == 0 && ((uintptr_t)a.U % 16) == 0 &&
                      ((uintptr_t)a.Wl % 16) == 0 && ((uintptr_t)a.vn % 16) == 0,
                      "made_xpool_fused: pointers / strides must keep 16-byte alignment");
+    p = MadeXpoolPlan{};
+    p.kernel = MADE_XPOOL_KERNEL_FUSED;
+    p.videos_per_wg = PQ;
+    if (a.Nv == 0 || a.Nm == 0) return MADE_OK;
+    // chunks of tracks per video tile: enough workgroups to fill the chip a few times over, as few partial rounds as possible
+    // (a workgroup's prologue -- weight, Q and cosine fragments -- costs about as much as three tracks)
+    const int64_t nvt = (a.Nv + PQ - 1) / PQ;
+    int64_t chunks = a.Nm;
+    if (nvt * a.Nm > 2048) {
+        const int64_t lo = (1024 + nvt - 1) / nvt, hi = lo + 24 < a.Nm ? lo + 24 : a.Nm;
+        double best = 1e30;
+        for (int64_t cch = lo; cch <= hi; ++cch) {
+            const int64_t per = (a.Nm + cch - 1) / cch, rounds = (nvt * ((a.Nm + per - 1) / per) + 255) / 256;
+            const double cost = (double)rounds * (double)(per + 3);
+            if (cost < best) { best = cost; chunks = (a.Nm + per - 1) / per; }
+        }
+    }
+    int64_t per = (a.Nm + chunks - 1) / chunks;
+    // MADE_XPOOL_FUSED_PER: exactly that many tracks per chunk
+    const char* knob = made_variant_env("MADE_XPOOL_FUSED_PER");
+    if (knob && atoi(knob) > 0) per = atoi(knob);
+    if (per > PMAX_TRACKS) per = PMAX_TRACKS;                 // (the kernel's track table)
+    p.video_tiles = (int32_t)nvt;
+    p.tracks_per_chunk = (int32_t)per;
+    p.chunks = p.chunks_launched = (int32_t)((a.Nm + per - 1) / per);
+    return MADE_OK;
+}
+
+extern "C" int made_xpool_fused_plan(const MadeXpoolFusedArgs* args, MadeXpoolPlan* plan) {
+    MADE_REQUIRE(plan != nullptr, "made_xpool_fused_plan: null plan");
+    return xpool_fused_plan(args, *plan);
+}
+
+extern "C" int made_xpool_fused(const MadeXpoolFusedArgs* args, void* stream) {
+    MadeXpoolPlan pl;
+    const int prc = xpool_fused_plan(args, pl);
+    if (prc != MADE_OK) return prc;
+    const MadeXpoolFusedArgs& a = *args;
     if (a.Nv == 0 || a.Nm == 0) return MADE_OK;
     static bool attr_done = false;
     if (!attr_done) {
@@ -654,22 +693,8 @@ extern "C" int made_xpool_fused(const MadeXpoolFusedArgs* args, void* stream) {
         info = (int*)(wsc + WS_INFO);
         hipLaunchKernelGGL(xpool_track_info_kernel, dim3((unsigned)((a.Nm + 3) / 4)), dim3(XT), 0, (hipStream_t)stream, a.key_mask, a.S, a.Nm, info);
     }
-    // chunks of tracks per video tile: enough workgroups to fill the chip a few times over, as few partial rounds as possible
-    // (a workgroup's prologue -- weight, Q and cosine fragments -- costs about as much as three tracks)
-    const int64_t nvt = (a.Nv + PQ - 1) / PQ;
-    int64_t chunks = a.Nm;
-    if (nvt * a.Nm > 2048) {
-        const int64_t lo = (1024 + nvt - 1) / nvt, hi = lo + 24 < a.Nm ? lo + 24 : a.Nm;
-        double best = 1e30;
-        for (int64_t cch = lo; cch <= hi; ++cch) {
-            const int64_t per = (a.Nm + cch - 1) / cch, rounds = (nvt * ((a.Nm + per - 1) / per) + 255) / 256;
-            const double cost = (double)rounds * (double)(per + 3);
-            if (cost < best) { best = cost; chunks = (a.Nm + per - 1) / per; }
-        }
-    }
-    int per = (int)((a.Nm + chunks - 1) / chunks);
-    if (per > PMAX_TRACKS) per = PMAX_TRACKS;                 // (the kernel's track table)
-    dim3 grid((unsigned)nvt, (unsigned)((a.Nm + per - 1) / per)), block(PT);
+    const int per = pl.tracks_per_chunk;
+    dim3 grid((unsigned)pl.video_tiles, (unsigned)pl.chunks_launched), block(PT);
     // MADE_XPOOL_DBG=33: the phase-stamp build of the kernel (tools/xpool_stamps.py): no similarity is written, workgroup (0, 0)
     // writes cycle stamps into the sims buffer instead
     static const bool stamps = made_variant_env("MADE_XPOOL_DBG") && atoi(made_variant_env("MADE_XPOOL_DBG")) == 33;

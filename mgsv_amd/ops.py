@@ -695,31 +695,73 @@ def xpool_fused_ws_floats(Nv: int, Nm: int, D: int = 256) -> int:
     return Nv * (D + 2) + 4 + 2 * D + D * D // 2 + 4 * Nm
 
 
-def xpool_fused(Q: Tensor, K: Tensor, U: Tensor, key_mask: Optional[Tensor], ln2, Wl: Tensor, bl: Tensor, ln3, vn: Tensor,
-                sims: Tensor, scale: float, eps: float = 1e-5, ws: Optional[Tensor] = None, prepare_ws: bool = True) -> Tensor:
-    """All-pairs X-Pool scoring in one launch (made_xpool_fused; bf16, D = 256): Q [Nv,D], K / U [Nm,S,D] (unit inner stride),
-    key_mask [Nm,S] or None, ln2 / ln3 = (gamma, beta) f32, Wl [D,D] bf16, bl f32, vn [Nv,D] f32 (L2-normalised videos)
-    -> sims[n, m] written into `sims` ([Nv, >= Nm] f32 view)."""
+class XpoolPlan(NamedTuple):
+    """made_xpool_{sims,fused,attention}_plan (include/made_hip.h MadeXpoolPlan): how a call is cut into workgroups"""
+    kernel: str                 # XPOOL_KERNELS
+    videos_per_wg: int
+    video_tiles: int
+    tracks_per_chunk: int
+    chunks: int                 # chunks that hold a track
+    chunks_launched: int        # made_xpool_sims pads to a multiple of 8 from 8 chunks on
+    xcd_order: bool
+
+
+# MadeXpoolKernel codes -> kernel symbols
+XPOOL_KERNELS = {0: "xpool_sims32_kernel", 1: "xpool_sims64_kernel", 2: "xpool_fused_persist_kernel", 3: "xpool_attn_kernel<256>",
+                 4: "xpool_attn_kernel<512>"}
+
+
+def _xpool_plan(fn, a, what: str) -> XpoolPlan:
+    pl = _lib.MadeXpoolPlan()
+    check(fn(C.byref(a), C.byref(pl)), what)
+    return XpoolPlan(XPOOL_KERNELS[pl.kernel], pl.videos_per_wg, pl.video_tiles, pl.tracks_per_chunk, pl.chunks, pl.chunks_launched,
+                     bool(pl.xcd_order))
+
+
+def xpool_fused_args(Q: Tensor, K: Tensor, U: Tensor, key_mask: Optional[Tensor], ln2, Wl: Tensor, bl: Tensor, ln3, vn: Tensor,
+                     sims: Tensor, scale: float, eps: float = 1e-5, ws: Optional[Tensor] = None, prepare_ws: bool = True,
+                     launchable: bool = True):
+    """the MadeXpoolFusedArgs of an xpool_fused() call (nothing launched) and the tensors it points into.  launchable=False takes tensors
+    of any device, for a made_xpool_fused_plan question asked without a GPU; such arguments are never handed to made_xpool_fused."""
     from ._lib import MadeXpoolFusedArgs
+    ptr = _p if launchable else _host_ptr
     Nv, D = Q.shape
     Nm, S, _ = K.shape
     assert Q.dtype == K.dtype == U.dtype == Wl.dtype == torch.bfloat16 and Q.stride(1) == 1 and K.stride(2) == 1 and U.stride(2) == 1
     assert U.shape == K.shape and Wl.shape == (D, D) and Wl.stride(1) == 1 and vn.shape == (Nv, D) and vn.dtype == torch.float32
     assert sims.dtype == torch.float32 and sims.stride(1) == 1 and sims.shape[0] == Nv and sims.shape[1] >= Nm
     a = MadeXpoolFusedArgs()
-    a.Q, a.ldq = _p(Q), Q.stride(0)
-    a.K, a.U, a.k_bs, a.ldk, a.u_bs, a.ldu = _p(K), _p(U), K.stride(0), K.stride(1), U.stride(0), U.stride(1)
-    a.key_mask = _p(_f32(key_mask.contiguous(), "key_mask")) if key_mask is not None else None
-    a.ln2_g, a.ln2_b, a.ln3_g, a.ln3_b = _p(_f32(ln2[0], "ln2")), _p(_f32(ln2[1], "ln2")), _p(_f32(ln3[0], "ln3")), _p(_f32(ln3[1], "ln3"))
-    a.Wl, a.ldw, a.bl = _p(Wl), Wl.stride(0), _p(_f32(bl, "bl"))
-    a.vn, a.ldvn = _p(vn), vn.stride(0)
-    a.sims, a.ld_sims = _p(sims), sims.stride(0)
+    a.Q, a.ldq = ptr(Q), Q.stride(0)
+    a.K, a.U, a.k_bs, a.ldk, a.u_bs, a.ldu = ptr(K), ptr(U), K.stride(0), K.stride(1), U.stride(0), U.stride(1)
+    km = _f32(key_mask.contiguous(), "key_mask") if key_mask is not None else None
+    a.key_mask = ptr(km)
+    a.ln2_g, a.ln2_b, a.ln3_g, a.ln3_b = ptr(_f32(ln2[0], "ln2")), ptr(_f32(ln2[1], "ln2")), ptr(_f32(ln3[0], "ln3")), ptr(_f32(ln3[1], "ln3"))
+    a.Wl, a.ldw, a.bl = ptr(Wl), Wl.stride(0), ptr(_f32(bl, "bl"))
+    a.vn, a.ldvn = ptr(vn), vn.stride(0)
+    a.sims, a.ld_sims = ptr(sims), sims.stride(0)
     a.Nv, a.Nm, a.S, a.D, a.scale, a.eps = Nv, Nm, S, D, scale, eps
     if ws is None:
         ws = torch.empty(xpool_fused_ws_floats(Nv, Nm, D), device=Q.device, dtype=torch.float32)
         prepare_ws = True
     assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= xpool_fused_ws_floats(Nv, Nm, D)
-    a.ws, a.prepare_ws = _p(ws), 1 if prepare_ws else 0
+    a.ws, a.prepare_ws = ptr(ws), 1 if prepare_ws else 0
+    return a, (km, ws)
+
+
+def xpool_fused_plan(*args, **kw) -> XpoolPlan:
+    """made_xpool_fused_plan of an xpool_fused() call with the same arguments (tensors of any device; nothing is launched)"""
+    a, _keep = xpool_fused_args(*args, launchable=False, **kw)
+    return _xpool_plan(lib().made_xpool_fused_plan, a, "made_xpool_fused_plan")
+
+
+def xpool_fused(Q: Tensor, K: Tensor, U: Tensor, key_mask: Optional[Tensor], ln2, Wl: Tensor, bl: Tensor, ln3, vn: Tensor,
+                sims: Tensor, scale: float, eps: float = 1e-5, ws: Optional[Tensor] = None, prepare_ws: bool = True) -> Tensor:
+    """All-pairs X-Pool scoring in one launch (made_xpool_fused; bf16, D = 256): Q [Nv,D], K / U [Nm,S,D] (unit inner stride),
+    key_mask [Nm,S] or None, ln2 / ln3 = (gamma, beta) f32, Wl [D,D] bf16, bl f32, vn [Nv,D] f32 (L2-normalised videos)
+    -> sims[n, m] written into `sims` ([Nv, >= Nm] f32 view)."""
+    a, _keep = xpool_fused_args(Q, K, U, key_mask, ln2, Wl, bl, ln3, vn, sims, scale, eps, ws, prepare_ws)
+    Nv, D = Q.shape
+    Nm, S, _ = K.shape
     flops = 2.0 * Nv * Nm * (2 * S * D + D * D)
     desc = ""
     if _timer is not None and key_mask is not None:             # executed work: the valid segments of each track only
@@ -735,32 +777,49 @@ def xpool_sims_ws_bytes(Nv: int, Nm: int, D: int = 256) -> int:
     return int(lib().made_xpool_sims_ws_bytes(Nv, Nm, D))
 
 
-def xpool_sims(Q: Tensor, K: Tensor, UU: Tensor, key_mask: Optional[Tensor], av: Tensor, bv: Tensor, ln3, vn: Tensor, sims: Tensor, scale: float,
-               eps: float = 1e-5, ws: Optional[Tensor] = None, prepare_ws: bool = True) -> Tensor:
-    """All-pairs X-Pool scoring with the per-pair Linear moved onto the values (made_xpool_sims; bf16, D = 256, S <= 96): Q [Nv, D],
-    K [Nm, S, D], UU [Nm, S, 2 D] = value rows u_s | W'' u_s (unit inner stride), key_mask [Nm, S] or None, av = b'' and bv = W'' 1 [D] f32,
-    ln3 = (gamma, beta) f32, vn [Nv, D] f32 (L2-normalised videos) -> sims[n, m] written into `sims` ([Nv, >= Nm] f32 view)."""
+def xpool_sims_args(Q: Tensor, K: Tensor, UU: Tensor, key_mask: Optional[Tensor], av: Tensor, bv: Tensor, ln3, vn: Tensor, sims: Tensor,
+                    scale: float, eps: float = 1e-5, ws: Optional[Tensor] = None, prepare_ws: bool = True, launchable: bool = True):
+    """the MadeXpoolSimsArgs of an xpool_sims() call (nothing launched) and the tensors it points into; launchable=False: see xpool_fused_args"""
     from ._lib import MadeXpoolSimsArgs
+    ptr = _p if launchable else _host_ptr
     Nv, D = Q.shape
     Nm, S, _ = K.shape
     assert Q.dtype == K.dtype == UU.dtype == torch.bfloat16 and Q.stride(1) == 1 and K.stride(2) == 1 and UU.stride(2) == 1
     assert UU.shape == (Nm, S, 2 * D) and vn.shape == (Nv, D) and vn.dtype == torch.float32 and av.shape == (D,) and bv.shape == (D,)
     assert sims.dtype == torch.float32 and sims.stride(1) == 1 and sims.shape[0] == Nv and sims.shape[1] >= Nm
     a = MadeXpoolSimsArgs()
-    a.Q, a.ldq = _p(Q), Q.stride(0)
-    a.K, a.UU, a.k_bs, a.ldk, a.u_bs, a.ldu = _p(K), _p(UU), K.stride(0), K.stride(1), UU.stride(0), UU.stride(1)
-    a.key_mask = _p(_f32(key_mask.contiguous(), "key_mask")) if key_mask is not None else None
-    a.av, a.bv = _p(_f32(av, "av")), _p(_f32(bv, "bv"))
-    a.ln3_g, a.ln3_b = _p(_f32(ln3[0], "ln3")), _p(_f32(ln3[1], "ln3"))
-    a.vn, a.ldvn = _p(vn), vn.stride(0)
-    a.sims, a.ld_sims = _p(sims), sims.stride(0)
+    a.Q, a.ldq = ptr(Q), Q.stride(0)
+    a.K, a.UU, a.k_bs, a.ldk, a.u_bs, a.ldu = ptr(K), ptr(UU), K.stride(0), K.stride(1), UU.stride(0), UU.stride(1)
+    km = _f32(key_mask.contiguous(), "key_mask") if key_mask is not None else None
+    a.key_mask = ptr(km)
+    a.av, a.bv = ptr(_f32(av, "av")), ptr(_f32(bv, "bv"))
+    a.ln3_g, a.ln3_b = ptr(_f32(ln3[0], "ln3")), ptr(_f32(ln3[1], "ln3"))
+    a.vn, a.ldvn = ptr(vn), vn.stride(0)
+    a.sims, a.ld_sims = ptr(sims), sims.stride(0)
     a.Nv, a.Nm, a.S, a.D, a.scale, a.eps = Nv, Nm, S, D, scale, eps
     need = int(lib().made_xpool_sims_ws_bytes(Nv, Nm, D))
     if ws is None:
         ws = torch.empty(need, device=Q.device, dtype=torch.uint8)
         prepare_ws = True
     assert ws.is_contiguous() and ws.numel() * ws.element_size() >= need
-    a.ws, a.prepare_ws = _p(ws), 1 if prepare_ws else 0
+    a.ws, a.prepare_ws = ptr(ws), 1 if prepare_ws else 0
+    return a, (km, ws)
+
+
+def xpool_sims_plan(*args, **kw) -> XpoolPlan:
+    """made_xpool_sims_plan of an xpool_sims() call with the same arguments (tensors of any device; nothing is launched)"""
+    a, _keep = xpool_sims_args(*args, launchable=False, **kw)
+    return _xpool_plan(lib().made_xpool_sims_plan, a, "made_xpool_sims_plan")
+
+
+def xpool_sims(Q: Tensor, K: Tensor, UU: Tensor, key_mask: Optional[Tensor], av: Tensor, bv: Tensor, ln3, vn: Tensor, sims: Tensor, scale: float,
+               eps: float = 1e-5, ws: Optional[Tensor] = None, prepare_ws: bool = True) -> Tensor:
+    """All-pairs X-Pool scoring with the per-pair Linear moved onto the values (made_xpool_sims; bf16, D = 256, S <= 96): Q [Nv, D],
+    K [Nm, S, D], UU [Nm, S, 2 D] = value rows u_s | W'' u_s (unit inner stride), key_mask [Nm, S] or None, av = b'' and bv = W'' 1 [D] f32,
+    ln3 = (gamma, beta) f32, vn [Nv, D] f32 (L2-normalised videos) -> sims[n, m] written into `sims` ([Nv, >= Nm] f32 view)."""
+    a, _keep = xpool_sims_args(Q, K, UU, key_mask, av, bv, ln3, vn, sims, scale, eps, ws, prepare_ws)
+    Nv, D = Q.shape
+    Nm, S, _ = K.shape
     flops = 2.0 * Nv * Nm * (2 * S * D + D * D)                    # the reference's work per pair (the kernel executes 3 S D per pair)
     desc = ""
     if _timer is not None and key_mask is not None:
@@ -801,26 +860,44 @@ def xpool_sims_pairs(Q: Tensor, K: Tensor, UU: Tensor, key_mask: Optional[Tensor
     return score
 
 
-def xpool_attention(Q: Tensor, K: Tensor, U: Tensor, key_mask: Optional[Tensor], out: Tensor, scale: float, normalize: bool = True,
-                    eps: float = 1e-5, ws: Optional[Tensor] = None) -> Tensor:
-    """The X-Pool attention at retrieval scale, head dim = D = 256 or 512, S <= 512 (made_xpool_attention): Q [Nv, D], K / U [Nm, S, D]
-    bf16 (unit inner stride), key_mask [Nm, S] or None -> out [Nm, Nv, D] bf16: softmax_s(Q K^T * scale + mask) U, then (normalize)
-    (x - mean) * rstd over D -- LayerNorm2 without its affine part, which the caller folds into the Linear behind it."""
+def xpool_attention_args(Q: Tensor, K: Tensor, U: Tensor, key_mask: Optional[Tensor], out: Tensor, scale: float, normalize: bool = True,
+                         eps: float = 1e-5, ws: Optional[Tensor] = None, launchable: bool = True):
+    """the MadeXpoolAttnArgs of an xpool_attention() call (nothing launched) and the tensors it points into; launchable=False: see
+    xpool_fused_args"""
     from ._lib import MadeXpoolAttnArgs
+    ptr = _p if launchable else _host_ptr
     Nv, D = Q.shape
     Nm, S, _ = K.shape
     assert Q.dtype == K.dtype == U.dtype == out.dtype == torch.bfloat16 and Q.stride(1) == 1 and K.stride(2) == 1 and U.stride(2) == 1
     assert U.shape == K.shape and out.dim() == 3 and tuple(out.shape) == (Nm, Nv, D) and out.stride(2) == 1 and out.stride(0) == Nv * out.stride(1)
     a = MadeXpoolAttnArgs()
-    a.Q, a.ldq = _p(Q), Q.stride(0)
-    a.K, a.U, a.k_bs, a.ldk, a.u_bs, a.ldu = _p(K), _p(U), K.stride(0), K.stride(1), U.stride(0), U.stride(1)
-    a.key_mask = _p(_f32(key_mask.contiguous(), "key_mask")) if key_mask is not None else None
-    a.out, a.ldo = _p(out), out.stride(1)
+    a.Q, a.ldq = ptr(Q), Q.stride(0)
+    a.K, a.U, a.k_bs, a.ldk, a.u_bs, a.ldu = ptr(K), ptr(U), K.stride(0), K.stride(1), U.stride(0), U.stride(1)
+    km = _f32(key_mask.contiguous(), "key_mask") if key_mask is not None else None
+    a.key_mask = ptr(km)
+    a.out, a.ldo = ptr(out), out.stride(1)
     a.Nv, a.Nm, a.S, a.D, a.scale, a.eps, a.normalize = Nv, Nm, S, D, scale, eps, 1 if normalize else 0
     if ws is None:
         ws = torch.empty(Nm * 32, device=Q.device, dtype=torch.int32)
     assert ws.dtype == torch.int32 and ws.is_contiguous() and ws.numel() >= Nm * 32
-    a.ws = _p(ws)
+    a.ws = ptr(ws)
+    return a, (km, ws)
+
+
+def xpool_attention_plan(*args, **kw) -> XpoolPlan:
+    """made_xpool_attention_plan of an xpool_attention() call with the same arguments (tensors of any device; nothing is launched)"""
+    a, _keep = xpool_attention_args(*args, launchable=False, **kw)
+    return _xpool_plan(lib().made_xpool_attention_plan, a, "made_xpool_attention_plan")
+
+
+def xpool_attention(Q: Tensor, K: Tensor, U: Tensor, key_mask: Optional[Tensor], out: Tensor, scale: float, normalize: bool = True,
+                    eps: float = 1e-5, ws: Optional[Tensor] = None) -> Tensor:
+    """The X-Pool attention at retrieval scale, head dim = D = 256 or 512, S <= 512 (made_xpool_attention): Q [Nv, D], K / U [Nm, S, D]
+    bf16 (unit inner stride), key_mask [Nm, S] or None -> out [Nm, Nv, D] bf16: softmax_s(Q K^T * scale + mask) U, then (normalize)
+    (x - mean) * rstd over D -- LayerNorm2 without its affine part, which the caller folds into the Linear behind it."""
+    a, _keep = xpool_attention_args(Q, K, U, key_mask, out, scale, normalize, eps, ws)
+    Nv, D = Q.shape
+    Nm, S, _ = K.shape
     flops = 4.0 * Nv * Nm * S * D
     desc = ""
     if _timer is not None and key_mask is not None:             # executed work: the valid segments of each track only
