@@ -207,7 +207,16 @@ int made_linear_variant(const MadeLinearArgs* args);
  *     A   = bf16(x) (+ add[row % add_row_mod])  add: bf16 rows of K elements (query_pos) or NULL; x itself -> x_out (bf16) or NULL
  *     out = act(A W^T + bias) + R               R: bf16 [M, N] or NULL; res_from_x: + bf16(x) instead (needs N == K, no add)
  * bf16 MFMA, f32 accumulate; K (the LayerNorm width) is 256 or 512; out is f32 (raw rows for the next stage's norm) or bf16.
- * One launch of ceil(N / 32) x ceil(M / 64) workgroups, no split-K workspace, no finish launch. */
+ * One launch of ceil(N / 16) x ceil(M / 16) workgroups (16 x 16 tiles), no split-K workspace, no finish launch.
+ * Where the kernels round (everything else is f32):
+ *   - the f32-row instances take mean and variance in two passes (centred); the bf16-row instances take them in ONE pass,
+ *     var = max(Sxx / K - mean^2, 0).  The second norm is two-pass in every instance and reads the f32 x, not the stored one.
+ *   - x_out = bf16(x), x2_out = bf16(x2).
+ *   - A = bf16(x) without add; with add, A = bf16(bf16(x) + add), the sum taken in f32.  a_out holds the same bits as the matrix operand.
+ *   - the product takes the bf16 A and W and accumulates in f32; bias, activation, dropout (x 1 / (1 - p), dropped: +0) and the
+ *     residual follow in f32; res_from_x adds bf16(x); out is rounded once at the store (bf16) or not at all (f32).
+ *   - dropout draws element row * drop_ld + col / max(drop_col_div, 1) whatever ldo is.
+ * Rows M .. of the last row tile and columns N .. of the last column tile are computed on clamped addresses and never stored. */
 typedef struct MadeDecStageArgs {
     const void*  Zin; int64_t ldz;                 /* f32 rows (zin_dtype = MADE_F32, the eval chain) or bf16 rows (MADE_BF16, the training chain) */
     const float* ln_g; const float* ln_b;
@@ -227,6 +236,16 @@ typedef struct MadeDecStageArgs {
 } MadeDecStageArgs;
 int made_dec_stage(const MadeDecStageArgs* args, void* stream);
 
+/* Which kernel instance made_dec_stage runs these arguments on, or the negative status with which it refuses them (every argument
+ * check of made_dec_stage lives here; no launch). */
+enum MadeDecStageVariant {
+    MADE_DEC_STAGE_256_F32 = 0,     /* dec_stage_kernel<4, false, false>: K = 256, f32 rows (the eval chain) */
+    MADE_DEC_STAGE_256_BF16 = 1,    /* dec_stage_kernel<4, true, true>: K = 256, bf16 rows, the training options */
+    MADE_DEC_STAGE_512_F32 = 2,     /* dec_stage_kernel<8, false, false> */
+    MADE_DEC_STAGE_512_BF16 = 3     /* dec_stage_kernel<8, true, true> */
+};
+int made_dec_stage_variant(const MadeDecStageArgs* args);
+
 /* made_dec_stage_bwd: a stage of the decoder's BACKWARD chain with a LayerNorm backward in the prologue of the dX product that
  * consumes it (reference music_detr/transformer.py:273-307 read backwards; bf16 rows, K = the norm's width = 256 or 512):
  *     g   = dy (+ add),  or with a second norm stacked on the first (xb != NULL: norm 3 + the shared output norm, :306 and :136)
@@ -234,7 +253,18 @@ int made_dec_stage(const MadeDecStageArgs* args, void* stream);
  *     dx  = LN_a'(g; xa, gamma_a)       -> dx_out [M, K] (may be NULL);  dgamma / dbeta of the norm(s) accumulated (may be NULL)
  *     A   = dropout_a(dx)               -> a_out [M, K] (may be NULL): element index row * drop_a_ld + col
  *     out = dropout_o((A W^T) * [G != 0] * gate_scale) + R        W [N, K] bf16; G, R, out [M, N] bf16; drop_o index row * drop_o_ld + col / drop_o_col_div
- * One launch of ceil(N / 32) x ceil(M / 64) workgroups replaces made_layernorm_bwd (or made_layernorm_bwd2) + made_linear. */
+ * One launch of ceil(N / 16) x ceil(M / 16) workgroups (16 x 16 tiles) replaces made_layernorm_bwd (or made_layernorm_bwd2) + made_linear.
+ * Where the kernels round (everything else is f32):
+ *   - every LayerNorm backward takes all four row sums (Sx, Sxx, Sg, Sgx; g = dy * gamma) in ONE pass:
+ *     mean = Sx / K, var = max(Sxx / K - mean^2, 0), s1 = Sg / K, s2 = rstd (Sgx - mean Sg) / K, dx = rstd (g - s1 - xhat s2).
+ *   - dy + add (one norm) and the inner g = LN_b'(dy) + add (two norms) stay in f32.
+ *   - dx_out = bf16(dx);  A = bf16(dropout_a(dx)) (x 1 / (1 - p), dropped: +0), rounded separately from dx_out; a_out holds the bits
+ *     of the matrix operand.
+ *   - the product takes the bf16 A and W and accumulates in f32; gate (G == +-0: +0), gate_scale, dropout_o and R follow in f32; out is
+ *     rounded once at the store.
+ *   - dgamma / dbeta: dgamma += sum_rows dy * xhat, dbeta += sum_rows dy (for norm a with dy = g).  The workgroups of column tile 0 alone
+ *     accumulate them, with ONE f32 atomic per column and row tile of 16 rows; the pad rows of a ragged last tile add nothing.  With
+ *     M <= 16 the result is therefore reproducible bit for bit, beyond that up to the order of ceil(M / 16) atomics per column. */
 typedef struct MadeDecStageBwdArgs {
     const void* xa; const float* gamma_a; int64_t ldxa;
     const void* xb; const float* gamma_b; int64_t ldxb;      /* second (outer) norm or NULL */
@@ -252,6 +282,17 @@ typedef struct MadeDecStageBwdArgs {
     int64_t M, N, K;
 } MadeDecStageBwdArgs;
 int made_dec_stage_bwd(const MadeDecStageBwdArgs* args, void* stream);
+
+/* The same for made_dec_stage_bwd: the instance code, or the negative status (no launch). */
+enum MadeDecStageBwdVariant {
+    MADE_DEC_STAGE_BWD_256_ONE = 0, /* dec_stage_bwd_kernel<4, 0>: K = 256, one norm */
+    MADE_DEC_STAGE_BWD_256_ADD = 1, /* dec_stage_bwd_kernel<4, 1>: one norm, g = dy + add */
+    MADE_DEC_STAGE_BWD_256_TWO = 2, /* dec_stage_bwd_kernel<4, 2>: two stacked norms (xb), with or without add */
+    MADE_DEC_STAGE_BWD_512_ONE = 3, /* dec_stage_bwd_kernel<8, 0> */
+    MADE_DEC_STAGE_BWD_512_ADD = 4, /* dec_stage_bwd_kernel<8, 1> */
+    MADE_DEC_STAGE_BWD_512_TWO = 5  /* dec_stage_bwd_kernel<8, 2> */
+};
+int made_dec_stage_bwd_variant(const MadeDecStageBwdArgs* args);
 
 /* y = act(sum_s ws[s] + bias) + R[row % r_row_mod]  -> out (any dtype, may be NULL);
  * then optionally z1 = LayerNorm(y; ln1) -> ln1_out, and z2 = LayerNorm(z1; ln2) -> ln2_out (the decoder's

@@ -262,6 +262,8 @@ SIGNATURES = {
     "made_splitk_finish": (C.c_int, [C.POINTER(MadeFinishArgs), vp]),
     "made_dec_stage": (C.c_int, [C.POINTER(MadeDecStageArgs), vp]),
     "made_dec_stage_bwd": (C.c_int, [C.POINTER(MadeDecStageBwdArgs), vp]),
+    "made_dec_stage_variant": (C.c_int, [C.POINTER(MadeDecStageArgs)]),
+    "made_dec_stage_bwd_variant": (C.c_int, [C.POINTER(MadeDecStageBwdArgs)]),
     "made_attention": (C.c_int, [C.POINTER(MadeAttnArgs), vp]),
     "made_attention_wide": (C.c_int, [C.POINTER(MadeWideAttnArgs), vp]),
     "made_attention_wide_bwd": (C.c_int, [C.POINTER(MadeWideAttnBwdArgs), vp]),

@@ -578,7 +578,7 @@ __global__ __launch_bounds__(DS_THREADS) void dec_stage_bwd_kernel(const MadeDec
 
 }  // namespace
 
-extern "C" int made_dec_stage_bwd(const MadeDecStageBwdArgs* args, void* stream) {
+extern "C" int made_dec_stage_bwd_variant(const MadeDecStageBwdArgs* args) {
     MADE_REQUIRE(args != nullptr, "made_dec_stage_bwd: null args");
     const MadeDecStageBwdArgs& a = *args;
     MADE_REQUIRE(a.xa && a.gamma_a && a.dy && a.W && a.out, "made_dec_stage_bwd: null xa, gamma_a, dy, W or out");
@@ -590,21 +590,28 @@ extern "C" int made_dec_stage_bwd(const MadeDecStageBwdArgs* args, void* stream)
                      ((uintptr_t)a.dx_out % 16) == 0 && ((uintptr_t)a.a_out % 16) == 0 && ((uintptr_t)a.W % 16) == 0,
                      "made_dec_stage_bwd: rows must be 16-byte aligned");
     MADE_REQUIRE(a.drop_a.p >= 0.f && a.drop_a.p < 1.f && a.drop_o.p >= 0.f && a.drop_o.p < 1.f, "made_dec_stage_bwd: dropout p out of [0,1)");
+    const int mode = a.xb ? 2 : (a.add ? 1 : 0);
+    return (a.K == 512 ? MADE_DEC_STAGE_BWD_512_ONE : MADE_DEC_STAGE_BWD_256_ONE) + mode;
+}
+
+extern "C" int made_dec_stage_bwd(const MadeDecStageBwdArgs* args, void* stream) {
+    const int variant = made_dec_stage_bwd_variant(args);
+    if (variant < 0) return variant;
+    const MadeDecStageBwdArgs& a = *args;
     const dim3 grid((unsigned)((a.N + DS_BN - 1) / DS_BN), (unsigned)((a.M + DS_BM - 1) / DS_BM)), block(DS_THREADS);
     hipStream_t st = (hipStream_t)stream;
-    if (a.K == 512) {
-        if (a.xb) hipLaunchKernelGGL((dec_stage_bwd_kernel<8, 2>), grid, block, 0, st, a);
-        else if (a.add) hipLaunchKernelGGL((dec_stage_bwd_kernel<8, 1>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((dec_stage_bwd_kernel<8, 0>), grid, block, 0, st, a);
-    } else {
-        if (a.xb) hipLaunchKernelGGL((dec_stage_bwd_kernel<4, 2>), grid, block, 0, st, a);
-        else if (a.add) hipLaunchKernelGGL((dec_stage_bwd_kernel<4, 1>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((dec_stage_bwd_kernel<4, 0>), grid, block, 0, st, a);
+    switch (variant) {
+        case MADE_DEC_STAGE_BWD_256_ONE: hipLaunchKernelGGL((dec_stage_bwd_kernel<4, 0>), grid, block, 0, st, a); break;
+        case MADE_DEC_STAGE_BWD_256_ADD: hipLaunchKernelGGL((dec_stage_bwd_kernel<4, 1>), grid, block, 0, st, a); break;
+        case MADE_DEC_STAGE_BWD_256_TWO: hipLaunchKernelGGL((dec_stage_bwd_kernel<4, 2>), grid, block, 0, st, a); break;
+        case MADE_DEC_STAGE_BWD_512_ONE: hipLaunchKernelGGL((dec_stage_bwd_kernel<8, 0>), grid, block, 0, st, a); break;
+        case MADE_DEC_STAGE_BWD_512_ADD: hipLaunchKernelGGL((dec_stage_bwd_kernel<8, 1>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((dec_stage_bwd_kernel<8, 2>), grid, block, 0, st, a); break;
     }
     return made_check_launch("made_dec_stage_bwd");
 }
 
-extern "C" int made_dec_stage(const MadeDecStageArgs* args, void* stream) {
+extern "C" int made_dec_stage_variant(const MadeDecStageArgs* args) {
     MADE_REQUIRE(args != nullptr, "made_dec_stage: null args");
     const MadeDecStageArgs& a = *args;
     MADE_REQUIRE(a.Zin && a.W && a.out, "made_dec_stage: null Zin, W or out");
@@ -627,14 +634,20 @@ extern "C" int made_dec_stage(const MadeDecStageArgs* args, void* stream) {
     // two instances per width: the eval chain (f32 raw rows, no dropout) and the training chain (bf16 rows, dropout, a_out)
     MADE_UNSUPPORTED((a.zin_dtype == MADE_BF16) == train || !train, "made_dec_stage: dropout / a_out need bf16 Zin rows");
     const bool tr = a.zin_dtype == MADE_BF16;
+    return a.K == 512 ? (tr ? MADE_DEC_STAGE_512_BF16 : MADE_DEC_STAGE_512_F32) : (tr ? MADE_DEC_STAGE_256_BF16 : MADE_DEC_STAGE_256_F32);
+}
+
+extern "C" int made_dec_stage(const MadeDecStageArgs* args, void* stream) {
+    const int variant = made_dec_stage_variant(args);
+    if (variant < 0) return variant;
+    const MadeDecStageArgs& a = *args;
     const dim3 grid((unsigned)((a.N + DS_BN - 1) / DS_BN), (unsigned)((a.M + DS_BM - 1) / DS_BM)), block(DS_THREADS);
     hipStream_t st = (hipStream_t)stream;
-    if (a.K == 512) {
-        if (tr) hipLaunchKernelGGL((dec_stage_kernel<8, true, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((dec_stage_kernel<8, false, false>), grid, block, 0, st, a);
-    } else {
-        if (tr) hipLaunchKernelGGL((dec_stage_kernel<4, true, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((dec_stage_kernel<4, false, false>), grid, block, 0, st, a);
+    switch (variant) {
+        case MADE_DEC_STAGE_256_F32: hipLaunchKernelGGL((dec_stage_kernel<4, false, false>), grid, block, 0, st, a); break;
+        case MADE_DEC_STAGE_256_BF16: hipLaunchKernelGGL((dec_stage_kernel<4, true, true>), grid, block, 0, st, a); break;
+        case MADE_DEC_STAGE_512_F32: hipLaunchKernelGGL((dec_stage_kernel<8, false, false>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((dec_stage_kernel<8, true, true>), grid, block, 0, st, a); break;
     }
     return made_check_launch("made_dec_stage");
 }

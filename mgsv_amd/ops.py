@@ -351,47 +351,66 @@ def splitk_finish(ws: Tensor, split_k: int, M: int, N: int, bias: Optional[Tenso
     check(lib().made_splitk_finish(C.byref(f), _stream()), "made_splitk_finish")
 
 
-def dec_stage(Zin: Tensor, W: Tensor, bias: Optional[Tensor], out: Tensor, *, ln=None, ln2=None, x2_out: Optional[Tensor] = None,
-              add: Optional[Tensor] = None, x_out: Optional[Tensor] = None, R: Optional[Tensor] = None, res_from_x: bool = False,
-              act: int = ACT_NONE, eps: float = 1e-5, a_out: Optional[Tensor] = None, drop=None, drop_ld: Optional[int] = None,
-              drop_col_div: int = 1) -> Tensor:
-    """One decoder stage with the previous stage's LayerNorm in its prologue (made_dec_stage): x = LayerNorm(Zin; ln) (ln = (gamma,
-    beta) or None: x = Zin), x2_out = LayerNorm(x; ln2), x_out = bf16(x), out = dropout(act((x + add) W^T + bias)) + R (or + x).
-    Zin [M, K] f32 (eval chain) or bf16 (training chain: then a_out = bf16(x) + add and drop = (seed, site, p) are available);
-    W [N, K] bf16; add [rows, K] bf16 (row modulo); R [M, N] bf16; out [M, N] f32 or bf16."""
+# made_dec_stage_variant codes (include/made_hip.h: MadeDecStageVariant)
+DEC_STAGE_VARIANTS = {0: "dec_stage_kernel<4,f32>", 1: "dec_stage_kernel<4,bf16>", 2: "dec_stage_kernel<8,f32>", 3: "dec_stage_kernel<8,bf16>"}
+
+
+def dec_stage_args(Zin: Tensor, W: Tensor, bias: Optional[Tensor], out: Tensor, *, ln=None, ln2=None, x2_out: Optional[Tensor] = None,
+                   add: Optional[Tensor] = None, add_row_mod: Optional[int] = None, x_out: Optional[Tensor] = None, R: Optional[Tensor] = None,
+                   res_from_x: bool = False, act: int = ACT_NONE, eps: float = 1e-5, a_out: Optional[Tensor] = None, drop=None,
+                   drop_ld: Optional[int] = None, drop_col_div: int = 1, launchable: bool = True) -> MadeDecStageArgs:
+    """the MadeDecStageArgs of a dec_stage() call: every field filled, nothing launched (dec_stage() calls this, then made_dec_stage).
+    add_row_mod: the rows of `add` that are used (default: all of them).  launchable=False takes tensors of any device, for a
+    made_dec_stage_variant question asked without a GPU; such arguments are never handed to made_dec_stage."""
+    ptr = _p if launchable else _host_ptr
     assert Zin.dim() == 2 and W.dim() == 2 and out.dim() == 2 and W.dtype == torch.bfloat16
     assert Zin.stride(1) == 1 and W.stride(1) == 1 and out.stride(1) == 1
     M, K = Zin.shape
     N = W.shape[0]
     assert W.shape[1] == K and tuple(out.shape) == (M, N)
     a = MadeDecStageArgs()
-    a.Zin, a.ldz, a.zin_dtype = _p(Zin), Zin.stride(0), dt_of(Zin)
+    a.Zin, a.ldz, a.zin_dtype = ptr(Zin), Zin.stride(0), dt_of(Zin)
     if ln is not None:
-        a.ln_g, a.ln_b = _p(_f32(ln[0], "ln.g")), _p(_f32(ln[1], "ln.b"))
+        a.ln_g, a.ln_b = ptr(_f32(ln[0], "ln.g")), ptr(_f32(ln[1], "ln.b"))
     if ln2 is not None:
         assert x2_out is not None and x2_out.dtype == torch.bfloat16 and x2_out.stride(1) == 1
-        a.ln2_g, a.ln2_b, a.x2_out, a.ldx2 = _p(_f32(ln2[0], "ln2.g")), _p(_f32(ln2[1], "ln2.b")), _p(x2_out), x2_out.stride(0)
+        a.ln2_g, a.ln2_b, a.x2_out, a.ldx2 = ptr(_f32(ln2[0], "ln2.g")), ptr(_f32(ln2[1], "ln2.b")), ptr(x2_out), x2_out.stride(0)
     if add is not None:
         assert add.dim() == 2 and add.dtype == torch.bfloat16 and add.is_contiguous() and add.shape[1] == K
-        a.add, a.add_row_mod = _p(add), add.shape[0]
+        assert add_row_mod is None or 1 <= add_row_mod <= add.shape[0]
+        a.add, a.add_row_mod = ptr(add), add.shape[0] if add_row_mod is None else add_row_mod
     if x_out is not None:
         assert x_out.dtype == torch.bfloat16 and x_out.stride(1) == 1 and tuple(x_out.shape) == (M, K)
-        a.x_out, a.ldx = _p(x_out), x_out.stride(0)
+        a.x_out, a.ldx = ptr(x_out), x_out.stride(0)
     if a_out is not None:
-        assert a_out.dtype == torch.bfloat16 and a_out.stride(1) == 1 and tuple(a_out.shape) == (M, K) and Zin.dtype == torch.bfloat16
-        a.a_out, a.lda_out = _p(a_out), a_out.stride(0)
+        assert a_out.dtype == torch.bfloat16 and a_out.stride(1) == 1 and tuple(a_out.shape) == (M, K)
+        a.a_out, a.lda_out = ptr(a_out), a_out.stride(0)
     if drop is not None and drop[2] > 0.0:
-        assert Zin.dtype == torch.bfloat16
         set_drop(a.drop, drop)
         a.drop_ld = N if drop_ld is None else drop_ld
         a.drop_col_div = int(drop_col_div)
-    a.W, a.ldw, a.bias = _p(W), W.stride(0), _p(_f32(bias, "bias"))
+    a.W, a.ldw, a.bias = ptr(W), W.stride(0), ptr(_f32(bias, "bias"))
     if R is not None:
         assert R.dtype == torch.bfloat16 and R.stride(1) == 1 and tuple(R.shape) == (M, N)
-        a.R, a.ldr = _p(R), R.stride(0)
-    a.out, a.ldo, a.out_dtype = _p(out), out.stride(0), dt_of(out)
+        a.R, a.ldr = ptr(R), R.stride(0)
+    a.out, a.ldo, a.out_dtype = ptr(out), out.stride(0), dt_of(out)
     a.act, a.res_from_x, a.eps = act, 1 if res_from_x else 0, eps
     a.M, a.N, a.K = M, N, K
+    return a
+
+
+def dec_stage_variant(*args, **kw) -> int:
+    """made_dec_stage_variant of a dec_stage() call on tensors of any device (no launch): the instance code, or the negative status"""
+    return lib().made_dec_stage_variant(C.byref(dec_stage_args(*args, launchable=False, **kw)))
+
+
+def dec_stage(Zin: Tensor, W: Tensor, bias: Optional[Tensor], out: Tensor, **kw) -> Tensor:
+    """One decoder stage with the previous stage's LayerNorm in its prologue (made_dec_stage): x = LayerNorm(Zin; ln) (ln = (gamma,
+    beta) or None: x = Zin), x2_out = LayerNorm(x; ln2), x_out = bf16(x), out = dropout(act((x + add) W^T + bias)) + R (or + x).
+    Zin [M, K] f32 (eval chain) or bf16 (training chain: then a_out = bf16(x) + add and drop = (seed, site, p) are available);
+    W [N, K] bf16; add [rows, K] bf16 (row modulo); R [M, N] bf16; out [M, N] f32 or bf16.  Keywords: see dec_stage_args."""
+    a = dec_stage_args(Zin, W, bias, out, **kw)
+    (M, K), N = Zin.shape, W.shape[0]
     _timed("dec_stage_kernel", 2.0 * M * N * K, float(M * K * Zin.element_size() * ((N + 31) // 32) + N * K * 2 + M * N * out.element_size()),
            lambda: check(lib().made_dec_stage(C.byref(a), _stream()), "made_dec_stage"), f"M={M} N={N} K={K}")
     return out

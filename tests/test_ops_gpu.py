@@ -141,7 +141,8 @@ def test_linear_big_tile_fast_epilogue(dev, M, N, K, act, tile, monkeypatch):
 @pytest.mark.parametrize("variant", ["plain", "ln_add_xout", "ln_ln2_resx", "ln_R_relu_bf16"])
 def test_dec_stage(dev, M, N, K, variant):
     """made_dec_stage (one stage of the fused decoder chain): LayerNorm prologue, second norm output, + add, x written out, Linear,
-    activation, residual from R or from x, f32 / bf16 output -- against the same math in f32 on bf16-rounded operands."""
+    activation, residual from R or from x, f32 / bf16 output -- against the same math in f32 on bf16-rounded operands.
+    (The tighter check of every instance, option and edge against float64 is tests/test_dec_stage_parity_gpu.py.)"""
     if variant == "ln_ln2_resx" and N != K:
         pytest.skip("res_from_x needs N == K")
     z, W, b = rnd(M, K, seed=1) * 2 + 0.3, rnd(N, K, seed=2) / math.sqrt(K), rnd(N, seed=3) * 0.1

@@ -799,7 +799,8 @@ def test_posbn_relu_forward_backward_match_torch_batchnorm(T, dtype, tol, B, Tn,
 def test_dec_stage_training_options_match_the_separate_launches(T, D, N, p):
     """made_dec_stage with bf16 raw rows: LayerNorm prologue (+ add), x_out / a_out, ReLU, dropout per element and per group of
     columns -- against made_layernorm_add + made_linear with the same stateless masks (reference music_detr/transformer.py:273-307
-    forward_post in train mode).  The dropout pattern is identical; values agree to bf16 rounding (one rounding point differs)."""
+    forward_post in train mode).  The dropout pattern is identical; values agree to bf16 rounding (one rounding point differs).
+    (The tighter check, against float64 with the keep mask bit for bit, is tests/test_dec_stage_parity_gpu.py.)"""
     ops, tr = T
     M = 64
     z = _rand(M, D, dtype=torch.bfloat16, seed=1)
@@ -1019,7 +1020,8 @@ def test_two_chained_layernorms_backward(T, dtype, tol, rows, D):
 def test_dec_stage_bwd_matches_the_separate_launches(T, D, N, mode, gate, col_div):
     """made_dec_stage_bwd (a LayerNorm backward -- or norm 3 + the output norm -- in the prologue of the dX product that consumes it)
     against made_layernorm_bwd / made_layernorm_bwd2 + made_linear with the same stateless masks: same dropout pattern, values to
-    bf16 rounding, parameter gradients to f32 summation order."""
+    bf16 rounding, parameter gradients to f32 summation order.
+    (The tighter check, against float64 row by row and on rows that are not centred, is tests/test_dec_stage_parity_gpu.py.)"""
     ops, tr = T
     from mgsv_amd import _lib
     M, p = 64, 0.1
