@@ -1661,6 +1661,70 @@ int made_bar_pick(const float* B, const int64_t* beat_start, const float* time, 
                   int32_t metre_mask, int32_t low_bins, float low_weight, int32_t min_bars, float min_strength, float* evidence,
                   int32_t* metre, int32_t* phase, float* strength, float* down_time, int64_t cap_d, int32_t* down_count, void* stream);
 
+/* ---- Section boundaries (mgsv_amd/sections.py; csrc/sections.hip) ---------------------------------------------------------------
+ * Where the timbre of a track changes, from its beat-synchronous spectra B (made_beat_sync_mean).  A boundary list is again "a CSR of
+ * ascending times per track": made_fit_moments and made_sync_moments take it where they take the onsets, the beats or the downbeats.
+ * The rule is Foote's novelty -- a checkerboard kernel slid along the diagonal of the cosine self-similarity matrix -- with the
+ * rank-one kernel C(i, j) = c_i c_j (a sign pattern times a separable taper), for which sum_ij c_i c_j <u_{k+i}, u_{k+j}> is the
+ * squared distance between the weighted sum of the L beats after beat k and that of the L beats before it: no n x n matrix is
+ * formed and B is read once.  The reference has no counterpart.
+ *
+ * made_section_novelty.  B [total, 128] f32, beat_start [N + 1] device int64 (track t has the rows r0 = beat_start[t] .. r1 =
+ * beat_start[t + 1], n = r1 - r0 beats), weights [L] device f32 (ops.section_weights: the taper, computed on the host, so no device
+ * expf enters the contract), 1 <= L <= 64; output novelty [total] f32.  Every step is one rounded f32 operation (no contraction).
+ * Per track:
+ *   1. For each beat k: m = (the sum of the row's 128 bins) * 2^-7, x = B[k] - m, q = sum x * x, and u_k = x / sqrt(q) (a correctly
+ *      rounded square root, then one division per bin) when q > 0 and q is finite, a row of +0 otherwise (a silent or constant beat,
+ *      a row holding a NaN or an infinity).
+ *   2. For L <= k <= n - L: a = sum_{i = 0}^{L - 1} weights[i] * u_{k + i}, b = sum_{i = 0}^{L - 1} weights[i] * u_{k - 1 - i} (per
+ *      bin), novelty[k] = sum over the 128 bins of (a - b) * (a - b).  Every other beat of the track gets exactly +0; with n < 2 L
+ *      the whole track is zeros.
+ * Summation orders (they depend on L and on nothing else: not on k, n, N, total, the track's place in the batch or the tile of the
+ * launch a beat falls in, so a track's novelty has the same bits alone and in any batch).  A 128-term sum (m, q, novelty) meets as
+ * t[l] + t[l + 64] for l = 0 .. 63, then in the tree of depth 6 over l that made_bar_pick's step 1 states: 7 rounded additions on a
+ * term's way.  An L-term sum (a, b) is one chain per bin, i ascending from +0, each product rounded before it is added: a term
+ * passes through its product and at most L additions (the first one, to +0, is exact).  Error, to first order with eps = 2^-24:
+ * |m - exact| <= 7 eps mean|B[k]|, so the computed x is off by dx with |dx|_2 <= sqrt(128) 7 eps mean|B[k]| + eps |x|_2, and
+ * |u_k - exact|_2 <= e_k = 2 |dx|_2 / |x|_2 + 6 eps (the squares, the 7 additions, the root and the division scale a unit vector);
+ * |a - exact|_2 <= sum_i weights[i] (e_{k+i} + (L + 1) eps), likewise b; with d = a - b and E = the two of them + eps |d|_2,
+ * |novelty - exact| <= 2 |d|_2 E + E^2 + 8 eps novelty (tests/sections_ref.py computes exactly this from the inputs).  The bound
+ * grows with mean|B[k]| / |x|_2: a nearly constant row has no direction to speak of.
+ * A track whose range is negative or runs outside [0, total] (r0 < 0, r1 < r0, r1 > total) is skipped: nothing of it is read or
+ * written and its neighbours are unaffected.  A workgroup of sixteen waves takes 64 beats of one track: the tile's rows and L rows
+ * either side are normalised into LDS once, a wave taking two rows at a time, ((64 + 2 L) * 512 bytes of dynamic LDS: 96 KB at L =
+ * 64, 48 KB at L = 16); then a wave per beat walks the 2 L rows of LDS.  A track of any length is walked tile by tile (grid (N, min(ceil(total / 64),
+ * 1024)), a block striding over the rest).  No atomics, no workspace, no scratch.  N == 0 or total == 0 is a no-op.  Refused before
+ * any launch: negative sizes, L outside [1, 64], N or total >= 2^31, a null pointer with total > 0. */
+int made_section_novelty(const float* B, const int64_t* beat_start, int64_t N, int64_t total, const float* weights, int32_t L,
+                         float* novelty, void* stream);
+
+/* made_section_pick: the boundaries of N tracks from their novelty.  novelty [total] f32, beat_start as above, time [N, cap] f32 the
+ * beat times (made_beat_track's), metre / phase [N] device int32 or both NULL (made_bar_pick's), 1 <= L <= 64 (the novelty's), 1 <=
+ * w <= 256, thresh_factor and floor finite f32.  Outputs bound_time / bound_strength [N, cap_s] f32, bound_beat [N, cap_s] int32,
+ * bound_count [N] int32, mean [N] f32.  Every step is one rounded f32 operation.  Per track:
+ *   1. The candidates are the beats k with L <= k <= n - L; when metre != NULL and metre[t] > 0 only those with (k - phase[t]) mod
+ *      metre[t] == 0 (the mathematical, non-negative remainder): a section starts on a bar line when the track has one.
+ *   2. mean[t] = (novelty summed over the candidates: one chain, ascending, from +0) / (float)(their number); NaN without candidates.
+ *   3. thresh = mean[t] * thresh_factor (the host passes 1 + delta).  Candidate k with x = novelty[k] is a boundary iff x > 0, x >
+ *      novelty[j] for every candidate j in [k - w, k), x >= novelty[j] for every candidate j in (k, k + w], x >= floor and x >= thresh.
+ *      Of equal neighbours the earlier wins; a NaN anywhere in the window, or a NaN mean, makes no boundary.  Two boundaries are
+ *      therefore at least w + 1 beats apart, no greedy
+ *      pass is needed and the rule is decided per beat.
+ *   4. The boundaries are written ascending in k: bound_time[t * cap_s + i] = time[t * cap + k] (the beat's own f32 time), bound_beat =
+ *      k, bound_strength = x / mean[t].  bound_count[t] = their number; entries from bound_count on are not written.  A track with
+ *      more than cap_s boundaries gets bound_count = -1 (its first cap_s entries hold its first cap_s boundaries).  cap_s >=
+ *      ceil(cap / (w + 1)) cannot overflow.
+ * A track whose list does not fit its arrays (n < 0, n > cap, rows outside [0, total]) gets bound_count = -1 and mean = NaN, and
+ * nothing of it is read.  One workgroup of four waves per track: the novelty is staged through LDS 1024 beats at a time, one thread
+ * walks the chain of step 2, then every thread decides beats of step 3 and each quarter of a pass is compacted in beat order -- a
+ * ballot and a prefix popcount inside the wave, the waves' counts through LDS, a running offset -- as made_onset_peaks does.  No
+ * atomics, no workspace, no scratch.  N == 0 is a no-op.  Refused: negative sizes, L outside [1, 64], w outside [1, 256], a
+ * thresh_factor or floor that is not finite, metre without phase, N or total >= 2^31, null pointers (novelty may be NULL when total
+ * == 0, time when cap == 0, the three lists when cap_s == 0). */
+int made_section_pick(const float* novelty, const int64_t* beat_start, const float* time, int64_t cap, int64_t N, int64_t total,
+                      const int32_t* metre, const int32_t* phase, int32_t L, int32_t w, float thresh_factor, float floor, float* bound_time,
+                      int32_t* bound_beat, float* bound_strength, int64_t cap_s, int32_t* bound_count, float* mean, void* stream);
+
 /* ---- Cuts (mgsv_amd/cuts.py; csrc/cuts.hip) -------------------------------------------------------------------------------------
  * Where a video's shots change, from its decoded frames: the list made_sync_moments takes as cut_start / cut_time.  A video is F
  * frames of one size H x W, RGB uint8 interleaved [H, W, 3]; P = H * W, 1 <= P <= 2^24; videos of mixed sizes may share a call.

@@ -364,6 +364,8 @@ SIGNATURES = {
     "made_beat_track": (C.c_int, [vp, i64, vp, vp, vp, i64, f32, i64, vp, vp, vp, vp, vp]),
     "made_beat_sync_mean": (C.c_int, [vp, i64, vp, vp, i64, vp, vp, i64, i64, vp, vp]),
     "made_bar_pick": (C.c_int, [vp, vp, vp, i64, i64, i64, i32, i32, f32, i32, f32, vp, vp, vp, vp, vp, i64, vp, vp]),
+    "made_section_novelty": (C.c_int, [vp, vp, i64, i64, vp, i32, vp, vp]),
+    "made_section_pick": (C.c_int, [vp, vp, vp, i64, i64, i64, vp, vp, i32, i32, f32, f32, vp, vp, vp, i64, vp, vp, vp]),
     "made_frame_hist": (C.c_int, [vp, i64, vp, i64, vp, vp]),
     "made_hist_distance": (C.c_int, [vp, vp, i64, vp, vp]),
     "made_cut_peaks": (C.c_int, [vp, i64, vp, i64, vp, i32, i32, i32, i64, vp, vp, vp, vp]),

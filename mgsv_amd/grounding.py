@@ -30,7 +30,8 @@ a tolerance; the grounded moments stay in `raw_start` / `raw_end`.  Without it n
 video is cut) the launch is made_sync_moments instead: the start is chosen so that the video's beginning and its cuts land on attacks,
 and `anchor`, `sync` and `hits` say how well they do.  With `Fit.grid = "beats"` the table of either launch is the track's beat grid
 (mgsv_amd/beats.py, `beats=`) instead of its onsets, and `tempo` is set; with `Fit.grid = "downbeats"` it is the track's downbeats
-(mgsv_amd/bars.py, `bars=`), and `metre` is set.
+(mgsv_amd/bars.py, `bars=`), and `metre` is set; with `Fit.grid = "sections"` it is the track's section boundaries
+(mgsv_amd/sections.py, `sections=`), and `boundary_strength` is set.
 
 A pair's localization depends on that pair's video and track only (every kernel after the towers computes a sample's rows
 independently of the rest of the batch), so the moment found in the ground-truth track is the one the batched evaluation scores.
@@ -79,6 +80,7 @@ class Grounding:
     hits: Optional[Tensor] = None          # ... and how many of them land within cut_tol of one, int32 (-1 where there is no moment)
     tempo: Optional[Tensor] = None         # fitted with Fit.grid = "beats" (`onset` then indexes the track's beats): the track's tempo, f32 BPM, the shape of track (NaN: no track or no tempo)
     metre: Optional[Tensor] = None         # fitted with Fit.grid = "downbeats" (`onset` then indexes the track's downbeats): the track's metre, int32 beats per bar, the shape of track (0: no metre, -1: no track)
+    boundary_strength: Optional[Tensor] = None  # fitted with Fit.grid = "sections" (`onset` then indexes the track's boundaries): the strength of the boundary the start was snapped to, f32, the shape of track (of a track's first moment where it has several; NaN: not snapped or no track)
 
     @property
     def k(self) -> int:
@@ -93,7 +95,8 @@ class Grounding:
         every moment's -- dict also holds "raw_start", "raw_end" and "snapped" (whether the start or a cut was put on an onset), and, fitted
         to the video's cuts (`anchor` is set), "anchor", "sync" and "hits" beside them.  Fitted on the beat grid (`tempo` is set), every
         track's dict also holds "grid": "beats" and "tempo" (BPM; None where the track has none); fitted on the downbeats (`metre` is
-        set), "grid": "downbeats" and "metre" (beats per bar; None where the track has none)."""
+        set), "grid": "downbeats" and "metre" (beats per bar; None where the track has none); fitted on the section boundaries
+        (`boundary_strength` is set), "grid": "sections" and "boundary_strength" (None where the start sits on no boundary)."""
         if self.windows is not None:
             return self._window_records(video_ids, music_ids)
         tr, sc, st, en, cf = (t.cpu().numpy() for t in (self.track, self.score, self.start, self.end, self.confidence))
@@ -121,6 +124,9 @@ class Grounding:
     def _beat_fields(self):
         """f(v, j) -> {"grid", "tempo"} of result j of video v ({"grid", "metre"} when fitted on the downbeats); nothing when the
         results were not fitted on a grid"""
+        if self.boundary_strength is not None:
+            bs = self.boundary_strength.cpu().numpy()
+            return lambda v, j: dict(grid="sections", boundary_strength=None if math.isnan(bs[v, j]) else float(bs[v, j]))
         if self.metre is not None:
             mt = self.metre.cpu().numpy()
             return lambda v, j: dict(grid="downbeats", metre=None if mt[v, j] <= 0 else int(mt[v, j]))
@@ -337,8 +343,10 @@ class Fit:
     grid (a `Beats`, mgsv_amd/beats.py: `beats=`, or a library that carries one), so that the start and the cuts land on the beat
     and not on the nearest attack.  Nothing else about the launch changes; `Grounding.onset` then indexes the track's beats and
     `Grounding.tempo` is set.  "downbeats": the track's bar lines (a `Bars`, mgsv_amd/bars.py: `bars=`, or a library that carries
-    one) in the same way; `Grounding.onset` then indexes the track's downbeats and `Grounding.metre` is set.  "beats" and
-    "downbeats" need snap."""
+    one) in the same way; `Grounding.onset` then indexes the track's downbeats and `Grounding.metre` is set.  "sections": the track's
+    section boundaries (a `Sections`, mgsv_amd/sections.py: `sections=`, or a library that carries one) in the same way;
+    `Grounding.onset` then indexes the track's boundaries and `Grounding.boundary_strength` is set.  "beats", "downbeats" and
+    "sections" need snap."""
     length: object = None
     snap: Optional[float] = None
     cuts: object = None
@@ -347,12 +355,14 @@ class Fit:
 
     def __post_init__(self):
         self._cut_csr = None
-        if self.grid not in ("onsets", "beats", "downbeats"):
-            raise ValueError(f"grid = {self.grid!r}: 'onsets', 'beats' or 'downbeats'")
+        if self.grid not in ("onsets", "beats", "downbeats", "sections"):
+            raise ValueError(f"grid = {self.grid!r}: 'onsets', 'beats', 'downbeats' or 'sections'")
         if self.grid == "beats" and self.snap is None:
             raise ValueError("Fit(grid='beats') needs snap= (how far a start may move to sit on a beat)")
         if self.grid == "downbeats" and self.snap is None:
             raise ValueError("Fit(grid='downbeats') needs snap= (how far a start may move to sit on a bar line)")
+        if self.grid == "sections" and self.snap is None:
+            raise ValueError("Fit(grid='sections') needs snap= (how far a start may move to sit on a section boundary)")
         self.cut_tol = float(self.cut_tol)
         if not (math.isfinite(self.cut_tol) and self.cut_tol > 0.0):
             raise ValueError(f"cut_tol = {self.cut_tol!r}: a tolerance in seconds, finite and > 0")
@@ -410,11 +420,19 @@ def _onsets_on(onsets, dev):
     return cache[str(dev)]
 
 
-def _fit_table(fit: Fit, onsets, beats, n_tracks: Optional[int], bars=None):
-    """the table `fit.snap` works on -- `onsets`, with fit.grid == "beats" the beat grid's, with "downbeats" the bar grid's -- checked
-    (None without snap)"""
+def _fit_table(fit: Fit, onsets, beats, n_tracks: Optional[int], bars=None, sections=None):
+    """the table `fit.snap` works on -- `onsets`, with fit.grid == "beats" the beat grid's, with "downbeats" the bar grid's, with
+    "sections" the boundaries' -- checked (None without snap)"""
     if fit.snap is None:
         return None
+    if fit.grid == "sections":
+        if sections is None:
+            raise ValueError("Fit(grid='sections') needs the tracks' sections (sections=..., or a library that carries them)")
+        if not (hasattr(sections, "table") and hasattr(sections, "strength") and hasattr(sections, "beat")):      # (by its fields, as for beats)
+            raise TypeError(f"sections must be a Sections, got {type(sections).__name__}")
+        if n_tracks is not None and len(sections) != n_tracks:
+            raise ValueError(f"the section table holds {len(sections)} tracks, there are {n_tracks}")
+        return sections.table
     if fit.grid == "downbeats":
         if bars is None:
             raise ValueError("Fit(grid='downbeats') needs the tracks' bars (bars=..., or a library that carries them)")
@@ -456,8 +474,23 @@ def _track_metre(track: Tensor, bars) -> Tensor:
     return torch.from_numpy(mt).to(track.device)
 
 
+def _boundary_strength(track: Tensor, onset: Tensor, sections) -> Tensor:
+    """f32, the shape of track: sections.strength at the boundary `onset` names inside its track's list (a track's first moment
+    where it has several), NaN where the start was not snapped or there is no track -- a gather on track's device"""
+    dev = track.device
+    start = torch.from_numpy(sections.table.start).to(dev)
+    strength = torch.from_numpy(sections.strength).to(dev)
+    on = onset.reshape(tuple(track.shape) + (-1,))[..., 0].to(torch.int64)
+    ok = (track >= 0) & (on >= 0)
+    nan = torch.full(tuple(track.shape), float("nan"), dtype=torch.float32, device=dev)
+    if strength.numel() == 0:
+        return nan
+    at = (start[track.clamp_min(0).to(torch.int64)] + on.clamp_min(0)).clamp_max(strength.numel() - 1)
+    return torch.where(ok, strength[at], nan)
+
+
 def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None, onsets=None, backend: Optional[str] = None,
-                  beats=None, bars=None) -> Grounding:
+                  beats=None, bars=None, sections=None) -> Grounding:
     """`g` with every moment fitted (made_fit_moments; include/made_hip.h states the arithmetic): given the length `fit.length` asks
     for -- centred on the grounded moment, clamped to the track -- and, with `fit.snap`, its start moved onto the track's nearest
     onset within that tolerance that still leaves the moment inside the track.  start / end become the fitted values; raw_start /
@@ -474,7 +507,8 @@ def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None
     With `fit.grid == "beats"` the table is `beats.table` (a `Beats` in the same numbering) instead of `onsets`, which is then not
     read: `onset` indexes the track's beats and `tempo` = beats.tempo[track] is set.  With `fit.grid == "downbeats"` it is
     `bars.table` (a `Bars`), neither `onsets` nor `beats` is read, `onset` indexes the track's downbeats and `metre` =
-    bars.metre[track] is set."""
+    bars.metre[track] is set.  With `fit.grid == "sections"` it is `sections.table` (a `Sections`), `onset` indexes the track's
+    boundaries and `boundary_strength` = the strength of that boundary is set."""
     if g.raw_start is not None:
         raise ValueError("this Grounding is fitted already (fit its raw_start / raw_end instead)")
     Nv = g.track.shape[0]
@@ -495,11 +529,13 @@ def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None
         want = _seconds(fit.length, Nv, "Fit.length")
     tol = 0.0
     if fit.snap is not None:
-        onsets = _fit_table(fit, onsets, beats, len(tlen), bars)
+        onsets = _fit_table(fit, onsets, beats, len(tlen), bars, sections)
         tol = fit.snap
     on_beats = dict(tempo=_track_tempo(g.track, beats)) if fit.snap is not None and fit.grid == "beats" else {}
     if fit.snap is not None and fit.grid == "downbeats":
         on_beats = dict(metre=_track_metre(g.track, bars))
+    on_sections = fit.snap is not None and fit.grid == "sections"
+    strength_of = lambda on: dict(boundary_strength=_boundary_strength(g.track, on, sections)) if on_sections else {}
     if fit._cut_csr is not None and len(fit._cut_csr[0]) - 1 != Nv:
         raise ValueError(f"Fit.cuts holds {len(fit._cut_csr[0]) - 1} rows, there are {Nv} videos")
     if backend is None:
@@ -518,7 +554,7 @@ def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None
                                    torch.from_numpy(tlen).to(dev), *_onsets_on(onsets, dev), *(torch.from_numpy(a).to(dev) for a in fit._cut_csr),
                                    snap=tol, cut_tol=fit.cut_tol)
         st, en, sh, on, an, sy, hi = (t.view(shape) for t in out)
-        return replace(g, start=st, end=en, raw_start=g.start, raw_end=g.end, shift=sh, onset=on, anchor=an, sync=sy, hits=hi, **on_beats)
+        return replace(g, start=st, end=en, raw_start=g.start, raw_end=g.end, shift=sh, onset=on, anchor=an, sync=sy, hits=hi, **on_beats, **strength_of(on))
     if backend == "host":
         out = ops.fit_moments(g.start.reshape(-1), g.end.reshape(-1), _entry_tracks(g.track, shape), expand(torch.from_numpy(want)), tlen,
                               None if tol == 0.0 else onsets.start, None if tol == 0.0 else onsets.time, tol, backend="host")
@@ -528,10 +564,10 @@ def fit_grounding(g: Grounding, fit: Fit, video_duration=None, track_length=None
         st, en, sh, on = (t.view(shape) for t in ops.fit_moments(
             g.start.to(torch.float32).contiguous().reshape(-1), g.end.to(torch.float32).contiguous().reshape(-1),
             _entry_tracks(g.track, shape), expand(torch.from_numpy(want).to(dev)), torch.from_numpy(tlen).to(dev), table[0], table[1], tol))
-    return replace(g, start=st, end=en, raw_start=g.start, raw_end=g.end, shift=sh, onset=on, **on_beats)
+    return replace(g, start=st, end=en, raw_start=g.start, raw_end=g.end, shift=sh, onset=on, **on_beats, **strength_of(on))
 
 
-def _check_fit(fit: Optional[Fit], videos: Encoded, onsets, beats=None, n_tracks: Optional[int] = None, bars=None) -> None:
+def _check_fit(fit: Optional[Fit], videos: Encoded, onsets, beats=None, n_tracks: Optional[int] = None, bars=None, sections=None) -> None:
     """the ValueErrors of `fit_grounding` that need no result, raised before anything is computed"""
     if fit is None:
         return
@@ -539,8 +575,8 @@ def _check_fit(fit: Optional[Fit], videos: Encoded, onsets, beats=None, n_tracks
         raise TypeError(f"fit must be a Fit, got {type(fit).__name__}")
     if isinstance(fit.length, str) and videos.duration is None:
         raise ValueError("Fit(length='video') needs the videos' durations (videos.duration is None)")
-    if fit.grid in ("beats", "downbeats"):
-        _fit_table(fit, onsets, beats, n_tracks, bars)
+    if fit.grid in ("beats", "downbeats", "sections"):
+        _fit_table(fit, onsets, beats, n_tracks, bars, sections)
     elif fit.snap is not None and onsets is None:
         raise ValueError("Fit(snap=...) needs the tracks' onsets (onsets=..., or a library that carries them)")
     if fit._cut_csr is not None and len(fit._cut_csr[0]) - 1 != len(videos):
@@ -848,7 +884,8 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
            pair_batch: int = 64, windows: Optional[Windows] = None, windows_per_track: int = 1, moments: int = 1,
            nms_iou: float = 0.5, constraints: Optional[Constraints] = None, tags=None, length=None,
            shortlist: Optional[int] = None, diversity: Optional[float] = None, max_similarity: Optional[float] = None,
-           pool: Optional[int] = None, candidates=None, fit: Optional[Fit] = None, onsets=None, beats=None, bars=None) -> Grounding:
+           pool: Optional[int] = None, candidates=None, fit: Optional[Fit] = None, onsets=None, beats=None, bars=None,
+           sections=None) -> Grounding:
     """Each video's best k tracks (groups of columns sharing a music id when group_id [N_m] is given) and the moment in each.
     constraints: per-video `Constraints` on the tracks' `tags` (int64 [tracks]) and `length` (f32 seconds [tracks]; default: the
     durations) -- the selection then runs on every row with its ineligible columns removed (made_eligibility, then the masked
@@ -877,14 +914,15 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     within `snap` seconds (with `Fit.cuts`: chosen within `snap` so that the video's cuts land on onsets; `anchor`, `sync` and `hits`
     are then set too).  onsets: the `Onsets` table of the tracks, in `Grounding.track`'s numbering (mgsv_amd/onsets.py); beats: their
     `Beats` (mgsv_amd/beats.py), the table `Fit(grid="beats")` works on instead -- `tempo` is then set too; bars: their `Bars`
-    (mgsv_amd/bars.py), the table of `Fit(grid="downbeats")` -- `metre` is then set.  The
+    (mgsv_amd/bars.py), the table of `Fit(grid="downbeats")` -- `metre` is then set; sections: their `Sections`
+    (mgsv_amd/sections.py), the table of `Fit(grid="sections")` -- `boundary_strength` is then set.  The
     track length is what the moments were clamped to: min(max_m_duration, duration) per column, `default_length` over windows."""
     dev = engine.device
     Nv, Nm = len(videos), len(music)
     candidates = check_candidates(engine.cfg, candidates, Nv, shortlist, sims is not None)
     shortlist = check_shortlist(engine.cfg, shortlist, sims is not None)
     div = check_diversity(k, diversity, max_similarity, pool)
-    _check_fit(fit, videos, onsets, beats, windows.n_tracks if windows is not None else Nm, bars)
+    _check_fit(fit, videos, onsets, beats, windows.n_tracks if windows is not None else Nm, bars, sections)
     if shortlist is None and candidates is None:
         if sims is None:
             sims = similarity_matrix(engine, videos.vec, music.tokens, music.mask, music.vec)
@@ -925,7 +963,7 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     if windows is not None:
         g = _ground_windows(engine, videos, music, k, sims, group_id, pair_batch, windows, windows_per_track, moments, float(nms_iou),
                             bits, cand, div)
-        return g if fit is None else fit_grounding(g, fit, videos.duration, default_length(music.duration, windows), onsets, beats=beats, bars=bars)
+        return g if fit is None else fit_grounding(g, fit, videos.duration, default_length(music.duration, windows), onsets, beats=beats, bars=bars, sections=sections)
     gid, G = _group_tensor(group_id, Nm, dev)
     kk = max(1, min(int(k), G))
     ks = _pool_size(div, kk, G)
@@ -944,7 +982,7 @@ def ground(engine: MadeEngine, videos: Encoded, music: Encoded, k: int, sims: Op
     g = Grounding(track=track, score=score, start=start.view(Nv, kk), end=end.view(Nv, kk), confidence=conf.view(Nv, kk),
                   cand_col=None if cand is None else cand[0], cand_score=None if cand is None else cand[1],
                   pool_rank=pool_rank, redundancy=redundancy)
-    return g if fit is None else fit_grounding(g, fit, videos.duration, clamp_length(music.duration, Nm, engine.cfg.max_m_duration), onsets, beats=beats, bars=bars)
+    return g if fit is None else fit_grounding(g, fit, videos.duration, clamp_length(music.duration, Nm, engine.cfg.max_m_duration), onsets, beats=beats, bars=bars, sections=sections)
 
 
 def _pad_pairs(vi: Tensor, mi: Tensor, min_pairs: int):
@@ -1554,7 +1592,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     library's slices and listed columns are widened into a scratch buffer; localization and the shortlist's second stage gather
     and widen the distinct selected columns (the whole library is never widened).  timings then receives dequantize_ms.
     fit = Fit(length=, snap=): `ground(..., fit=fit, onsets=library.onsets)` for the stored library, bit for bit, in every placement:
-    one made_fit_moments launch (made_sync_moments with `fit.cuts`) on the finished Grounding (`fit_grounding`) against `library.fit_length` and `library.onsets` (`library.beats` with `Fit(grid="beats")`, `library.bars` with `Fit(grid="downbeats")`).
+    one made_fit_moments launch (made_sync_moments with `fit.cuts`) on the finished Grounding (`fit_grounding`) against `library.fit_length` and `library.onsets` (`library.beats` with `Fit(grid="beats")`, `library.bars` with `Fit(grid="downbeats")`, `library.sections` with `Fit(grid="sections")`).
     fit None (the default): none of it runs."""
     c = engine.cfg
     dev = engine.device
@@ -1562,7 +1600,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
     shortlist = check_shortlist(c, shortlist, sims_fn is not None)
     div = check_diversity(k, diversity, max_similarity, pool)
     if fit is not None:
-        _check_fit(fit, videos, library.onsets, library.beats, library.n_tracks, library.bars)
+        _check_fit(fit, videos, library.onsets, library.beats, library.n_tracks, library.bars, library.sections)
     if c.moment_query_type == "xpool":
         raise NotImplementedError("moment_query_type=xpool: the decoder query is the track's pooled vector averaged over the videos of "
                                   "the batch (reference model/model_Uni.py:222-223), a property of the batch with no per-pair meaning")
@@ -1668,7 +1706,7 @@ def ground_library(engine: MadeEngine, videos: Encoded, library, k: int, pair_ba
         g = Grounding(track=_window_tracks(rep, track_of_col), score=score, start=start, end=end, confidence=conf,
                       window=torch.cat([p[3] for p in parts]), windows=windows, cand_col=cc, cand_score=cs,
                       pool_rank=pool_rank, redundancy=redundancy)
-    return g if fit is None else fit_grounding(g, fit, videos.duration, library.fit_length(c.max_m_duration), library.onsets, beats=library.beats, bars=library.bars)
+    return g if fit is None else fit_grounding(g, fit, videos.duration, library.fit_length(c.max_m_duration), library.onsets, beats=library.beats, bars=library.bars, sections=library.sections)
 
 
 def moment_iou(start: Tensor, end: Tensor, gt_moment: Tensor, m_duration: Tensor, max_m_duration: float) -> Tensor:

@@ -21,6 +21,10 @@ Optional bar grids for `ground_library(..., fit=Fit(snap=..., grid="downbeats"))
 + 1] and bar_time.npy f32, the tracks' downbeats as a CSR, bar_metre.npy int32 [n_tracks] (0: no metre), bar_phase.npy int32 and
 bar_strength.npy f32, and the manifest's "bars" entry holding the detection parameters; a directory without them loads as a library
 without bars.
+Optional section boundaries for `ground_library(..., fit=Fit(snap=..., grid="sections"))` (mgsv_amd/sections.py): section_start.npy
+int64 [n_tracks + 1] and section_time.npy f32, the tracks' boundaries as a CSR, section_beat.npy int32 and section_strength.npy f32,
+one entry per boundary, section_mean.npy f32 [n_tracks], and the manifest's "sections" entry holding the detection parameters; a
+directory without them loads as a library without sections.
 
 FP8 token storage (dtype "fp8"): tokens.npy is uint8 [N, S, D], one OCP e4m3fn byte per value, and tokens_exp.npy int8 [N, S] holds
 one power-of-two exponent per token row (the format: include/made_hip.h, csrc/fp8_format.h); the manifest says "dtype": "fp8" and
@@ -202,7 +206,8 @@ class MusicLibrary:
 
     def __init__(self, tokens, mask, vec, col_group, source, dtype: str, duration=None, windows: Optional[Windows] = None,
                  ids: Optional[Sequence] = None, group_id=None, tags=None, length=None, tag_names: Optional[Sequence[str]] = None,
-                 tokens_exp=None, compute: Optional[str] = None, onsets=None, beats=None, bars=None):
+                 tokens_exp=None, compute: Optional[str] = None, onsets=None, beats=None, bars=None,
+                 sections=None):
         if dtype not in ("f32", "bf16", "fp8"):
             raise ValueError(f"dtype = {dtype!r}: a library holds f32, bf16 or fp8 tokens")
         self.tokens, self.mask, self.vec, self.duration = tokens, mask, vec, duration
@@ -256,6 +261,8 @@ class MusicLibrary:
         self.set_beats(beats)
         self.bars = None
         self.set_bars(bars)
+        self.sections = None
+        self.set_sections(sections)
         self._device_attrs: Dict[str, tuple] = {}                  # ground_library's column attributes, uploaded once per device
         self._plans: Dict[int, dict] = {}
         self._stages: Dict[str, object] = {}                       # ground_library's pinned staging sets, reused across calls
@@ -318,6 +325,13 @@ class MusicLibrary:
             raise ValueError(f"bars needs one entry per track ({self.n_tracks}), got {len(bars)}")
         self.bars = bars
 
+    def set_sections(self, sections) -> None:
+        """Attach (or with None remove) the tracks' section boundaries, an `mgsv_amd.sections.Sections` with one entry per track in
+        this library's numbering (`ids`' order)."""
+        if sections is not None and len(sections) != self.n_tracks:
+            raise ValueError(f"sections needs one entry per track ({self.n_tracks}), got {len(sections)}")
+        self.sections = sections
+
     def fit_length(self, max_m_duration: float) -> np.ndarray:
         """f32 [tracks]: the length `ground_library` clamps a track's moments to, and `fit_grounding` fits them in: min(max_m_duration,
         duration) per column without windows, the end of the track's last window with them (computed once)."""
@@ -364,13 +378,13 @@ class MusicLibrary:
     @classmethod
     def build(cls, music: Encoded, group_id=None, windows: Optional[Windows] = None, ids: Optional[Sequence] = None, tags=None,
               length=None, tag_names: Optional[Sequence[str]] = None, onsets=None, beats=None,
-              bars=None) -> "MusicLibrary":
+              bars=None, sections=None) -> "MusicLibrary":
         """A host library of an `Encoded` (device or host tensors).  group_id: one entry per column, or per TRACK with windows.
         Columns are reordered only if a group's columns are not contiguous: groups by first appearance, stable inside a group.
         The Windows keep their track numbering; only the per-column arrays are permuted (and `ids`, one per column, without
         windows).  tags (int64) / length (f32 seconds): one entry per track, permuted like `ids`.  onsets: an `Onsets` table
         (mgsv_amd/onsets.py), one entry per track, permuted like `ids`, too; beats: a `Beats` (mgsv_amd/beats.py), likewise; bars: a `Bars`
-        (mgsv_amd/bars.py), likewise."""
+        (mgsv_amd/bars.py), likewise; sections: a `Sections` (mgsv_amd/sections.py), likewise."""
         N = len(music)
         gid = None if group_id is None else _host(group_id, np.int32).reshape(-1)
         if windows is not None:
@@ -411,6 +425,10 @@ class MusicLibrary:
             raise ValueError("bars needs one entry per track")
         if windows is None and bars is not None and not same:
             bars = bars.take(order)
+        if sections is not None and len(sections) != (windows.n_tracks if windows is not None else N):
+            raise ValueError("sections needs one entry per track")
+        if windows is None and sections is not None and not same:
+            sections = sections.take(order)
         if windows is None:
             if ids is not None and not same:
                 ids = [ids[i] for i in order]
@@ -419,7 +437,8 @@ class MusicLibrary:
             length = None if length is None else take(length)
         return cls(take(_tokens_to_host(music.tokens)), take(_host(music.mask, np.float32)), take(_host(music.vec, np.float32)),
                    take(col_group), order, _dtype_name(music.tokens.dtype), duration=dur, windows=win, ids=ids, group_id=gid,
-                   tags=tags, length=length, tag_names=tag_names, onsets=onsets, beats=beats, bars=bars)
+                   tags=tags, length=length, tag_names=tag_names, onsets=onsets, beats=beats, bars=bars,
+                   sections=sections)
 
     def to(self, device) -> "MusicLibrary":
         """The same library with tokens / mask / vec / duration as tensors on `device` (the host tables stay on the host)."""
@@ -430,7 +449,7 @@ class MusicLibrary:
                             duration=None if self.duration is None else up(self.duration), windows=self.windows, ids=self.ids,
                             group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
                             tokens_exp=None if self.tokens_exp is None else up(self.tokens_exp), compute=self._compute_arg,
-                            onsets=self.onsets, beats=self.beats, bars=self.bars)
+                            onsets=self.onsets, beats=self.beats, bars=self.bars, sections=self.sections)
 
     def pin(self) -> "MusicLibrary":
         """The same library with tokens / mask / vec / duration copied into pinned host tensors: `ground_library` uploads its
@@ -441,7 +460,7 @@ class MusicLibrary:
                             duration=None if self.duration is None else pin(self.duration), windows=self.windows, ids=self.ids,
                             group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
                             tokens_exp=None if self.tokens_exp is None else pin(self.tokens_exp), compute=self._compute_arg,
-                            onsets=self.onsets, beats=self.beats, bars=self.bars)
+                            onsets=self.onsets, beats=self.beats, bars=self.bars, sections=self.sections)
 
     @property
     def pinned(self) -> bool:
@@ -467,7 +486,7 @@ class MusicLibrary:
         """this library with other tokens"""
         return MusicLibrary(tokens, self.mask, self.vec, self.col_group, self.source, dtype, duration=self.duration, windows=self.windows,
                             ids=self.ids, group_id=self.group_id, tags=self.tags, length=self.length, tag_names=self.tag_names,
-                            tokens_exp=tokens_exp, onsets=self.onsets, beats=self.beats, bars=self.bars)
+                            tokens_exp=tokens_exp, onsets=self.onsets, beats=self.beats, bars=self.bars, sections=self.sections)
 
     def quantize(self, device=None) -> "MusicLibrary":
         """The FP8 library of a bf16 library: the same arrays with the tokens as e4m3fn bytes and one power-of-two exponent per
@@ -538,7 +557,8 @@ class MusicLibrary:
         _write_tables(path, self.windows, self.group_id, self.ids)
         _write_manifest(path, self.dtype, len(self), self.S, self.D, self.duration is not None, self.windows, self.ids is not None,
                         self.group_id is not None, _write_attributes(path, self.tags, self.length, self.tag_names), self._compute_arg,
-                        write_onsets(path, self.onsets), write_beats(path, self.beats), write_bars(path, self.bars))
+                        write_onsets(path, self.onsets), write_beats(path, self.beats), write_bars(path, self.bars),
+                        write_sections(path, self.sections))
 
     @classmethod
     def load(cls, path: str, mmap: bool = True) -> "MusicLibrary":
@@ -578,7 +598,7 @@ class MusicLibrary:
                    tags=np.load(os.path.join(path, "tags.npy")) if attr.get("tags") else None,
                    length=np.load(os.path.join(path, "length.npy")) if attr.get("length") else None, tag_names=attr.get("tag_names"),
                    tokens_exp=tokens_exp, compute=man.get("compute") if man["dtype"] == "fp8" else None, onsets=_read_onsets(path, man),
-                   beats=_read_beats(path, man), bars=_read_bars(path, man))
+                   beats=_read_beats(path, man), bars=_read_bars(path, man), sections=_read_sections(path, man))
 
     # ------------------------------------------------------------------ the chunk plan
     def chunk_plan(self, chunk_cols: int) -> List[Tuple[int, int]]:
@@ -766,9 +786,39 @@ def _read_bars(path: str, man: dict):
     return Bars(Onsets(np.load(files[0]), np.load(files[1]), dict(params)), np.load(files[2]), np.load(files[3]), np.load(files[4]), params)
 
 
+SECTION_FILES = ("section_start.npy", "section_time.npy", "section_beat.npy", "section_strength.npy", "section_mean.npy")
+
+
+def write_sections(path: str, sections) -> Optional[dict]:
+    """section_start.npy / section_time.npy / section_beat.npy / section_strength.npy / section_mean.npy and the manifest's
+    "sections" entry, the detection parameters (None, and no files, for a library without sections)"""
+    if sections is None:
+        for name in SECTION_FILES:                                 # (a table an earlier save left here is not this library's)
+            if os.path.isfile(os.path.join(path, name)):
+                os.remove(os.path.join(path, name))
+        return None
+    np.save(os.path.join(path, "section_start.npy"), np.ascontiguousarray(sections.table.start, dtype=np.int64))
+    np.save(os.path.join(path, "section_time.npy"), np.ascontiguousarray(sections.table.time, dtype=np.float32))
+    np.save(os.path.join(path, "section_beat.npy"), np.ascontiguousarray(sections.beat, dtype=np.int32))
+    np.save(os.path.join(path, "section_strength.npy"), np.ascontiguousarray(sections.strength, dtype=np.float32))
+    np.save(os.path.join(path, "section_mean.npy"), np.ascontiguousarray(sections.mean, dtype=np.float32))
+    return dict(sections.params)
+
+
+def _read_sections(path: str, man: dict):
+    """the stored section boundaries, None when the directory has none"""
+    files = [os.path.join(path, name) for name in SECTION_FILES]
+    if not all(os.path.isfile(f) for f in files):
+        return None
+    from .onsets import Onsets
+    from .sections import Sections
+    params = dict(man.get("sections") or {})
+    return Sections(Onsets(np.load(files[0]), np.load(files[1]), dict(params)), np.load(files[2]), np.load(files[3]), np.load(files[4]), params)
+
+
 def _write_manifest(path: str, dtype: str, N: int, S: int, D: int, duration: bool, windows: Optional[Windows], ids: bool,
                     grouped: bool, attributes: Optional[dict] = None, compute: Optional[str] = None, onsets: Optional[dict] = None,
-                    beats: Optional[dict] = None, bars: Optional[dict] = None) -> None:
+                    beats: Optional[dict] = None, bars: Optional[dict] = None, sections: Optional[dict] = None) -> None:
     man = dict(format=FORMAT, version=VERSION, dtype=dtype, N=int(N), S=int(S), D=int(D), duration=bool(duration),
                windows=windows is not None, ids=bool(ids), grouped=bool(grouped),
                n_tracks=int(windows.n_tracks) if windows is not None else None)
@@ -782,6 +832,8 @@ def _write_manifest(path: str, dtype: str, N: int, S: int, D: int, duration: boo
         man["beats"] = beats
     if bars is not None:                                           # the detection parameters of bar_start.npy ... bar_strength.npy
         man["bars"] = bars
+    if sections is not None:                                       # the detection parameters of section_start.npy ... section_mean.npy
+        man["sections"] = sections
     with open(os.path.join(path, "manifest.json"), "w") as f:
         json.dump(man, f, indent=1)
         f.write("\n")

@@ -1659,6 +1659,175 @@ def bar_pick(B, beat_start, time, metres=BAR_METRES, low_bins: int = 16, low_wei
     return evidence, metre, phase, strength, down_time, down_count
 
 
+SECTION_MAX_L = 64                       # the half-width made_section_novelty takes, beats
+SECTION_MAX_W = 256                      # the window made_section_pick takes, beats
+
+
+def _section_params(L, sigma, w, delta, floor):
+    """(L, sigma, w, delta, floor), checked"""
+    try:
+        exact = float(L) == int(L) and float(w) == int(w)
+        L, w, sigma, delta, floor = int(L), int(w), float(sigma), float(delta), float(floor)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"L = {L!r}, w = {w!r}: integers; sigma = {sigma!r}, delta = {delta!r}, floor = {floor!r}: numbers")
+    if not exact:
+        raise ValueError(f"L = {L!r}, w = {w!r}: must be integers")
+    if not 1 <= L <= SECTION_MAX_L:
+        raise ValueError(f"L = {L}: must lie in [1, {SECTION_MAX_L}]")
+    if not 1 <= w <= SECTION_MAX_W:
+        raise ValueError(f"w = {w}: must lie in [1, {SECTION_MAX_W}]")
+    if not (math.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"sigma = {sigma}: must be finite and > 0")
+    if not (math.isfinite(delta) and delta >= 0):
+        raise ValueError(f"delta = {delta}: must be finite and >= 0")
+    if not (math.isfinite(floor) and floor >= 0):
+        raise ValueError(f"floor = {floor}: must be finite and >= 0")
+    return L, sigma, w, delta, floor
+
+
+def section_weights(L: int, sigma: float = 0.5):
+    """The taper of made_section_novelty, numpy f32 [L]: exp(-0.5 ((i + 0.5) / (sigma L))^2) for i < L, normalised to sum 1,
+    computed in float64 and rounded to f32 once (the kernel takes the table: no device expf enters the contract)."""
+    import numpy as np
+    L, sigma, _, _, _ = _section_params(L, sigma, 1, 0.0, 0.0)
+    g = np.exp(-0.5 * ((np.arange(L, dtype=np.float64) + 0.5) / (sigma * L)) ** 2)
+    if not g.sum() > 0:
+        raise ValueError(f"sigma = {sigma}: the taper underflows to nothing at L = {L}")
+    return (g / g.sum()).astype(np.float32)
+
+
+def section_novelty(B: Tensor, beat_start: Tensor, weights, novelty: Optional[Tensor] = None) -> Tensor:
+    """made_section_novelty: novelty [total] f32 of the beat-synchronous spectra B [total, 128] f32 (`beat_sync_mean`) of N tracks,
+    beat_start [N + 1] int64 on the device.  weights: `section_weights(L, sigma)` (an array, or an f32 tensor on B's device), L =
+    its length.  novelty[k] is the squared distance between the weighted sums of the L normalised beats from k on and of the L
+    before it, for L <= k <= n - L inside a track of n beats, and +0 at every other beat; a track whose rows lie outside B is
+    skipped.  novelty: a contiguous [total] f32 tensor to write into."""
+    assert B.dim() == 2 and B.shape[1] == 128 and B.dtype == torch.float32 and B.is_contiguous()
+    assert beat_start.dtype == torch.int64 and beat_start.is_contiguous() and beat_start.dim() == 1 and beat_start.numel() >= 1
+    assert beat_start.device == B.device
+    N, total = beat_start.numel() - 1, B.shape[0]
+    if not isinstance(weights, Tensor):
+        import numpy as np
+        weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)).to(B.device)
+    assert weights.dtype == torch.float32 and weights.is_contiguous() and weights.dim() == 1 and weights.device == B.device
+    L = weights.numel()
+    if not 1 <= L <= SECTION_MAX_L:
+        raise ValueError(f"L = {L} weights: must lie in [1, {SECTION_MAX_L}]")
+    if novelty is None:
+        novelty = torch.empty(total, device=B.device, dtype=torch.float32)
+    assert novelty.dtype == torch.float32 and novelty.is_contiguous() and novelty.numel() == total and novelty.device == B.device
+    check(lib().made_section_novelty(_p(B) if total else None, _p(beat_start), N, total, _p(weights), L, _p(novelty) if total else None,
+                                     _stream()), "made_section_novelty")
+    return novelty
+
+
+def section_cap(cap: int, w: int) -> int:
+    """the boundaries a track of `cap` beats can hold: two of them are at least w + 1 beats apart, so ceil(cap / (w + 1))"""
+    return (int(cap) + int(w)) // (int(w) + 1)
+
+
+def section_pick_host(novelty, beat_start, time, L: int, w: int = 16, delta: float = 0.5, floor: float = 0.0, metre=None, phase=None,
+                      cap_s: Optional[int] = None):
+    """made_section_pick restated in numpy float32 on a given `novelty` [total] (include/made_hip.h states the contract): the same
+    bits as the kernel.  beat_start int64 [N + 1], time f32 [N, cap], metre / phase int32 [N] or None -> (bound_time f32 [N, cap_s],
+    bound_beat int32 [N, cap_s], bound_strength f32 [N, cap_s] (NaN / -1 past a track's boundaries: the kernel leaves those entries
+    unwritten), bound_count int32 [N], mean f32 [N])."""
+    import numpy as np
+    f32 = np.float32
+    L, _, w, delta, floor = _section_params(L, 1.0, w, delta, floor)
+    if metre is not None and phase is None:
+        raise ValueError("metre given without phase")
+    nov = np.ascontiguousarray(novelty, dtype=f32).reshape(-1)
+    start = np.ascontiguousarray(beat_start, dtype=np.int64).reshape(-1)
+    time = np.ascontiguousarray(time, dtype=f32)
+    assert time.ndim == 2 and len(start) == time.shape[0] + 1
+    N, cap = time.shape
+    cap_s = section_cap(cap, w) if cap_s is None else int(cap_s)
+    if cap_s < 0:
+        raise ValueError(f"cap_s = {cap_s}: must be >= 0")
+    factor, floor = f32(1.0 + delta), f32(floor)
+    b_time, b_strength = np.full((N, cap_s), np.nan, f32), np.full((N, cap_s), np.nan, f32)
+    b_beat, count, mean = np.full((N, cap_s), -1, np.int32), np.zeros(N, np.int32), np.full(N, np.nan, f32)
+    chain = lambda a: np.add.accumulate(np.concatenate([np.zeros(1, f32), a]), dtype=f32)[-1]      # one f32 chain, ascending, from +0
+    for t in range(N):
+        r0, r1 = int(start[t]), int(start[t + 1])
+        n = r1 - r0
+        if r0 < 0 or n < 0 or r1 > len(nov) or n > cap:
+            count[t] = -1
+            continue
+        x = nov[r0:r1]
+        m = int(metre[t]) if metre is not None else 0
+        cand = np.arange(L, n - L + 1)
+        if m > 0:
+            cand = cand[(cand - int(phase[t])) % m == 0]
+        if not len(cand):
+            continue
+        with np.errstate(all="ignore"):
+            mu = f32(chain(x[cand]) / f32(len(cand)))
+            thresh = f32(mu * factor)
+            found = []
+            for k in cand:
+                v = x[k]
+                if not (v > 0 and v >= floor and v >= thresh):
+                    continue
+                before, after = cand[(cand >= k - w) & (cand < k)], cand[(cand > k) & (cand <= k + w)]
+                if np.all(v > x[before]) and np.all(v >= x[after]):
+                    found.append(int(k))
+            mean[t] = mu
+            keep = found[:cap_s]
+            b_time[t, :len(keep)] = time[t, keep]
+            b_beat[t, :len(keep)] = keep
+            b_strength[t, :len(keep)] = x[keep] / mu
+        count[t] = len(found) if len(found) <= cap_s else -1
+    return b_time, b_beat, b_strength, count, mean
+
+
+def section_pick(novelty, beat_start, time, L: int, w: int = 16, delta: float = 0.5, floor: float = 0.0, metre=None, phase=None,
+                 cap_s: Optional[int] = None, backend: Optional[str] = None):
+    """made_section_pick: the boundaries of N tracks from their novelty [total] f32 (`section_novelty` with the same L),
+    beat_start [N + 1] int64 and the beat times time [N, cap] f32 -> (bound_time [N, cap_s] f32, bound_beat [N, cap_s] int32,
+    bound_strength [N, cap_s] f32, bound_count int32 [N], mean f32 [N]).  The candidates are the beats L <= k <= n - L, with metre /
+    phase int32 [N] (`bar_pick`'s) only the bar lines of a track that has a metre; mean is the candidates' mean novelty (NaN
+    without candidates); a candidate is a boundary iff its novelty is positive, greater than every candidate's up to w beats
+    before it, at least every candidate's up to w beats after it, at least `floor` and at least mean * (1 + delta) (the factor
+    rounded to f32 once).  bound_strength = novelty / mean.  Only the first bound_count[t] entries of a track are written; cap_s
+    defaults to `section_cap(cap, w)`, which cannot overflow (a track with more boundaries than cap_s has count -1).  The defaults
+    are a starting value that nobody has tuned on real music.  backend None: device tensors in and out, one launch.  backend
+    "host": `section_pick_host`, arrays or host tensors in, numpy arrays out -- the same bits, on any machine."""
+    if backend == "host":
+        host = lambda a: a.detach().cpu().numpy() if isinstance(a, Tensor) else a
+        return section_pick_host(host(novelty), host(beat_start), host(time), L, w, delta, floor, host(metre), host(phase), cap_s)
+    if backend is not None:
+        raise ValueError(f"backend = {backend!r}: None (the device) or 'host'")
+    L, _, w, delta, floor = _section_params(L, 1.0, w, delta, floor)
+    if metre is not None and phase is None:
+        raise ValueError("metre given without phase")
+    assert novelty.dim() == 1 and novelty.dtype == torch.float32 and novelty.is_contiguous()
+    dev = novelty.device
+    assert time.dim() == 2 and time.dtype == torch.float32 and time.is_contiguous() and time.device == dev
+    N, cap = time.shape
+    assert beat_start.dtype == torch.int64 and beat_start.is_contiguous() and beat_start.numel() == N + 1 and beat_start.device == dev
+    if metre is not None:
+        for a in (metre, phase):
+            assert a.dtype == torch.int32 and a.is_contiguous() and a.numel() == N and a.device == dev
+    total = novelty.numel()
+    cap_s = section_cap(cap, w) if cap_s is None else int(cap_s)
+    if cap_s < 0:
+        raise ValueError(f"cap_s = {cap_s}: must be >= 0")
+    b_time, b_strength = (torch.empty(N, cap_s, device=dev, dtype=torch.float32) for _ in range(2))
+    b_beat = torch.empty(N, cap_s, device=dev, dtype=torch.int32)
+    count = torch.empty(N, device=dev, dtype=torch.int32)
+    mean = torch.empty(N, device=dev, dtype=torch.float32)
+    import numpy as np
+    some = N * cap_s > 0
+    check(lib().made_section_pick(_p(novelty) if total else None, _p(beat_start), _p(time) if time.numel() else None, cap, N, total,
+                                  _p(metre) if metre is not None else None, _p(phase) if metre is not None else None, L, w,
+                                  float(np.float32(1.0 + delta)), float(np.float32(floor)), _p(b_time) if some else None,
+                                  _p(b_beat) if some else None, _p(b_strength) if some else None, cap_s, _p(count), _p(mean), _stream()),
+          "made_section_pick")
+    return b_time, b_beat, b_strength, count, mean
+
+
 def fit_moments_host(start, end, track, want, tlen, onset_start=None, onset_time=None, tol: float = 0.0):
     """made_fit_moments restated in numpy float32, one rounded operation per step (include/made_hip.h states the contract): the
     same bits as the kernel.  Arrays of E entries -> (out_start, out_end, shift f32 [E], onset int32 [E])."""
